@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- iCEM inner planning loop on MI355X: traj-steps/s of whole MPC steps.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 A "step" is one MPC step = all CEM iterations (sample -> rollout -> cost -> top-k -> refit) of one
 `get_action`, on synthetic HalfCheetah-shaped input already resident in HBM.  Workload c2 (default;
@@ -23,7 +23,13 @@ torch.distributed all-gather -- every leg says which one ran (`exchange.kind`), 
 fine-grained and how many waits timed out.  torch.distributed carries handles / ids once at set-up and the barriers
 around the timed region, nothing inside it.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, from HIP events recorded on
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W untimed and K timed steps and prints the headline (`value`,
+`ms_per_step` = milliseconds per timed step, `dtype`, `config`, `build`, the loop's floors in `attainable`).
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step (executed action, best cost,
+mean / std left for the next step, the elite set) as DIR/<name>.npy; the inputs are seeded, so that two builds compare
+output for output.  Everything below is measured only with `--full` (which `--no-also` / `--no-cpu-baseline` trim): the
+spread over further blocks of K steps (a plain run's `timed_region` holds the first block alone), the per-kernel times,
+`exchange`, `also*` / `strong` and the CPU baselines.  `roofline` is for the dominant kernel, from HIP events recorded on
 the launch stream inside the library (icem_profile_*), in a second pass over the same steps: SURVEY 8(d)'s HBM
 definition (`bound`/`achieved`/`peak`/`frac`) plus the same launch priced against the f32 vector / matrix peak
 (`compute`) and which of the two roofs is nearer (`binding_roof`).  `cpu_baseline` times oracle/icem_oracle.c (a
@@ -420,11 +426,12 @@ class RecordsPathFailed(RuntimeError):
     """Some rank's launches reported a failure of the path the ranks' elite records travel on (agreed on by all ranks)."""
 
 
-def timed_steps(pl, steps, warmup, world, spread=None):
+def timed_steps(pl, steps, warmup, world, spread=None, cover_s=10e-3, on_timed=None):
     """W untimed steps, then K timed ones between barrier + synchronize pairs; the MAX over ranks.  That first block of
-    exactly K steps is what `value` is computed from.  A block shorter than 10 ms says little about a box (clock ramps, a
-    neighbour's interrupt): when `spread` (a dict) is given, further blocks of K steps are timed the same way until 10 ms
-    have been covered, and their min / median / max ms per step are recorded in it.
+    exactly K steps is what `value` is computed from; `on_timed()` is called right after it (before any further block), so
+    that what its last step computed can be kept.  A block shorter than 10 ms says little about a box (clock ramps, a
+    neighbour's interrupt): when `spread` (a dict) is given, further blocks of K steps are timed the same way until `cover_s`
+    seconds have been covered (0: the first block alone), and their min / median / max ms per step are recorded in it.
     world > 1: a rank whose step raises (a bounded wait for a peer's records ran out) does NOT leave the collective
     pattern -- every block ends in the same all-reduce, which carries the ranks' failure flags; if any is set, every rank
     raises RecordsPathFailed and the caller degrades the path on all of them (timed_with_fallback)."""
@@ -485,9 +492,11 @@ def timed_steps(pl, steps, warmup, world, spread=None):
         return el
     block(warmup)
     el = block(steps)
+    if on_timed is not None:
+        on_timed()
     if spread is not None:
         blocks = [el]
-        while sum(blocks) < 10e-3 and len(blocks) < 64:   # (el is the max over ranks: every rank takes the same number)
+        while sum(blocks) < cover_s and len(blocks) < 64:   # (el is the max over ranks: every rank takes the same number)
             blocks.append(block(steps))
         per = sorted(1e3 * b / steps for b in blocks)
         spread.update({"blocks_of_k_steps": len(blocks), "covered_ms": 1e3 * sum(blocks), "ms_per_step_first_block": 1e3 * el / steps,
@@ -495,7 +504,7 @@ def timed_steps(pl, steps, warmup, world, spread=None):
     return el
 
 
-def timed_with_fallback(pl, steps, warmup, world, spread=None):
+def timed_with_fallback(pl, steps, warmup, world, spread=None, cover_s=10e-3, on_timed=None):
     """timed_steps; where the records' path fails at run time, all ranks step down together (IcemPlanner.degrade_exchange:
     in-library exchange -> in-library RCCL all-gather -> host-driven all-gather) and the measurement starts over."""
     degraded, disagreed = [], 0
@@ -503,7 +512,7 @@ def timed_with_fallback(pl, steps, warmup, world, spread=None):
         try:
             if spread is not None:
                 spread.clear()
-            el = timed_steps(pl, steps, warmup, world, spread)
+            el = timed_steps(pl, steps, warmup, world, spread, cover_s, on_timed)
             if spread is not None:
                 if degraded:
                     spread["records_path_degraded_to"] = degraded
@@ -654,10 +663,11 @@ def exchange_report(pl):
             "host_collectives_in_timed_loop": 0}
 
 
-def measure_c5(w, steps, warmup, cpu=True):
+def measure_c5(w, steps, warmup, cpu=True, full=True, outputs=None):
     """--workload c5: one step = MpcICemHip.get_action with DeviceRSSMModel (sampling / top-K / refit kernels + one fused
     RSSM rollout launch per CEM iteration); roofline bound = the bf16 matrix cores for the rollout kernel; CPU baseline =
-    oracle/rssm_oracle.py (NumPy, float64) on the same populations."""
+    oracle/rssm_oracle.py (NumPy, float64) on the same populations.  full=False: the timed steps alone (no roofline pass,
+    no CPU baseline).  `outputs` (a dict): filled with what the last timed step handed its caller."""
     from icem_amd import DeviceRSSMModel, MpcICemHip, halfcheetah_env
     env = halfcheetah_env(17)   # action space only (d=6, +-1)
     model = DeviceRSSMModel(seed=3)
@@ -673,11 +683,22 @@ def measure_c5(w, steps, warmup, cpu=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        ctrl.get_action(obs, None)
+        act = ctrl.get_action(obs, None)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(executed_action=np.asarray(act), best_cost=np.asarray([ctrl.last_min_cost], dtype=np.float64),
+                       mean=ctrl.planner.mean.detach().clone(), std=ctrl.planner.std.detach().clone())
     pops = ctrl.planner.population_sizes
     ts = sum(pops) * w["h"]
+    out = {"metric": "traj-steps/sec (N x h), iCEM inner planning loop", "value": ts * steps / elapsed, "unit": "traj-steps/s",
+           "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+           "config": {"workload": w["name"], "per_gpu_population": w["N"], "traj_per_mpc_step": sum(pops),
+                      "model": "declared RSSM, random weights (icem_amd.models.declared_rssm)", "cost": "-reward head",
+                      "rng": "Philox4x32-10-seeded xoshiro128++ + Box-Muller", "parallelism": "n-shard x1"}}
+    if not full:
+        return out
     # second pass: the rollout kernel alone, HIP events on the stream it is launched on (torch's current stream)
     orig, spans = model.rollout_cost, []
 
@@ -706,13 +727,7 @@ def measure_c5(w, steps, warmup, cpu=True):
                 "traffic_source": src, "rocprof_trace_avg_us": trace_us,
                 "kernel": "rssm_split_kernel" if max(n for _, _, n in spans) <= 65536 else "rssm_rollout_kernel", "avg_launch_us": 1e3 * ms / len(spans), "launches": len(spans),
                 "algorithmic_flops_per_traj_step": 2.0 * macs, "dtype": "bf16 operands, f32 accumulation"}
-    out = {"metric": "traj-steps/sec (N x h), iCEM inner planning loop", "value": ts * steps / elapsed, "unit": "traj-steps/s",
-           "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-           "config": {"workload": w["name"], "per_gpu_population": w["N"], "traj_per_mpc_step": sum(pops),
-                      "model": "declared RSSM, random weights (icem_amd.models.declared_rssm)", "cost": "-reward head",
-                      "rng": "Philox4x32-10-seeded xoshiro128++ + Box-Muller", "parallelism": "n-shard x1"},
-           "roofline": roofline, "cpu_baseline": None}
+    out.update(roofline=roofline, cpu_baseline=None)
     if cpu:
         from oracle import rssm_oracle as RO
         P = RO.params_from_state_dict(model.reference.state_dict())
@@ -769,6 +784,34 @@ def dtype_name(tile_arith):
     return "f32 storage; model step 2xfp16 planes (3 products), f32 accumulate" if tile_arith else "f32"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def planner_outputs(pl):
+    """What a caller of the timed path has from its last MPC step: the executed action (what IcemPlanner.plan_step returns),
+    the best cost of the last pool, the distribution left for the next step and the elite set behind the action (device
+    copies, taken while nothing else runs)."""
+    ea, ec = pl.current_elites()
+    return {k: v.detach().clone() for k, v in (("executed_action", pl.executed), ("best_cost", pl.best_cost), ("mean", pl.mean),
+                                               ("std", pl.std), ("elite_actions", ea), ("elite_costs", ec))}
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, in float32 or float64 (the precision it was computed in; anything
+    else as float64), at most DUMP_LIMIT_BYTES in all.  Returns the bytes written."""
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    return total
+
+
 def main():
     if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-numpy-child":   # children of extra_cpu_baselines
         return numpy_baseline_child(sys.argv[2], float(sys.argv[3]))
@@ -787,8 +830,13 @@ def main():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS), help="c2 = the metric's configuration (default)")
     ap.add_argument("--cost-mode", default="sum", choices=["sum", "best", "final"],
                     help="cost_along_trajectory (abstract_controller.py:82-87); the metric is quoted on 'sum'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra measurements (c4 per GPU; c5 on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the spread over further timed blocks, per-kernel times and roofline, the exchange "
+                         "report, the extra measurements and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra measurements (c4 per GPU; c5 on one GPU)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -838,31 +886,41 @@ def main():
     build["options_from_environment"] = _L.apply_env_options()
 
     w = WORKLOADS[args.workload]
+    dump = args.dump_outputs if rank == 0 else None
+    outputs = {}
     if args.workload == "c5":
         if world != 1:
             sys.exit("--workload c5 is a single-GPU configuration")
-        out = measure_c5(w, args.steps, args.warmup, cpu=not args.no_cpu_baseline)
+        out = measure_c5(w, args.steps, args.warmup, cpu=args.full and not args.no_cpu_baseline, full=args.full,
+                         outputs=outputs if dump else None)
+        if dump:
+            write_outputs(dump, outputs)
         out["build"] = build
         print(json.dumps(out), flush=True)
         return
     pl, model, env = make_planner(w, rank, world, cost_mode=args.cost_mode)
     per_step_trajsteps = sum(pl.population_sizes) * w["h"]  # global (all ranks) traj-steps per MPC step
     spread = {}
-    elapsed = timed_with_fallback(pl, args.steps, args.warmup, world, spread)
+    # a plain run times the K steps once; --full goes on timing blocks of K steps until 10 ms are covered (timed_region)
+    elapsed = timed_with_fallback(pl, args.steps, args.warmup, world, spread, cover_s=10e-3 if args.full else 0.0,
+                                  on_timed=(lambda: outputs.update(planner_outputs(pl))) if dump else None)
+    if dump:
+        write_outputs(dump, outputs)
     tile_arith = pl.tile_arith if w["o"] <= 32 else 0
 
-    # second pass: per-kernel durations from HIP events on the launch stream
-    pl.profile_enable(True)
-    n_prof = min(args.steps, 50)
-    run_steps(pl, n_prof, world)
-    torch.cuda.synchronize()
-    raw_prof = pl.profile_read()
-    pl.profile_enable(False)
-    bracket = event_bracket_us(pl)
-    prof, fit = fit_to_step(without_bracket(raw_prof, bracket), n_prof, 1e3 * elapsed / args.steps)
-    exchange = exchange_report(pl) if world > 1 else None   # collective: every rank
-    also = strong = None
-    if args.workload == "c2" and not args.no_also:
+    exchange = also = strong = None
+    if args.full:
+        # second pass: per-kernel durations from HIP events on the launch stream
+        pl.profile_enable(True)
+        n_prof = min(args.steps, 50)
+        run_steps(pl, n_prof, world)
+        torch.cuda.synchronize()
+        raw_prof = pl.profile_read()
+        pl.profile_enable(False)
+        bracket = event_bracket_us(pl)
+        prof, fit = fit_to_step(without_bracket(raw_prof, bracket), n_prof, 1e3 * elapsed / args.steps)
+        exchange = exchange_report(pl) if world > 1 else None   # collective: every rank
+    if args.full and args.workload == "c2" and not args.no_also:
         del pl
         # (ranks that share ONE GPU cannot run 65536 rows each: a rank's launch fills the chip and spins on a peer that
         #  cannot get a CU until the bounded waits give up -- DESIGN section 6; the debugging run skips that leg)
@@ -874,7 +932,6 @@ def main():
             strong["debug_population"] = shared_gpu
 
     if rank == 0:
-        roofline = roofline_of(prof, w, args.workload if world == 1 else None, fit, tile_arith)
         out = {
             "metric": "traj-steps/sec (N x h), iCEM inner planning loop", "value": per_step_trajsteps * args.steps / elapsed,
             "unit": "traj-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -888,13 +945,16 @@ def main():
                        "cost": {"humanoid": "HumanoidStandup cost_fn", "door": "Door cost terms", "relocate": "Relocate cost terms",
                      "fpp": "FetchPickAndPlace cost terms"}.get(w.get("env"), "HalfCheetah cost_fn"), "cost_along_trajectory": args.cost_mode, "rng": "Philox4x32-10-seeded xoshiro128++ + Box-Muller", "parallelism": f"n-shard x{world}"},
             "ms_per_mpc_step": 1e3 * elapsed / args.steps, "timed_region": spread,
-            "roofline": roofline,
-            "kernels_us": {k: round(1e3 * v[0] / v[1], 2) for k, v in prof.items()},
-            "kernels_us_events": {k: round(1e3 * v[0] / v[1], 2) for k, v in without_bracket(raw_prof, bracket).items()},
-            "kernels_us_with_event_bracket": {k: round(1e3 * v[0] / v[1], 2) for k, v in raw_prof.items()},
-            "event_bracket": bracket, "kernel_times_vs_step": fit,
-            "build": build,
         }
+        if args.full:
+            out.update({
+                "roofline": roofline_of(prof, w, args.workload if world == 1 else None, fit, tile_arith),
+                "kernels_us": {k: round(1e3 * v[0] / v[1], 2) for k, v in prof.items()},
+                "kernels_us_events": {k: round(1e3 * v[0] / v[1], 2) for k, v in without_bracket(raw_prof, bracket).items()},
+                "kernels_us_with_event_bracket": {k: round(1e3 * v[0] / v[1], 2) for k, v in raw_prof.items()},
+                "event_bracket": bracket, "kernel_times_vs_step": fit,
+            })
+        out["build"] = build
         if w["o"] <= 32:
             out["attainable"] = loop_floor_ms(w, per_step_trajsteps / w["h"] / world, tile_arith)
             out["attainable"]["frac_of_attainable"] = out["attainable"]["attainable_ms"] / out["ms_per_step"]
@@ -906,7 +966,7 @@ def main():
             out["also"] = also
         if strong is not None:
             out["strong"] = strong
-        if world == 1 and args.workload == "c2" and not args.no_also:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_also:
             try:   # BASELINE configs[2] at the env's real width o = 378 (the f32 GEMM rollout): 30 MPC steps
                 out["also_c3"] = measure_also("c3", 0, 1, steps=30, warmup=3)
             except Exception as ex:
@@ -919,17 +979,18 @@ def main():
                 out["also_f64"] = measure_f64("c2")
             except Exception as ex:
                 out["also_f64"] = {"error": repr(ex)[:300]}
-            try:   # BASELINE configs[4] in the default run: the learned-dynamics line, GPU part only
+            try:   # BASELINE configs[4] in the --full run: the learned-dynamics line, GPU part only
                 c5 = measure_c5(WORKLOADS["c5"], 200, 20, cpu=False)
                 out["also_c5"] = {k: c5[k] for k in ("value", "unit", "ms_per_step", "dtype", "config", "roofline")}
             except Exception as ex:
                 out["also_c5"] = {"error": repr(ex)[:300]}
-        if not args.no_cpu_baseline and world == 1 and args.cost_mode == "sum" and w.get("env") not in ("door", "relocate", "fpp"):   # the C oracle's loop: sum, HalfCheetah / HumanoidStandup form
-            out["cpu_baseline"] = cpu_baseline(args.workload, c_port_threads(w))
-            out["cpu_baseline"]["host_logical_cpus"] = usable_cores()
-            out["cpu_baselines"] = extra_cpu_baselines(args.workload, w, model, env)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            if not args.no_cpu_baseline and world == 1 and args.cost_mode == "sum" and w.get("env") not in ("door", "relocate", "fpp"):   # the C oracle's loop: sum, HalfCheetah / HumanoidStandup form
+                out["cpu_baseline"] = cpu_baseline(args.workload, c_port_threads(w))
+                out["cpu_baseline"]["host_logical_cpus"] = usable_cores()
+                out["cpu_baselines"] = extra_cpu_baselines(args.workload, w, model, env)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -54,3 +54,17 @@ def test_loop_floor_matches_the_metric_definition(bench):
     f = bench.loop_floor_ms(w, 13764, 1)
     assert abs(f["hbm_floor_ms"] - 13764 * 30 * (48 + 8 / 30) / 8e12 * 1e3) < 1e-12
     assert f["attainable_ms"] == max(f["hbm_floor_ms"], f["alu_floor_ms"])
+
+
+def test_dumped_outputs_are_float32_or_float64_and_bounded(bench, tmp_path):
+    import numpy as np
+    import torch
+    arrays = {"action": torch.arange(6, dtype=torch.float32), "cost": np.array([1.5]), "index": np.arange(4, dtype=np.int32)}
+    total = bench.write_outputs(str(tmp_path / "out"), arrays)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in arrays}
+    assert got["action"].dtype == np.float32 and np.array_equal(got["action"], np.arange(6))
+    assert got["cost"].dtype == np.float64 and got["index"].dtype == np.float64 and np.array_equal(got["index"], np.arange(4))
+    assert total == 6 * 4 + 8 + 4 * 8
+    with pytest.raises(ValueError):   # more than 64 MB in all: refused before anything is written
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros((bench.DUMP_LIMIT_BYTES // 8 + 1,))})
+    assert not (tmp_path / "big").exists()

@@ -33,7 +33,7 @@ def _bench(fault):
         env["ICEM_XCHG_FAIL"] = fault
         env["ICEM_XCHG_MAX_POLLS"] = "20000"   # a lost peer costs milliseconds, not the default's seconds (bench.py maps it onto icem_set_option)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-also"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-also"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

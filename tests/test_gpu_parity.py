@@ -2382,7 +2382,7 @@ def test_bench_two_ranks_without_a_launcher():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -2399,6 +2399,46 @@ def test_bench_two_ranks_without_a_launcher():
     assert j["strong"]["scaling"] == "strong" and j["strong"]["n_gpus"] == 2
     if torch.cuda.device_count() >= 2:
         assert j["strong"]["global_population"] == 65536 and "also" in j
+
+
+def test_bench_plain_run_dumps_its_last_timed_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the plain run times exactly K steps once and prints
+    the headline alone (nothing that --full measures); DIR holds what the planner handed back after its W + K steps -- the
+    same bits in a second run (seeded inputs) and in a planner of the same workload stepped W + K times in this process."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    names = ("executed_action", "best_cost", "mean", "std", "elite_actions", "elite_costs")
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 7 and j["warmup"] == 3 and j["value"] > 0 and j["higher_is_better"] is True
+        assert abs(j["value"] - j["config"]["traj_per_mpc_step"] * 30 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        assert j["timed_region"]["blocks_of_k_steps"] == 1
+        assert not {"roofline", "kernels_us", "cpu_baseline", "also", "also_c5", "exchange"} & set(j), sorted(j)
+        assert sorted(os.listdir(d)) == sorted(f"{n}.npy" for n in names)
+        runs.append({n: np.load(d / f"{n}.npy") for n in names})
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    pl, _, _ = bench.make_planner(bench.WORKLOADS["c2"], 0, 1)
+    bench.run_steps(pl, 3 + 7, 1)
+    torch.cuda.synchronize()
+    want = {k: np_(v) for k, v in bench.planner_outputs(pl).items()}
+    for n in names:
+        assert runs[0][n].dtype == np.float32 and np.isfinite(runs[0][n]).all(), n
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+        assert np.array_equal(runs[0][n], want[n]), n
 
 
 @pytest.mark.parametrize("N", [4096, 40000])

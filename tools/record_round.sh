@@ -16,18 +16,18 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.txt 2>&1; tai
 cp $ROOT/gpurun_out/literal_bounds.jsonl $OUT/literal_bounds.jsonl 2> /dev/null
 for w in c2 c4 c3 c5; do timeout 900 bash tools/profile_round.sh $TAG $w > /dev/null 2>&1; done
 cd $ROOT
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.json
-timeout 300 python bench.py --workload c5 --steps 200 --warmup 20 > $OUT/c5_bench.json 2> /dev/null
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.json
+timeout 300 python bench.py --full --workload c5 --steps 200 --warmup 20 > $OUT/c5_bench.json 2> /dev/null
 # cost_along_trajectory = best / final on the headline workload, and the reference's other shipped settings (cost-term envs)
-for m in best final; do timeout 300 python bench.py --cost-mode $m --no-also --no-cpu-baseline > $OUT/bench_c2_$m.json 2> /dev/null; done
-for w in door relocate fpp; do timeout 300 python bench.py --workload $w --no-also --no-cpu-baseline > $OUT/bench_$w.json 2> /dev/null; done
+for m in best final; do timeout 300 python bench.py --full --cost-mode $m --no-also --no-cpu-baseline > $OUT/bench_c2_$m.json 2> /dev/null; done
+for w in door relocate fpp; do timeout 300 python bench.py --full --workload $w --no-also --no-cpu-baseline > $OUT/bench_$w.json 2> /dev/null; done
 # first-contact drills of the records' path: two ranks on this box's GPU(s), every injected failure must end on a fallback path
 {
   for f in none connect selftest:0 timeout:1:40; do
     # (the product library carries no fault injection: the drills load its twin, libicem_hip_faults.so)
     if [ $f = none ]; then unset ICEM_XCHG_FAIL ICEM_HIP_LIB; else export ICEM_XCHG_FAIL=$f ICEM_HIP_LIB=$ROOT/icem_amd/libicem_hip_faults.so; fi
-    echo "# ICEM_XCHG_FAIL=$f python bench.py --gpus 2 --steps 30 --warmup 5 --no-cpu-baseline --no-also  ->  exchange / timed_region of the line"
-    ICEM_XCHG_MAX_POLLS=20000 timeout 300 python bench.py --gpus 2 --steps 30 --warmup 5 --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
+    echo "# ICEM_XCHG_FAIL=$f python bench.py --gpus 2 --steps 30 --warmup 5 --full --no-cpu-baseline --no-also  ->  exchange / timed_region of the line"
+    ICEM_XCHG_MAX_POLLS=20000 timeout 300 python bench.py --gpus 2 --steps 30 --warmup 5 --full --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
   done
   unset ICEM_XCHG_FAIL ICEM_HIP_LIB
   echo "# tools/dbg/shared_gpu_worlds.py 2 4 8: the exchange between 2 / 4 / 8 PROCESSES sharing this GPU, at a population whose workgroups are resident together"
@@ -40,11 +40,11 @@ for w in door relocate fpp; do timeout 300 python bench.py --workload $w --no-al
   timeout 600 python tools/dbg/shared_gpu_rank_time.py 2 4 8 2>&1 | grep "^world"
   echo "# python bench.py --gpus {4,8} (self-launched ranks: each rank of a shared GPU gets its own slice of the CUs, HSA_CU_MASK): the same population, the in-library exchange carries the records"
   for n in 4 8; do
-    timeout 600 python bench.py --gpus $n --steps 20 --warmup 5 --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'n_gpus': j['n_gpus'], 'ranks_share_a_gpu': j['ranks_share_a_gpu'], 'launched_by': j['launched_by'], 'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
+    timeout 600 python bench.py --gpus $n --steps 20 --warmup 5 --full --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'n_gpus': j['n_gpus'], 'ranks_share_a_gpu': j['ranks_share_a_gpu'], 'launched_by': j['launched_by'], 'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
   done
   echo "# ... and under torch.distributed.run (no CU slices):"
   for n in 4 8; do
-    timeout 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2951$n bench.py --gpus $n --steps 20 --warmup 5 --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'n_gpus': j['n_gpus'], 'ranks_share_a_gpu': j['ranks_share_a_gpu'], 'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
+    timeout 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2951$n bench.py --gpus $n --steps 20 --warmup 5 --full --no-cpu-baseline --no-also 2> /dev/null | grep '^{' | python -c "import sys, json; j = json.loads(sys.stdin.read()); print(json.dumps({'n_gpus': j['n_gpus'], 'ranks_share_a_gpu': j['ranks_share_a_gpu'], 'ms_per_step': j['ms_per_step'], 'exchange': j['exchange'], 'timed_region': j['timed_region']}))"
   done
 } > $OUT/exchange_fault_drills.txt 2>&1
 {
