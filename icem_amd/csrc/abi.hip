@@ -476,9 +476,10 @@ int icem_set_model(icem_handle* h, int32_t kind, int32_t obs_dim, const double* 
         update_paths(h);
         return sync_wide_cost(h);
     }
-    h->wide = false;
     const int O = pick_O(obs_dim);
     if (obs_dim < 1 || O < 0) return fail(ICEM_E_UNSUPPORTED, "obs_dim must be in [1, 384]");
+    // (a refused call leaves the handle as it was: a wide handle stays wide)
+    h->wide = false;
     std::vector<double> A((size_t)O * O, 0.0), B((size_t)d * O, 0.0);
     for (int k = 0; k < obs_dim; ++k)
         for (int i = 0; i < obs_dim; ++i) A[(size_t)k * O + i] = A_host[(size_t)k * obs_dim + i];

@@ -730,9 +730,14 @@ def rollout_cost_magnitudes(model: SyntheticModel, cost: CostSpec, obs0, actions
         mag += abs(cost.ctrl_weight) * (a * a).sum(axis=1)
         if cost.lin_weight != 0:
             mag += abs(cost.lin_weight) * np.abs(obs[:, cost.lin_idx])
+        nxt = model.predict(obs, a)
+        if getattr(cost, "diff_idx", -1) >= 0:   # |diff_weight| (|next_obs[i]| + |obs[i]|): both operands of the difference
+            mag += abs(cost.diff_weight) * (np.abs(nxt[:, cost.diff_idx]) + np.abs(obs[:, cost.diff_idx]))
+        if getattr(cost, "health_idx", -1) >= 0:   # the health penalty where it is scored
+            mag += abs(cost.health_penalty) * cost.unhealthy(obs)
         for tm in getattr(cost, "terms", ()):   # the term list (icem_cost_terms): |weight x f x gate| of every term
             mag += np.abs(cost.term_value(tm, obs))
-        obs = model.predict(obs, a)
+        obs = nxt
     return mag
 
 

@@ -18,49 +18,15 @@ import pytest
 import torch
 
 from oracle import icem_oracle as O
+from oracle_loop import ATOL, RTOL, DeviceNormals, full_loop, np_
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-5, 2e-6  # north_star: 1e-5 relative; the floor covers entries near zero (actions live in [-1, 1])
+# (RTOL, ATOL = 1e-5, 2e-6: north_star: 1e-5 relative; the floor covers entries near zero (actions live in [-1, 1]))
 # Trajectory costs are sums of h step costs whose positive (control, penalty) and negative (velocity / height) terms
 # cancel: "1e-5 relative" is taken relative to the MAGNITUDE of that sum -- sum_t sum |addend|, the scale rounding errors
 # have (oracle.rollout_cost_magnitudes) -- with no absolute floor on top: a cost is never granted more than 1e-5 of what
 # was added up to make it.
-
-
-def np_(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-class DeviceNormals:
-    """Noise callback for the oracle that hands it the device's own f32 normals, call for call (the offsets of
-    :class:`oracle.icem_oracle.PhiloxNoiseSchedule`)."""
-
-    def __init__(self, planner, iters, shift=True, white=False):
-        self.pl, self.iters, self.shift, self.white = planner, iters, shift, white
-        self.step = -1
-        self.begin_step()
-
-    def begin_step(self):
-        self.step += 1
-        self.it = 0
-        self.shift_done = False
-
-    def __call__(self, num):
-        base = self.step * (self.iters + 1)
-        if self.shift and self.step > 0 and self.it == 1 and not self.shift_done:
-            self.shift_done = True
-            off = base + self.iters
-        else:
-            off = base + self.it
-            self.it += 1
-        z_r, z_i = self.pl.philox_normals(num, offset=off)
-        z_r, z_i = np_(z_r), np_(z_i)
-        if self.white:
-            F = self.pl.F
-            g = np.concatenate([z_r, z_i[..., 1:1 + (self.pl.h - F)]], axis=-1)
-            return np.ascontiguousarray(g.transpose([0, 2, 1])), None
-        return z_r, z_i
 
 
 def _make(N, iters, h, d, o, kind, beta, seed, env_kind, cost_mode="sum", arith=None, model_ab=None):
@@ -202,90 +168,19 @@ def test_full_loop_with_a_model_that_outgrows_fp16_range(env_kind, d, o, rate, b
 
 
 def _full_loop(N, iters, h, d, o, kind, beta, env_kind, seed, cost_mode, arith=None, expect_arith=None, model_ab=None, rtol=None):
-    RTOL_C = rtol if rtol is not None else RTOL   # (costs; mean / std / actions keep the module's RTOL)
+    """The whole-loop comparison (tests/oracle_loop.py: full_loop) on the env factories above, plus the literal bound."""
+    RTOL_C = rtol if rtol is not None else RTOL
     env, model, oc, mk = _make(N, iters, h, d, o, kind, beta, seed, env_kind, cost_mode, arith, model_ab)
     om = O.SyntheticModel(model.A, model.B, model.kind)
-    split, fused, rng = mk(), mk(), mk()
-    if expect_arith is not None:
-        assert split.tile_arith == expect_arith
-    noise = DeviceNormals(rng, iters)
-    low, high = env.action_space.low.astype(np.float64), env.action_space.high.astype(np.float64)
-    orc = O.IcemOracle(O.IcemParams(horizon=h, num_simulated_trajectories=N, opt_iterations=iters, noise_beta=beta),
-                       low, high, lambda ob, ac: O.rollout_costs(om, oc, ob, ac, mode=cost_mode), noise)
-    orc.beginning_of_rollout()
-    K, n_reuse = split.K, split.n_reuse
-    n_steps = 2
-    for s in range(n_steps):
-        obs = 0.1 * np.random.RandomState(100 + s).randn(o)
-        if s:
-            noise.begin_step()
-        want = orc.get_action(obs)
-        trace = orc.trace[-1]
-        seen = []
 
-        def on_iteration(it):
-            n_it = split.population_sizes[it]
-            n_extra = n_reuse if (it == 0 and s > 0) else 0
-            n_keep = n_reuse if it > 0 else 0
-            g = (s * iters + it) & 1  # elite buffer the merge of this iteration read (the previous set) ...
-            pool_costs = split.costs[:n_it + n_extra]
-            if n_keep:
-                pool_costs = torch.cat([pool_costs, split.elites_costs[g][:n_keep]])
-            seen.append(dict(costs=pool_costs.cpu().numpy().copy(),
-                             actions=np_(split.actions[:n_it + n_extra]),
-                             elites=np_(split.elites_actions[g ^ 1]), elite_costs=np_(split.elites_costs[g ^ 1]),
-                             mean=None if it == iters - 1 else np_(split.mean), std=None if it == iters - 1 else np_(split.std)))
-
-        got_split = np_(split.plan_step(obs, on_iteration=on_iteration)).copy()
-        got_fused = np_(fused.plan_step(obs)).copy()
-        kept_mag = np.zeros(0)
-        for it, (dev, ref) in enumerate(zip(seen, trace)):
-            tag = f"step {s} iteration {it}"
-            # the sampled pool (inverse DFT + affine + clip on the device's normals)
-            np.testing.assert_allclose(dev["actions"], ref.actions, rtol=RTOL, atol=ATOL, err_msg=tag)
-            # every trajectory cost, not only the elites': within 1e-5 of the magnitude of the sum it is (kept elites
-            # behind the simulated rows carry cost and magnitude over from the iteration that simulated them)
-            mag = np.concatenate([O.rollout_cost_magnitudes(om, oc, obs, ref.actions), kept_mag])
-            assert mag.shape == ref.costs.shape, tag
-            err = np.abs(dev["costs"].astype(np.float64) - ref.costs)
-            worst = int(np.argmax(err - RTOL_C * mag))
-            assert err[worst] <= RTOL_C * mag[worst], (tag, worst, err[worst], mag[worst], ref.costs[worst])
-            assert np.all(np.isfinite(dev["costs"])), tag
-            # ... and LITERALLY 1e-5 of |cost| wherever the sum does not cancel below half of what was added up
-            case = f"{env_kind} N={N}x{iters} d={d} o={o} kind={kind} {cost_mode} arith={split.tile_arith if o <= 48 else split.wide_arith}" + (" growing-model" if model_ab is not None else "")
-            row = _literal_record(tag, case, err, ref.costs, mag)
-            if row["buckets"][0]["max_err_over_cost"] is not None:
-                assert row["buckets"][0]["max_err_over_cost"] <= 2 * RTOL_C, (tag, row)
-            kept_mag = mag[ref.elite_idx[:n_reuse]]
-            # device top-K == sorted order of the device's own costs (ties by index), bit for bit ...
-            idx_dev = O.topk_sorted(dev["costs"], K)
-            assert np.array_equal(dev["elite_costs"], dev["costs"][idx_dev].astype(np.float64)), tag
-            # ... and the SAME elite index set as the float64 oracle's (north_star: elite index sets bit-exact); inside the
-            # set two elites may trade places only where their float64 costs agree to 1e-5
-            assert set(idx_dev.tolist()) == set(ref.elite_idx.tolist()), (tag, idx_dev, ref.elite_idx)
-            moved = idx_dev != ref.elite_idx
-            assert np.all(np.abs(ref.costs[idx_dev[moved]] - ref.costs[ref.elite_idx[moved]]) <= RTOL_C * mag[idx_dev[moved]]), tag
-            if it == iters - 1:
-                assert idx_dev[0] == ref.elite_idx[0], tag  # the executed action comes from the same trajectory
-            pool = dev["actions"]
-            sim = idx_dev < pool.shape[0]
-            assert np.array_equal(dev["elites"][sim], pool[idx_dev[sim]]), tag  # gathered rows, bit-exact
-            if dev["mean"] is not None:
-                np.testing.assert_allclose(dev["mean"], ref.mean, rtol=RTOL, atol=ATOL, err_msg=tag)
-                np.testing.assert_allclose(dev["std"], ref.std, rtol=RTOL, atol=ATOL, err_msg=tag)
-        np.testing.assert_allclose(got_split, want, rtol=RTOL, atol=ATOL)
-        np.testing.assert_allclose(np_(split.mean), orc.mean, rtol=RTOL, atol=ATOL)
-        np.testing.assert_allclose(np_(split.std), orc.std, rtol=RTOL, atol=ATOL)
-        assert abs(np_(split.best_cost)[0] - orc.last_min_cost) <= RTOL_C * mag[idx_dev[0]]
-        # the launches the benchmark times (merge prologues, ping-pong buffers) == the split run, bit for bit
-        assert np.array_equal(got_fused, got_split)
-        assert np.array_equal(np_(fused.mean), np_(split.mean)) and np.array_equal(np_(fused.std), np_(split.std))
-        ea_f, ec_f = fused.current_elites()
-        ea_s, ec_s = split.current_elites()
-        assert np.array_equal(np_(ea_f), np_(ea_s)) and np.array_equal(np_(ec_f), np_(ec_s))
-        n_last = split.population_sizes[-1]
-        assert np.array_equal(np_(fused.costs[:n_last]), np_(split.costs[:n_last]))
-        assert np.array_equal(np_(fused.actions[:n_last]), np_(split.actions[:n_last]))
+    def literal(tag, err, cost, mag, split):
+        # ... and LITERALLY 1e-5 of |cost| wherever the sum does not cancel below half of what was added up
+        case = f"{env_kind} N={N}x{iters} d={d} o={o} kind={kind} {cost_mode} arith={split.tile_arith if o <= 48 else split.wide_arith}" + (" growing-model" if model_ab is not None else "")
+        row = _literal_record(tag, case, err, cost, mag)
+        if row["buckets"][0]["max_err_over_cost"] is not None:
+            assert row["buckets"][0]["max_err_over_cost"] <= 2 * RTOL_C, (tag, row)
+    full_loop(mk, om, oc, N=N, iters=iters, h=h, o=o, beta=beta, cost_mode=cost_mode, low=env.action_space.low,
+              high=env.action_space.high, rtol=rtol, expect_arith=expect_arith, on_iter_record=literal)
 
 
 @pytest.mark.parametrize("exact", [0, 1, 2])   # icem_set_wide_exact: fp16 planes (default) / exact f32 / bf16 planes
