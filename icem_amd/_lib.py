@@ -139,7 +139,6 @@ SYMBOLS = [
     ("icem_profile_overhead", C.c_int, [_VP, _I32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icem_plan_step_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, _VP]),
     ("icem_batch_uploads", C.c_int64, [_H]),
-    ("icem_step_status", C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP]),
     ("icem_tile_growth", C.c_double, [_H]),
     ("icem_nonfinite_costs", C.c_int, [_H, C.POINTER(C.c_int64), _VP]),
     ("icem_set_option", C.c_int, [C.c_char_p, C.c_double]),
@@ -151,7 +150,7 @@ SYMBOLS = [
 
 IPC_HANDLE_BYTES = 64
 RCCL_ID_BYTES = 128
-ABI_VERSION = 5   # include/icem_hip.h: ICEM_ABI_VERSION
+ABI_VERSION = 6   # include/icem_hip.h: ICEM_ABI_VERSION
 
 
 def lib_path() -> str:

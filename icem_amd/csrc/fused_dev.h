@@ -1313,44 +1313,28 @@ __device__ __forceinline__ int keep_index0(const MergeSingleArgs& a) { return a.
 // Global sorted top-K of the candidate lists (+ kept elites): ONE wavefront; sel[0..K) receives the keys.
 // Lane t owns lists t, t+64, t+128, t+192 (each sorted) in registers; key r of list w sits at
 // part_k[r * n_lists + w], so every load is one contiguous 512 bytes.
-// KEPT_APART: the kept elites are offered as candidates of their own behind the lists' survivors instead of being
-// inserted into their lanes' first lists (a KREG-step compare-exchange chain, 0.56 us).  Measured per caller: the last
-// merge 6.52 -> 6.21 us and the one-tile single-launch kernel 10.07 -> 9.80 us with it, but the two- and four-tile
-// single-launch kernels +0.8 / +0.5 us per launch (N = 8192: 83.3 -> 87.7 us per MPC step) -- those keep the insertion.
-// COH: every load of another workgroup's data bypasses this CU's L1 (sc1: served by the L2) -- for callers INSIDE a launch whose
-// lists were written by other workgroups of the same launch (step_xcd_kernel); LISTS: lists per lane (64 x LISTS >= n_lists).
-template <bool COH, class T>
-__device__ __forceinline__ T ld_coh(const T* p) {
-    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <int KREG, bool KEPT_APART = false, bool COH = false, int LISTS = LPL>
+template <int KREG>
 __device__ __forceinline__ void merge_select(const MergeSingleArgs& a, int lane, unsigned long long* cand,
                                              unsigned long long* sel) {
-    unsigned long long k[LISTS][KREG];
+    unsigned long long k[LPL][KREG];
     // (the kept elite's cost comes from another buffer: requested first, consumed behind the lists)
-    const float keep_cost = a.elites_cost_cur ? ld_coh<COH>(a.elites_cost_cur + (lane < a.n_keep ? lane : 0)) : 0.f;
+    const float keep_cost = a.elites_cost_cur ? a.elites_cost_cur[lane < a.n_keep ? lane : 0] : 0.f;
 #pragma unroll
-    for (int l = 0; l < LISTS; ++l) {
+    for (int l = 0; l < LPL; ++l) {
         const int list = lane + l * 64;
 #pragma unroll
         for (int i = 0; i < KREG; ++i)
-            k[l][i] = ld_coh<COH>(a.part_k + (size_t)(i < a.K ? i : 0) * a.n_lists + (list < a.n_lists ? list : 0));
+            k[l][i] = a.part_k[(size_t)(i < a.K ? i : 0) * a.n_lists + (list < a.n_lists ? list : 0)];
     }
 #pragma unroll
-    for (int l = 0; l < LISTS; ++l) {
+    for (int l = 0; l < LPL; ++l) {
         const bool has_list = lane + l * 64 < a.n_lists;
 #pragma unroll
         for (int i = 0; i < KREG; ++i) k[l][i] = (has_list && i < a.K) ? k[l][i] : KEY_SENTINEL;
     }
     if (a.dbg && threadIdx.x == 0) a.dbg[1] = wall_clock64();
-    // kept elite `lane` (icem.py:143-145): joins this lane's first list, order preserved -- or (KEPT_APART) stays one
-    // more candidate of this lane, offered behind the lists' survivors (the threshold below then comes from the lists
-    // alone: still an upper bound of the K-th smallest key overall)
-    unsigned long long kept = KEY_SENTINEL;
-    if constexpr (KEPT_APART) {
-        kept = lane < a.n_keep ? make_key(keep_cost, keep_index0(a) + lane) : KEY_SENTINEL;
-    } else if (lane < a.n_keep) {
+    // kept elite `lane` (icem.py:143-145): joins this lane's first list by a KREG-step compare-exchange chain, order preserved
+    if (lane < a.n_keep) {
         unsigned long long v = make_key(keep_cost, keep_index0(a) + lane);
 #pragma unroll
         for (int i = 0; i < KREG; ++i) {
@@ -1368,37 +1352,28 @@ __device__ __forceinline__ void merge_select(const MergeSingleArgs& a, int lane,
     if (a.dbg && threadIdx.x == 0) a.dbg[2] = wall_clock64();
     unsigned long long mine = k[0][0];
 #pragma unroll
-    for (int l = 1; l < LISTS; ++l) mine = k[l][0] < mine ? k[l][0] : mine;
+    for (int l = 1; l < LPL; ++l) mine = k[l][0] < mine ? k[l][0] : mine;
     const unsigned srt = wave_sort64_u32((unsigned)(mine >> 32), lane);
     const unsigned T = __shfl(srt, a.K - 1, 64);
     unsigned n_cand = 0;  // wave-uniform
 #pragma unroll
     for (int i = 0; i < KREG; ++i) {
-        bool p[LISTS];
+        bool p[LPL];
         bool any_lane = false;
 #pragma unroll
-        for (int l = 0; l < LISTS; ++l) {
+        for (int l = 0; l < LPL; ++l) {
             p[l] = (unsigned)(k[l][i] >> 32) <= T && k[l][i] != KEY_SENTINEL;
             any_lane |= p[l];
         }
         if (__ballot(any_lane) == 0) break;
 #pragma unroll
-        for (int l = 0; l < LISTS; ++l) {
+        for (int l = 0; l < LPL; ++l) {
             const unsigned long long m = __ballot(p[l]);
             if (m != 0) {
                 const unsigned pos = n_cand + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
                 if (p[l] && pos < 64) cand[pos] = k[l][i];
                 n_cand += (unsigned)__popcll(m);
             }
-        }
-    }
-    if constexpr (KEPT_APART) {   // the kept elites at or below the threshold
-        const bool p = (unsigned)(kept >> 32) <= T && kept != KEY_SENTINEL;
-        const unsigned long long m = __ballot(p);
-        if (m != 0) {
-            const unsigned pos = n_cand + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (p && pos < 64) cand[pos] = kept;
-            n_cand += (unsigned)__popcll(m);
         }
     }
     if (a.dbg && threadIdx.x == 0) a.dbg[3] = wall_clock64();
@@ -1408,19 +1383,15 @@ __device__ __forceinline__ void merge_select(const MergeSingleArgs& a, int lane,
         key = wave_sort_n(key, lane, n_cand);
         if (lane < a.K) sel[lane] = key;
     } else {
-        // more than 64 keys tie at or below T: K tournament rounds over the list heads (and the kept elites)
+        // more than 64 keys tie at or below T: K tournament rounds over the list heads
         for (int r = 0; r < a.K; ++r) {
             unsigned long long head = k[0][0];
 #pragma unroll
-            for (int l = 1; l < LISTS; ++l) head = k[l][0] < head ? k[l][0] : head;
-            if constexpr (KEPT_APART) head = kept < head ? kept : head;
+            for (int l = 1; l < LPL; ++l) head = k[l][0] < head ? k[l][0] : head;
             const unsigned long long best = wave_min_u64(head);
             if (best != KEY_SENTINEL) {  // keys embed the trajectory index: exactly one (lane, list) matches
-                if constexpr (KEPT_APART) {
-                    if (kept == best) kept = KEY_SENTINEL;
-                }
 #pragma unroll
-                for (int l = 0; l < LISTS; ++l) {
+                for (int l = 0; l < LPL; ++l) {
                     if (k[l][0] == best) {
 #pragma unroll
                         for (int i = 0; i + 1 < KREG; ++i) k[l][i] = k[l][i + 1];

@@ -43,9 +43,6 @@ constexpr int LDS_CHUNKS = 10;       // chunks parked in LDS (one tile per workg
 // round trips long (3.7 us of a 5.3 us step); spread two by two between the resident ones, over all four phases, a
 // request is a quarter of a step ahead of its use (EXPERIMENTS R4.11: six placements measured).
 enum { REG = 0, STR = 1, LDS = 2 };
-#ifndef ICEM_RSSM_PLAN
-#define ICEM_RSSM_PLAN 0   // (development: other placements, measured in EXPERIMENTS R4.11)
-#endif
 // element offset of chunk c of the class-A wave that owns GRU / W4 blocks ob0 and ob1 (the order the wave consumes them in)
 __host__ __device__ constexpr size_t class_a_chunk(int c, int ob0, int ob1) {
     return c < 3 ? WGH + (size_t)(c * DETB + ob0) * DETK * BLK
@@ -57,24 +54,13 @@ __host__ __device__ constexpr size_t class_a_chunk(int c, int ob0, int ob1) {
 template <bool CLASS_A, int TT>
 struct ChunkPlan {
     static constexpr int NCH = CLASS_A ? 14 : 7;
-    static constexpr int RING = TT == 1 ? (CLASS_A ? (ICEM_RSSM_PLAN >= 1 && ICEM_RSSM_PLAN <= 3 ? 3 : 2) : 0) : (CLASS_A ? RING_A2 : RING_B2);
+    static constexpr int RING = TT == 1 ? (CLASS_A ? 2 : 0) : (CLASS_A ? RING_A2 : RING_B2);
     static constexpr int kind(int c) {
         if (TT == 1) {
             if (!CLASS_A) return REG;
             // H(w) r u n | H(w+8) r u n | I(w) r u n | I(w+8) r u n | W4(w) W4(w+8)   (class_a_chunk)
-#if ICEM_RSSM_PLAN == 1     // three ring slots, the two LDS chunks where the first form stalled
-            return c == 4 || c == 7 ? LDS : c == 2 || c == 5 || c == 8 ? REG : STR;
-#elif ICEM_RSSM_PLAN == 2   // three ring slots, every gate's n chunk resident
-            return c == 11 || c == 13 ? LDS : c == 2 || c == 5 || c == 8 ? REG : STR;
-#elif ICEM_RSSM_PLAN == 3
-            return c == 4 || c == 10 ? LDS : c == 2 || c == 7 || c == 12 ? REG : STR;
-#elif ICEM_RSSM_PLAN == 4   // two ring slots, the streamed pairs a quarter of a step apart
-            return c == 8 || c == 11 ? LDS : c == 2 || c == 3 || c == 6 || c == 7 ? REG : STR;
-#elif ICEM_RSSM_PLAN == 5
-            return c == 10 || c == 11 ? LDS : c == 2 || c == 3 || c == 6 || c == 7 ? REG : STR;
-#else                       // two ring slots: four chunks in registers, eight streamed
+            // two ring slots: four chunks in registers, eight streamed
             return c == 11 || c == 13 ? LDS : c == 2 || c == 5 || c == 8 || c == 12 ? REG : STR;
-#endif
         }
         return c < (CLASS_A ? RES_A2 : RES_B2) ? REG : STR;
     }
@@ -479,10 +465,6 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, int wg, int tiles
         if (k < 32) s.zA[e] = to_bf16(k < STOCH ? s.ob[DET + k] : 0.f);
         else if (k >= 32 + ACT) s.zA[e] = 0;
     }
-#ifdef ICEM_RSSM_ROT   // (development: the class-A waves' blocks rotated per workgroup -- do CUs in lockstep on the same lines cost?)
-    if (w < 5) recurrence_steps<true, TT>(s, __builtin_amdgcn_readfirstlane((w + wg) % 5), lane, base, n, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
-    else
-#endif
     if (w < 5) recurrence_steps<true, TT>(s, w, lane, base, n, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
     else recurrence_steps<false, TT>(s, w, lane, base, n, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
 }

@@ -32,8 +32,8 @@ def test_header_symbols_all_exported(lib):
         assert hasattr(lib, name)
 
 
-def test_abi_version_and_error_string(lib):
-    assert lib.icem_abi_version() == L.ABI_VERSION == 5
+def test_abi_version_6_and_error_string(lib):
+    assert lib.icem_abi_version() == L.ABI_VERSION == 6
     assert isinstance(lib.icem_last_error(), bytes)
 
 

@@ -26,11 +26,6 @@ ALLOWED = [
      "4096 rows): the text of iter_ahead_kernel (iter_ahead_body.h) with the block's scalars held across the roles -- 9-23 "
      "spills on 128 registers, the same class as the by-value kernel's, and the batch is faster with it than on the "
      "single-launch kernels (EXPERIMENTS R6.3)"),
-    (r"step_xcd_kernel<\d+, \d+, \d+, [01], [01]>", 56,
-     "the one-launch step inside one XCD (option step_xcd = 1, OFF by default): 9-50 spills around the raw-noise vectors it keeps "
-     "in registers across the merge -- and not what decides it: eight rollout waves on one CU are pipe-bound at 6.6 us per "
-     "iteration against 3.9 for a lone wave per CU; it measured 87 against 61 us per MPC step and is not the shipped path "
-     "(EXPERIMENTS R6.4)"),
     (r"iter_ahead_kernel<30, 6, 17, [01], [48], [012], 1>", 16,
      "the fp16-plane tile (Tile16H: two operand planes of the model and of the state) on the 128 registers of the noise-ahead "
      "launch: 9-14 spills, at the staging points every ten steps -- and the launch wins by 11-14 %: 140.8 vs 157.2 us per MPC "

@@ -20,9 +20,8 @@ __global__ __launch_bounds__(64) void select_kernel(MergeSingleArgs a, unsigned 
     sel[lane] = 0ull;
     __syncthreads();
     if (WHICH == 0) merge_select<12>(a, lane, cand, sel);
-    if (WHICH == 1) merge_select<12, true>(a, lane, cand, sel);
-    if (WHICH == 2) merge_select_stream(a, lane, cand, sel);
-    if (WHICH == 3) merge_select_shallow<3>(a, lane, cand, sel);
+    if (WHICH == 1) merge_select_stream(a, lane, cand, sel);
+    if (WHICH == 2) merge_select_shallow<3>(a, lane, cand, sel);
     __syncthreads();
     if (lane < a.K) out[lane] = sel[lane];
 }
@@ -101,12 +100,11 @@ int main() {
         a.d = 6;
         a.part_k = d_part;
         a.elites_cost_cur = d_keep;
-        for (int which = 0; which < 4; ++which) {
+        for (int which = 0; which < 3; ++which) {
             (void)hipMemset(d_out, 0, 64 * 8);
             if (which == 0) select_kernel<0><<<1, 64>>>(a, d_out);
             if (which == 1) select_kernel<1><<<1, 64>>>(a, d_out);
             if (which == 2) select_kernel<2><<<1, 64>>>(a, d_out);
-            if (which == 3) select_kernel<3><<<1, 64>>>(a, d_out);
             unsigned long long got[64];
             if (hipDeviceSynchronize() != hipSuccess) { printf("launch failed\n"); return 2; }
             (void)hipMemcpy(got, d_out, sizeof(got), hipMemcpyDeviceToHost);

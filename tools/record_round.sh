@@ -76,9 +76,6 @@ for w in door relocate fpp; do timeout 300 python bench.py --full --workload $w 
   timeout 200 python tools/dbg/ahead_stamps.py 65536 2>&1 | grep -v amdgpu.ids
   echo "# round 6: tools/dbg/sharded_stamps.py 8 4096 (one sharded launch itemised, records ranked by the whole workgroup)"
   timeout 120 python tools/dbg/sharded_stamps.py 8 4096 2>&1 | grep -v amdgpu.ids
-  echo "# round 6: tools/dbg/xcd_stamps.py / xcd_step_check.py (the one-launch step inside one XCD, option step_xcd = 1: stamps, bit-equality, time)"
-  timeout 120 python tools/dbg/xcd_stamps.py 4096 5 2>&1 | grep -v amdgpu.ids
-  timeout 300 python tools/dbg/xcd_step_check.py 2>&1 | grep -v amdgpu.ids | tail -6
   echo "# round 6: tools/ubench/xcd_barrier (a 32-arrival barrier inside one XCD)"
   (cd tools/ubench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o xcd_barrier xcd_barrier.hip 2> /dev/null; timeout 120 ./xcd_barrier)
   echo "# round 6: tools/dbg/batch_host_time.py (icem_plan_step_batch: host enqueue time against the step's GPU time)"
