@@ -398,7 +398,7 @@ static int sync_wide_cost(icem_handle* h);
 int icem_set_tile_arith(icem_handle* h, int32_t mode) {
     if (check_handle(h)) return ICEM_E_INVALID;
     if (mode < -1 || mode > 1) return fail(ICEM_E_INVALID, "tile arithmetic: -1 (by configuration), 0 (exact f32) or 1 (fp16 planes)");
-    if (h->pm_pending || h->pk_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending || h->ride.pack_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     h->tile_arith_mode = mode;
     update_paths(h);
     h->ahead.next_valid = h->ahead.pre_valid = false;   // (noise drawn ahead for the other launch shapes is redrawn)
@@ -726,7 +726,7 @@ int icem_set_wide_arith(icem_handle* h, int32_t mode) {
     if (check_handle(h)) return ICEM_E_INVALID;
     if (mode < ICEM_WIDE_AUTO || mode > ICEM_WIDE_BF16X3)
         return fail(ICEM_E_INVALID, "wide arithmetic: ICEM_WIDE_AUTO (-1), ICEM_WIDE_F16X2 (0), ICEM_WIDE_F32 (1) or ICEM_WIDE_BF16X3 (2)");
-    if (h->pm_pending || h->pk_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending || h->ride.pack_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     h->wide_mode = mode;
     update_paths(h);
     return ICEM_OK;

@@ -129,7 +129,7 @@ int icem_rccl_unique_id(void* id_out_host) {
 int icem_rccl_connect(icem_handle* h, const void* id_host) {
     if (check_handle(h)) return ICEM_E_INVALID;
     if (!id_host) return fail(ICEM_E_INVALID, "null id");
-    if (h->pm_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     int rc = rccl_bind(nullptr);
     if (rc) return rc;
     rccl_release(h);
@@ -160,7 +160,7 @@ int icem_rccl_adopt(icem_handle* h, void* nccl_comm) {
 
 int icem_rccl_disconnect(icem_handle* h) {
     if (check_handle(h)) return ICEM_E_INVALID;
-    if (h->pm_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     rccl_release(h);
     return ICEM_OK;
 }

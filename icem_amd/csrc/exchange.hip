@@ -313,7 +313,7 @@ int icem_exchange_create(icem_handle* h, void* ipc_out_host) {
 
 int icem_exchange_disable(icem_handle* h) {
     if (check_handle(h)) return ICEM_E_INVALID;
-    if (h->pm_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     xchg_destroy(h);
     return ICEM_OK;
 }

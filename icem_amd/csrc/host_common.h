@@ -74,19 +74,31 @@ struct icem_handle {
     };
     bool use_fast = true;
     long long* dbg = nullptr;
-    int fast_lists = 0;  // candidate lists written by the last matrix-pipe rollout (0 = generic path ran)
-    int fast_tail_rows = 0;  // ... and shifted-elite rows behind them that the merge scores through the cost array
+    // what the local launch of an iteration tells its merge (icem_plan_iter_local and icem_plan_iter_merge are separate calls)
+    struct LocalReport {
+        int lists = 0;      // candidate lists written by the last matrix-pipe rollout (0 = generic path ran)
+        int tail_rows = 0;  // ... and shifted-elite rows behind them that the merge scores through the cost array
+        // generic path, world == 1: the iteration's selection waits for the merge call (gk_select_refit: one launch for top-K +
+        // gather + refit); sel_cand > 0 = rows with a cost in b->costs, sel_loc of them sampled rows
+        int sel_cand = 0, sel_loc = 0;
+        void clear() { *this = LocalReport(); }
+    } local;
     // icem_plan_step (world == 1): an iteration's merge can ride in the prologue of the next iteration's launch,
     // which then reads the previous pool / lists / distribution while writing new ones -> ping-pong partners of
     // the caller's actions / workspace buffers and of mean | std, owned by the handle
     void* actions_alt = nullptr;
     void* ws_alt = nullptr;
     float* pp_stats = nullptr;          // [2][2 * hd]
-    bool defer_merge = false;           // plan_iter_merge: stash the merge instead of launching it
-    bool pm_pending = false;            // a stashed merge waits for the next local launch
-    icem::MergeSingleArgs pm_args;
-    float* merge_mean_out = nullptr;    // where the next merge writes mean / std (nullptr: in place)
-    float* merge_std_out = nullptr;
+    // what rides into the next launch
+    struct Riding {
+        bool merge_pending = false;     // a stashed merge waits for the next local launch
+        icem::MergeSingleArgs merge;
+        // sharded runs with merge deferral: an iteration's record pack + push can ride in the NEXT local launch too
+        // (workgroup 0 of sample_rollout_kernel) instead of being a launch of its own
+        bool pack_pending = false;
+        icem::PackPrev pack;
+        void clear() { merge_pending = pack_pending = false; }
+    } ride;
     // world > 1 with icem_set_merge_deferral(on): the same folding across the split calls; the distribution of the
     // running MPC step lives at cur_mean / cur_std (the caller's buffers or pp_stats)
     bool deferral = false;
@@ -126,9 +138,6 @@ struct icem_handle {
     int wide_mode = -1;          // icem_set_wide_arith: ICEM_WIDE_AUTO (-1) / F16X2 (0) / F32 (1) / BF16X3 (2) as asked for ...
     int wide_eff = 0;            // ... and the one in effect (update_paths: AUTO = fp16 planes unless the balanced model is not)
     int wide_imbalance = 0;      // wide_model_imbalance_log2 of the current model
-    // generic path, world == 1: the iteration's selection waits for the merge call (gk_select_refit: one launch for top-K +
-    // gather + refit); gen_sel_cand > 0 = rows with a cost in b->costs, gen_sel_loc of them sampled rows
-    int gen_sel_cand = 0, gen_sel_loc = 0;
     int wide_packed = -2;        // which arithmetic Mw_dev / Mwh_dev / Mws_dev currently hold the model for (-2: none)
                                  // (k_rollout_wide.hip + its row kernel), 2 = bf16 planes (6 products)
     void* wide_cs_dev = nullptr; // CostArgs<float> (cost spec + terms) for k_rollout_wide, refreshed by the cost setters
@@ -142,10 +151,6 @@ struct icem_handle {
     icem::Exchange* xchg = nullptr;  // in-library elite exchange (icem_exchange_*), world > 1
     icem::XchgWait xw_last;          // ... and what the merge of the running iteration waits for (set by the push)
     uint64_t episode = 0;            // folded into the noise stream offset (icem_set_episode)
-    // sharded runs with merge deferral: an iteration's record pack + push can ride in the NEXT local launch too
-    // (workgroup 0 of sample_rollout_kernel) instead of being a launch of its own
-    bool pk_pending = false;
-    icem::PackPrev pk_args;
     float* pub_dev = nullptr;        // published merge (PackPrev::pub): [2 * hd] floats, then the flag word
     unsigned pub_seq = 0;
     // noise-ahead pipeline (plan.hip::plan_step_ahead; world == 1, large populations): every iteration's launch

@@ -309,16 +309,18 @@ constexpr int ICEM_MAX_BATCH = 32;
 struct BatchBases {          // by value in the kernel-argument segment: the noise stream offset of this MPC step per problem
     unsigned long long v[ICEM_MAX_BATCH];   // (the offsets in the argument blocks are stored RELATIVE to it: the blocks of a
 };                                          //  steady-state step are the previous same-parity step's, and are not uploaded again)
+// which launcher recorded a BatchRecord (host side only: the batched kernels never see it)
+enum BatchKind : int { BATCH_NONE = 0, BATCH_SAMPLE_ROLLOUT = 1, BATCH_MERGE_SINGLE = 2, BATCH_MERGE_NOISE = 3, BATCH_ITER_AHEAD = 4 };
 struct BatchRecord {
-    int kind = 0;            // 1 sample_rollout, 2 merge_single, 3 merge_noise, 4 iter_ahead (rw = waves per workgroup, grid = rollout workgroups)
-    // kind 1
+    BatchKind kind = BATCH_NONE;   // (iter_ahead: rw = waves per workgroup, grid = rollout workgroups)
+    // BATCH_SAMPLE_ROLLOUT
     FastIterArgs it;
     int h = 0, d = 0, O = 0, model_kind = 0, rw = 0, grid = 0;
     bool prologue = false;
-    // kinds 2, 3
+    // BATCH_MERGE_SINGLE, BATCH_MERGE_NOISE
     MergeSingleArgs m;
     FastSampleArgs z1, z2;
-    // kind 4
+    // BATCH_ITER_AHEAD
     IterAheadArgs ia;
 };
 struct BatchState {

@@ -458,7 +458,7 @@ void launch_sample_rollout(const FastIterArgs& a, int h, int d, int O, int kind,
             return;
         }
         BatchRecord r;
-        r.kind = 1;
+        r.kind = BATCH_SAMPLE_ROLLOUT;
         r.it = a;
         r.h = h, r.d = d, r.O = O, r.model_kind = kind, r.rw = rw, r.grid = grid;
         r.prologue = merge_prologue;

@@ -306,7 +306,7 @@ bool merge_noise_ok(const MergeSingleArgs& a, int rounds) {
 void launch_merge_noise(const MergeSingleArgs& a, const FastSampleArgs& z, const FastSampleArgs& z2, hipStream_t st) {
     if (g_batch.rec) {   // icem_plan_step_batch: recorded, launched for all problems at once (launch_merge_batch)
         BatchRecord r;
-        r.kind = 3;
+        r.kind = BATCH_MERGE_NOISE;
         r.m = a;
         r.z1 = z;
         r.z2 = z2;
@@ -326,17 +326,17 @@ void launch_merge_noise(const MergeSingleArgs& a, const FastSampleArgs& z, const
 #undef X
 }
 
-// n problems' last merges (+ the next step's first noise, kind 3) in one launch; the lists form with K <= 11 only
+// n problems' last merges (+ the next step's first noise, BATCH_MERGE_NOISE) in one launch; the lists form with K <= 11 only
 void launch_merge_batch(const BatchRecord& s, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
     const MergeSingleArgs& a = s.m;
     int wgs1 = 0, wgs2 = 0, tpw = 1;
-    if (s.kind == 3) {
+    if (s.kind == BATCH_MERGE_NOISE) {
         tpw = MERGE_WG / s.z1.d;
         wgs1 = (s.z1.n + tpw - 1) / tpw;
         wgs2 = s.z2.n > 0 ? (s.z2.n + tpw - 1) / tpw : 0;
     }
     const dim3 grid(1 + wgs1 + wgs2, n);
-    const size_t lds = std::max((size_t)a.h * a.d, s.kind == 3 ? (size_t)tpw * s.z1.h * s.z1.d : (size_t)0) * sizeof(float);
+    const size_t lds = std::max((size_t)a.h * a.d, s.kind == BATCH_MERGE_NOISE ? (size_t)tpw * s.z1.h * s.z1.d : (size_t)0) * sizeof(float);
 #define X(HH)                                                                                                              \
     if (a.h == HH) {                                                                                                       \
         hipLaunchKernelGGL((merge_noise_batch_kernel<HH, 12>), grid, dim3(MERGE_WG), lds, st, args_dev, bases, wgs1);      \
@@ -353,7 +353,7 @@ void launch_merge_single(const MergeSingleArgs& a, hipStream_t st) {
             return;
         }
         BatchRecord r;
-        r.kind = 2;
+        r.kind = BATCH_MERGE_SINGLE;
         r.m = a;
         g_batch.rec->push_back(r);
         return;

@@ -128,7 +128,7 @@ void launch_iter_ahead(const IterAheadArgs& a_in, int h, int d, int O, int kind,
             return;
         }
         BatchRecord r;
-        r.kind = 4;
+        r.kind = BATCH_ITER_AHEAD;
         a.n_noise = a.z.n > 0 ? (a.z.n + (64 * waves) / d - 1) / ((64 * waves) / d) : 0;   // (AheadLds::TPW = threads / d)
         r.ia = a;
         r.h = h, r.d = d, r.O = O, r.model_kind = kind, r.rw = waves, r.grid = grid;

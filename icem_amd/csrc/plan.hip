@@ -352,379 +352,79 @@ bool prologue_possible(const icem_handle* h, int n_rows) {
     return sample_folded_merge_ok(c.horizon, c.act_dim, c.rng_rounds, K);
 }
 
-// a stashed merge that found no launch to ride in
-int launch_pending_merge(icem_handle* h, hipStream_t st) {
-    if (g_batch.rec) {
-        g_batch.unsupported = true;
-        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a merge found no launch to ride in");
-    }
-    const MergeSingleArgs& m = h->pm_args;
-    if (m.records == nullptr) {
-        ProfScope prof(h, ICEM_K_MERGE_REFIT, m.n_lists * m.K + m.n_keep, st);
-        launch_merge_single(m, st);
-    } else {
-        MergeArgsV a{};
-        a.n_rec = m.n_rec;
-        a.n_keep = m.n_keep;
-        a.K = m.K;
-        a.h = m.h;
-        a.d = m.d;
-        a.n_global = m.n_global;
-        a.last = 0;
-        a.alpha = m.alpha;
-        a.init_std = m.init_std;
-        a.records = m.records;
-        a.elites_cur = m.elites_cur;
-        a.elites_cost_cur = m.elites_cost_cur;
-        a.elites_next = m.elites_next;
-        a.elites_cost_next = m.elites_cost_next;
-        a.mean_in = m.mean;
-        a.std_in = m.std;
-        a.mean = m.mean_out;
-        a.std = m.std_out;
-        a.low = m.low;
-        a.high = m.high;
-        a.executed = m.executed;
-        a.best_cost = m.best_cost;
-        a.xw = m.xw;
-        return gk_merge_refit(h, a, st);
-    }
-    ICEM_HIP_TRY(hipGetLastError());
-    return ICEM_OK;
+// ---- rules that every path of a step must agree on, each written once ---------------------------------------------------
+
+// Noise stream offset of an MPC step's sampling calls: episode in the high word (icem_set_episode; the reference's
+// np.random stream runs on across episodes, icem.py:73), sampling call number of the episode in the low one --
+// iteration `it` draws at call_base + it, the shifted elites at call_base + opt_iters.
+static uint64_t call_base(const icem_handle* h, int mpc_step) {
+    return (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(h->cfg.opt_iters + 1);
 }
 
-// will the merge-prologue launch of an iteration with n_rows local rows take the previous iteration's pack along?
-static bool next_launch_takes_pack(const icem_handle* h, int n_rows) {
-    const icem_config& c = h->cfg;
-    if (one_launch_lists(h, n_rows) > 0)
-        return sample_rollout_pack_ok(c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, c.num_elites);
-    return sample_folded_pack_ok(c.horizon, c.act_dim, c.rng_rounds, c.num_elites);
+// shifted elites, simulated at iteration 0 of every MPC step but the first (icem.py:131-137): rows behind the sampled ones.
+// (icem_create does not refuse a negative fraction_reused, which makes n_reuse negative: the launches then build no such
+// rows, while the lists merge's pool size and the batch's dry run have always taken the count as it is -- at_least_0 = false.)
+static int shift_rows(const icem_handle* h, int mpc_step, int it, bool at_least_0 = true) {
+    if (it != 0 || !h->cfg.shift_elites || mpc_step <= 0) return 0;
+    return at_least_0 ? std::max(0, h->n_reuse) : h->n_reuse;
 }
 
-// a stashed pack that found no launch to ride in
-int launch_pending_pack(icem_handle* h, hipStream_t st) {
-    const PackPrev& pp = h->pk_args;
-    MergeSingleArgs pk{};
-    pk.n_lists = pp.n_lists;
-    pk.n_pool = pp.n_pool;
-    pk.n_global = pp.n_global;
-    pk.K = pp.K;
-    pk.h = h->cfg.horizon;
-    pk.d = h->cfg.act_dim;
-    pk.part_k = pp.part_k;
-    pk.actions = pp.actions;
-    pk.n_keep = pp.n_keep;
-    pk.elites_cost_cur = pp.keep_costs;
-    pk.keep_base = pp.n_loc;
-    {
-        ProfScope prof(h, ICEM_K_LOCAL_PACK, pp.n_lists * pp.K, st);
-        launch_pack_records(pk, pp.n_loc, pp.shard_lo, pp.records, st, pp.px);
-    }
-    ICEM_HIP_TRY(hipGetLastError());
-    h->pk_pending = false;
-    return ICEM_OK;
-}
+// which of the two elite buffers iteration `it` of step `mpc_step` reads (it writes the other): the global iteration's parity
+static int elite_parity(const icem_handle* h, int mpc_step, int it) { return (int)(((long long)mpc_step * h->cfg.opt_iters + it) & 1); }
 
-// rows of this rank's shard at iteration `it`
-static int local_rows(const icem_handle* h, int it) {
+// this rank's shard of iteration `it`: rows [lo, lo + n_loc) of the population (world 1: all of it)
+struct Shard {
+    int lo, n_loc;
+};
+static Shard shard_of(const icem_handle* h, int it) {
     const int n_global = h->pop[it];
     const int chunk = shard_chunk(n_global, h->cfg.world);
     const int lo = std::min(n_global, h->cfg.rank * chunk);
-    return std::max(0, std::min(n_global - lo, chunk));
+    return {lo, std::max(0, std::min(n_global - lo, chunk))};
 }
 
-template <typename T>
-int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st) {
-    const icem_config& c = h->cfg;
-    const int hd = h->hd, K = c.num_elites;
-    const int n_global = h->pop[it];
-    const int chunk = shard_chunk(n_global, c.world);
-    const int lo = std::min(n_global, c.rank * chunk);
-    const int n_loc = std::max(0, std::min(n_global - lo, chunk));
-    // noise stream offset of this call: episode in the high word (icem_set_episode; the reference's np.random stream
-    // runs on across episodes, icem.py:73), sampling call number of the episode in the low one
-    const uint64_t call_base = (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(c.opt_iters + 1);
-    const bool last = it == c.opt_iters - 1;
-    T* actions = (T*)b->actions;
-    // shifted elites, simulated at iteration 0 of every MPC step but the first (icem.py:131-137)
-    int n_extra = 0;
-    const T* shift_src = nullptr;
-    bool shift_in_sampler = false;
-    if (it == 0 && c.shift_elites && mpc_step > 0 && h->n_reuse > 0) {
-        n_extra = h->n_reuse;
-        const int g = (int)(((long long)mpc_step * c.opt_iters) & 1);  // elite buffer holding the previous step's set
-        shift_src = (const T*)b->elites + (size_t)g * K * hd;
-        // the fast sampler prepares them in an extra workgroup of its own launch
-        shift_in_sampler = std::is_same<T, float>::value && b->z_r == nullptr && b->z_r_shift == nullptr &&
-                           fast_rollout_ok(h, K) && fast_sample_ok(h) &&
-                           n_extra * c.act_dim <= 256;
-        if (!shift_in_sampler) {
-            T* dst = actions + (size_t)n_loc * hd;
-            int rc = gk_shift_elites(h, n_extra, shift_src, dst, st);
-            if (rc) return rc;
-            rc = gk_sample(h, n_extra, 0, b->mean, b->std, b->low, b->high, b->z_r_shift, b->z_i_shift,
-                           call_base + (uint64_t)c.opt_iters, c.horizon - 1, 0, dst, st);
-            if (rc) return rc;
-        }
-    }
-    // candidates: the shard, plus the shifted elites on rank 0 only (they are replicated)
-    const int n_cand = n_loc + (c.rank == 0 ? n_extra : 0);
-    const int row0 = (last && c.use_mean_actions) ? 1 : 0;
-    T* rec = (T*)b->records + (size_t)c.rank * K * (hd + 2);
-    h->fast_lists = 0;
-    h->gen_sel_cand = 0;
-    if constexpr (std::is_same<T, float>::value) {
-        if (fast_rollout_ok(h, K)) {
-            // f32 throughput path.  External white noise (b->z_r: the reference's own draws, tests/golden) takes it too: the
-            // generic sampler turns the caller's z into the pool (it is the only kernel that reads z), and from there on the
-            // tile rollout, the lists and the threshold merges are the ones device noise gets -- the reference's draws reach
-            // Tile16 / Tile16H and merge_select*, not only the generic kernels.
-            const bool ext_z = b->z_r != nullptr;
-            const uint64_t off = call_base + (uint64_t)it;
-            int rc = ensure_fast_model(h);
-            if (rc) return rc;
-            int lists = 0;
-            float* pc;
-            int* pi;
-            const int n_rows = n_loc + n_extra;
-            int tail_rows = 0;  // shifted-elite rows scored through the cost array instead of a list (world 1 only)
-            const int one = (!ext_z && fast_sample_ok(h) && (n_extra == 0 || shift_in_sampler))
-                                ? one_launch_lists(h, n_rows, shift_in_sampler ? n_extra : 0, &tail_rows) : 0;
-            h->fast_tail_rows = one > 0 ? tail_rows : 0;
-            // the merge finds the lists' indices behind `lists * K` costs
-            split_partial_ws<float>(b->workspace, one > 0 ? one : rollout_lists(c.horizon, c.act_dim, h->Of, n_rows), K, &pc, &pi);
-            bool prologue = false, ride = false;
-            if (h->pm_pending) {
-                prologue = !ext_z && n_extra == 0 && prologue_possible(h, n_rows);
-                // a stashed pack rides with the merge whose records it produces, or runs now -- in front of that merge
-                ride = prologue && h->pk_pending && next_launch_takes_pack(h, n_rows);
-                if (h->pk_pending && !ride) {
-                    rc = launch_pending_pack(h, st);
-                    if (rc) return rc;
-                }
-                if (!prologue) {  // cannot ride along after all: run it now
-                    rc = launch_pending_merge(h, st);
-                    if (rc) return rc;
-                }
-                h->pm_pending = false;
-            } else if (h->pk_pending) {
-                rc = launch_pending_pack(h, st);
-                if (rc) return rc;
-            }
-            h->pk_pending = false;
-            if (one > 0) {
-                // small populations: sample + rollout + top-K in one launch
-                FastIterArgs fa = zeroed_args<FastIterArgs>();
-                fa.m.keep_base = -1;
-                if (prologue) fa.m = h->pm_args;
-                if (ride) fa.p = h->pk_args;
-                fa.s = fast_sample_args(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions,
-                                        shift_in_sampler ? n_extra : 0, shift_src, call_base + (uint64_t)c.opt_iters);
-                if (it == 0 && c.world == 1 && h->ahead.pre_valid) {
-                    // this step's first noise (and the shifted elites') was drawn beside the previous step's last merge -- on
-                    // pre_stream: a step enqueued on another stream is not ordered behind that launch and redraws instead
-                    if (h->ahead.pre_episode == h->episode && h->ahead.pre_step == mpc_step && h->ahead.pre_stream == st) fa.s.raw_src = (const float*)h->ahead.pre_raw;
-                    h->ahead.pre_valid = false;
-                }
-                fa.r = fast_rollout_args(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi);
-                fa.r.part_k = (unsigned long long*)b->workspace;  // read by merge_single_kernel / pack_records_kernel
-                fa.r.list_wgs = tail_rows > 0 ? one : 0;
-                {
-                    ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n_rows * c.horizon, st);
-                    launch_sample_rollout(fa, c.horizon, c.act_dim, h->Of, h->model_kind, prologue, st);
-                }
-                ICEM_HIP_TRY(hipGetLastError());
-                lists = one;
-            }
-            if (one == 0) {
-                if (prologue) {
-                    FastSampleMergeArgs sm;
-                    sm.s = fast_sample_args(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, 0, nullptr, 0);
-                    sm.m = h->pm_args;
-                    if (ride) {
-                        sm.p = h->pk_args;
-                        // published merge: workgroup 0 merges the records once and publishes mean | std to the rest
-                        const int pub_on = opt_i(OPT_PUBLISHED_MERGE);
-                        if (pub_on && sm.m.records) {
-                            if (!h->pub_dev) {
-                                ICEM_HIP_TRY(hipMalloc((void**)&h->pub_dev, ((size_t)2 * hd + 16) * sizeof(float)));
-                                ICEM_HIP_TRY(hipMemsetAsync(h->pub_dev, 0, ((size_t)2 * hd + 16) * sizeof(float), st));
-                            }
-                            sm.p.pub = h->pub_dev;
-                            sm.p.pub_flag = reinterpret_cast<unsigned*>(h->pub_dev + 2 * hd);
-                            sm.p.pub_seq = ++h->pub_seq;
-                        }
-                    }
-                    {
-                        ProfScope prof(h, ICEM_K_SAMPLE, (long long)n_loc * c.horizon, st);
-                        launch_sample_folded_merge(sm, st);
-                    }
-                    ICEM_HIP_TRY(hipGetLastError());
-                    rc = ICEM_OK;
-                } else if (ext_z) {
-                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, off, 0, row0, actions, st);
-                } else if (fast_sample_ok(h)) {
-                    rc = launch_fast_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, st,
-                                            shift_in_sampler ? n_extra : 0, shift_src, call_base + (uint64_t)c.opt_iters);
-                } else {
-                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, nullptr, nullptr, off, 0, row0, actions, st);
-                }
-                if (rc) return rc;
-                int tail2 = 0;
-                rc = launch_fast_rollout(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi, st, &lists,
-                                         (unsigned long long*)b->workspace, (c.world == 1 && it == 0) ? n_extra : 0, &tail2);
-                if (rc) return rc;
-                h->fast_tail_rows = tail2;
-            }
-            h->fast_lists = lists;
-            if (c.world > 1) {
-                // this rank's K best -> records for the all-gather (same selection code as the merge)
-                MergeSingleArgs pk{};
-                pk.n_lists = lists;
-                pk.n_keep = 0;
-                pk.n_pool = n_rows;
-                pk.n_global = n_global;
-                pk.K = K;
-                pk.h = c.horizon;
-                pk.d = c.act_dim;
-                pk.part_k = (const unsigned long long*)b->workspace;
-                pk.actions = (const float*)actions;
-                if (one > 0 && tail_rows > 0 && c.rank == 0) {
-                    // rank 0's shifted elites sit behind the list-writing workgroups: extra candidates of the pack, costs
-                    // from the cost array, key index = their local pool row
-                    pk.n_keep = tail_rows;
-                    pk.elites_cost_cur = (const float*)b->costs + n_loc;
-                    pk.keep_base = n_loc;
-                }
-                XchgPush px;  // in-library exchange: the pack kernel pushes the records itself where they fit its LDS
-                const bool fold_push = xchg_connected(h) && pack_can_push(K, c.horizon, c.act_dim);
-                if (fold_push) {
-                    rc = xchg_begin(h, &px, &h->xw_last);
-                    if (rc) return rc;
-                }
-                // Riding pack: where this iteration's merge will ride in the next local launch (h->deferral, same
-                // conditions as icem_plan_iter_merge's fold) and that launch is a single-launch kernel, the pack rides
-                // there too, as its workgroup 0.  Stashed; the next icem_plan_iter_local consumes it (or launches it).
-                // (the step's LAST pack: stashed for the merge that waits for its records -- pack_merge_kernel, one launch)
-                const int fuse_last = opt_i(OPT_PACK_MERGE);
-                const bool rides_next = !last && it + 1 < c.opt_iters;
-                if (fold_push && xchg_concurrent_peers(h) && h->deferral && (rides_next || (last && fuse_last)) && lists > 0 && c.world * K <= 128 && K <= 32) {
-                    const int n_next = rides_next ? local_rows(h, it + 1) : 0;
-                    if (!rides_next || (prologue_possible(h, n_next) && next_launch_takes_pack(h, n_next))) {
-                        PackPrev& pp = h->pk_args;
-                        pp.part_k = pk.part_k;
-                        pp.actions = pk.actions;
-                        pp.n_lists = pk.n_lists;
-                        pp.n_pool = pk.n_pool;
-                        pp.n_global = pk.n_global;
-                        pp.K = K;
-                        pp.n_loc = n_loc;
-                        pp.shard_lo = lo;
-                        pp.n_keep = pk.n_keep;
-                        pp.keep_costs = pk.elites_cost_cur;
-                        pp.records = (float*)rec;
-                        pp.px = px;
-                        h->pk_pending = true;
-                        return ICEM_OK;
-                    }
-                }
-                {
-                    ProfScope prof(h, ICEM_K_LOCAL_PACK, lists * K, st);
-                    launch_pack_records(pk, n_loc, lo, (float*)rec, st, px);
-                }
-                ICEM_HIP_TRY(hipGetLastError());
-                if (xchg_connected(h) && !fold_push) return xchg_push(h, rec, st, &h->xw_last);
-            }
-            ICEM_HIP_TRY(hipGetLastError());
-            return ICEM_OK;
-        }
-    }
-    // generic path (f64, external noise, shapes outside the fast list): one kernel per stage
-    int rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, call_base + (uint64_t)it, 0, row0,
-                       actions, st);
-    if (rc) return rc;
-    rc = gk_rollout(h, n_loc + n_extra, b->obs0, actions, b->costs, nullptr, st);
-    if (rc) return rc;
-    h->gen_sel_cand = 0;
-    if (c.world == 1 && gk_select_ok(h, n_cand, h->n_reuse, K)) {
-        // one GPU: nothing to exchange -- the merge call selects straight from the cost array (select_refit_kernel)
-        h->gen_sel_cand = n_cand;
-        h->gen_sel_loc = n_loc;
-        return ICEM_OK;
-    }
-    const int nblk = std::max(1, topk_blocks(n_cand));
-    rc = gk_topk_partial(h, n_cand, K, b->costs, b->workspace, nblk, st);
-    if (rc) return rc;
-    rc = gk_local_pack(h, nblk, K, n_loc, lo, n_global, b->workspace, actions, rec, st);
-    if (rc) return rc;
-    if (c.world > 1 && xchg_connected(h)) return xchg_push(h, rec, st, &h->xw_last);
+// the gathered records fit the prologue's selection, which holds two records per lane (128 records at most)
+static bool records_fit_prologue(const icem_handle* h) { return h->cfg.world * h->cfg.num_elites <= 128 && h->cfg.num_elites <= 32; }
+
+// published merge (PackPrev::pub): workgroup 0 merges the records once and publishes mean | std to the rest
+static int ensure_pub(icem_handle* h, hipStream_t st) {
+    if (h->pub_dev) return ICEM_OK;
+    const size_t bytes = ((size_t)2 * h->hd + 16) * sizeof(float);
+    ICEM_HIP_TRY(hipMalloc((void**)&h->pub_dev, bytes));
+    ICEM_HIP_TRY(hipMemsetAsync(h->pub_dev, 0, bytes, st));
     return ICEM_OK;
 }
+static void set_pub(icem_handle* h, PackPrev& p) {
+    p.pub = h->pub_dev;
+    p.pub_flag = reinterpret_cast<unsigned*>(h->pub_dev + 2 * h->hd);
+    p.pub_seq = ++h->pub_seq;
+}
 
+// Where an iteration's merge goes: launched now or stashed for the next launch's prologue, and where it writes mean / std
+// (nullptr: in place).
+struct MergeRoute {
+    bool defer = false;
+    float* mean_out = nullptr;
+    float* std_out = nullptr;
+};
+// the last iteration's distribution goes to the caller's buffers, a folded one to the handle's ping-pong pair, any other in place
+static MergeRoute merge_route(const icem_handle* h, const icem_plan_buffers* b, int it, bool fold) {
+    if (it == h->cfg.opt_iters - 1) return {false, (float*)b->mean, (float*)b->std};
+    if (!fold) return {};
+    float* pp = h->pp_stats + (size_t)(it & 1) * 2 * h->hd;
+    return {true, pp, pp + h->hd};
+}
+
+// ---- argument blocks ----------------------------------------------------------------------------------------------------
+
+// the fields every form of iteration `it`'s merge shares, in the handle's dtype
 template <typename T>
-int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st) {
+static MergeArgsV merge_args(const icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, MergeRoute route) {
     const icem_config& c = h->cfg;
     const int hd = h->hd, K = c.num_elites;
-    const long long g = (long long)mpc_step * c.opt_iters + it;  // global iteration number
-    const int cur = (int)(g & 1), nxt = cur ^ 1;
+    const int cur = elite_parity(h, mpc_step, it), nxt = cur ^ 1;
     T* el = (T*)b->elites;
     T* elc = el + (size_t)2 * K * hd;
-    if constexpr (std::is_same<T, float>::value) {
-        if (c.world == 1 && h->fast_lists > 0) {
-            MergeSingleArgs m = zeroed_args<MergeSingleArgs>();
-            m.keep_base = -1;
-            m.n_lists = h->fast_lists;
-            m.n_keep = (it > 0 && c.keep_previous_elites) ? h->n_reuse : 0;
-            const int n_extra = (it == 0 && c.shift_elites && mpc_step > 0) ? h->n_reuse : 0;
-            // iteration 0: shifted elites that sit behind the list-writing workgroups (sample_rollout_lists) come in
-            // through the kept-elite slot: costs from the cost array, rows from the pool (index n_global + e < n_pool)
-            const bool tail = it == 0 && h->fast_tail_rows > 0;
-            if (tail) m.n_keep = h->fast_tail_rows;
-            m.n_pool = h->pop[it] + n_extra;
-            m.n_global = h->pop[it];
-            m.K = K;
-            m.h = c.horizon;
-            m.d = c.act_dim;
-            m.last = it == c.opt_iters - 1;
-            m.alpha = (float)c.alpha;
-            m.init_std = (float)c.init_std;
-            m.part_k = (const unsigned long long*)b->workspace;
-            m.records = nullptr;
-            m.n_rec = 0;
-            m.actions = (const float*)b->actions;
-            m.elites_cur = (const float*)el + (size_t)cur * K * hd;
-            m.elites_cost_cur = tail ? (const float*)b->costs + h->pop[it] : (const float*)elc + (size_t)cur * K;
-            m.elites_next = (float*)el + (size_t)nxt * K * hd;
-            m.elites_cost_next = (float*)elc + (size_t)nxt * K;
-            m.mean = (const float*)b->mean;
-            m.std = (const float*)b->std;
-            m.mean_out = h->merge_mean_out ? h->merge_mean_out : (float*)b->mean;
-            m.std_out = h->merge_std_out ? h->merge_std_out : (float*)b->std;
-            m.low = (const float*)b->low;
-            m.high = (const float*)b->high;
-            m.executed = (float*)b->executed;
-            m.best_cost = (float*)b->best_cost;
-            m.dbg = h->dbg;
-            if (h->defer_merge && !m.last) {  // rides in the next iteration's launch (icem_plan_step)
-                h->pm_args = m;
-                h->pm_pending = true;
-                return ICEM_OK;
-            }
-            if (h->pk_pending) {  // (cannot happen at world == 1; kept symmetrical)
-                const int rc = launch_pending_pack(h, st);
-                if (rc) return rc;
-            }
-            ProfScope prof(h, ICEM_K_MERGE_REFIT, h->fast_lists * K + m.n_keep, st);
-            if (h->ahead.tail_pending && merge_noise_ok(m, c.rng_rounds)) {
-                launch_merge_noise(m, h->ahead.tail_args, h->ahead.tail2_args, st);  // + (the rest of) the next step's first noise
-                h->ahead.tail_pending = false;
-            } else {
-                launch_merge_single(m, st);
-            }
-            ICEM_HIP_TRY(hipGetLastError());
-            return ICEM_OK;
-        }
-    }
     MergeArgsV a{};
     a.n_rec = c.world * K;
     a.n_keep = (it > 0 && c.keep_previous_elites) ? h->n_reuse : 0;
@@ -746,73 +446,415 @@ int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
     a.elites_cost_next = elc + (size_t)nxt * K;
     a.mean_in = b->mean;
     a.std_in = b->std;
-    a.mean = h->merge_mean_out ? (void*)h->merge_mean_out : b->mean;
-    a.std = h->merge_std_out ? (void*)h->merge_std_out : b->std;
+    a.mean = route.mean_out ? (void*)route.mean_out : b->mean;
+    a.std = route.std_out ? (void*)route.std_out : b->std;
     a.low = b->low;
     a.high = b->high;
     a.executed = b->executed;
     a.best_cost = b->best_cost;
+    return a;
+}
+
+// ... as the f32 merge kernels take them: sets the shared fields of `m` in place (a zeroed block keeps its defined padding)
+static void fill_single(MergeSingleArgs& m, const MergeArgsV& a) {
+    m.n_keep = a.n_keep;
+    m.n_global = a.n_global;
+    m.K = a.K;
+    m.h = a.h;
+    m.d = a.d;
+    m.last = a.last;
+    m.alpha = (float)a.alpha;
+    m.init_std = (float)a.init_std;
+    m.elites_cur = (const float*)a.elites_cur;
+    m.elites_cost_cur = (const float*)a.elites_cost_cur;
+    m.elites_next = (float*)a.elites_next;
+    m.elites_cost_next = (float*)a.elites_cost_next;
+    m.mean = (const float*)a.mean_in;
+    m.std = (const float*)a.std_in;
+    m.mean_out = (float*)a.mean;
+    m.std_out = (float*)a.std;
+    m.low = (const float*)a.low;
+    m.high = (const float*)a.high;
+    m.executed = (float*)a.executed;
+    m.best_cost = (float*)a.best_cost;
+}
+
+// ... and back, for a stashed records merge that runs on the generic kernel after all
+static MergeArgsV generic_from(const MergeSingleArgs& m) {
+    MergeArgsV a{};
+    a.n_rec = m.n_rec;
+    a.n_keep = m.n_keep;
+    a.K = m.K;
+    a.h = m.h;
+    a.d = m.d;
+    a.n_global = m.n_global;
+    a.last = m.last;
+    a.alpha = m.alpha;
+    a.init_std = m.init_std;
+    a.records = m.records;
+    a.elites_cur = m.elites_cur;
+    a.elites_cost_cur = m.elites_cost_cur;
+    a.elites_next = m.elites_next;
+    a.elites_cost_next = m.elites_cost_next;
+    a.mean_in = m.mean;
+    a.std_in = m.std;
+    a.mean = m.mean_out;
+    a.std = m.std_out;
+    a.low = m.low;
+    a.high = m.high;
+    a.executed = m.executed;
+    a.best_cost = m.best_cost;
+    a.xw = m.xw;
+    return a;
+}
+
+// A sharded rank's K best of its candidate lists -> records for the all-gather (same selection code as the merge): the
+// pack launched on its own.  tail > 0: rank 0's shifted elites sit behind the list-writing workgroups -- extra candidates
+// of the pack, costs from the cost array (from row n_loc on), key index = their local pool row.
+static MergeSingleArgs local_pack_args(const icem_handle* h, int it, int lists, int n_pool, const void* part_k, const float* actions,
+                                       int n_loc, int tail, const void* costs) {
+    MergeSingleArgs pk{};
+    pk.n_lists = lists;
+    pk.n_pool = n_pool;
+    pk.n_global = h->pop[it];
+    pk.K = h->cfg.num_elites;
+    pk.h = h->cfg.horizon;
+    pk.d = h->cfg.act_dim;
+    pk.part_k = (const unsigned long long*)part_k;
+    pk.actions = actions;
+    if (tail > 0) {
+        pk.n_keep = tail;
+        pk.elites_cost_cur = (const float*)costs + n_loc;
+        pk.keep_base = n_loc;
+    }
+    return pk;
+}
+
+// ... the same pack as a rider of a later launch
+static PackPrev make_pack(const MergeSingleArgs& pk, Shard sh, float* records, const XchgPush& px) {
+    PackPrev pp;
+    pp.part_k = pk.part_k;
+    pp.actions = pk.actions;
+    pp.n_lists = pk.n_lists;
+    pp.n_pool = pk.n_pool;
+    pp.n_global = pk.n_global;
+    pp.K = pk.K;
+    pp.n_loc = sh.n_loc;
+    pp.shard_lo = sh.lo;
+    pp.n_keep = pk.n_keep;
+    pp.keep_costs = pk.elites_cost_cur;
+    pp.records = records;
+    pp.px = px;
+    return pp;
+}
+
+// ... and a rider that runs as a launch after all (launch_pack_records / launch_pack_merge)
+static MergeSingleArgs pack_launch_args(const icem_handle* h, const PackPrev& pp) {
+    MergeSingleArgs pk{};
+    pk.n_lists = pp.n_lists;
+    pk.n_pool = pp.n_pool;
+    pk.n_global = pp.n_global;
+    pk.K = pp.K;
+    pk.h = h->cfg.horizon;
+    pk.d = h->cfg.act_dim;
+    pk.part_k = pp.part_k;
+    pk.actions = pp.actions;
+    pk.n_keep = pp.n_keep;
+    pk.elites_cost_cur = pp.keep_costs;
+    pk.keep_base = pp.n_loc;
+    return pk;
+}
+
+// a stashed merge that found no launch to ride in
+int launch_pending_merge(icem_handle* h, hipStream_t st) {
+    if (g_batch.rec) {
+        g_batch.unsupported = true;
+        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a merge found no launch to ride in");
+    }
+    const MergeSingleArgs& m = h->ride.merge;
+    if (m.records != nullptr) return gk_merge_refit(h, generic_from(m), st);
+    {
+        ProfScope prof(h, ICEM_K_MERGE_REFIT, m.n_lists * m.K + m.n_keep, st);
+        launch_merge_single(m, st);
+    }
+    ICEM_HIP_TRY(hipGetLastError());
+    return ICEM_OK;
+}
+
+// will the merge-prologue launch of an iteration with n_rows local rows take the previous iteration's pack along?
+static bool next_launch_takes_pack(const icem_handle* h, int n_rows) {
+    const icem_config& c = h->cfg;
+    if (one_launch_lists(h, n_rows) > 0)
+        return sample_rollout_pack_ok(c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, c.num_elites);
+    return sample_folded_pack_ok(c.horizon, c.act_dim, c.rng_rounds, c.num_elites);
+}
+
+// a stashed pack that found no launch to ride in
+int launch_pending_pack(icem_handle* h, hipStream_t st) {
+    const PackPrev& pp = h->ride.pack;
+    {
+        ProfScope prof(h, ICEM_K_LOCAL_PACK, pp.n_lists * pp.K, st);
+        launch_pack_records(pack_launch_args(h, pp), pp.n_loc, pp.shard_lo, pp.records, st, pp.px);
+    }
+    ICEM_HIP_TRY(hipGetLastError());
+    h->ride.pack_pending = false;
+    return ICEM_OK;
+}
+
+template <typename T>
+int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st) {
+    const icem_config& c = h->cfg;
+    const int hd = h->hd, K = c.num_elites;
+    const int n_global = h->pop[it];
+    const Shard sh = shard_of(h, it);
+    const int lo = sh.lo, n_loc = sh.n_loc;
+    const uint64_t base = call_base(h, mpc_step);
+    const bool last = it == c.opt_iters - 1;
+    T* actions = (T*)b->actions;
+    const int n_extra = shift_rows(h, mpc_step, it);
+    const T* shift_src = nullptr;
+    bool shift_in_sampler = false;
+    if (n_extra > 0) {
+        shift_src = (const T*)b->elites + (size_t)elite_parity(h, mpc_step, 0) * K * hd;  // the elite buffer holding the previous step's set
+        // the fast sampler prepares them in an extra workgroup of its own launch
+        shift_in_sampler = std::is_same<T, float>::value && b->z_r == nullptr && b->z_r_shift == nullptr &&
+                           fast_rollout_ok(h, K) && fast_sample_ok(h) &&
+                           n_extra * c.act_dim <= 256;
+        if (!shift_in_sampler) {
+            T* dst = actions + (size_t)n_loc * hd;
+            int rc = gk_shift_elites(h, n_extra, shift_src, dst, st);
+            if (rc) return rc;
+            rc = gk_sample(h, n_extra, 0, b->mean, b->std, b->low, b->high, b->z_r_shift, b->z_i_shift,
+                           base + (uint64_t)c.opt_iters, c.horizon - 1, 0, dst, st);
+            if (rc) return rc;
+        }
+    }
+    // candidates: the shard, plus the shifted elites on rank 0 only (they are replicated)
+    const int n_cand = n_loc + (c.rank == 0 ? n_extra : 0);
+    const int row0 = (last && c.use_mean_actions) ? 1 : 0;
+    T* rec = (T*)b->records + (size_t)c.rank * K * (hd + 2);
+    h->local.lists = 0;
+    h->local.sel_cand = 0;
     if constexpr (std::is_same<T, float>::value) {
-        const bool fast_records = h->fast_lists > 0 && a.n_rec <= 128 && K <= 32;
-        if (fast_records) {  // f32 throughput path: the selection / refit code of the single-GPU merge on the records
+        if (fast_rollout_ok(h, K)) {
+            // f32 throughput path.  External white noise (b->z_r: the reference's own draws, tests/golden) takes it too: the
+            // generic sampler turns the caller's z into the pool (it is the only kernel that reads z), and from there on the
+            // tile rollout, the lists and the threshold merges are the ones device noise gets -- the reference's draws reach
+            // Tile16 / Tile16H and merge_select*, not only the generic kernels.
+            const bool ext_z = b->z_r != nullptr;
+            const uint64_t off = base + (uint64_t)it;
+            int rc = ensure_fast_model(h);
+            if (rc) return rc;
+            int lists = 0;
+            float* pc;
+            int* pi;
+            const int n_rows = n_loc + n_extra;
+            int tail_rows = 0;  // shifted-elite rows scored through the cost array instead of a list (world 1 only)
+            const int one = (!ext_z && fast_sample_ok(h) && (n_extra == 0 || shift_in_sampler))
+                                ? one_launch_lists(h, n_rows, shift_in_sampler ? n_extra : 0, &tail_rows) : 0;
+            h->local.tail_rows = one > 0 ? tail_rows : 0;
+            // the merge finds the lists' indices behind `lists * K` costs
+            split_partial_ws<float>(b->workspace, one > 0 ? one : rollout_lists(c.horizon, c.act_dim, h->Of, n_rows), K, &pc, &pi);
+            bool prologue = false, ride = false;
+            if (h->ride.merge_pending) {
+                prologue = !ext_z && n_extra == 0 && prologue_possible(h, n_rows);
+                // a stashed pack rides with the merge whose records it produces, or runs now -- in front of that merge
+                ride = prologue && h->ride.pack_pending && next_launch_takes_pack(h, n_rows);
+                if (h->ride.pack_pending && !ride) {
+                    rc = launch_pending_pack(h, st);
+                    if (rc) return rc;
+                }
+                if (!prologue) {  // cannot ride along after all: run it now
+                    rc = launch_pending_merge(h, st);
+                    if (rc) return rc;
+                }
+                h->ride.merge_pending = false;
+            } else if (h->ride.pack_pending) {
+                rc = launch_pending_pack(h, st);
+                if (rc) return rc;
+            }
+            h->ride.pack_pending = false;
+            if (one > 0) {
+                // small populations: sample + rollout + top-K in one launch
+                FastIterArgs fa = zeroed_args<FastIterArgs>();
+                fa.m.keep_base = -1;
+                if (prologue) fa.m = h->ride.merge;
+                if (ride) fa.p = h->ride.pack;
+                fa.s = fast_sample_args(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions,
+                                        shift_in_sampler ? n_extra : 0, shift_src, base + (uint64_t)c.opt_iters);
+                if (it == 0 && c.world == 1 && h->ahead.pre_valid) {
+                    // this step's first noise (and the shifted elites') was drawn beside the previous step's last merge -- on
+                    // pre_stream: a step enqueued on another stream is not ordered behind that launch and redraws instead
+                    if (h->ahead.pre_episode == h->episode && h->ahead.pre_step == mpc_step && h->ahead.pre_stream == st) fa.s.raw_src = (const float*)h->ahead.pre_raw;
+                    h->ahead.pre_valid = false;
+                }
+                fa.r = fast_rollout_args(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi);
+                fa.r.part_k = (unsigned long long*)b->workspace;  // read by merge_single_kernel / pack_records_kernel
+                fa.r.list_wgs = tail_rows > 0 ? one : 0;
+                {
+                    ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n_rows * c.horizon, st);
+                    launch_sample_rollout(fa, c.horizon, c.act_dim, h->Of, h->model_kind, prologue, st);
+                }
+                ICEM_HIP_TRY(hipGetLastError());
+                lists = one;
+            }
+            if (one == 0) {
+                if (prologue) {
+                    FastSampleMergeArgs sm;
+                    sm.s = fast_sample_args(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, 0, nullptr, 0);
+                    sm.m = h->ride.merge;
+                    if (ride) {
+                        sm.p = h->ride.pack;
+                        // published merge: workgroup 0 merges the records once and publishes mean | std to the rest
+                        const int pub_on = opt_i(OPT_PUBLISHED_MERGE);
+                        if (pub_on && sm.m.records) {
+                            rc = ensure_pub(h, st);
+                            if (rc) return rc;
+                            set_pub(h, sm.p);
+                        }
+                    }
+                    {
+                        ProfScope prof(h, ICEM_K_SAMPLE, (long long)n_loc * c.horizon, st);
+                        launch_sample_folded_merge(sm, st);
+                    }
+                    ICEM_HIP_TRY(hipGetLastError());
+                    rc = ICEM_OK;
+                } else if (ext_z) {
+                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, off, 0, row0, actions, st);
+                } else if (fast_sample_ok(h)) {
+                    rc = launch_fast_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, st,
+                                            shift_in_sampler ? n_extra : 0, shift_src, base + (uint64_t)c.opt_iters);
+                } else {
+                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, nullptr, nullptr, off, 0, row0, actions, st);
+                }
+                if (rc) return rc;
+                int tail2 = 0;
+                rc = launch_fast_rollout(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi, st, &lists,
+                                         (unsigned long long*)b->workspace, (c.world == 1 && it == 0) ? n_extra : 0, &tail2);
+                if (rc) return rc;
+                h->local.tail_rows = tail2;
+            }
+            h->local.lists = lists;
+            if (c.world > 1) {
+                // this rank's K best -> records for the all-gather
+                const MergeSingleArgs pk = local_pack_args(h, it, lists, n_rows, b->workspace, (const float*)actions, n_loc,
+                                                           (one > 0 && c.rank == 0) ? tail_rows : 0, b->costs);
+                XchgPush px;  // in-library exchange: the pack kernel pushes the records itself where they fit its LDS
+                const bool fold_push = xchg_connected(h) && pack_can_push(K, c.horizon, c.act_dim);
+                if (fold_push) {
+                    rc = xchg_begin(h, &px, &h->xw_last);
+                    if (rc) return rc;
+                }
+                // Riding pack: where this iteration's merge will ride in the next local launch (h->deferral, same
+                // conditions as icem_plan_iter_merge's fold) and that launch is a single-launch kernel, the pack rides
+                // there too, as its workgroup 0.  Stashed; the next icem_plan_iter_local consumes it (or launches it).
+                // (the step's LAST pack: stashed for the merge that waits for its records -- pack_merge_kernel, one launch)
+                const int fuse_last = opt_i(OPT_PACK_MERGE);
+                const bool rides_next = !last && it + 1 < c.opt_iters;
+                if (fold_push && xchg_concurrent_peers(h) && h->deferral && (rides_next || (last && fuse_last)) && lists > 0 && records_fit_prologue(h)) {
+                    const int n_next = rides_next ? shard_of(h, it + 1).n_loc : 0;
+                    if (!rides_next || (prologue_possible(h, n_next) && next_launch_takes_pack(h, n_next))) {
+                        h->ride.pack = make_pack(pk, sh, (float*)rec, px);
+                        h->ride.pack_pending = true;
+                        return ICEM_OK;
+                    }
+                }
+                {
+                    ProfScope prof(h, ICEM_K_LOCAL_PACK, lists * K, st);
+                    launch_pack_records(pk, n_loc, lo, (float*)rec, st, px);
+                }
+                ICEM_HIP_TRY(hipGetLastError());
+                if (xchg_connected(h) && !fold_push) return xchg_push(h, rec, st, &h->xw_last);
+            }
+            ICEM_HIP_TRY(hipGetLastError());
+            return ICEM_OK;
+        }
+    }
+    // generic path (f64, external noise, shapes outside the fast list): one kernel per stage
+    int rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, base + (uint64_t)it, 0, row0,
+                       actions, st);
+    if (rc) return rc;
+    rc = gk_rollout(h, n_loc + n_extra, b->obs0, actions, b->costs, nullptr, st);
+    if (rc) return rc;
+    h->local.sel_cand = 0;
+    if (c.world == 1 && gk_select_ok(h, n_cand, h->n_reuse, K)) {
+        // one GPU: nothing to exchange -- the merge call selects straight from the cost array (select_refit_kernel)
+        h->local.sel_cand = n_cand;
+        h->local.sel_loc = n_loc;
+        return ICEM_OK;
+    }
+    const int nblk = std::max(1, topk_blocks(n_cand));
+    rc = gk_topk_partial(h, n_cand, K, b->costs, b->workspace, nblk, st);
+    if (rc) return rc;
+    rc = gk_local_pack(h, nblk, K, n_loc, lo, n_global, b->workspace, actions, rec, st);
+    if (rc) return rc;
+    if (c.world > 1 && xchg_connected(h)) return xchg_push(h, rec, st, &h->xw_last);
+    return ICEM_OK;
+}
+
+template <typename T>
+int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st, MergeRoute route = MergeRoute()) {
+    const icem_config& c = h->cfg;
+    const int K = c.num_elites;
+    const MergeArgsV a = merge_args<T>(h, b, mpc_step, it, route);
+    if constexpr (std::is_same<T, float>::value) {
+        if (c.world == 1 && h->local.lists > 0) {  // lists form: the candidate lists of this GPU's own rollout
+            MergeSingleArgs m = zeroed_args<MergeSingleArgs>();
+            m.keep_base = -1;
+            fill_single(m, a);
+            m.n_lists = h->local.lists;
+            // iteration 0: shifted elites that sit behind the list-writing workgroups (sample_rollout_lists) come in
+            // through the kept-elite slot: costs from the cost array, rows from the pool (index n_global + e < n_pool)
+            if (it == 0 && h->local.tail_rows > 0) {
+                m.n_keep = h->local.tail_rows;
+                m.elites_cost_cur = (const float*)b->costs + h->pop[it];
+            }
+            m.n_pool = h->pop[it] + shift_rows(h, mpc_step, it, false);
+            m.part_k = (const unsigned long long*)b->workspace;
+            m.actions = (const float*)b->actions;
+            m.dbg = h->dbg;
+            if (route.defer && !m.last) {  // rides in the next iteration's launch (icem_plan_step)
+                h->ride.merge = m;
+                h->ride.merge_pending = true;
+                return ICEM_OK;
+            }
+            if (h->ride.pack_pending) {  // (cannot happen at world == 1; kept symmetrical)
+                const int rc = launch_pending_pack(h, st);
+                if (rc) return rc;
+            }
+            ProfScope prof(h, ICEM_K_MERGE_REFIT, h->local.lists * K + m.n_keep, st);
+            if (h->ahead.tail_pending && merge_noise_ok(m, c.rng_rounds)) {
+                launch_merge_noise(m, h->ahead.tail_args, h->ahead.tail2_args, st);  // + (the rest of) the next step's first noise
+                h->ahead.tail_pending = false;
+            } else {
+                launch_merge_single(m, st);
+            }
+            ICEM_HIP_TRY(hipGetLastError());
+            return ICEM_OK;
+        }
+        if (h->local.lists > 0 && records_fit_prologue(h)) {
+            // records form -- f32 throughput path: the selection / refit code of the single-GPU merge on the records
             MergeSingleArgs m{};
-            m.n_lists = 0;
-            m.n_keep = a.n_keep;
-            m.n_pool = 0;
-            m.n_global = a.n_global;
-            m.K = K;
-            m.h = a.h;
-            m.d = a.d;
-            m.last = 0;
-            m.alpha = (float)a.alpha;
-            m.init_std = (float)a.init_std;
-            m.part_k = nullptr;
+            fill_single(m, a);
             m.records = (const float*)a.records;
             m.xw = a.xw;
             m.n_rec = a.n_rec;
-            m.actions = nullptr;
-            m.elites_cur = (const float*)a.elites_cur;
-            m.elites_cost_cur = (const float*)a.elites_cost_cur;
-            m.elites_next = (float*)a.elites_next;
-            m.elites_cost_next = (float*)a.elites_cost_next;
-            m.mean = (const float*)a.mean_in;
-            m.std = (const float*)a.std_in;
-            m.mean_out = (float*)a.mean;
-            m.std_out = (float*)a.std;
-            m.low = (const float*)a.low;
-            m.high = (const float*)a.high;
-            m.executed = (float*)a.executed;
-            m.best_cost = (float*)a.best_cost;
-            m.dbg = nullptr;
-            if (h->defer_merge && !a.last) {  // rides in the next iteration's launch
-                h->pm_args = m;
-                h->pm_pending = true;
+            if (route.defer && !a.last) {  // rides in the next iteration's launch
+                h->ride.merge = m;
+                h->ride.merge_pending = true;
                 return ICEM_OK;
             }
-            m.last = a.last;
             const int fuse_on = opt_i(OPT_PACK_MERGE);
-            if (h->pk_pending && fuse_on && m.records != nullptr && xchg_connected(h)) {
+            if (h->ride.pack_pending && fuse_on && m.records != nullptr && xchg_connected(h)) {
                 // the merge runs now, and so must the pack whose records it waits for: ONE launch for the two
-                const PackPrev& pp = h->pk_args;
-                MergeSingleArgs pk{};
-                pk.n_lists = pp.n_lists;
-                pk.n_pool = pp.n_pool;
-                pk.n_global = pp.n_global;
-                pk.K = pp.K;
-                pk.h = h->cfg.horizon;
-                pk.d = h->cfg.act_dim;
-                pk.part_k = pp.part_k;
-                pk.actions = pp.actions;
-                pk.n_keep = pp.n_keep;
-                pk.elites_cost_cur = pp.keep_costs;
-                pk.keep_base = pp.n_loc;
+                const PackPrev& pp = h->ride.pack;
                 ProfScope prof(h, ICEM_K_MERGE_REFIT, a.n_rec + a.n_keep, st);
-                launch_pack_merge(pk, pp.n_loc, pp.shard_lo, pp.records, pp.px, m, st);
+                launch_pack_merge(pack_launch_args(h, pp), pp.n_loc, pp.shard_lo, pp.records, pp.px, m, st);
                 ICEM_HIP_TRY(hipGetLastError());
-                h->pk_pending = false;
+                h->ride.pack_pending = false;
                 return ICEM_OK;
             }
-            if (h->pk_pending) {  // (records gathered by a collective between the two: separate launches)
+            if (h->ride.pack_pending) {  // (records gathered by a collective between the two: separate launches)
                 const int rc = launch_pending_pack(h, st);
                 if (rc) return rc;
             }
@@ -822,14 +864,14 @@ int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
             return ICEM_OK;
         }
     }
-    if (h->pk_pending) {
+    if (h->ride.pack_pending) {
         const int rc = launch_pending_pack(h, st);
         if (rc) return rc;
     }
-    if (c.world == 1 && h->gen_sel_cand > 0 && h->fast_lists == 0) {
-        const int n_cand = h->gen_sel_cand;
-        h->gen_sel_cand = 0;
-        return gk_select_refit(h, n_cand, h->gen_sel_loc, b->costs, b->actions, a, st);
+    if (c.world == 1 && h->local.sel_cand > 0 && h->local.lists == 0) {
+        const int n_cand = h->local.sel_cand;
+        h->local.sel_cand = 0;
+        return gk_select_refit(h, n_cand, h->local.sel_loc, b->costs, b->actions, a, st);
     }
     return gk_merge_refit(h, a, st);
 }
@@ -880,11 +922,11 @@ static bool ahead_eligible(icem_handle* h, const icem_plan_buffers* b, bool shar
         // the records merge's two-per-lane layout, the published merge switched on
         const int on = opt_i(OPT_NOISE_AHEAD_SHARDED);
         if (!on || !xchg_connected(h) || !xchg_concurrent_peers(h) || !pack_can_push(c.num_elites, c.horizon, c.act_dim) ||
-            c.world * c.num_elites > 128 || c.num_elites > 32)
+            !records_fit_prologue(h))
             return false;
     }
     for (size_t it = 0; it < h->pop.size(); ++it) {
-        const int n = sharded ? local_rows(h, (int)it) : h->pop[it];
+        const int n = sharded ? shard_of(h, (int)it).n_loc : h->pop[it];
         if (n < A.min_rows || !rollout_ahead_ok(c.horizon, c.act_dim, h->Of, c.num_elites, n)) return false;
     }
     if (c.shift_elites && h->n_reuse > 16) return false;  // (the shift role rolls its rows out as one 16-row tile)
@@ -915,123 +957,184 @@ static int ahead_setup(icem_handle* h) {
     return ICEM_OK;
 }
 
-static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
-    icem_handle::Ahead& A = h->ahead;
-    const icem_config& c = h->cfg;
-    const int iters = c.opt_iters, K = c.num_elites, hd = h->hd;
-    int rc = ahead_setup(h);
-    if (rc) return rc;
-    rc = ensure_fast_model(h);
-    if (rc) return rc;
-    const uint64_t call_base = (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(iters + 1);
-    auto pool_of = [&](int it) -> float* { return it == iters - 1 ? (float*)b->actions : (float*)A.pool[(A.ctr + (unsigned)it) % 3]; };
-    auto noise_args = [&](int n, uint64_t off, void* out) {
-        return fast_sample_args(h, n, 0, nullptr, nullptr, nullptr, nullptr, off, 0, out, 0, nullptr, 0);
-    };
-    float* cur_mean = (float*)b->mean;
-    float* cur_std = (float*)b->std;
-    const int n_extra = (c.shift_elites && mpc_step > 0 && h->n_reuse > 0) ? h->n_reuse : 0;
-    int n1_done = 0;   // rows of iteration 1's noise that are there already
-    for (int it = 0; it < iters; ++it) {
-        const bool last = it == iters - 1;
-        const int n = h->pop[it];
-        float* pool = pool_of(it);
+// What the pipeline's two forms (one GPU: plan_step_ahead; a rank of a sharded run: plan_step_sharded_ahead) share:
+// set-up, the pool rotation, the step's first noise and arming the next step's, the arguments of the roles, the merge routing.
+struct AheadStep {
+    icem_handle* h;
+    const icem_plan_buffers* b;
+    int mpc_step;
+    hipStream_t st;
+    const char* name;
+    uint64_t base = 0;
+    float* cur_mean = nullptr;  // where the current distribution lives
+    float* cur_std = nullptr;
+
+    int begin() {
+        int rc = ahead_setup(h);
+        if (rc) return rc;
+        rc = ensure_fast_model(h);
+        if (rc) return rc;
+        base = call_base(h, mpc_step);
+        cur_mean = (float*)b->mean;
+        cur_std = (float*)b->std;
+        return ICEM_OK;
+    }
+    // the last iteration's pool is the caller's `actions`; the others rotate through the handle's three
+    float* pool_of(int it) const {
+        return it == h->cfg.opt_iters - 1 ? (float*)b->actions : (float*)h->ahead.pool[(h->ahead.ctr + (unsigned)it) % 3];
+    }
+    // ... and the pool that iteration 0 of the NEXT MPC step will find at its pool_of(0)
+    void* next_step_pool(unsigned it = 0) const { return h->ahead.pool[(h->ahead.ctr + (unsigned)(h->cfg.opt_iters - 1) + it) % 3]; }
+    // rows [first_index, first_index + n) of the sampling call `off`, raw, -> out
+    FastSampleArgs noise_args(int n, long long first_index, uint64_t off, void* out) const {
+        return fast_sample_args(h, n, first_index, nullptr, nullptr, nullptr, nullptr, off, 0, out, 0, nullptr, 0);
+    }
+    // iteration `it`'s buffers: its pool, and the distribution where the previous merge left it
+    icem_plan_buffers buffers(int it) const {
         icem_plan_buffers bb = *b;
-        bb.actions = pool;
-        if (it & 1) bb.workspace = h->ws_alt;
+        bb.actions = pool_of(it);
         bb.mean = cur_mean;
         bb.std = cur_std;
-        if (it == 0) {
-            // this step's first noise: drawn by the previous step's last launch -- or, for a step nobody predicted, here
-            const bool hit = A.next_valid && A.next_episode == h->episode && A.next_step == mpc_step && A.next_pool == pool &&
-                             A.next_stream == st;   // (another stream is not ordered behind the launch that drew it: a miss)
-            A.next_valid = false;
-            if (!hit) {
-                const FastSampleArgs za = noise_args(n, call_base, pool);
-                ProfScope prof(h, ICEM_K_SAMPLE, (long long)n * c.horizon, st);
-                launch_noise_rows(za, c.rng_rounds, st);
-            }
-            ICEM_HIP_TRY(hipGetLastError());
-            // the head of iteration 1's noise may have been drawn beside the previous step's last merge as well
-            n1_done = (hit && iters > 1 && A.next1_pool == pool_of(1)) ? std::min(A.next1_rows, h->pop[1]) : 0;
-            A.next1_rows = 0;
+        return bb;
+    }
+    // this step's first noise: drawn by the previous step's last launch -- or, for a step nobody predicted, here
+    int first_noise(Shard sh, float* pool, bool* hit_out) {
+        icem_handle::Ahead& A = h->ahead;
+        const bool hit = A.next_valid && A.next_episode == h->episode && A.next_step == mpc_step && A.next_pool == pool &&
+                         A.next_stream == st;   // (another stream is not ordered behind the launch that drew it: a miss)
+        A.next_valid = false;
+        if (!hit) {
+            const FastSampleArgs za = noise_args(sh.n_loc, sh.lo, base, pool);
+            ProfScope prof(h, ICEM_K_SAMPLE, (long long)sh.n_loc * h->cfg.horizon, st);
+            launch_noise_rows(za, h->cfg.rng_rounds, st);
         }
-        IterAheadArgs ia = zeroed_args<IterAheadArgs>();
-        ia.m.keep_base = -1;
-        ia.r = fast_rollout_args(h, n, n, K, b->obs0, pool, b->costs, nullptr, nullptr);
+        ICEM_HIP_TRY(hipGetLastError());
+        *hit_out = hit;
+        return ICEM_OK;
+    }
+    // ... and the next step's, which this step's last launch draws into `np` (same episode, step + 1 -- checked when it comes)
+    void arm_next(void* np) {
+        icem_handle::Ahead& A = h->ahead;
+        A.next_valid = true;
+        A.next_episode = h->episode;
+        A.next_step = mpc_step + 1;
+        A.next_pool = np;
+        A.next_stream = st;
+    }
+    // the rollout role of iteration `it`: map the shard's raw noise of bb.actions with the current distribution, roll out
+    void roll_role(IterAheadArgs& ia, int it, Shard sh, const icem_plan_buffers& bb) const {
+        const icem_config& c = h->cfg;
+        ia.r = fast_rollout_args(h, sh.n_loc, sh.n_loc, c.num_elites, b->obs0, bb.actions, b->costs, nullptr, nullptr);
         ia.r.part_k = (unsigned long long*)bb.workspace;
-        ia.dbg_slot = it;
-        ia.has_merge = h->pm_pending ? 1 : 0;
-        if (h->pm_pending) ia.m = h->pm_args;
-        h->pm_pending = false;
-        ia.n_xf = n;
-        ia.row0_mean = (last && c.use_mean_actions) ? 1 : 0;
-        ia.store_back = last ? 1 : 0;
-        ia.pool = pool;
+        ia.n_xf = sh.n_loc;
+        ia.row0_mean = (it == c.opt_iters - 1 && c.use_mean_actions && sh.lo == 0) ? 1 : 0;
+        ia.pool = (float*)bb.actions;
         ia.mean = cur_mean;
         ia.std = cur_std;
-        ia.lo = A.lo;
-        ia.hi = A.hi;
-        // the noise role: the next sampling call
-        if (!last) {
-            const int skip = it == 0 ? n1_done : 0;
-            ia.z = noise_args(h->pop[it + 1] - skip, call_base + (uint64_t)(it + 1), pool_of(it + 1) + (size_t)skip * hd);
-            ia.z.first_index = skip;
-        } else {
-            // iteration 0 of the NEXT MPC step (same episode, step + 1 -- checked when it comes)
-            // -- split: what fits beside this launch's rollout here, the rest beside the step's last merge, a launch that
-            // leaves 255 of the 256 CUs idle (ICEM_AHEAD_TAIL_FRAC: share of the rows that goes there)
-            void* np = A.pool[(A.ctr + (unsigned)(iters - 1)) % 3];
-            const uint64_t off0 = (h->episode << 32) + (uint64_t)(mpc_step + 1) * (uint64_t)(iters + 1);
-            const double tail_frac = opt(OPT_AHEAD_TAIL_FRAC);
-            int n_tail = (int)(tail_frac * h->pop[0]);
-            n_tail = std::max(0, std::min(h->pop[0], n_tail));
-            const int n_here = h->pop[0] - n_tail;
-            ia.z = noise_args(n_here, off0, np);
-            A.tail_pending = n_tail > 0;
-            A.tail2_args = zeroed_args<FastSampleArgs>();
-            A.tail2_args.n = 0;
-            if (n_tail > 0) {
-                A.tail_args = noise_args(n_tail, off0, (float*)np + (size_t)n_here * hd);
-                A.tail_args.first_index = n_here;
-                // ... and the head of the next step's iteration-1 noise, into the pool that step will find at pool_of(1)
-                // (this step's iteration-2 pool: its last reader was iteration 3's prologue) -- ICEM_AHEAD_NEXT1_FRAC of it
-                const double frac1 = opt(OPT_AHEAD_NEXT1_FRAC);
-                const int n1 = iters > 2 ? std::max(0, std::min(h->pop[1], (int)(frac1 * h->pop[1]))) : 0;
-                if (n1 > 0) {
-                    void* np1 = A.pool[(A.ctr + (unsigned)(iters - 1) + 1u) % 3];
-                    A.tail2_args = noise_args(n1, off0 + 1u, np1);
-                    A.next1_rows = n1;
-                    A.next1_pool = np1;
-                }
-            }
-            A.next_valid = true;
-            A.next_episode = h->episode;
-            A.next_step = mpc_step + 1;
-            A.next_pool = np;
-            A.next_stream = st;
-        }
-        // the shift role (icem.py:91-104, 131-137): rows [n, n + n_extra) of this pool, costs behind costs[n]
-        if (it == 0 && n_extra > 0) {
-            const int g = (int)(((long long)mpc_step * iters) & 1);  // elite buffer holding the previous step's set
-            ia.s = fast_sample_args(h, n, 0, cur_mean, cur_std, b->low, b->high, call_base, 0, pool, n_extra,
-                                    (const float*)b->elites + (size_t)g * K * hd, call_base + (uint64_t)iters);
-        }
+        ia.lo = h->ahead.lo;
+        ia.hi = h->ahead.hi;
+    }
+    // the shift role (icem.py:91-104, 131-137): rows [n, n + rows) of this pool, costs behind costs[n]
+    void shift_role(IterAheadArgs& ia, int n, float* pool, int rows) const {
+        if (rows <= 0) return;
+        const icem_config& c = h->cfg;
+        // (the elite buffer holding the previous step's set)
+        const float* src = (const float*)b->elites + (size_t)elite_parity(h, mpc_step, 0) * c.num_elites * h->hd;
+        ia.s = fast_sample_args(h, n, 0, cur_mean, cur_std, b->low, b->high, base, 0, pool, rows, src, base + (uint64_t)c.opt_iters);
+    }
+    int launch(const IterAheadArgs& ia, int n) {
+        const icem_config& c = h->cfg;
         {
             ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n * c.horizon, st);
             launch_iter_ahead(ia, c.horizon, c.act_dim, h->Of, h->model_kind, st);
         }
         ICEM_HIP_TRY(hipGetLastError());
-        h->fast_lists = ahead_roll_workgroups(n);
-        h->fast_tail_rows = it == 0 ? n_extra : 0;
+        h->local.lists = ahead_roll_workgroups(n);
+        return ICEM_OK;
+    }
+    // iteration `it`'s merge: stashed for the next launch, its distribution going to the handle's ping-pong pair, or (last) launched
+    int merge(const icem_plan_buffers& bb, int it) {
+        const MergeRoute route = merge_route(h, b, it, true);
+        const int rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st, route);
+        if (rc || it == h->cfg.opt_iters - 1) return rc;
+        if (!h->ride.merge_pending) return fail(ICEM_E_STATE, std::string(name) + ": the merge did not defer");
+        cur_mean = route.mean_out;
+        cur_std = route.std_out;
+        return ICEM_OK;
+    }
+    void end() { h->ahead.ctr += (unsigned long long)(h->cfg.opt_iters - 1); }
+};
+
+static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
+    icem_handle::Ahead& A = h->ahead;
+    const icem_config& c = h->cfg;
+    const int iters = c.opt_iters, hd = h->hd;
+    AheadStep s{h, b, mpc_step, st, "noise-ahead"};
+    int rc = s.begin();
+    if (rc) return rc;
+    const int n_extra = shift_rows(h, mpc_step, 0);
+    int n1_done = 0;   // rows of iteration 1's noise that are there already
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        const int n = h->pop[it];
+        icem_plan_buffers bb = s.buffers(it);
+        if (it & 1) bb.workspace = h->ws_alt;
+        float* pool = (float*)bb.actions;
+        if (it == 0) {
+            bool hit = false;
+            rc = s.first_noise({0, n}, pool, &hit);
+            if (rc) return rc;
+            // the head of iteration 1's noise may have been drawn beside the previous step's last merge as well
+            n1_done = (hit && iters > 1 && A.next1_pool == s.pool_of(1)) ? std::min(A.next1_rows, h->pop[1]) : 0;
+            A.next1_rows = 0;
+        }
+        IterAheadArgs ia = zeroed_args<IterAheadArgs>();
+        ia.m.keep_base = -1;
+        s.roll_role(ia, it, {0, n}, bb);
+        ia.dbg_slot = it;
+        ia.has_merge = h->ride.merge_pending ? 1 : 0;
+        if (h->ride.merge_pending) ia.m = h->ride.merge;
+        h->ride.merge_pending = false;
+        ia.store_back = last ? 1 : 0;
+        // the noise role: the next sampling call
+        if (!last) {
+            const int skip = it == 0 ? n1_done : 0;
+            ia.z = s.noise_args(h->pop[it + 1] - skip, skip, s.base + (uint64_t)(it + 1), s.pool_of(it + 1) + (size_t)skip * hd);
+        } else {
+            // iteration 0 of the NEXT MPC step
+            // -- split: what fits beside this launch's rollout here, the rest beside the step's last merge, a launch that
+            // leaves 255 of the 256 CUs idle (ICEM_AHEAD_TAIL_FRAC: share of the rows that goes there)
+            void* np = s.next_step_pool();
+            const uint64_t off0 = call_base(h, mpc_step + 1);
+            const double tail_frac = opt(OPT_AHEAD_TAIL_FRAC);
+            int n_tail = (int)(tail_frac * h->pop[0]);
+            n_tail = std::max(0, std::min(h->pop[0], n_tail));
+            const int n_here = h->pop[0] - n_tail;
+            ia.z = s.noise_args(n_here, 0, off0, np);
+            A.tail_pending = n_tail > 0;
+            A.tail2_args = zeroed_args<FastSampleArgs>();
+            A.tail2_args.n = 0;
+            if (n_tail > 0) {
+                A.tail_args = s.noise_args(n_tail, n_here, off0, (float*)np + (size_t)n_here * hd);
+                // ... and the head of the next step's iteration-1 noise, into the pool that step will find at pool_of(1)
+                // (this step's iteration-2 pool: its last reader was iteration 3's prologue) -- ICEM_AHEAD_NEXT1_FRAC of it
+                const double frac1 = opt(OPT_AHEAD_NEXT1_FRAC);
+                const int n1 = iters > 2 ? std::max(0, std::min(h->pop[1], (int)(frac1 * h->pop[1]))) : 0;
+                if (n1 > 0) {
+                    void* np1 = s.next_step_pool(1);
+                    A.tail2_args = s.noise_args(n1, 0, off0 + 1u, np1);
+                    A.next1_rows = n1;
+                    A.next1_pool = np1;
+                }
+            }
+            s.arm_next(np);
+        }
+        if (it == 0) s.shift_role(ia, n, pool, n_extra);
+        rc = s.launch(ia, n);
+        if (rc) return rc;
+        h->local.tail_rows = it == 0 ? n_extra : 0;
         // ---- its merge: stashed for the next launch's prologue, or (last) a launch of its own ----
-        float* pp = h->pp_stats + (size_t)(it & 1) * 2 * hd;
-        h->defer_merge = !last;
-        h->merge_mean_out = last ? (float*)b->mean : pp;
-        h->merge_std_out = last ? (float*)b->std : pp + hd;
-        rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st);
-        h->defer_merge = false;
-        h->merge_mean_out = h->merge_std_out = nullptr;
+        rc = s.merge(bb, it);
         if (rc) return rc;
         if (last && A.tail_pending) {  // (the merge could not take it along: launches of their own)
             if (g_batch.rec) g_batch.unsupported = true;   // (icem_plan_step_batch: these would run AHEAD of the recorded launches)
@@ -1041,15 +1144,12 @@ static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_s
             A.tail_pending = false;
         }
         if (!last) {
-            if (!h->pm_pending) return fail(ICEM_E_STATE, "noise-ahead: the merge did not defer");
-            h->pm_args.n_raw = n;  // this pool keeps its noise: the next prologue maps the elite rows among rows [0, n)
-            h->pm_args.xf_lo = A.lo;
-            h->pm_args.xf_hi = A.hi;
-            cur_mean = pp;
-            cur_std = pp + hd;
+            h->ride.merge.n_raw = n;  // this pool keeps its noise: the next prologue maps the elite rows among rows [0, n)
+            h->ride.merge.xf_lo = A.lo;
+            h->ride.merge.xf_hi = A.hi;
         }
     }
-    A.ctr += (unsigned long long)(iters - 1);
+    s.end();
     return ICEM_OK;
 }
 
@@ -1060,171 +1160,72 @@ static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_s
 // (replicated) shifted elites.  Every pool is written back (the record pack gathers actions).  The last iteration's
 // pack and merge share one launch of their own, as on the sampler + rollout path.
 static int plan_step_sharded_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
-    icem_handle::Ahead& A = h->ahead;
     const icem_config& c = h->cfg;
     const int iters = c.opt_iters, K = c.num_elites, hd = h->hd;
-    int rc = ahead_setup(h);
+    AheadStep s{h, b, mpc_step, st, "noise-ahead (sharded)"};
+    int rc = s.begin();
     if (rc) return rc;
-    rc = ensure_fast_model(h);
+    rc = ensure_pub(h, st);
     if (rc) return rc;
-    if (!h->pub_dev) {
-        ICEM_HIP_TRY(hipMalloc((void**)&h->pub_dev, ((size_t)2 * hd + 16) * sizeof(float)));
-        ICEM_HIP_TRY(hipMemsetAsync(h->pub_dev, 0, ((size_t)2 * hd + 16) * sizeof(float), st));
-    }
-    const uint64_t call_base = (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(iters + 1);
-    auto pool_of = [&](int it) -> float* { return it == iters - 1 ? (float*)b->actions : (float*)A.pool[(A.ctr + (unsigned)it) % 3]; };
-    auto shard = [&](int it, int* lo_out) {
-        const int n_global = h->pop[it], chunk = shard_chunk(n_global, c.world);
-        const int lo = std::min(n_global, c.rank * chunk);
-        *lo_out = lo;
-        return std::max(0, std::min(n_global - lo, chunk));
-    };
-    auto noise_args = [&](int n, int lo, uint64_t off, void* out) {
-        return fast_sample_args(h, n, lo, nullptr, nullptr, nullptr, nullptr, off, 0, out, 0, nullptr, 0);
-    };
-    float* cur_mean = (float*)b->mean;
-    float* cur_std = (float*)b->std;
-    const int n_extra = (c.shift_elites && mpc_step > 0 && h->n_reuse > 0) ? h->n_reuse : 0;
+    const int n_extra = shift_rows(h, mpc_step, 0);
     float* rec = (float*)b->records + (size_t)c.rank * K * (hd + 2);
     PackPrev pack{};        // the previous iteration's pack, riding in this iteration's launch
     bool pack_pending = false;
     for (int it = 0; it < iters; ++it) {
         const bool last = it == iters - 1;
-        int lo = 0;
-        const int n_loc = shard(it, &lo);
-        const int n_global = h->pop[it];
-        float* pool = pool_of(it);
-        icem_plan_buffers bb = *b;
-        bb.actions = pool;
-        bb.mean = cur_mean;
-        bb.std = cur_std;
+        const Shard sh = shard_of(h, it);
+        const icem_plan_buffers bb = s.buffers(it);
+        float* pool = (float*)bb.actions;
         if (it == 0) {
-            const bool hit = A.next_valid && A.next_episode == h->episode && A.next_step == mpc_step && A.next_pool == pool &&
-                             A.next_stream == st;   // (another stream is not ordered behind the launch that drew it: a miss)
-            A.next_valid = false;
-            if (!hit) {
-                const FastSampleArgs za = noise_args(n_loc, lo, call_base, pool);
-                ProfScope prof(h, ICEM_K_SAMPLE, (long long)n_loc * c.horizon, st);
-                launch_noise_rows(za, c.rng_rounds, st);
-            }
-            ICEM_HIP_TRY(hipGetLastError());
+            bool hit = false;
+            rc = s.first_noise(sh, pool, &hit);
+            if (rc) return rc;
         }
         const int tail = (it == 0 && c.rank == 0) ? n_extra : 0;  // shifted elites: rank 0 submits them (they are replicated)
         IterAheadArgs ia{};
-        ia.r = fast_rollout_args(h, n_loc, n_loc, K, b->obs0, pool, b->costs, nullptr, nullptr);
-        ia.r.part_k = (unsigned long long*)b->workspace;
-        ia.n_xf = n_loc;
-        ia.row0_mean = (last && c.use_mean_actions && lo == 0) ? 1 : 0;
+        s.roll_role(ia, it, sh, bb);
         ia.store_back = 1;
-        ia.pool = pool;
-        ia.mean = cur_mean;
-        ia.std = cur_std;
-        ia.lo = A.lo;
-        ia.hi = A.hi;
         if (it > 0) {
-            if (!h->pm_pending || !pack_pending) return fail(ICEM_E_STATE, "noise-ahead (sharded): merge / pack not stashed");
+            if (!h->ride.merge_pending || !pack_pending) return fail(ICEM_E_STATE, "noise-ahead (sharded): merge / pack not stashed");
             ia.has_merge = 2;
-            ia.m = h->pm_args;
+            ia.m = h->ride.merge;
             ia.p = pack;
-            ia.p.pub = h->pub_dev;
-            ia.p.pub_flag = reinterpret_cast<unsigned*>(h->pub_dev + 2 * hd);
-            ia.p.pub_seq = ++h->pub_seq;
-            h->pm_pending = false;
+            set_pub(h, ia.p);
+            h->ride.merge_pending = false;
             pack_pending = false;
         }
+        // the noise role: the shard's rows of the next sampling call, or (last) of iteration 0 of the NEXT MPC step
+        const Shard nx = shard_of(h, last ? 0 : it + 1);
         if (!last) {
-            int lo1 = 0;
-            const int n1 = shard(it + 1, &lo1);
-            ia.z = noise_args(n1, lo1, call_base + (uint64_t)(it + 1), pool_of(it + 1));
+            ia.z = s.noise_args(nx.n_loc, nx.lo, s.base + (uint64_t)(it + 1), s.pool_of(it + 1));
         } else {
-            int lo0 = 0;
-            const int n0 = shard(0, &lo0);
-            void* np = A.pool[(A.ctr + (unsigned)(iters - 1)) % 3];
-            ia.z = noise_args(n0, lo0, (h->episode << 32) + (uint64_t)(mpc_step + 1) * (uint64_t)(iters + 1), np);
-            A.next_valid = true;
-            A.next_episode = h->episode;
-            A.next_step = mpc_step + 1;
-            A.next_pool = np;
-            A.next_stream = st;
+            void* np = s.next_step_pool();
+            ia.z = s.noise_args(nx.n_loc, nx.lo, call_base(h, mpc_step + 1), np);
+            s.arm_next(np);
         }
-        if (tail > 0) {
-            const int g = (int)(((long long)mpc_step * iters) & 1);
-            ia.s = fast_sample_args(h, n_loc, 0, cur_mean, cur_std, b->low, b->high, call_base, 0, pool, tail,
-                                    (const float*)b->elites + (size_t)g * K * hd, call_base + (uint64_t)iters);
-        }
-        {
-            ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n_loc * c.horizon, st);
-            launch_iter_ahead(ia, c.horizon, c.act_dim, h->Of, h->model_kind, st);
-        }
-        ICEM_HIP_TRY(hipGetLastError());
-        const int lists = ahead_roll_workgroups(n_loc);
-        h->fast_lists = lists;
-        h->fast_tail_rows = 0;
-        // ---- this iteration's pack: stashed for the next launch's workgroup 0, or (last) a launch of its own ----
-        MergeSingleArgs pk{};
-        pk.n_lists = lists;
-        pk.n_pool = n_loc + tail;
-        pk.n_global = n_global;
-        pk.K = K;
-        pk.h = c.horizon;
-        pk.d = c.act_dim;
-        pk.part_k = (const unsigned long long*)b->workspace;
-        pk.actions = pool;
-        if (tail > 0) {  // rank 0's shifted elites: extra candidates of the pack, costs from the cost array
-            pk.n_keep = tail;
-            pk.elites_cost_cur = (const float*)b->costs + n_loc;
-            pk.keep_base = n_loc;
-        }
+        s.shift_role(ia, sh.n_loc, pool, tail);
+        rc = s.launch(ia, sh.n_loc);
+        if (rc) return rc;
+        h->local.tail_rows = 0;
+        // ---- this iteration's pack: stashed for the next launch's workgroup 0, or (last) for the merge below, which takes
+        // it along in its own launch (pack_merge_kernel) ----
+        const MergeSingleArgs pk = local_pack_args(h, it, h->local.lists, sh.n_loc + tail, b->workspace, pool, sh.n_loc, tail, b->costs);
         XchgPush px;
         rc = xchg_begin(h, &px, &h->xw_last);
         if (rc) return rc;
         if (!last) {
-            pack.part_k = pk.part_k;
-            pack.actions = pk.actions;
-            pack.n_lists = pk.n_lists;
-            pack.n_pool = pk.n_pool;
-            pack.n_global = pk.n_global;
-            pack.K = K;
-            pack.n_loc = n_loc;
-            pack.shard_lo = lo;
-            pack.n_keep = pk.n_keep;
-            pack.keep_costs = pk.elites_cost_cur;
-            pack.records = rec;
-            pack.px = px;
+            pack = make_pack(pk, sh, rec, px);
             pack_pending = true;
         } else {
-            // the step's last pack: stashed for the merge below, which takes it along in its own launch (pack_merge_kernel)
-            PackPrev& pp = h->pk_args;
-            pp.part_k = pk.part_k;
-            pp.actions = pk.actions;
-            pp.n_lists = pk.n_lists;
-            pp.n_pool = pk.n_pool;
-            pp.n_global = pk.n_global;
-            pp.K = K;
-            pp.n_loc = n_loc;
-            pp.shard_lo = lo;
-            pp.n_keep = pk.n_keep;
-            pp.keep_costs = pk.elites_cost_cur;
-            pp.records = rec;
-            pp.px = px;
-            h->pk_pending = true;
+            h->ride.pack = make_pack(pk, sh, rec, px);
+            h->ride.pack_pending = true;
         }
         // ---- its merge (records form): stashed for the next launch's pack role, or (last) a launch with the pack ----
-        float* pp = h->pp_stats + (size_t)(it & 1) * 2 * hd;
-        h->defer_merge = !last;
-        h->merge_mean_out = last ? (float*)b->mean : pp;
-        h->merge_std_out = last ? (float*)b->std : pp + hd;
-        rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st);
-        h->defer_merge = false;
-        h->merge_mean_out = h->merge_std_out = nullptr;
+        rc = s.merge(bb, it);
         if (rc) return rc;
-        if (!last) {
-            if (!h->pm_pending || h->pm_args.records == nullptr) return fail(ICEM_E_STATE, "noise-ahead (sharded): the merge did not defer");
-            cur_mean = pp;
-            cur_std = pp + hd;
-        }
+        if (!last && h->ride.merge.records == nullptr) return fail(ICEM_E_STATE, "noise-ahead (sharded): the merge did not defer");
     }
-    A.ctr += (unsigned long long)(iters - 1);
+    s.end();
     return ICEM_OK;
 }
 
@@ -1239,13 +1240,13 @@ void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step,
     const int on = opt_i(OPT_PREDRAW);
     A.pre_valid = false;
     if (!on || c.world != 1 || c.dtype != ICEM_F32 || b->z_r != nullptr || !h->use_fast || gemm_rollout(h) || c.rng_rounds != 10 ||
-        h->dbg != nullptr || h->fast_lists <= 0 || c.num_elites + 1 > 12 || !fast_rollout_ok(h, c.num_elites) || !fast_sample_ok(h))
+        h->dbg != nullptr || h->local.lists <= 0 || c.num_elites + 1 > 12 || !fast_rollout_ok(h, c.num_elites) || !fast_sample_ok(h))
         return;
     const int n0 = h->pop[0];
     // (measured: N = 1000 66.7 -> 64.9, N = 4096 67.9 -> 65.9 us per MPC step; 8192 unchanged; at 16 384 the noise outlasts
     //  the merge it rides with, 89.4 -> 91.1: up to 8192 rows)
     if (n0 > 8192) return;
-    const int n_shift = (c.shift_elites && h->n_reuse > 0) ? h->n_reuse : 0;   // (mpc_step + 1 > 0: the next step shifts)
+    const int n_shift = shift_rows(h, mpc_step + 1, 0);
     if (n_shift * c.act_dim > 256) return;
     int tail_rows = 0;
     if (one_launch_lists(h, n0 + n_shift, n_shift, &tail_rows) <= 0) return;
@@ -1254,7 +1255,7 @@ void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step,
         A.pre_raw = nullptr;
         return;
     }
-    const uint64_t base_next = (h->episode << 32) + (uint64_t)(mpc_step + 1) * (uint64_t)(c.opt_iters + 1);
+    const uint64_t base_next = call_base(h, mpc_step + 1);
     A.tail_args = fast_sample_args(h, n0, 0, nullptr, nullptr, nullptr, nullptr, base_next, 0, A.pre_raw, 0, nullptr, 0);
     A.tail2_args = fast_sample_args(h, n_shift, 0, nullptr, nullptr, nullptr, nullptr, base_next + (uint64_t)c.opt_iters, 0,
                                     (float*)A.pre_raw + (size_t)n0 * h->hd, 0, nullptr, 0);
@@ -1331,7 +1332,7 @@ static bool deferral_active(const icem_handle* h, const icem_plan_buffers* b) {
 
 int icem_set_merge_deferral(icem_handle* h, int32_t on) {
     if (check_handle(h)) return ICEM_E_INVALID;
-    if (h->pm_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
+    if (h->ride.merge_pending) return fail(ICEM_E_STATE, "a deferred merge is pending: finish the MPC step first");
     h->deferral = on != 0;
     return ICEM_OK;
 }
@@ -1352,41 +1353,34 @@ int icem_plan_iter_local(icem_handle* h, const icem_plan_buffers* b, int32_t mpc
     return ICEM_DISPATCH(h, plan_iter_local_t<float>(h, &bb, mpc_step, it, st), plan_iter_local_t<double>(h, &bb, mpc_step, it, st));
 }
 
-int icem_plan_iter_merge(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, void* stream) {
-    int rc = check_plan(h, b, mpc_step, it, (hipStream_t)stream);
+// icem_plan_iter_merge with the merge's route given (icem_plan_step folds merges at world == 1 too)
+static int plan_iter_merge_routed(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, hipStream_t st, MergeRoute route) {
+    const int rc = check_plan(h, b, mpc_step, it, st);
     if (rc) return rc;
+    return ICEM_DISPATCH(h, plan_iter_merge_t<float>(h, b, mpc_step, it, st, route), plan_iter_merge_t<double>(h, b, mpc_step, it, st, route));
+}
+
+int icem_plan_iter_merge(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!deferral_active(h, b) || !h->cur_mean)
-        return ICEM_DISPATCH(h, plan_iter_merge_t<float>(h, b, mpc_step, it, st), plan_iter_merge_t<double>(h, b, mpc_step, it, st));
+    const bool deferred = h && b && deferral_active(h, b) && h->cur_mean;
+    if (!deferred) return plan_iter_merge_routed(h, b, mpc_step, it, st, MergeRoute());  // launched now, in place
+    int rc = check_plan(h, b, mpc_step, it, st);
+    if (rc) return rc;
     // sharded, deferral on: a non-last merge may ride in the next icem_plan_iter_local launch (mean / std / elites in
     // the caller's buffers are then current again only after that launch; the last merge always runs here)
     rc = ensure_pp_stats(h);
     if (rc) return rc;
     const bool last = it == h->cfg.opt_iters - 1;
-    // (the prologue's record selection holds two records per lane: world * K <= 128)
-    const bool fold = !last && h->fast_lists > 0 && h->cfg.world * h->cfg.num_elites <= 128 && h->cfg.num_elites <= 32 &&
-                      prologue_possible(h, local_rows(h, it + 1));
+    const bool fold = !last && h->local.lists > 0 && records_fit_prologue(h) && prologue_possible(h, shard_of(h, it + 1).n_loc);
     icem_plan_buffers bb = *b;
     bb.mean = h->cur_mean;
     bb.std = h->cur_std;
-    float* pp = h->pp_stats + (size_t)(it & 1) * 2 * h->hd;
-    h->defer_merge = fold;
-    if (last) {
-        h->merge_mean_out = (float*)b->mean;
-        h->merge_std_out = (float*)b->std;
-    } else if (fold) {
-        h->merge_mean_out = pp;
-        h->merge_std_out = pp + h->hd;
-    } else {
-        h->merge_mean_out = h->merge_std_out = nullptr;
-    }
-    rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st);
-    h->defer_merge = false;
-    h->merge_mean_out = h->merge_std_out = nullptr;
+    const MergeRoute route = merge_route(h, b, it, fold);
+    rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st, route);
     if (rc) return rc;
-    if (fold && h->pm_pending) {
-        h->cur_mean = pp;
-        h->cur_std = pp + h->hd;
+    if (fold && h->ride.merge_pending) {
+        h->cur_mean = route.mean_out;
+        h->cur_std = route.std_out;
     }
     if (last) h->cur_mean = h->cur_std = nullptr;
     return ICEM_OK;
@@ -1394,14 +1388,14 @@ int icem_plan_iter_merge(icem_handle* h, const icem_plan_buffers* b, int32_t mpc
 
 // A step that failed half way must not leave arguments armed for a later step's launches (stale merge / pack / noise
 // arguments would reach kernels with buffers of a step that never completed).
+static void disarm(icem_handle* h) {
+    h->ride.clear();
+    h->local.clear();
+    h->ahead.tail_pending = h->ahead.next_valid = h->ahead.pre_valid = false;
+    h->ahead.next1_rows = 0;
+}
 static int disarm_on_error(icem_handle* h, int rc) {
-    if (rc != ICEM_OK) {
-        h->ahead.tail_pending = h->ahead.next_valid = h->ahead.pre_valid = false;
-        h->ahead.next1_rows = 0;
-        h->pm_pending = h->pk_pending = false;
-        h->defer_merge = false;
-        h->merge_mean_out = h->merge_std_out = nullptr;
-    }
+    if (rc != ICEM_OK) disarm(h);
     return rc;
 }
 
@@ -1416,7 +1410,7 @@ static int plan_step_sharded_body(icem_handle* h, const icem_plan_buffers* b, in
     if (xchg_status_peek(h) & 1u)
         return fail(ICEM_E_STATE, "in-library exchange: a wait for a peer's elite records timed out in an earlier MPC step "
                                   "(icem_exchange_status reads and clears the word); the plans since then are not valid");
-    if (b && check_plan(h, b, mpc_step, 0, (hipStream_t)stream) == ICEM_OK && !h->pm_pending && !h->pk_pending && ahead_eligible(h, b, true))
+    if (b && check_plan(h, b, mpc_step, 0, (hipStream_t)stream) == ICEM_OK && !h->ride.merge_pending && !h->ride.pack_pending && ahead_eligible(h, b, true))
         return plan_step_sharded_ahead(h, b, mpc_step, (hipStream_t)stream);
     const bool was = h->deferral;
     h->deferral = true;  // non-last merges ride in the next local launch
@@ -1468,29 +1462,17 @@ static int plan_step_body(icem_handle* h, const icem_plan_buffers* b, int32_t mp
         const bool last = it == iters - 1;
         if (last) predraw_next_step(h, b, mpc_step, (hipStream_t)stream);  // small populations: the next step's first noise rides with the last merge
         bool fold = false;
-        if (pingpong && !last && h->fast_lists > 0) fold = prologue_possible(h, h->pop[it + 1]);
-        h->defer_merge = fold;
-        float* pp = pingpong ? h->pp_stats + (size_t)(it & 1) * 2 * h->hd : nullptr;
-        if (last) {  // the final distribution goes to the caller's buffers
-            h->merge_mean_out = (float*)b->mean;
-            h->merge_std_out = (float*)b->std;
-        } else if (fold) {
-            h->merge_mean_out = pp;
-            h->merge_std_out = pp + h->hd;
-        } else {
-            h->merge_mean_out = h->merge_std_out = nullptr;  // in place
-        }
-        rc = icem_plan_iter_merge(h, &bb, mpc_step, it, stream);
-        h->defer_merge = false;
-        h->merge_mean_out = h->merge_std_out = nullptr;
+        if (pingpong && !last && h->local.lists > 0) fold = prologue_possible(h, h->pop[it + 1]);
+        const MergeRoute route = merge_route(h, b, it, fold);
+        rc = plan_iter_merge_routed(h, &bb, mpc_step, it, (hipStream_t)stream, route);
         if (rc) return rc;
         if (last && h->ahead.tail_pending) {  // the merge that ran was not one that takes noise along: no noise was drawn
             h->ahead.tail_pending = false;
             h->ahead.pre_valid = false;
         }
-        if (fold && h->pm_pending) {
-            cur_mean = pp;
-            cur_std = pp + h->hd;
+        if (fold && h->ride.merge_pending) {
+            cur_mean = route.mean_out;
+            cur_std = route.std_out;
         }
     }
     return ICEM_OK;
@@ -1528,6 +1510,11 @@ static void batch_ctx_free(void* p) {
     delete c;
 }
 
+// bytes of one problem's argument block in the device array of a recorded launch
+static size_t batch_block_bytes(BatchKind kind) {
+    return kind == BATCH_SAMPLE_ROLLOUT ? sizeof(FastIterArgs) : kind == BATCH_ITER_AHEAD ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
+}
+
 static void sub_base(uint32_t& lo, uint32_t& hi, unsigned long long base) {
     const unsigned long long v = (((unsigned long long)hi << 32) | lo) - base;
     lo = (uint32_t)v;
@@ -1545,7 +1532,7 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     if (h->profiling || h->dbg) return "per-kernel profiling / debug stamps are per handle: switch them off";
     if (gemm_rollout(h) || h->hn_tile || h->Of == 0) return "only the 16-trajectory tile kernels (o <= 20 shapes) are batched";
     if (!fast_rollout_ok(h, K) || !fast_sample_ok(h) || K + 1 > 12 || c.rng_rounds != 10) return "shape outside the single-launch kernels";
-    if (h->pm_pending || h->pk_pending) return "a deferred merge is pending: finish the MPC step first";
+    if (h->ride.merge_pending || h->ride.pack_pending) return "a deferred merge is pending: finish the MPC step first";
     if (c.opt_iters < 1) return "opt_iters";
     // (g_batch.mult is set: the shapes below are the batch's.)  Where every iteration's rows of ALL problems together fill the
     // noise-ahead launch (>= 4 waves per rollout workgroup), the batch takes that path -- rollout, next noise and shifted elites
@@ -1560,7 +1547,7 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     }
     if (ahead_eligible(h, b)) return nullptr;   // (false without g_batch.ahead: option batch_ahead = 0)
     for (int it = 0; it < c.opt_iters; ++it) {
-        const int n_extra = (it == 0 && c.shift_elites && mpc_step > 0) ? h->n_reuse : 0;
+        const int n_extra = shift_rows(h, mpc_step, it, false);
         if (n_extra * c.act_dim > 256) return "too many shifted elites for the sampling launch";
         if (one_launch_lists(h, h->pop[it] + n_extra, n_extra) <= 0) return "an iteration's population has no single-launch kernel";
         if (it > 0 && !prologue_possible(h, h->pop[it])) return "an iteration cannot carry the previous merge in its prologue";
@@ -1607,11 +1594,21 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         if (const char* why = batch_ineligible(handles[i], &buffers[i], mpc_step))
             return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_batch: ") + why);
     // ---- the host side of every problem's step, recorded ----
+    // From here on the handles' host state runs ahead of the device: whatever return leaves before the last launch is
+    // enqueued takes every handle's armed state with it.
+    struct DisarmGuard {
+        icem_handle* const* handles;
+        int n;
+        bool armed = true;
+        ~DisarmGuard() {
+            for (int i = 0; armed && i < n; ++i) disarm(handles[i]);
+        }
+    } disarm_all{handles, n};
     std::vector<std::vector<BatchRecord>> recs(n);
     int rc = ICEM_OK;
     for (int i = 0; i < n && rc == ICEM_OK; ++i) {
         g_batch.rec = &recs[i];
-        rc = disarm_on_error(handles[i], plan_step_body(handles[i], &buffers[i], mpc_step, stream));
+        rc = plan_step_body(handles[i], &buffers[i], mpc_step, stream);
     }
     g_batch.rec = nullptr;
     if (rc == ICEM_OK && g_batch.unsupported) rc = fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a launch without a batched form was reached");
@@ -1621,44 +1618,41 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         for (size_t l = 0; l < L && rc == ICEM_OK; ++l) {
             const BatchRecord &x = recs[i][l], &y = recs[0][l];
             bool same = x.kind == y.kind;
-            if (same && x.kind == 1)
+            if (same && x.kind == BATCH_SAMPLE_ROLLOUT)
                 same = x.h == y.h && x.d == y.d && x.O == y.O && x.model_kind == y.model_kind && x.rw == y.rw && x.grid == y.grid &&
                        x.prologue == y.prologue && x.it.r.arith == y.it.r.arith;
-            if (same && x.kind == 4)
+            if (same && x.kind == BATCH_ITER_AHEAD)
                 same = x.h == y.h && x.d == y.d && x.O == y.O && x.model_kind == y.model_kind && x.rw == y.rw && x.grid == y.grid &&
                        x.ia.has_merge == y.ia.has_merge && x.ia.r.arith == y.ia.r.arith && x.ia.z.n == y.ia.z.n &&
                        x.ia.s.n_shift == y.ia.s.n_shift && x.ia.n_noise == y.ia.n_noise;
-            if (same && x.kind != 1 && x.kind != 4)
-                same = x.m.h == y.m.h && x.m.d == y.m.d && (x.kind == 2 || (x.z1.n == y.z1.n && x.z2.n == y.z2.n && x.z1.d == y.z1.d && x.z1.h == y.z1.h));
+            if (same && x.kind != BATCH_SAMPLE_ROLLOUT && x.kind != BATCH_ITER_AHEAD)
+                same = x.m.h == y.m.h && x.m.d == y.m.d && (x.kind == BATCH_MERGE_SINGLE || (x.z1.n == y.z1.n && x.z2.n == y.z2.n && x.z1.d == y.z1.d && x.z1.h == y.z1.h));
             if (!same) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' launches differ in shape");
         }
     }
-    if (rc != ICEM_OK) {   // nothing was launched: the handles' half-armed state goes
-        for (int i = 0; i < n; ++i) (void)disarm_on_error(handles[i], rc);
-        return rc;
-    }
+    if (rc != ICEM_OK) return rc;   // nothing was launched: the handles' half-armed state goes
     // ---- argument blocks: offsets relative to each problem's base of this step, one array per launch ----
     BatchBases bases{};
     for (int i = 0; i < n; ++i)
-        bases.v[i] = (handles[i]->episode << 32) + (unsigned long long)mpc_step * (unsigned long long)(handles[i]->cfg.opt_iters + 1);
+        bases.v[i] = call_base(handles[i], mpc_step);
     std::vector<size_t> at(L);
     size_t bytes = 0;
     for (size_t l = 0; l < L; ++l) {
         at[l] = bytes;
-        const size_t one = recs[0][l].kind == 1 ? sizeof(FastIterArgs) : recs[0][l].kind == 4 ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
+        const size_t one = batch_block_bytes(recs[0][l].kind);
         bytes += ((one * (size_t)n + 255) / 256) * 256;
     }
     std::vector<unsigned char> blob(bytes, 0);
     for (size_t l = 0; l < L; ++l)
         for (int i = 0; i < n; ++i) {
             BatchRecord& r = recs[i][l];
-            if (r.kind == 1) {
+            if (r.kind == BATCH_SAMPLE_ROLLOUT) {
                 FastIterArgs a = r.it;
                 if (a.s.n_shift == 0) a.s.off2_lo = (uint32_t)bases.v[i], a.s.off2_hi = (uint32_t)(bases.v[i] >> 32);   // (unused: kept at relative 0)
                 sub_base(a.s.off_lo, a.s.off_hi, bases.v[i]);
                 sub_base(a.s.off2_lo, a.s.off2_hi, bases.v[i]);
                 std::memcpy(blob.data() + at[l] + (size_t)i * sizeof(FastIterArgs), &a, sizeof(a));
-            } else if (r.kind == 4) {
+            } else if (r.kind == BATCH_ITER_AHEAD) {
                 IterAheadArgs a = r.ia;
                 a.r.dbg = nullptr;
                 if (a.z.n > 0) sub_base(a.z.off_lo, a.z.off_hi, bases.v[i]);
@@ -1677,7 +1671,7 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
             } else {
                 MergeNoiseBatchArgs g{};
                 g.a = r.m;
-                if (r.kind == 3) {
+                if (r.kind == BATCH_MERGE_NOISE) {
                     g.z1 = r.z1;
                     g.z2 = r.z2;
                     if (g.z1.n > 0) sub_base(g.z1.off_lo, g.z1.off_hi, bases.v[i]);
@@ -1714,10 +1708,10 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         if (opt_i(OPT_AHEAD_STAMPS) && ctx->shadow[slot].size() == bytes) {   // development: which bytes moved
             int shown = 0;
             for (size_t l = 0; l < L && shown < 12; ++l) {
-                const size_t one = recs[0][l].kind == 1 ? sizeof(FastIterArgs) : recs[0][l].kind == 4 ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
+                const size_t one = batch_block_bytes(recs[0][l].kind);
                 for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
                     if (blob[at[l] + o] != ctx->shadow[slot][at[l] + o]) {
-                        std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, recs[0][l].kind, o / one, o % one);
+                        std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, (int)recs[0][l].kind, o / one, o % one);
                         ++shown;
                         o = (o / 8 + 1) * 8 - 1;
                     }
@@ -1732,11 +1726,12 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
     for (size_t l = 0; l < L; ++l) {
         const BatchRecord& s = recs[0][l];
         const unsigned char* base = (const unsigned char*)ctx->dev[slot] + at[l];
-        if (s.kind == 1) launch_sample_rollout_batch(s, (const FastIterArgs*)base, bases, n, st);
-        else if (s.kind == 4) launch_iter_ahead_batch(s, (const IterAheadArgs*)base, bases, n, st);
+        if (s.kind == BATCH_SAMPLE_ROLLOUT) launch_sample_rollout_batch(s, (const FastIterArgs*)base, bases, n, st);
+        else if (s.kind == BATCH_ITER_AHEAD) launch_iter_ahead_batch(s, (const IterAheadArgs*)base, bases, n, st);
         else launch_merge_batch(s, (const MergeNoiseBatchArgs*)base, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
     }
+    disarm_all.armed = false;
     return ICEM_OK;
 }
 

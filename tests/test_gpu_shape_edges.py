@@ -66,7 +66,7 @@ CASES += [
 for _o in (7, 8, 9):   # pick_O's first padded width 8 (abi.hip:127): 7 pads, 8 does not, 9 pads to 16
     for _dt in ("f32", "f64"):
         CASES.append(_case(f"o{_o}_{_dt}", 12, 3, _o, dtype=_dt, kind=_o % 2, expect=GEMM if _dt == "f32" else None))
-# (30, 17, O = 24): o = 19..23 pad to the two-tile Tile16 (plan.hip:109-133) -- the tile route, padding columns included
+# (30, 17, O = 24): o = 19..23 pad to the two-tile Tile16 (plan.hip::ensure_fast_model) -- the tile route, padding columns included
 for _o in (19, 20, 21, 22, 23, 24):
     CASES.append(_case(f"o{_o}_d17_tile", 30, 17, _o, N=256, kind=1, beta=2.0, expect=TILE,
                        cost=dict(lin_idx=_o - 1, flip_idx=2, flip_thresh=0.5)))
@@ -92,7 +92,7 @@ CASES += [_case("K16_N33_f32", 12, 3, 8, K=16, N=33, expect=GEMM), _case("K17_N3
 for _K in (11, 12, 16, 17, 32, 33):   # ... and on the compiled tile shape (30, 6, 17)
     CASES.append(_case(f"K{_K}_tile_30_6_17", 30, 6, 17, K=_K, N=4 * _K + 1, kind=1, expect=TILE if _K <= 32 else None,
                        cost=dict(flip_thresh=1.2)))
-# ---- cost spec on a compiled shape (30, 6, 17): the tile's static cost columns (plan.hip:110-121)
+# ---- cost spec on a compiled shape (30, 6, 17): the tile's static cost columns (plan.hip::ensure_fast_model)
 CASES += [
     _case("cost_flip_eq_lin_tile", 30, 6, 17, N=512, expect=TILE, cost=dict(lin_idx=3, flip_idx=3, flip_thresh=0.4)),
     _case("cost_flip_eq_lin_tile_f64", 30, 6, 17, N=300, dtype="f64", cost=dict(lin_idx=3, flip_idx=3, flip_thresh=0.4)),
@@ -296,7 +296,7 @@ def test_set_model_refusals_leave_the_handle_planning(dtype, K, o_bad, o_good):
 
 # ---------------------------------------------------------------------------------------------- reconfiguration
 def test_reconfigured_handle_equals_a_fresh_one():
-    """The packed model is cached and invalidated by hand (ensure_fast_model, plan.hip:40; abi.hip:308, 382, 394, 537): one
+    """The packed model is cached and invalidated by hand (plan.hip::ensure_fast_model; abi.hip:308, 382, 394, 537): one
     handle taken through a sequence of route switches computes, after each, what a freshly built handle with the same final
     configuration computes -- rollout costs and one MPC step, bit for bit."""
     from icem_amd import IcemConfig, IcemPlanner, halfcheetah_env
