@@ -86,7 +86,8 @@ def up_to_date() -> bool:
     return not build_info()["stale"]
 
 
-def _compile(unit, headers_digest, verbose, faults=False):
+def _object(unit, headers_digest, faults=False):
+    """(compile command without -o, path of the object) of one unit for the sources in the tree."""
     src = os.path.join(CSRC, unit)
     extra = [f'-DICEM_BUILD_HASH="{source_hash()}"'] if unit == "abi.hip" else []  # the marker lives in one object
     if faults:
@@ -94,7 +95,18 @@ def _compile(unit, headers_digest, verbose, faults=False):
     cmd = [_hipcc(), *FLAGS, *UNIT_FLAGS.get(unit, []), *extra, "-I", CSRC, "-c", src]
     key = _digest([src], " ".join(cmd[1:-1]) + headers_digest)
     stem = os.path.splitext(unit)[0] + ("_faults" if faults else "")
-    obj = os.path.join(OBJ, f"{stem}.{key}.o")
+    return cmd, os.path.join(OBJ, f"{stem}.{key}.o")
+
+
+def object_path(unit: str) -> str:
+    """Where build() puts (or has put) the object of `unit` ("k_merge.hip") for the sources and flags as they are now --
+    for tools and tests that read the built code objects; the file exists only after a build of these sources."""
+    return _object(unit, _digest(_headers()))[1]
+
+
+def _compile(unit, headers_digest, verbose, faults=False):
+    cmd, obj = _object(unit, headers_digest, faults)
+    stem = os.path.splitext(unit)[0] + ("_faults" if faults else "")
     if not os.path.exists(obj):
         for f in os.listdir(OBJ):  # drop older objects of this unit
             if f.startswith(stem + ".") and f.endswith(".o"):

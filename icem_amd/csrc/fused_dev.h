@@ -1306,9 +1306,31 @@ __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned x) {
     return x;
 }
 
+// A key another lane / wave parked in LDS, re-read behind the fence (volatile: not forwarded from this lane's own store).
+// Typed as an LDS access: a volatile access through a generic pointer is a flat_load, which counts on BOTH memory counters
+// and is waited for with vmcnt(0) -- behind every global load still in flight.  (The candidate arrays are always __shared__.)
+// A pointer into device memory would be truncated to 32 bits by the cast: builds with -DICEM_DEBUG check it.
+__device__ __forceinline__ unsigned long long lds_reread_u64(const unsigned long long* p) {
+#ifdef ICEM_DEBUG
+    if (!__builtin_amdgcn_is_shared(p)) __builtin_trap();
+#endif
+    return *(const volatile __attribute__((address_space(3))) unsigned long long*)p;
+}
+
 // index the first kept candidate carries in its key: n_global (kept / shifted elites of the merges), or keep_base where
 // the caller indexes differently (a sharded rank's pack: its local pool row n_loc)
 __device__ __forceinline__ int keep_index0(const MergeSingleArgs& a) { return a.keep_base >= 0 ? a.keep_base : a.n_global; }
+
+// the kept elite's cost of lane `lane` (icem.py:143-145), requested in front of the lists' keys and consumed behind them.
+// The load is UNCONDITIONAL (no kept elites: the first word of part_k, and the value is dropped): behind a branch on the
+// pointer the compiler waits for it at the join -- one whole memory round trip in front of the keys' loads.  For the LISTS
+// form only: every caller reads part_k itself right behind this; the records form has no part_k (null) and must not call it.
+__device__ __forceinline__ float merge_keep_cost(const MergeSingleArgs& a, int lane) {
+    const bool has = a.elites_cost_cur != nullptr;
+    const float* src = has ? a.elites_cost_cur : reinterpret_cast<const float*>(a.part_k);
+    const float v = src[(has && lane < a.n_keep) ? lane : 0];
+    return has ? v : 0.f;
+}
 
 // Global sorted top-K of the candidate lists (+ kept elites): ONE wavefront; sel[0..K) receives the keys.
 // Lane t owns lists t, t+64, t+128, t+192 (each sorted) in registers; key r of list w sits at
@@ -1318,7 +1340,7 @@ __device__ __forceinline__ void merge_select(const MergeSingleArgs& a, int lane,
                                              unsigned long long* sel) {
     unsigned long long k[LPL][KREG];
     // (the kept elite's cost comes from another buffer: requested first, consumed behind the lists)
-    const float keep_cost = a.elites_cost_cur ? a.elites_cost_cur[lane < a.n_keep ? lane : 0] : 0.f;
+    const float keep_cost = merge_keep_cost(a, lane);
 #pragma unroll
     for (int l = 0; l < LPL; ++l) {
         const int list = lane + l * 64;
@@ -1379,7 +1401,7 @@ __device__ __forceinline__ void merge_select(const MergeSingleArgs& a, int lane,
     if (a.dbg && threadIdx.x == 0) a.dbg[3] = wall_clock64();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (n_cand <= 64) {
-        unsigned long long key = lane < (int)n_cand ? *((volatile unsigned long long*)&cand[lane]) : KEY_SENTINEL;
+        unsigned long long key = lane < (int)n_cand ? lds_reread_u64(&cand[lane]) : KEY_SENTINEL;
         key = wave_sort_n(key, lane, n_cand);
         if (lane < a.K) sel[lane] = key;
     } else {
@@ -1448,7 +1470,7 @@ __device__ __forceinline__ void merge_select_stream(const MergeSingleArgs& a, in
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (n_cand <= 64) {
-        unsigned long long key = lane < (int)n_cand ? *((volatile unsigned long long*)&cand[lane]) : KEY_SENTINEL;
+        unsigned long long key = lane < (int)n_cand ? lds_reread_u64(&cand[lane]) : KEY_SENTINEL;
         key = wave_sort_n(key, lane, n_cand);
         if (lane < K) sel[lane] = key;
     } else {
@@ -1484,7 +1506,7 @@ template <int DEPTH>
 __device__ __forceinline__ void merge_select_shallow(const MergeSingleArgs& a, int lane, unsigned long long* cand,
                                                      unsigned long long* sel) {
     const int K = a.K, nl = a.n_lists;
-    const float keep_cost = a.elites_cost_cur ? a.elites_cost_cur[lane < a.n_keep ? lane : 0] : 0.f;
+    const float keep_cost = merge_keep_cost(a, lane);
     unsigned long long k[LPL][DEPTH];
 #pragma unroll
     for (int l = 0; l < LPL; ++l) {
@@ -1536,7 +1558,7 @@ __device__ __forceinline__ void merge_select_shallow(const MergeSingleArgs& a, i
     offer(kept);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (n_cand <= 64) {
-        unsigned long long key = lane < (int)n_cand ? *((volatile unsigned long long*)&cand[lane]) : KEY_SENTINEL;
+        unsigned long long key = lane < (int)n_cand ? lds_reread_u64(&cand[lane]) : KEY_SENTINEL;
         key = wave_sort_n(key, lane, n_cand);
         if (lane < K) sel[lane] = key;
     } else {
@@ -1673,7 +1695,7 @@ __device__ __forceinline__ void merge_select_split_stage1(const MergeSingleArgs&
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     unsigned long long* out = wsel + w * 16;
     if (n_cand <= 64) {
-        unsigned long long key = lane < (int)n_cand ? *((volatile unsigned long long*)&cand[lane]) : KEY_SENTINEL;
+        unsigned long long key = lane < (int)n_cand ? lds_reread_u64(&cand[lane]) : KEY_SENTINEL;
         key = wave_sort_n(key, lane, n_cand);
         if (lane < 16) out[lane] = lane < a.K ? key : KEY_SENTINEL;
     } else {
@@ -1690,17 +1712,14 @@ __device__ __forceinline__ void merge_select_split_stage1(const MergeSingleArgs&
         if (lane >= a.K && lane < 16) out[lane] = KEY_SENTINEL;
     }
 }
-// the kept elite's cost of lane `lane` (icem.py:143-145) for stage 2: a cold load of its own -- callers request it in front
-// of stage 1 so that it travels with the lists' keys instead of behind the workgroup barrier
-__device__ __forceinline__ float merge_keep_cost(const MergeSingleArgs& a, int lane) {
-    return a.elites_cost_cur ? a.elites_cost_cur[lane < a.n_keep ? lane : 0] : 0.f;
-}
+// (the kept elite's cost for stage 2 -- merge_keep_cost, above -- is a cold load of its own: callers request it in front of
+// stage 1 so that it travels with the lists' keys instead of behind the workgroup barrier)
 __device__ __forceinline__ void merge_select_split_stage2(const MergeSingleArgs& a, int lane, int nw, const unsigned long long* wsel,
                                                           unsigned long long* cand, unsigned long long* sel, float keep_cost) {
     // nw * 16 <= 256 slots (sentinels behind each wave's K keys): four per lane, + kept elite `lane` (icem.py:143-145)
     unsigned long long k[5];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) k[j] = (lane + 64 * j < nw * 16) ? *((volatile const unsigned long long*)&wsel[lane + 64 * j]) : KEY_SENTINEL;
+    for (int j = 0; j < 4; ++j) k[j] = (lane + 64 * j < nw * 16) ? lds_reread_u64(&wsel[lane + 64 * j]) : KEY_SENTINEL;
     k[4] = (lane < a.n_keep && a.elites_cost_cur) ? make_key(keep_cost, keep_index0(a) + lane) : KEY_SENTINEL;
     unsigned long long mine = k[0];
 #pragma unroll
@@ -1718,7 +1737,7 @@ __device__ __forceinline__ void merge_select_split_stage2(const MergeSingleArgs&
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (n_cand <= 64) {
-        unsigned long long key = lane < (int)n_cand ? *((volatile unsigned long long*)&cand[lane]) : KEY_SENTINEL;
+        unsigned long long key = lane < (int)n_cand ? lds_reread_u64(&cand[lane]) : KEY_SENTINEL;
         key = wave_sort_n(key, lane, n_cand);
         if (lane < a.K) sel[lane] = key;
     } else {
@@ -1795,13 +1814,16 @@ __device__ __forceinline__ void merge_rows(const MergeSingleArgs& a, const unsig
     const float* mine;
     if (REC) mine = v < a.n_rec ? a.records + (size_t)v * (hd + 2) + 2 : a.elites_cur + (size_t)(v - a.n_rec) * hd;   // sharded run: candidates are records
     else mine = v < a.n_pool ? a.actions + (size_t)v * hd : a.elites_cur + (size_t)(v - a.n_global) * hd;
+    // ... as GLOBAL addresses: an integer turned back into a plain pointer is generic, and the whole gather would be
+    // flat_load (both counters, vmcnt(0) lgkmcnt(0) behind it); every row lives in device memory (pool, records, elites).
+    typedef const float __attribute__((address_space(1))) * GRow;
     const unsigned long long bits = (unsigned long long)(size_t)mine;
 #pragma unroll
     for (int r = 0; r < KREG; ++r) {
         const int rr = r < a.K ? r : 0;
         const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, rr);
         const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), rr);
-        rows[r] = reinterpret_cast<const float*>((size_t)(((unsigned long long)hi << 32) | lo));
+        rows[r] = (const float*)reinterpret_cast<GRow>((size_t)(((unsigned long long)hi << 32) | lo));
     }
 }
 

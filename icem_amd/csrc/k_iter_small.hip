@@ -109,8 +109,14 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
     const int base = wg * TPB;          // one slab of TPB trajectories per workgroup (launch_sample_rollout)
     if (base >= n_rows) return;
     if (ra.dbg && tid == 0 && wg == 0) ra.dbg[8] = wall_clock64();
-    // Order matters at this size: kernel arguments arrive through serialized scalar loads, so everything the RNG
-    // chain does not need (start observation, model operands, bounds) is fetched AFTER the sampling got going.
+    // Order matters at this size, and a load whose data the previous launch wrote is a memory round trip nothing overlaps,
+    // so every load whose address is known here is requested here and waited for ONCE:
+    //  * iteration 0 (no prologue): distribution, start observation, model operands, bounds and -- with the noise drawn
+    //    ahead -- the thread's share of the slab's raw rows and the shifted elites' values it will place: one wait, the
+    //    LDS writes, one barrier, then the affine map from LDS;
+    //  * merge-prologue launches: kernel arguments arrive through serialized scalar loads, so the sampling threads request
+    //    only their bounds (two registers parked across the draws) and get the RNG chain going; start observation and model
+    //    operands follow once the sampling is under way, in flight across the prologue's barriers.
     const int rowi = QS ? tid >> 2 : tid, q = tid & 3;  // QS: lane q of the row's quad
     const int nl = rowi / D, jd = rowi - nl * D;
     const bool has_row = rowi < ROWS;
@@ -129,28 +135,82 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             for (int i = 0; i < WPL; ++i) wreg[i] = sa.W[(i * 64 + lane) < WROWS * HMAX ? i * 64 + lane : 0];
         }
     }
-    if (!PM) {  // iteration 0 of an MPC step: the distribution is in memory; the model operands ride the same wait
+    const int r_mine = base + nl;
+    // the bounds of this thread's action dimension (jd < D whatever the thread): requested in front of everything that waits
+    float lo_reg = 0.f, hi_reg = 0.f;
+    if ((PM || pre_drawn) && tid < NT) {
+        lo_reg = sa.low[jd];
+        hi_reg = sa.high[jd];
+    }
+    // drawn-ahead iteration 0: the slab's raw rows (sampled rows, then the shifted elites' rows of stream off2) are one
+    // contiguous block, NVR vectors of it per thread (more than 4: the first 4 ride the entry's wait, the rest follow in rounds)
+    constexpr int NVR = !PM ? (TPB * (HD / VW) + NTT - 1) / NTT : 1;
+    constexpr int NVB = NVR < 4 ? NVR : 4;
+    // a shifted elite's row (QS: the quad lane's quarter of it) comes from the elite set: at most NEL values per thread
+    constexpr int NEL = !PM && QS ? (H - 1 + 3) / 4 : 1;
+    typedef float RawV __attribute__((ext_vector_type(VW)));   // (a native vector: an array of float4 structs stays in scratch)
+    RawV rawv[NVB];
+    float elv[NEL];
+    if (!PM) {  // iteration 0 of an MPC step: the distribution is in memory; everything below rides ONE wait
+        const int total4 = (n_rows - base < TPB ? n_rows - base : TPB) * (HD / VW);
+        RawV* t4 = reinterpret_cast<RawV*>(tile_rows);
+        float mreg[(HD + NTT - 1) / NTT], sreg[(HD + NTT - 1) / NTT];
+#pragma unroll
+        for (int i = 0; i < (HD + NTT - 1) / NTT; ++i) {
+            const int e = tid + i * NTT;
+            mreg[i] = sa.mean[e < HD ? e : 0];
+            sreg[i] = sa.std[e < HD ? e : 0];
+        }
+        if (pre_drawn) {
+            const RawV* g4 = reinterpret_cast<const RawV*>(sa.raw_src + (size_t)base * HD);
+#pragma unroll
+            for (int i = 0; i < NVB; ++i) {
+                const int e = tid + i * NTT;
+                rawv[i] = g4[e < total4 ? e : 0];
+            }
+            // (shapes without quad sampling -- none of them the headline's -- would hold H - 1 values per thread: they still
+            // fetch a shifted elite's row behind the barrier, below)
+            if constexpr (QS) {
+                if (has_row && tid < NT && r_mine >= sa.n && r_mine < n_rows) {
+                    const float* src = sa.elites_src + (size_t)(r_mine - sa.n) * HD + jd;
+#pragma unroll
+                    for (int i = 0; i < NEL; ++i) elv[i] = src[(q + 4 * i < H - 1 ? q + 4 * i + 1 : 1) * D];
+                }
+            }
+        }
         obs_reg = ra.obs0[(tid < 32 && tid < ra.o) ? tid : 0];
         if (wave < RWV) tile.load(ra, lane);
-        for (int e = tid; e < HD; e += NTT) {
-            ms[e] = sa.mean[e];
-            ms[HD + e] = sa.std[e];
+#pragma unroll
+        for (int i = 0; i < (HD + NTT - 1) / NTT; ++i) {
+            const int e = tid + i * NTT;
+            if (e < HD) {
+                ms[e] = mreg[i];
+                ms[HD + e] = sreg[i];
+            }
+        }
+        if (pre_drawn) {
+#pragma unroll
+            for (int i = 0; i < NVB; ++i) {
+                const int e = tid + i * NTT;
+                if (e < total4) t4[e] = rawv[i];
+            }
+            if constexpr (NVR > NVB) {
+                const RawV* g4 = reinterpret_cast<const RawV*>(sa.raw_src + (size_t)base * HD);
+                for (int e0 = tid + NVB * NTT; e0 < total4; e0 += NVB * NTT) {
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i) rawv[i] = g4[e0 + i * NTT < total4 ? e0 + i * NTT : 0];
+#pragma unroll
+                    for (int i = 0; i < NVB; ++i)
+                        if (e0 + i * NTT < total4) t4[e0 + i * NTT] = rawv[i];
+                }
+            }
         }
         __syncthreads();
     }
     if (ra.dbg && tid == 0 && wg == 0) ra.dbg[9] = wall_clock64();
-    const int r_mine = base + nl;
     if (pre_drawn) {
-        // the slab's raw rows (sampled rows, then the shifted elites' rows of stream off2) are one contiguous block
-        {
-            const int total4 = (n_rows - base < TPB ? n_rows - base : TPB) * (HD / VW);
-            const Vec* g4 = reinterpret_cast<const Vec*>(sa.raw_src + (size_t)base * HD);
-            Vec* t4 = reinterpret_cast<Vec*>(tile_rows);
-            for (int e = tid; e < total4; e += NTT) t4[e] = g4[e];
-        }
-        __syncthreads();
         if (has_row && tid < NT) {
-            const float lo = sa.low[jd], hi = sa.high[jd];
+            const float lo = lo_reg, hi = hi_reg;
             constexpr int QN = QS ? 4 : 1;
             const int q0 = QS ? q : 0;
             if (r_mine < sa.n) {  // y * std + mean, clipped (icem.py:79): the samplers' fmaf + v_med3
@@ -164,7 +224,13 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
                     const float v = __builtin_fmaf(trow[(H - 1) * D], mrow[HD + (H - 1) * D], mrow[(H - 1) * D]);
                     trow[(H - 1) * D] = __builtin_amdgcn_fmed3f(v, lo, hi);
                 }
-                for (int t = q0; t < H - 1; t += QN) trow[t * D] = src[(t + 1) * D];
+                if constexpr (QS) {
+#pragma unroll
+                    for (int i = 0; i < NEL; ++i)
+                        if (q + 4 * i < H - 1) trow[(q + 4 * i) * D] = elv[i];
+                } else {
+                    for (int t = q0; t < H - 1; t += QN) trow[t * D] = src[(t + 1) * D];
+                }
             } else {
                 for (int t = q0; t < H; t += QN) trow[t * D] = 0.f;  // past the end: rolled out, dropped
             }
@@ -217,6 +283,9 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             __syncthreads();
         }
         if (ra.dbg && tid == 0 && wg == 0) ra.dbg[5] = wall_clock64();
+        // (stamps 5 / 6 are overwritten by the step's last merge, which has its own: the lists form repeats them in 15 / 7 --
+        // slot 7 belongs to the records form, slot 15 to nobody -- tools/dbg/stamps.py)
+        if (!REC && ra.dbg && tid == 0 && wg == 0) ra.dbg[15] = wall_clock64();
         // all threads: gather the elite rows + refit (icem.py:201-211) -> this workgroup's mean / std
         const float* rows[KREG > 0 ? KREG : 1];
         merge_rows<KREG, REC>(m, sel, slot, rows);
@@ -239,8 +308,9 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
         if (wg == 0 && tid < m.K) m.elites_cost_next[tid] = key_cost(sel[tid]);
         __syncthreads();
         if (ra.dbg && tid == 0 && wg == 0) ra.dbg[6] = wall_clock64();
-        if (has_row && r_mine < sa.n) {  // y * std + mean, clipped (icem.py:79)
-            const float lo = sa.low[jd], hi = sa.high[jd];
+        if (!REC && ra.dbg && tid == 0 && wg == 0) ra.dbg[7] = wall_clock64();
+        if (has_row && r_mine < sa.n) {  // y * std + mean, clipped (icem.py:79); the bounds: requested in front of the draws
+            const float lo = lo_reg, hi = hi_reg;
             for (int t = QS ? q : 0; t < H; t += QS ? 4 : 1) {
                 const float v = __builtin_fmaf(trow[t * D], mrow[HD + t * D], mrow[t * D]);
                 trow[t * D] = __builtin_amdgcn_fmed3f(v, lo, hi);

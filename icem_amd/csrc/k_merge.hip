@@ -13,47 +13,71 @@ __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsi
     __shared__ unsigned long long sel[64];
     __shared__ unsigned long long cand[64];
     __shared__ int slot[64];
-    float* new_mean = reinterpret_cast<float*>(smem_raw);
+    // (typed as LDS: written inside the lambda below through a generic pointer, the stores were flat_store)
+    typedef float __attribute__((address_space(3))) * LdsF;
+    const LdsF new_mean = (LdsF)smem_raw;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int hd = a.h * a.d;
     if (a.dbg && threadIdx.x == 0) a.dbg[0] = wall_clock64();
-    // old mean/std of this thread's elements: issued now, consumed after the selection
+    // old mean/std of this thread's elements: issued now, consumed after the selection -- and, in the step's last merge, the
+    // bounds its epilogue resets the std from (behind the final barrier they were one more memory round trip)
     constexpr int EPL = 4;
     const bool pre = hd <= MERGE_WG * EPL;
-    float om[EPL], os[EPL];
+    float om[EPL], os[EPL], blo[EPL], bhi[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) {
         const int e = tid + i * MERGE_WG;
         om[i] = (pre && e < hd) ? a.mean[e] : 0.f;
         os[i] = (pre && e < hd) ? a.std[e] : 0.f;
     }
+    // (the bounds' index is a division by d: the selecting wave asks for them BEHIND its selection, where they ride the
+    // gather's round trip -- in front of it they put 0.4 us of address arithmetic and older loads before the keys')
+    auto request_bounds = [&]() {
+#pragma unroll
+        for (int i = 0; i < EPL; ++i) {
+            const int e = tid + i * MERGE_WG;
+            blo[i] = (pre && a.last && e < hd) ? a.low[e % a.d] : 0.f;
+            bhi[i] = (pre && a.last && e < hd) ? a.high[e % a.d] : 0.f;
+        }
+    };
+    // who asks when: the records form and waves 1..3 of the lists form here, at entry; wave 0 of the lists form -- the one
+    // that selects -- behind its selection, below.  Every thread asks exactly once, and only in the step's last merge.
+    if (REC || tid >= 64) request_bounds();
     if constexpr (REC) {
         merge_select_records_wg(a, tid < 64, lane, tid, MERGE_WG, sel, slot);   // (all threads: the records' keys ranked by counting)
         if (a.dbg && threadIdx.x == 0) a.dbg[4] = wall_clock64();
     } else {
         if (tid < 64) merge_select_shallow<3>(a, lane, cand, sel);
         if (a.dbg && threadIdx.x == 0) a.dbg[4] = wall_clock64();
+        if (tid < 64) request_bounds();   // (wave 0: in flight across the barrier, consumed in the epilogue)
         __syncthreads();
     }
     // ---- all 4 waves: gather + refit (icem.py:201-211); row pointers first, then all K loads in flight ----
     const float* rows[KREG];
     merge_rows<KREG, REC>(a, sel, slot, rows);
+    // (stores count on the same counter as loads here: a store between two of the gather's loads makes every later wait a
+    // wait for that store's acknowledgement.  So: all K loads, ONE wait for them (the refit needs them all anyway), and only
+    // then the K stores, back to back with nothing left to wait for.)
+    float best0 = 0.f;   // element `tid` of the best row: the executed action's, where tid < d (the epilogue)
     auto finish_one = [&](int e, float old_mean, float old_std) {
         float xs[KREG];
 #pragma unroll
         for (int r = 0; r < KREG; ++r) xs[r] = rows[r][e];
 #pragma unroll
-        for (int r = 0; r < KREG; ++r)
-            if (r < a.K) a.elites_next[(size_t)r * hd + e] = xs[r];
+        for (int r = 0; r < KREG; ++r) asm volatile("" : "+v"(xs[r]));   // every row's value has arrived HERE
         float nm, ns;
         refit_element_regs<float, KREG>(a.K, a.alpha, old_mean, old_std, xs, nm, ns);
+#pragma unroll
+        for (int r = 0; r < KREG; ++r)
+            if (r < a.K) a.elites_next[(size_t)r * hd + e] = xs[r];
         if (!a.last) {
             a.mean_out[e] = nm;
             a.std_out[e] = ns;
         } else {
             new_mean[e] = nm;
         }
+        if (e == tid) best0 = xs[0];
     };
     if (pre) {
 #pragma unroll
@@ -68,12 +92,23 @@ __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsi
     if (tid < a.K) a.elites_cost_next[tid] = key_cost(sel[tid]);
     if (a.last) {
         __syncthreads();
-        for (int e = tid; e < hd; e += MERGE_WG) {
-            const int j = e % a.d;
-            a.mean_out[e] = (e + a.d < hd) ? new_mean[e + a.d] : new_mean[e];
-            a.std_out[e] = (a.high[j] - a.low[j]) / 2.f * a.init_std;
+        if (pre) {   // (the bounds are in registers: request_bounds; the loop below is the same epilogue for hd > EPL * MERGE_WG)
+#pragma unroll
+            for (int i = 0; i < EPL; ++i) {
+                const int e = tid + i * MERGE_WG;
+                if (e < hd) {
+                    a.mean_out[e] = (e + a.d < hd) ? new_mean[e + a.d] : new_mean[e];
+                    a.std_out[e] = (bhi[i] - blo[i]) / 2.f * a.init_std;
+                }
+            }
+        } else {
+            for (int e = tid; e < hd; e += MERGE_WG) {
+                const int j = e % a.d;
+                a.mean_out[e] = (e + a.d < hd) ? new_mean[e + a.d] : new_mean[e];
+                a.std_out[e] = (a.high[j] - a.low[j]) / 2.f * a.init_std;
+            }
         }
-        if (tid < a.d) a.executed[tid] = rows[0][tid];
+        if (tid < a.d) a.executed[tid] = best0;   // rows[0][tid]: this thread gathered it (d <= hd: element tid is its first)
         if (tid == 0) a.best_cost[0] = key_cost(sel[0]);
     }
     if (a.dbg && threadIdx.x == 0) a.dbg[6] = wall_clock64();

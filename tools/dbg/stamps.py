@@ -21,20 +21,25 @@ for _ in range(5):
     pl.plan_step(obs)
 torch.cuda.synchronize()
 acc = np.zeros(16)
+pro = np.zeros(2)
+gap = 0.0
 R = 20
 for _ in range(R):
     pl.plan_step(obs); torch.cuda.synchronize()
     d = dbg.cpu().numpy().astype(np.float64)
     acc[:7] += (d[:7] - d[0]) / 100.0
     acc[8:15] += (d[8:15] - d[8]) / 100.0
-    gap = (d[0] - d[14]) / 100.0
-    acc[15] += gap
+    gap += (d[0] - d[14]) / 100.0 / R   # (slot 15 itself is a stamp of the prologue: pro, below)
+    pro += np.array([d[15] - d[8], d[7] - d[8]]) / 100.0 / R
 acc /= R
 print("merge  [us from kernel start]: lists loaded %.2f | keep merged %.2f | threshold+compact %.2f | selected %.2f | gather+refit %.2f | end %.2f" % tuple(acc[1:7]))
 # (stamp 12, "wave 0 rolled out", exists only on the Tile16 path; the Tile4 path of small populations goes straight to 13)
 print("single [us from kernel start]: staged %.2f | sampled %.2f | tile->HBM issued %.2f | rolled out %.2f | end %.2f"
       % (acc[9], acc[10], acc[11], acc[13], acc[14]))
 print("       wave 0 through its 30 steps (stamp 12, in front of the top-K push and the list): %.2f" % acc[12])
-print("gap end(single, wg 0) -> start(merge): %.2f us" % acc[15])
+print("gap end(single, wg 0) -> start(merge): %.2f us" % gap)
+if ITERS > 1:   # the prologue's own stamps 5 / 6, which the last merge overwrites: the lists form repeats them in slots 15 / 7
+    print("prologue of the last single launch [us from kernel start]: selection and sampling waves met %.2f | gather + refit done %.2f"
+          % (pro[0], pro[1]))
 print("(with ITERS > 1 the stamps are those of the LAST iteration: the single-launch kernel then carries the previous merge in its prologue"
       " and 'sampled' includes selection + gather + refit + affine map)")
