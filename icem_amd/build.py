@@ -93,7 +93,9 @@ def _object(unit, headers_digest, faults=False):
     if faults:
         extra.append("-DICEM_FAULT_INJECTION")
     cmd = [_hipcc(), *FLAGS, *UNIT_FLAGS.get(unit, []), *extra, "-I", CSRC, "-c", src]
-    key = _digest([src], " ".join(cmd[1:-1]) + headers_digest)
+    # (the key names the include directory as "csrc", not by its path: a built tree that is copied or moved keeps objects
+    # that object_path() finds -- tests/test_chain_isa_cpu.py reads them)
+    key = _digest([src], " ".join("csrc" if a == CSRC else a for a in cmd[1:-1]) + headers_digest)
     stem = os.path.splitext(unit)[0] + ("_faults" if faults else "")
     return cmd, os.path.join(OBJ, f"{stem}.{key}.o")
 

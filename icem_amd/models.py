@@ -306,13 +306,20 @@ def pack_rssm(module):
 class DeviceRSSMModel(ForwardModel):
     """The declared RSSM with its whole h-step rollout + cost fused into one HIP launch on the bf16 matrix cores
     (``icem_rssm_rollout_cost``); ``MpcICemHip`` scores a population with it in a single kernel.  ``reference`` is the
-    f32 torch module the weights come from (``predict`` serves the reference-style NumPy interface through it)."""
+    f32 torch module the weights come from (``predict`` serves the reference-style NumPy interface through it):
+    ``declared_rssm(seed)``'s, or a copy of the caller's ``module`` -- any module of the declared sizes with the declared
+    parameter names, e.g. a ``declared_rssm(...).module`` whose weights were trained or edited."""
 
-    def __init__(self, seed: int = 0, device="cuda:0", env=None):
+    def __init__(self, seed: int = 0, device="cuda:0", env=None, module=None):
         super().__init__(env=env)
         import torch
         from . import _lib as L
-        self._tm = declared_rssm(seed=seed, device=device)
+        if module is None:
+            self._tm = declared_rssm(seed=seed, device=device)
+        else:
+            import copy
+            net = copy.deepcopy(module).float()
+            self._tm = TorchForwardModel(net, lambda o, a: -net.reward(o), net.det + net.stoch, 6, device=device, env=env)
         self.reference = self._tm.module
         self.obs_dim, self.act_dim = 230, 6
         self.device = torch.device(device)

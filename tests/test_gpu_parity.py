@@ -1876,35 +1876,10 @@ def test_fused_rssm_rollout_kernel(mode, n, h):
     obs = 0.3 * rs.randn(230)
     got = np_(m.rollout_cost(obs, torch.as_tensor(acts, dtype=torch.float32, device="cuda"), {"sum": 0, "best": 1, "final": 2}[mode]))
 
-    def bf(x):   # round to bf16 (nearest even), back to float64
-        return torch.as_tensor(np.asarray(x, dtype=np.float32)).to(torch.bfloat16).to(torch.float64).numpy()
-
-    P = {k: v.detach().cpu().double().numpy() for k, v in m.reference.state_dict().items()}
-    sig = lambda x: 1.0 / (1.0 + np.exp(-x))  # noqa: E731
-
-    def rollout(q):   # q: rounding applied to weights and to every GEMM input (identity = the exact network)
-        W = {k: (q(v) if k.endswith("weight") or "weight_" in k else v) for k, v in P.items()}
-        hh = np.broadcast_to(obs[:200].astype(np.float32).astype(np.float64), (n, 200)).copy()
-        z = np.broadcast_to(obs[200:].astype(np.float32).astype(np.float64), (n, 30)).copy()
-        steps = []
-        for t in range(h):
-            hq, zq, aq = q(hh), q(z), q(acts[:, t])
-            a1 = q(np.maximum(np.concatenate([hq, zq], -1) @ W["rew1.weight"].T + P["rew1.bias"], 0))
-            a2 = q(np.maximum(a1 @ W["rew2.weight"].T + P["rew2.bias"], 0))
-            steps.append(-(a2 @ W["rew3.weight"].T + P["rew3.bias"])[:, 0])
-            x = q(np.maximum(np.concatenate([zq, aq], -1) @ W["inp.weight"].T + P["inp.bias"], 0))
-            gi = x @ W["gru.weight_ih"].T + P["gru.bias_ih"]
-            gh = hq @ W["gru.weight_hh"].T + P["gru.bias_hh"]
-            r = sig(gi[:, :200] + gh[:, :200])
-            u = sig(gi[:, 200:400] + gh[:, 200:400])
-            nn = np.tanh(gi[:, 400:] + r * gh[:, 400:])
-            hh = (1 - u) * nn + u * hh
-            p = q(np.maximum(q(hh) @ W["prior1.weight"].T + P["prior1.bias"], 0))
-            z = p @ W["prior2.weight"].T + P["prior2.bias"]
-        s = np.stack(steps, 1)
-        return {"sum": s.sum(1), "best": s.min(1), "final": s[:, -1]}[mode]
-
-    emu, exact = rollout(bf), rollout(lambda x: x)
+    # q: rounding applied to weights and to every GEMM input (none = the exact network); oracle/rssm_oracle.py
+    from oracle import rssm_oracle as RO
+    P = RO.params_from_state_dict(m.reference.state_dict())
+    emu, exact = RO.emulated_costs(P, obs, acts, mode, q=RO.bf16), RO.emulated_costs(P, obs, acts, mode)
     scale = 1 + np.abs(exact).max()
     assert np.abs(got - emu).max() <= 2e-3 * scale, (np.abs(got - emu).max(), scale)
     assert np.abs(got - exact).max() <= 5e-2 * scale
