@@ -714,31 +714,159 @@ def rollout_costs(model: SyntheticModel, cost: CostSpec, obs0, actions, mode="su
     return acc
 
 
-def rollout_cost_magnitudes(model: SyntheticModel, cost: CostSpec, obs0, actions):
+def _magnitude_addends(cost: CostSpec, obs, a, nxt):
+    """The |addend|s of one step's cost, in the order :func:`rollout_cost_magnitudes` has always added them."""
+    if cost.flip_idx >= 0:
+        yield (np.abs(obs[:, cost.flip_idx]) > cost.flip_thresh) * abs(cost.flip_penalty)
+    yield abs(cost.ctrl_weight) * (a * a).sum(axis=1)
+    if cost.lin_weight != 0:
+        yield abs(cost.lin_weight) * np.abs(obs[:, cost.lin_idx])
+    if getattr(cost, "diff_idx", -1) >= 0:   # |diff_weight| (|next_obs[i]| + |obs[i]|): both operands of the difference
+        yield abs(cost.diff_weight) * (np.abs(nxt[:, cost.diff_idx]) + np.abs(obs[:, cost.diff_idx]))
+    if getattr(cost, "health_idx", -1) >= 0:   # the health penalty where it is scored
+        yield abs(cost.health_penalty) * cost.unhealthy(obs)
+    for tm in getattr(cost, "terms", ()):   # the term list (icem_cost_terms): |weight x f x gate| of every term
+        yield np.abs(cost.term_value(tm, obs))
+
+
+def rollout_cost_magnitudes(model: SyntheticModel, cost: CostSpec, obs0, actions, mode="sum"):
     """``sum_t sum |addend|`` of every trajectory's "sum"-mode cost (the HalfCheetah / HumanoidStandup form): the scale a
     rounding-error bound on that cost has to be relative to -- a trajectory whose positive and negative terms cancel has
     a small cost but not a small error.  Used by the at-size parity tests (north_star's 1e-5 relative, taken relative to
-    this magnitude instead of padded with an absolute floor); same rollout as :func:`rollout_costs`."""
+    this magnitude instead of padded with an absolute floor); same rollout as :func:`rollout_costs`.
+
+    ``mode="final"``: ``sum |addend|`` of the last scored step only; ``mode="best"``: that of the step the float64
+    minimum is taken at (the first such step, as ``np.argmin``) -- the scale of what those two reductions return."""
+    if mode not in ("sum", "best", "final"):
+        raise NotImplementedError(mode)
     actions = np.asarray(actions, dtype=np.float64)
     P, h, _ = actions.shape
     obs = np.broadcast_to(np.asarray(obs0, dtype=np.float64), (P, len(obs0))).copy()
     mag = np.zeros(P)
+    best = None
     for t in range(h):
         a = actions[:, t]
-        if cost.flip_idx >= 0:
-            mag += (np.abs(obs[:, cost.flip_idx]) > cost.flip_thresh) * abs(cost.flip_penalty)
-        mag += abs(cost.ctrl_weight) * (a * a).sum(axis=1)
-        if cost.lin_weight != 0:
-            mag += abs(cost.lin_weight) * np.abs(obs[:, cost.lin_idx])
         nxt = model.predict(obs, a)
-        if getattr(cost, "diff_idx", -1) >= 0:   # |diff_weight| (|next_obs[i]| + |obs[i]|): both operands of the difference
-            mag += abs(cost.diff_weight) * (np.abs(nxt[:, cost.diff_idx]) + np.abs(obs[:, cost.diff_idx]))
-        if getattr(cost, "health_idx", -1) >= 0:   # the health penalty where it is scored
-            mag += abs(cost.health_penalty) * cost.unhealthy(obs)
-        for tm in getattr(cost, "terms", ()):   # the term list (icem_cost_terms): |weight x f x gate| of every term
-            mag += np.abs(cost.term_value(tm, obs))
+        if mode == "sum":
+            for add in _magnitude_addends(cost, obs, a, nxt):
+                mag += add
+        else:
+            step = np.zeros(P)
+            for add in _magnitude_addends(cost, obs, a, nxt):
+                step += add
+            if mode == "final":
+                mag = step
+            else:
+                c = _step_cost(cost, obs, a, nxt, np.float64)
+                take = np.ones(P, dtype=bool) if best is None else (c < best) | np.isnan(c)
+                best = c if best is None else np.where(take, c, best)
+                mag = np.where(take, step, mag)
         obs = nxt
     return mag
+
+
+def trajectory_cost_magnitudes(cost: CostSpec, observations, actions, next_observations=None, mode="sum"):
+    """:func:`rollout_cost_magnitudes` over rollouts held as arrays (``observations / next_observations [P, h, o]``, ``actions
+    [P, h, d]``), as :func:`spec_trajectory_costs` is to :func:`rollout_costs`: the same additions on the same values."""
+    if mode not in ("sum", "best", "final"):
+        raise NotImplementedError(mode)
+    observations, actions = np.asarray(observations, dtype=np.float64), np.asarray(actions, dtype=np.float64)
+    P, h, _ = actions.shape
+    mag, best = np.zeros(P), None
+    for t in range(h):
+        obs, a = observations[:, t], actions[:, t]
+        nxt = None if next_observations is None else np.asarray(next_observations[:, t], dtype=np.float64)
+        if mode == "sum":
+            for add in _magnitude_addends(cost, obs, a, nxt):
+                mag += add
+            continue
+        step = np.zeros(P)
+        for add in _magnitude_addends(cost, obs, a, nxt):
+            step += add
+        if mode == "final":
+            mag = step
+        else:
+            c = _step_cost(cost, obs, a, nxt, np.float64)
+            take = np.ones(P, dtype=bool) if best is None else (c < best) | np.isnan(c)
+            best = c if best is None else np.where(take, c, best)
+            mag = np.where(take, step, mag)
+    return mag
+
+
+def _comparisons(cost: CostSpec, obs):
+    """(name, compared quantity - threshold) for every comparison the cost makes on the pre-action observations ``obs
+    [P, o]``: the sign of the difference is the comparison's outcome, its size the distance to the threshold."""
+    if cost.flip_idx >= 0:
+        ang = obs[:, cost.flip_idx]
+        yield "flip>", ang - cost.flip_thresh
+        yield "flip<", -cost.flip_thresh - ang
+    if cost.health_idx >= 0:
+        z = obs[:, cost.health_idx]
+        if np.isfinite(cost.health_lo):
+            yield "health_lo", z - cost.health_lo
+        if np.isfinite(cost.health_hi):
+            yield "health_hi", cost.health_hi - z
+        if cost.box_from >= 0:   # the box holds when every entry is inside: the entry nearest to a wall decides
+            st = obs[:, cost.box_from:]
+            yield "box", np.minimum(st - cost.box_lo, cost.box_hi - st).min(axis=1)
+    for j, tm in enumerate(cost.terms):
+        if tm.kind == TERM_STEP_GT:
+            yield f"term{j}:step_gt", obs[:, tm.a] - tm.thresh
+        elif tm.kind in (TERM_NORM_GT, TERM_NORM_LT):
+            v = obs[:, tm.a:tm.a + tm.len]
+            if tm.b >= 0:
+                v = v - obs[:, tm.b:tm.b + tm.len]
+            r = np.sqrt((v * v).sum(axis=1))
+            yield f"term{j}:{'norm_gt' if tm.kind == TERM_NORM_GT else 'norm_lt'}", \
+                (r - tm.thresh) if tm.kind == TERM_NORM_GT else (tm.thresh - r)
+        if tm.gate_idx >= 0:
+            yield f"term{j}:gate", obs[:, tm.gate_idx] - tm.gate_thresh
+
+
+def _kernel_inputs_rollout(model: SyntheticModel, obs0, actions):
+    """The float64 rollout of the inputs the f32 kernels see (observation and actions rounded to f32 first): ``[P, h, o]``."""
+    acts = np.asarray(actions).astype(np.float32).astype(np.float64)
+    ob = np.asarray(obs0).astype(np.float32).astype(np.float64)
+    return rollout_observations(model, ob, acts)
+
+
+def threshold_margins(model: SyntheticModel, cost: CostSpec, obs0, actions):
+    """Per trajectory, the smallest distance between a compared quantity and its threshold over all scored steps and all
+    comparisons of the spec -- flip (both signs), STEP_GT, NORM_GT, NORM_LT, every gate, the health range and the box --
+    divided by the trajectory's largest |state entry|: how large a relative state error has to be before an indicator
+    of this trajectory can come out the other way.  ``inf`` for a spec without comparisons.  Float64, on the rollout the
+    f32 kernels see (observation and actions rounded to f32 first)."""
+    return observation_margins(cost, _kernel_inputs_rollout(model, obs0, actions))
+
+
+def observation_margins(cost: CostSpec, observations):
+    """:func:`threshold_margins` of rollouts held as an array ``[P, h, o]`` of pre-action observations."""
+    obs = np.asarray(observations, dtype=np.float64)
+    P, h, _ = obs.shape
+    margin = np.full(P, np.inf)
+    for t in range(h):
+        for _, dist in _comparisons(cost, obs[:, t]):
+            margin = np.minimum(margin, np.abs(dist))
+    scale = np.abs(obs).max(axis=(1, 2))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(np.isfinite(margin), margin / scale, np.inf)
+
+
+def comparison_shares(model: SyntheticModel, cost: CostSpec, obs0, actions) -> dict:
+    """{comparison: share of the trajectories on which it is true at some scored step and false at another}: what a case
+    has to show before it can tell a wrong threshold, a dropped indicator or a wrong gate from the right one."""
+    return observation_comparison_shares(cost, _kernel_inputs_rollout(model, obs0, actions))
+
+
+def observation_comparison_shares(cost: CostSpec, observations) -> dict:
+    """:func:`comparison_shares` of rollouts held as an array ``[P, h, o]`` of pre-action observations."""
+    obs = np.asarray(observations, dtype=np.float64)
+    seen_true, seen_false = {}, {}
+    for t in range(obs.shape[1]):
+        for name, dist in _comparisons(cost, obs[:, t]):
+            seen_true[name] = seen_true.get(name, False) | (dist > 0)
+            seen_false[name] = seen_false.get(name, False) | ~(dist > 0)
+    return {name: float(np.mean(seen_true[name] & seen_false[name])) for name in seen_true}
 
 
 # --------------------------------------------------------------------------

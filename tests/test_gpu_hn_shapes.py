@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import cost_term_cases as CC
 from oracle import icem_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +58,15 @@ def test_rollout_on_tilehn_matches_the_float64_oracle(name, kind, mode):
     mag = O.rollout_cost_magnitudes(om, spec, obs0, acts)
     ok = np.abs(got - want) <= 1e-5 * mag
     assert ok.mean() > 0.99, (ok.mean(), np.abs(got - want).max())
+    # ... and the rows it excuses ARE the ones an f32 state can take across a threshold (oracle.threshold_margins; NEAR, the
+    # per-mode magnitude and the state term as in cost_term_cases.py, which holds these kernels to a table made for them)
+    near = O.threshold_margins(om, spec, obs0, acts) <= CC.NEAR
+    assert np.all(ok | near), (np.nonzero(~(ok | near))[0][:8], (np.abs(got - want) / mag)[~(ok | near)][:8])
+    mag_mode = O.rollout_cost_magnitudes(om, spec, obs0, acts, mode=mode)
+    smax = np.abs(O.rollout_observations(om, obs0.astype(np.float32).astype(np.float64), acts)).max(axis=(1, 2))
+    mag_mode = mag_mode + CC.state_weight(spec) * smax * (30 if mode == "sum" else 1)
+    ok_mode = np.abs(got - want) <= 1e-5 * mag_mode
+    assert np.all(ok_mode | near), (mode, np.nonzero(~(ok_mode | near))[0][:8], (np.abs(got - want) / mag_mode)[~(ok_mode | near)][:8])
     if mode == "sum":
         assert np.median(np.abs(got - want) / mag) < 2e-6
     # the exact-f32 GEMM kernel on request (icem_set_tile_arith 0): the same costs to f32 rounding
@@ -64,6 +74,7 @@ def test_rollout_on_tilehn_matches_the_float64_oracle(name, kind, mode):
     exact = np_(pl.rollout_cost(obs0, torch.as_tensor(acts, dtype=pl.dt, device=pl.device)))
     close = np.abs(exact - got) <= 1e-4 * (1 + np.abs(want))
     assert close.mean() > 0.99 and not np.array_equal(exact, got)
+    assert np.all(close | near), np.nonzero(~(close | near))[0][:8]
 
 
 @pytest.mark.parametrize("name", ["door", "relocate", "fpp"])
@@ -89,6 +100,8 @@ def test_whole_mpc_steps_on_tilehn(name):
         mag = O.rollout_cost_magnitudes(om, spec, ob.astype(np.float32).astype(np.float64), pool)
         dev = np_(pl.costs[:n_last])
         assert (np.abs(dev - rescored) <= 1e-5 * mag).mean() > 0.99
+        near = O.threshold_margins(om, spec, ob, pool) <= CC.NEAR   # the excused rows are near a threshold
+        assert np.all((np.abs(dev - rescored) <= 1e-5 * mag) | near), np.nonzero(~((np.abs(dev - rescored) <= 1e-5 * mag) | near))[0][:8]
 
 
 def test_term_lists_outside_the_compiled_programs_keep_the_gemm_kernel():

@@ -1368,6 +1368,9 @@ def test_rollout_and_plan_with_cost_terms(env_name, dtype):
     else:   # an f32 tanh one ulp off can move a step across a threshold: allow a few whole-penalty mismatches
         close = np.abs(got - want) <= 1e-4 * (1 + np.abs(want))
         assert close.mean() > 0.98
+        import cost_term_cases as CC   # ... and every excused row is near a threshold (oracle.threshold_margins)
+        near = O.threshold_margins(om, spec, obs0, acts) <= CC.NEAR
+        assert np.all(close | near), np.nonzero(~(close | near))[0][:8]
     if env_name == "hopper":   # trajectories with no, some and many unhealthy steps are all in the batch
         import dataclasses
         count = O.rollout_costs(om, dataclasses.replace(spec, diff_idx=-1, ctrl_weight=0.0, health_penalty=1.0), obs0, acts)
@@ -1463,6 +1466,9 @@ def test_wide_rollout_with_cost_terms(env_name):
     def close(a, b):   # an f32 tanh one ulp off can move a step across a threshold: a few whole-penalty mismatches
         return np.abs(a - b) <= 1e-4 * (1 + np.abs(b))
     assert close(got, want).mean() > 0.98, (np.abs(got - want).max(), close(got, want).mean())
+    import cost_term_cases as CC   # ... and every excused row is near a threshold (oracle.threshold_margins)
+    near = O.threshold_margins(om, spec, obs0, acts) <= CC.NEAR
+    assert np.all(close(got, want) | near), np.nonzero(~(close(got, want) | near))[0][:8]
     if env_name in ("ant", "humanoid"):   # no, some and many unhealthy steps are all in the batch
         import dataclasses
         count = O.rollout_costs(om, dataclasses.replace(spec, diff_idx=-1, ctrl_weight=0.0, lin_weight=0.0, health_penalty=1.0), obs0, acts)
@@ -1477,6 +1483,11 @@ def test_wide_rollout_with_cost_terms(env_name):
             gm = np_(pm.rollout_cost(obs0, torch.as_tensor(acts, dtype=pm.dt, device=pm.device)))
             wm = O.rollout_costs(om, spec, obs0, acts, mode=mode).astype(np.float64)
             assert close(gm, wm).mean() > 0.98, (mode, np.abs(gm - wm).max())
+            assert np.all(close(gm, wm) | near), (mode, np.nonzero(~(close(gm, wm) | near))[0][:8])
+            # the scale of what this reduction returns: the per-mode magnitude (+ the state term of cost_term_cases.py)
+            smax = np.abs(O.rollout_observations(om, obs0.astype(np.float32).astype(np.float64), acts)).max(axis=(1, 2))
+            mm = O.rollout_cost_magnitudes(om, spec, obs0, acts, mode=mode) + CC.state_weight(spec) * smax
+            assert np.all((np.abs(gm - wm) <= 1e-5 * mm) | near), (mode, (np.abs(gm - wm) / mm)[~near].max())
     for s_ in range(2):   # whole MPC steps: the pool of the last iteration holds sampled rows and shifted-elite rows
         ob = 0.2 * np.random.RandomState(20 + s_).randn(o)
         a0 = np_(pl.plan_step(ob))
@@ -1486,6 +1497,8 @@ def test_wide_rollout_with_cost_terms(env_name):
         rescored = O.rollout_costs(om, spec, ob.astype(np.float32).astype(np.float64), pool).astype(np.float64)
         dev = np_(pl.costs[:n_last]).astype(np.float64)
         assert close(dev, rescored).mean() > 0.98, (np.abs(dev - rescored).max(), close(dev, rescored).mean())
+        near_pool = O.threshold_margins(om, spec, ob, pool) <= CC.NEAR
+        assert np.all(close(dev, rescored) | near_pool), np.nonzero(~(close(dev, rescored) | near_pool))[0][:8]
     # one iteration per MPC step: from the second step on the pool is N sampled rows (whole tiles) + the shifted elites,
     # which rollout_rows_wide_kernel scores row by row
     p1 = IcemPlanner(IcemConfig(horizon=h, act_dim=d, num_traj=N, opt_iters=1, dtype="f32", seed=9),
