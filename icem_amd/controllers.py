@@ -23,6 +23,7 @@ from __future__ import annotations
 
 from abc import ABC, abstractmethod
 from collections.abc import Mapping
+from dataclasses import replace
 from importlib import import_module
 from typing import Callable, Optional, Union
 from warnings import warn
@@ -583,27 +584,37 @@ class MpcICemHip(MpcController):
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152) -- through ``icem_plan_step_batch``:
         every stage of the planning step is one launch for all of them.  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same hooks).  Device path with
-        device noise only; anything else: call ``get_action`` per controller."""
+        device noise; or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
+        one configuration: their populations are scored by ONE ``rollout_cost_batch`` launch per CEM iteration (sampling and
+        the distribution update stay one launch per controller).  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)
         n = len(ctrls)
         states = [None] * n if states is None else list(states)
         for c in ctrls:
             if not c.was_reset:
                 raise AttributeError("beginning_of_rollout() needs to be called before")
-            if not c.device_path or c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose:
-                raise NotImplementedError("get_action_batch: device path, Philox noise, one GPU, not verbose")
+        rssm = any(c.rssm_path for c in ctrls)   # learned dynamics: the stage-wise step around one cost launch per iteration
+        if rssm:
+            why = MpcICemHip._rssm_batch_refusal(ctrls)
+            if why:
+                raise NotImplementedError("get_action_batch: " + why)
+        elif any(not c.device_path or c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose for c in ctrls):
+            raise NotImplementedError("get_action_batch: device path, Philox noise, one GPU, not verbose")
         for c, ob, stt in zip(ctrls, observations, states):
             c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
                 observation=ob, env_state=stt, model_state=c.forward_model_state)
-        IcemPlanner.plan_step_batch([c.planner for c in ctrls], observations)
-        host = torch.stack([torch.cat([c.planner.executed, c.planner.best_cost]) for c in ctrls]).cpu().numpy().astype(np.float64)  # one D2H sync
-        # what icem_get_action reports for a solo step: non-finite costs out of a finite observation (ICEM_E_RANGE)
-        from ._lib import IcemError, ICEM_E_RANGE
-        for c, ob in zip(ctrls, observations):
-            seen = c.planner.nonfinite_costs()
-            fresh, c._nonfinite_seen = seen - getattr(c, "_nonfinite_seen", 0), seen
-            if fresh and np.all(np.isfinite(np.asarray(ob, dtype=np.float64))):
-                raise IcemError(ICEM_E_RANGE, f"{fresh} trajectories of this MPC step came back with a non-finite cost from a finite observation")
+        if rssm:
+            host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
+        else:
+            IcemPlanner.plan_step_batch([c.planner for c in ctrls], observations)
+            host = torch.stack([torch.cat([c.planner.executed, c.planner.best_cost]) for c in ctrls]).cpu().numpy().astype(np.float64)  # one D2H sync
+            # what icem_get_action reports for a solo step: non-finite costs out of a finite observation (ICEM_E_RANGE)
+            from ._lib import IcemError, ICEM_E_RANGE
+            for c, ob in zip(ctrls, observations):
+                seen = c.planner.nonfinite_costs()
+                fresh, c._nonfinite_seen = seen - getattr(c, "_nonfinite_seen", 0), seen
+                if fresh and np.all(np.isfinite(np.asarray(ob, dtype=np.float64))):
+                    raise IcemError(ICEM_E_RANGE, f"{fresh} trajectories of this MPC step came back with a non-finite cost from a finite observation")
         out = []
         for i, (c, ob) in enumerate(zip(ctrls, observations)):
             executed_action, c.last_min_cost = host[i, :-1].copy(), float(host[i, -1])
@@ -676,45 +687,101 @@ class MpcICemHip(MpcController):
         batch = self.simulate_trajectories(obs=obs, state=self.forward_model_state, action_sequences=acts)
         return batch
 
-    def _get_action_stagewise(self, obs, noise):
+    # -- the stage-wise step (every path but the built-in device model's): its stages, and the loop of one controller.
+    #    get_action_batch drives the same stages for several controllers around ONE cost launch per iteration.
+    def _stage_rows(self, i) -> int:
+        """Rows iteration ``i`` of this MPC step scores: its population, plus the shifted elites at iteration 0."""
         p = self.planner
-        K, it_n = self.num_elites, self.opt_iter
+        with_shift = i == 0 and self.shift_elites_over_time and self._elite_actions is not None and p.n_reuse > 0
+        return p.population_sizes[i] + (p.n_reuse if with_shift else 0)
+
+    def _stage_sample(self, i, noise, actions):
+        """Sample iteration ``i`` into ``actions [_stage_rows(i), h, d]`` (the shifted elites go into the tail of the same
+        buffer: nothing is concatenated)."""
+        p = self.planner
+        it_n, n_i = self.opt_iter, p.population_sizes[i]
         call_base = p.noise_offset(p.mpc_step * (it_n + 1))
-        pool = costs_dev = idx = None
-        for i, n_i in enumerate(p.population_sizes):
-            z = noise(n_i) if noise is not None else (None, None)
-            with_shift = i == 0 and self.shift_elites_over_time and self._elite_actions is not None and p.n_reuse > 0
-            # (the shifted elites are sampled into the tail of the same buffer: nothing is concatenated)
-            actions = torch.empty((n_i + (p.n_reuse if with_shift else 0), p.h, p.d), dtype=p.dt, device=p.device)
-            p.sample_clip(n_i, p.mean, p.std, z[0], z[1], offset=call_base + i,
-                          row0_mean=bool(self.use_mean_actions and i == it_n - 1), out=actions[:n_i])
-            if with_shift:
-                zs = noise(p.n_reuse) if noise is not None else (None, None)
-                shifted = actions[n_i:]
-                shifted[:, :-1] = self._elite_actions[:p.n_reuse, 1:]
-                p.sample_clip(p.n_reuse, p.mean, p.std, zs[0], zs[1], offset=call_base + it_n, t_begin=p.h - 1,
-                              out=shifted)
-            costs = self._costs_of(obs, actions)
+        z = noise(n_i) if noise is not None else (None, None)
+        p.sample_clip(n_i, p.mean, p.std, z[0], z[1], offset=call_base + i,
+                      row0_mean=bool(self.use_mean_actions and i == it_n - 1), out=actions[:n_i])
+        if actions.shape[0] > n_i:
+            zs = noise(p.n_reuse) if noise is not None else (None, None)
+            shifted = actions[n_i:]
+            shifted[:, :-1] = self._elite_actions[:p.n_reuse, 1:]
+            p.sample_clip(p.n_reuse, p.mean, p.std, zs[0], zs[1], offset=call_base + it_n, t_begin=p.h - 1,
+                          out=shifted)
+
+    def _stage_update(self, i, costs, actions):
+        """Elites and the refitted distribution from the costs of iteration ``i``'s ``actions``."""
+        p, K = self.planner, self.num_elites
+        keep = i > 0 and self.keep_previous_elites and p.n_reuse > 0
+        if p.can_update_in_one_launch(actions.shape[0] + (p.n_reuse if keep else 0), K):
+            # top-K over [pool | kept elites] + gather + refit in one launch, nothing concatenated
+            self._elite_costs, _, self._elite_actions = p.update_distribution(
+                costs, actions, K, p.mean, p.std,
+                self._elite_costs[:p.n_reuse] if keep else None, self._elite_actions[:p.n_reuse] if keep else None)
+        else:
             pool = actions
-            keep = i > 0 and self.keep_previous_elites and p.n_reuse > 0
-            if p.can_update_in_one_launch(actions.shape[0] + (p.n_reuse if keep else 0), K):
-                # top-K over [pool | kept elites] + gather + refit in one launch, nothing concatenated
-                costs_dev, idx, self._elite_actions = p.update_distribution(
-                    costs, actions, K, p.mean, p.std,
-                    self._elite_costs[:p.n_reuse] if keep else None, self._elite_actions[:p.n_reuse] if keep else None)
-            else:
-                if keep:
-                    pool = torch.cat([actions, self._elite_actions[:p.n_reuse]], dim=0)
-                    costs = torch.cat([costs, self._elite_costs[:p.n_reuse]])
-                costs_dev, idx = p.topk_sorted(costs, K)
-                self._elite_actions = p.gather_refit(pool, idx, p.mean, p.std)
-            self._elite_costs = costs_dev
+            if keep:
+                pool = torch.cat([actions, self._elite_actions[:p.n_reuse]], dim=0)
+                costs = torch.cat([costs, self._elite_costs[:p.n_reuse]])
+            self._elite_costs, idx = p.topk_sorted(costs, K)
+            self._elite_actions = p.gather_refit(pool, idx, p.mean, p.std)
+
+    def _stage_finish(self) -> torch.Tensor:
+        """Behind the last iteration: shift, count the step; -> [best of the last pool's first action (icem.py:163) | its
+        cost] on the device."""
+        p = self.planner
         p.shift(p.mean, p.std)
         p.mpc_step += 1
-        # best of the last pool (icem.py:163) and its cost: one device-to-host copy, one synchronisation
-        host = torch.cat([self._elite_actions[0, 0], costs_dev[:1]]).cpu().numpy().astype(np.float64)
+        return torch.cat([self._elite_actions[0, 0], self._elite_costs[:1]])
+
+    def _get_action_stagewise(self, obs, noise):
+        p = self.planner
+        for i in range(len(p.population_sizes)):
+            actions = torch.empty((self._stage_rows(i), p.h, p.d), dtype=p.dt, device=p.device)
+            self._stage_sample(i, noise, actions)
+            self._stage_update(i, self._costs_of(obs, actions), actions)
+        host = self._stage_finish().cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
         self.last_min_cost = float(host[-1])
         return host[:-1]
+
+    @staticmethod
+    def _rssm_batch_refusal(ctrls):
+        """Why these controllers' steps cannot share ``rollout_cost_batch`` launches (None: they can)."""
+        c0 = ctrls[0]
+        if not all(c.rssm_path for c in ctrls):
+            return "learned-dynamics controllers cannot be mixed with controllers of another path"
+        if not all(hasattr(c.forward_model, "rollout_cost_batch") for c in ctrls):
+            return "the learned-dynamics model has no rollout_cost_batch"
+        for c in ctrls:
+            if c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose:
+                return "Philox noise, one GPU, not verbose"
+            m, m0 = c.forward_model, c0.forward_model
+            if m is not m0 and not (m.params.data_ptr() == m0.params.data_ptr() and m.params.numel() == m0.params.numel()):
+                return "learned-dynamics controllers must share one parameter buffer (the same DeviceRSSMModel, or the same params storage)"
+            # (everything but the seed: IcemConfig is a dataclass, and rank / world are 0 / 1 here)
+            if replace(c.planner.cfg, seed=0) != replace(c0.planner.cfg, seed=0) or c.planner.device != c0.planner.device:
+                return "one configuration (horizon, populations, elites, iterations, cost mode, flags) on one device"
+        return None
+
+    @staticmethod
+    def _get_action_batch_rssm(ctrls, observations):
+        """The stage-wise step of several learned-dynamics controllers: per CEM iteration every controller samples into its
+        slice of one buffer, ONE launch scores all slices, every controller updates from its slice.  -> [B, d + 1] host
+        array of executed actions and best costs (one device-to-host copy, one synchronisation)."""
+        p0, m = ctrls[0].planner, ctrls[0].forward_model
+        obs_dev = torch.as_tensor(np.asarray(observations, dtype=np.float32).reshape(len(ctrls), -1), device=m.device)
+        for i in range(len(p0.population_sizes)):
+            rows = [c._stage_rows(i) for c in ctrls]   # (a controller reset later than its peers has no shifted elites)
+            actions = torch.empty((sum(rows), p0.h, p0.d), dtype=p0.dt, device=p0.device)
+            slices = list(torch.split(actions, rows))
+            for c, a in zip(ctrls, slices):
+                c._stage_sample(i, None, a)
+            costs = m.rollout_cost_batch(obs_dev, actions, rows, L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
+            for c, a, k in zip(ctrls, slices, torch.split(costs, rows)):
+                c._stage_update(i, k, a)
+        return torch.stack([c._stage_finish() for c in ctrls]).cpu().numpy().astype(np.float64)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -827,12 +827,8 @@ int icem_rssm_trim(void) {
     return ICEM_OK;
 }
 
-int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
-                           const void* actions, void* costs, void* stream) {
-    if (n < 0 || horizon < 1 || cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL || !params || !obs0 || !actions || !costs)
-        return fail(ICEM_E_INVALID, "null tensor / bad n, horizon or cost_mode");
-    const hipError_t e = launch_rssm_rollout(n, horizon, cost_mode, (const unsigned short*)params, (const float*)obs0,
-                                             (const float*)actions, (float*)costs, (hipStream_t)stream);
+// what a learned-dynamics launch's HIP result means to the caller (both entry points)
+static int rssm_launch_result(hipError_t e) {
     if (e == hipErrorStreamCaptureUnsupported)
         return fail(ICEM_E_STATE, "learned-dynamics rollout: the stream is capturing and this call would have to synchronise it (a larger "
                                   "population or horizon than the staging area holds, or recovery from a timed-out wait): make one call "
@@ -843,6 +839,31 @@ int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const 
                                   "launched by this call -- call again");
     ICEM_HIP_TRY(e);
     return ICEM_OK;
+}
+
+int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
+                           const void* actions, void* costs, void* stream) {
+    if (n < 0 || horizon < 1 || cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL || !params || !obs0 || !actions || !costs)
+        return fail(ICEM_E_INVALID, "null tensor / bad n, horizon or cost_mode");
+    return rssm_launch_result(launch_rssm_rollout(n, horizon, cost_mode, (const unsigned short*)params, (const float*)obs0,
+                                                  (const float*)actions, (float*)costs, (hipStream_t)stream));
+}
+
+int icem_rssm_rollout_cost_batch(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t cost_mode,
+                                 const void* params, const void* obs0, const void* actions, void* costs, void* stream) {
+    if (!rows_host || !params || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: null pointer");
+    if (n_problems < 1 || n_problems > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: n_problems must be in [1, 32]");
+    for (int p = 0; p < n_problems; ++p)
+        if (rows_host[p] < 1) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: every problem needs at least one row");
+    if (horizon < 1) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: horizon must be >= 1");
+    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: bad cost_mode");
+    // (no fused twin: a batch is served by the split launch or not at all)
+    const int tiles = rssm_batch_tiles(n_problems, rows_host);
+    if (tiles < 0 || !rssm_split_batch_ok(tiles, horizon))
+        return fail(ICEM_E_UNSUPPORTED, "icem_rssm_rollout_cost_batch: the batch's tiles (the sum over the problems of ceil(rows / 16)) "
+                                        "exceed the split launch's limit, or the split launch is switched off; nothing was launched");
+    return rssm_launch_result(launch_rssm_split_batch(n_problems, rows_host, horizon, cost_mode, (const unsigned short*)params,
+                                                      (const float*)obs0, (const float*)actions, (float*)costs, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ constexpr size_t TOTAL = B8 + 2 * 16;  // bf16 units
 constexpr int SPLIT_TILE_LIMIT = 8192;  // what the staging bookkeeping is sized for
 constexpr int SPLIT_TT1_TILES = 256;    // up to here one tile per recurrence workgroup, two beyond
 constexpr int SPLIT_MAX_TILES = 4096;  // populations up to 65 536: recurrence and reward head as separate workgroups (icem_rssm_split.hip)
+constexpr int BATCH_MAX = 32;          // problems of one batched split launch (their table travels in the kernel arguments)
 }  // namespace rssm
 
 // costs[i] = reduce_t -reward(state_t) along the rollout of actions[i] from obs0 (cost_mode: 0 sum, 1 best, 2 final)
@@ -43,4 +44,11 @@ void rssm_split_trim();                     // frees the split launch's per-(dev
 void rssm_set_stamps(long long* dev_ptr);   // development aid: 16 int64 of wall_clock64 phase stamps of tile 0 (NULL = off)
 hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
                              const float* actions, float* costs, hipStream_t st);
+// B <= BATCH_MAX problems that share `params` in ONE split launch: problem p has rows[p] >= 1 trajectories from its own
+// obs0 + 230 p, its rows back to back in actions / costs; every problem is cut into tiles of its own, so each cost is the
+// one a launch of its problem alone gives, bit for bit.  tiles = the sum of the problems' tile counts.
+int rssm_batch_tiles(int n_problems, const int* rows);   // (-1: more than the staging bookkeeping could ever hold)
+bool rssm_split_batch_ok(int tiles, int horizon);
+hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int cost_mode, const unsigned short* params,
+                                   const float* obs0, const float* actions, float* costs, hipStream_t st);
 }  // namespace icem

@@ -163,7 +163,7 @@ __device__ __forceinline__ void publish(const ProducerLds<TT>& s, int cur, unsig
 // about to use), and nobody issues a load it does not need (a "dummy" broadcast load costs the L1 more than a real
 // one: measured).  TT tiles per workgroup share every chunk (one request, TT accumulation chains).
 template <bool CLASS_A, int TT>
-__device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int lane, int base, int n, int horizon,
+__device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int lane, int base, int row_end, int horizon,
                                                  const unsigned short* __restrict__ Pg, const float* __restrict__ actions,
                                                  unsigned short* items, size_t tile_stride, unsigned* flag, int ntl,
                                                  long long* stamps, bool stamp) {
@@ -283,7 +283,7 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
 #pragma unroll
             for (int tt = 0; tt < TT; ++tt) {
                 const int rr = base + tt * 16 + j;
-                const float* ap = actions + ((size_t)(rr < n ? rr : n - 1) * horizon + (t + 1)) * ACT;
+                const float* ap = actions + ((size_t)(rr < row_end ? rr : row_end - 1) * horizon + (t + 1)) * ACT;
                 const int o = g & 1 ? 4 : 0;
                 an[tt][0] = ap[o]; an[tt][1] = ap[o + 1]; an[tt][2] = ap[g & 1 ? 5 : 2]; an[tt][3] = ap[g & 1 ? 5 : 3];
             }
@@ -382,16 +382,16 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
     if (w == WAVES - 1) publish<TT>(s, cur, items, tile_stride, horizon - 1, flag, ntl, lane);
 }
 
-// wg: the workgroup's index among the recurrence workgroups (tiles wg * TT ..)
+// The workgroup's ntl <= TT tiles are launch-global tiles tile0 .. (items and flags); their rows are base + 16 tt + j of
+// actions, all of ONE problem, which starts from obs0 and ends in front of row_end (rows past it repeat row_end - 1).
+// A launch of one problem has base = 16 tile0; in a batched launch a problem starts at any row.
 template <int TT>
-__device__ __forceinline__ void recurrence(ProducerLds<TT>& s, int wg, int tiles, int n, int horizon, const unsigned short* __restrict__ Pg,
-                                           const float* __restrict__ obs0, const float* __restrict__ actions,
-                                           unsigned short* stage, unsigned* flags, long long* stamps) {
+__device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, int tile0, int ntl, int base, int row_end, int horizon,
+                                           const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
+                                           const float* __restrict__ actions, unsigned short* stage, unsigned* flags, long long* stamps) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile0 = wg * TT, base = tile0 * 16;
-    const int ntl = tiles - tile0 < TT ? tiles - tile0 : TT;
-    const bool stamp = stamps && wg == 0 && tid == 0;   // development aid (icem_debug_stamps(NULL, buffer))
+    const bool stamp = stamps && first_wg && tid == 0;   // development aid (icem_debug_stamps(NULL, buffer))
     if (stamp) stamps[0] = wall_clock64();
     const size_t tile_stride = (size_t)horizon * ITEM;
     unsigned short* items = stage + (size_t)tile0 * tile_stride;
@@ -420,7 +420,7 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, int wg, int tiles
         float av = 0.f;
         if (tid < TT * 16 * ACT) {
             const int jj = tid / ACT;
-            av = actions[(size_t)(base + jj < n ? base + jj : n - 1) * horizon * ACT + tid % ACT];
+            av = actions[(size_t)(base + jj < row_end ? base + jj : row_end - 1) * horizon * ACT + tid % ACT];
         }
         s.ob[tid < 232 ? tid : 231] = tid < 232 ? ob : 0.f;
 #pragma unroll
@@ -465,13 +465,16 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, int wg, int tiles
         if (k < 32) s.zA[e] = to_bf16(k < STOCH ? s.ob[DET + k] : 0.f);
         else if (k >= 32 + ACT) s.zA[e] = 0;
     }
-    if (w < 5) recurrence_steps<true, TT>(s, w, lane, base, n, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
-    else recurrence_steps<false, TT>(s, w, lane, base, n, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
+    if (w < 5) recurrence_steps<true, TT>(s, w, lane, base, row_end, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
+    else recurrence_steps<false, TT>(s, w, lane, base, row_end, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
 }
 
 // tiles first, first + stride, ...: one tile per workgroup while both workgroup kinds fit the chip together, several for
-// the large populations whose reward workgroups run behind the recurrence workgroups (the head's weights are loaded once)
-__device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int stride, int tiles, int n, int horizon, int cost_mode,
+// the large populations whose reward workgroups run behind the recurrence workgroups (the head's weights are loaded once).
+// rows_of(tile, base, end): trajectory j of launch-global tile `tile` is row base + j of costs if that is below end
+// (asked once per tile, in ascending tile order, at the store).
+template <class RowsOf>
+__device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int stride, int tiles, RowsOf rows_of, int horizon, int cost_mode,
                                             const unsigned short* __restrict__ Pg, float* __restrict__ costs,
                                             const unsigned short* stage, unsigned* flags, unsigned* status, long long* stamps) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -584,8 +587,10 @@ __device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int strid
     }
     if (stamp && tile == 0) stamps[13] = wall_clock64();
     if (tid == 0) __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-    if (w == WAVES - 1 && g == 0 && tile * 16 + j < n)
-        costs[tile * 16 + j] = s.gave_up ? __builtin_nanf("") : acc_cost;   // (a workgroup that gave up once reports NaN from there on)
+    int base, end;
+    rows_of(tile, base, end);
+    if (w == WAVES - 1 && g == 0 && base + j < end)
+        costs[base + j] = s.gave_up ? __builtin_nanf("") : acc_cost;   // (a workgroup that gave up once reports NaN from there on)
     }
 }
 
@@ -597,9 +602,54 @@ __global__ __launch_bounds__(NTHR) void rssm_split_kernel(int n, int horizon, in
                                                          unsigned* status, int tiles, int prods, long long* stamps) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
     const int b = blockIdx.x;
-    if (b < prods) recurrence<TT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b, tiles, n, horizon, Pg, obs0, actions, stage, flags, stamps);
-    else reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles, n, horizon, cost_mode, Pg, costs, stage,
-                     flags, status, stamps);
+    if (b < prods) {
+        const int tile0 = b * TT;
+        recurrence<TT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tile0, tiles - tile0 < TT ? tiles - tile0 : TT, tile0 * 16, n, horizon, Pg,
+                       obs0, actions, stage, flags, stamps);
+    } else {
+        reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
+                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+    }
+}
+
+// The problems of a batched launch, by value in the kernel arguments (512 bytes: nothing to allocate, nothing to copy,
+// nothing a stream capture forbids).  Problem p owns the launch-global tiles tile0[p] .., the recurrence workgroups
+// wg0[p] .. and the rows row0[p] .. row0[p] + rows[p] of actions / costs; entries from n_problems on are not read.
+struct BatchTable {
+    int tile0[rssm::BATCH_MAX], wg0[rssm::BATCH_MAX], row0[rssm::BATCH_MAX], rows[rssm::BATCH_MAX];
+};
+
+// rssm_split_kernel for B problems that share the weights: the same two device bodies, every problem cut into tiles of
+// its own (trajectory r of a problem sits at row r % 16 of its tile, as in a launch of that problem alone; the padding
+// rows of its last tile repeat ITS last row; a two-tile recurrence workgroup takes two tiles of ONE problem, whose obs0 it
+// parks once).  Staging items and flags are indexed by the launch-global tile; all recurrence workgroups come first.
+// A workgroup finds its problem by a scan over the table: block and tile indices are wave-uniform, the table is read
+// with scalar loads, and what the scan finds lives in scalar registers.
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_split_batch_kernel(const BatchTable tab, int n_problems, int horizon, int cost_mode,
+                                                               const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
+                                                               const float* __restrict__ actions, float* __restrict__ costs,
+                                                               unsigned short* stage, unsigned* flags, unsigned* status, int tiles,
+                                                               int prods, long long* stamps) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
+    const int b = blockIdx.x;
+    if (b < prods) {
+        int p = 0;
+        for (int q = 1; q < n_problems; ++q) p = b >= tab.wg0[q] ? q : p;
+        const int lt0 = (b - tab.wg0[p]) * TT;                 // the workgroup's first tile within its problem
+        const int left = (tab.rows[p] + 15) / 16 - lt0;        // (a problem with an odd tile count ends in a one-tile workgroup)
+        recurrence<TT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tab.tile0[p] + lt0, left < TT ? left : TT, tab.row0[p] + lt0 * 16,
+                       tab.row0[p] + tab.rows[p], horizon, Pg, obs0 + (size_t)p * (DET + STOCH), actions, stage, flags, stamps);
+    } else {
+        int p = 0;   // (a walking workgroup's tiles ascend: the scan goes on from the problem of the tile before)
+        reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
+                    [&tab, &p, n_problems](int tile, int& base, int& end) {
+                        while (p + 1 < n_problems && tile >= tab.tile0[p + 1]) ++p;
+                        base = tab.row0[p] + (tile - tab.tile0[p]) * 16;
+                        end = tab.row0[p] + tab.rows[p];
+                    },
+                    horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+    }
 }
 
 // One staging area per (device, stream): launches on a stream are ordered, so they may share it.  (Areas live until
@@ -631,18 +681,29 @@ void rssm_split_trim() {
     g_staging.clear();
 }
 
-bool rssm_split_ok(int n, int horizon) {
+// may `tiles` tiles at this horizon take the split launch?  (a launch of one problem and a batch ask the same question)
+bool rssm_split_batch_ok(int tiles, int horizon) {
     const bool on = icem::opt_i(icem::OPT_RSSM_SPLIT) != 0;
     const int max_tiles = [] {   // (development: option rssm_split_max_n moves the population limit)
         const int v = icem::opt_i(icem::OPT_RSSM_SPLIT_MAX_N) / 16;
         return v < 1 ? 1 : v > rssm::SPLIT_TILE_LIMIT ? rssm::SPLIT_TILE_LIMIT : v;
     }();
-    return on && n > 0 && horizon >= 1 && (n + 15) / 16 <= max_tiles;
+    return on && tiles > 0 && horizon >= 1 && tiles <= max_tiles;
 }
 
-hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
-                             const float* actions, float* costs, hipStream_t st) {
-    const int tiles = (n + 15) / 16;
+bool rssm_split_ok(int n, int horizon) { return n > 0 && rssm_split_batch_ok((n + 15) / 16, horizon); }
+
+int rssm_batch_tiles(int n_problems, const int* rows) {
+    long long tiles = 0;
+    for (int p = 0; p < n_problems; ++p) tiles += ((long long)rows[p] + 15) / 16;
+    return tiles > rssm::SPLIT_TILE_LIMIT ? -1 : (int)tiles;
+}
+
+namespace {
+// What both launchers do in front of their kernel: this (device, stream)'s staging area -- created at the first call,
+// recovered behind a timed-out wait, grown to `tiles` tiles of `horizon` states -- with the area's lock held (`lk`) until
+// the caller has enqueued the kernel that uses the pointers.
+hipError_t staging_for(int tiles, int horizon, hipStream_t st, std::unique_lock<std::mutex>& lk, const Staging*& out) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -651,11 +712,11 @@ hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned s
     // happen between reading the pointers and enqueuing the kernel that uses them.
     Staging* sp;
     {
-        std::lock_guard<std::mutex> lk(g_mu);
+        std::lock_guard<std::mutex> lm(g_mu);
         sp = &g_staging[{dev, st}];
     }
     Staging& s = *sp;
-    std::lock_guard<std::mutex> lk(s.mu);
+    lk = std::unique_lock<std::mutex>(s.mu);
     // a capturing stream must not be synchronised (it would invalidate the capture): the two cases below that need to --
     // recovery from a timed-out wait, growing the area -- report instead
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -693,22 +754,62 @@ hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned s
         if ((e = hipMalloc(&s.flags, rssm::SPLIT_TILE_LIMIT * sizeof(unsigned))) != hipSuccess) return e;
         if ((e = hipMemsetAsync(s.flags, 0, rssm::SPLIT_TILE_LIMIT * sizeof(unsigned), st)) != hipSuccess) return e;
     }
-    const Staging& sg = s;
-    // Up to 256 tiles: one tile per recurrence workgroup and one reward workgroup per tile (up to 128 tiles both kinds are
-    // resident together).  Beyond: two tiles per recurrence workgroup (they share every weight chunk) and 512 reward
-    // workgroups that walk the tiles behind them.  (option rssm_split_tt = 1 | 2 overrides the tiles per workgroup.)
+    out = &s;
+    return hipSuccess;
+}
+
+// Up to 256 tiles: one tile per recurrence workgroup and one reward workgroup per tile (up to 128 tiles both kinds are
+// resident together).  Beyond: two tiles per recurrence workgroup (they share every weight chunk) and 512 reward
+// workgroups that walk the tiles behind them.  (option rssm_split_tt = 1 | 2 overrides the tiles per workgroup.)
+struct Arrangement { int tt, heads; };
+Arrangement arrangement(int tiles) {
     const int tt_opt = icem::opt_i(icem::OPT_RSSM_SPLIT_TT);
-    const int tt_env = (tt_opt == 1 || tt_opt == 2) ? tt_opt : 0;
-    const int tt = tt_env ? tt_env : (tiles > rssm::SPLIT_TT1_TILES ? 2 : 1);
-    const int heads = tiles > rssm::SPLIT_TT1_TILES ? std::min(tiles, 512) : tiles;
-    if (tt == 2) {
+    const int tt = (tt_opt == 1 || tt_opt == 2) ? tt_opt : (tiles > rssm::SPLIT_TT1_TILES ? 2 : 1);
+    return {tt, tiles > rssm::SPLIT_TT1_TILES ? std::min(tiles, 512) : tiles};
+}
+}  // namespace
+
+hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
+                             const float* actions, float* costs, hipStream_t st) {
+    const int tiles = (n + 15) / 16;
+    std::unique_lock<std::mutex> lk;
+    const Staging* sg = nullptr;
+    const hipError_t e = staging_for(tiles, horizon, st, lk, sg);
+    if (e != hipSuccess) return e;
+    const Arrangement a = arrangement(tiles);
+    if (a.tt == 2) {
         const int prods = (tiles + 1) / 2;
-        hipLaunchKernelGGL(rssm_split_kernel<2>, dim3(prods + heads), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions,
-                           costs, sg.stage, sg.flags, sg.status_dev, tiles, prods, g_stamps);
+        hipLaunchKernelGGL(rssm_split_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions,
+                           costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
     } else {
-        hipLaunchKernelGGL(rssm_split_kernel<1>, dim3(tiles + heads), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions, costs,
-                           sg.stage, sg.flags, sg.status_dev, tiles, tiles, g_stamps);
+        hipLaunchKernelGGL(rssm_split_kernel<1>, dim3(tiles + a.heads), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions, costs,
+                           sg->stage, sg->flags, sg->status_dev, tiles, tiles, g_stamps);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int cost_mode, const unsigned short* params,
+                                   const float* obs0, const float* actions, float* costs, hipStream_t st) {
+    const int tiles = rssm_batch_tiles(n_problems, rows);
+    if (n_problems < 1 || n_problems > rssm::BATCH_MAX || tiles < 1) return hipErrorInvalidValue;
+    const Arrangement a = arrangement(tiles);
+    BatchTable tab{};
+    int prods = 0;
+    for (int p = 0, tile = 0, row = 0; p < n_problems; ++p) {
+        const int pt = (rows[p] + 15) / 16;
+        tab.tile0[p] = tile; tab.wg0[p] = prods; tab.row0[p] = row; tab.rows[p] = rows[p];
+        tile += pt; prods += (pt + a.tt - 1) / a.tt; row += rows[p];
+    }
+    std::unique_lock<std::mutex> lk;
+    const Staging* sg = nullptr;
+    const hipError_t e = staging_for(tiles, horizon, st, lk, sg);
+    if (e != hipSuccess) return e;
+    if (a.tt == 2)
+        hipLaunchKernelGGL(rssm_split_batch_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, params,
+                           obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    else
+        hipLaunchKernelGGL(rssm_split_batch_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, params,
+                           obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
     return hipGetLastError();
 }
 }  // namespace icem

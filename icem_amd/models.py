@@ -347,5 +347,34 @@ class DeviceRSSMModel(ForwardModel):
                                                 C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
         return costs
 
+    def rollout_cost_batch(self, observations, actions, rows, cost_mode: int = 0):
+        """``rollout_cost`` of B problems in ONE launch (``icem_rssm_rollout_cost_batch``): problem p scores its ``rows[p]``
+        action sequences -- back to back in ``actions [sum rows, h, 6]`` (f32 device tensor) -- from ``observations[p]``
+        (``[B, 230]`` array-like, or an f32 device tensor that is used as is).  -> costs ``[sum rows]``, every problem's
+        slice bit for bit what ``rollout_cost`` gives for it alone; B = 1 is ``rollout_cost``."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        rows = [int(r) for r in rows]
+        if actions.ndim != 3 or actions.shape[2] != 6:
+            raise ValueError(f"actions must be [sum rows, h, 6], got {tuple(actions.shape)}")
+        if sum(rows) != actions.shape[0]:
+            raise ValueError(f"rows sum to {sum(rows)} but actions has {actions.shape[0]} rows")
+        on_device = isinstance(observations, torch.Tensor) and observations.is_cuda
+        if not on_device:
+            observations = np.asarray(observations, dtype=np.float32)
+        if tuple(observations.shape) != (len(rows), 230):
+            raise ValueError(f"observations must be [{len(rows)}, 230] (one start state per problem), got {tuple(observations.shape)}")
+        if on_device and (observations.dtype != torch.float32 or not observations.is_contiguous()):
+            raise ValueError("a device tensor of observations must be contiguous float32")
+        o = observations if on_device else torch.as_tensor(observations, device=self.device)
+        actions = actions.to(torch.float32).contiguous()
+        costs = torch.empty((actions.shape[0],), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_rssm_rollout_cost_batch(len(rows), (C.c_int32 * len(rows))(*rows), actions.shape[1], cost_mode,
+                                                      C.c_void_p(self.params.data_ptr()), C.c_void_p(o.data_ptr()),
+                                                      C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
+        return costs
+
     def predict(self, *, observations, states, actions):
         return self._tm.predict(observations=observations, states=states, actions=actions)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ICEM_ABI_VERSION 6 /* 6: icem_step_status removed; 5: ICEM_TILE_AUTO serves the fp16 planes only where no state can leave their range (icem_tile_growth), icem_nonfinite_costs / ICEM_E_RANGE, icem_set_option (the library reads no environment variable), icem_plan_step_batch; 2: icem_build_hash, icem_allgather_elites / icem_rccl_*, noise-ahead planning; ICEM_MAX_OBS_DIM 384; 3: icem_set_tile_arith; 4: icem_set_wide_arith (default AUTO), ICEM_TILE_AUTO = planes at every population */
+#define ICEM_ABI_VERSION 6 /* 6: icem_step_status removed (icem_rssm_rollout_cost_batch was added without a new number: an added symbol breaks no caller); 5: ICEM_TILE_AUTO serves the fp16 planes only where no state can leave their range (icem_tile_growth), icem_nonfinite_costs / ICEM_E_RANGE, icem_set_option (the library reads no environment variable), icem_plan_step_batch; 2: icem_build_hash, icem_allgather_elites / icem_rccl_*, noise-ahead planning; ICEM_MAX_OBS_DIM 384; 3: icem_set_tile_arith; 4: icem_set_wide_arith (default AUTO), ICEM_TILE_AUTO = planes at every population */
 
 enum { ICEM_F32 = 0, ICEM_F64 = 1 };
 enum { ICEM_COST_SUM = 0, ICEM_COST_BEST = 1, ICEM_COST_FINAL = 2 }; /* abstract_controller.py:82-87 */
@@ -528,6 +528,15 @@ size_t icem_rssm_param_elems(void);
 int icem_rssm_trim(void);
 int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
                            const void* actions, void* costs, void* stream);
+/* B planners' populations through the declared RSSM in ONE launch (the reference's parallel episodes, each with its own
+ * start state: icem/misc/rollout_utils.py:46-58, 129-152).  rows_host[p] >= 1 trajectories of problem p, back to back in
+ * actions [sum rows, horizon, 6] / costs [sum rows]; obs0 [n_problems, 230] (f32, device); one params buffer for all.
+ * costs of problem p: bit for bit icem_rssm_rollout_cost(rows_host[p], ..., obs0 + 230 p, its actions).
+ * n_problems in [1, 32].  Served by the split launch only: the sum over p of ceil(rows/16) tiles beyond its limit, or the
+ * split launch switched off: ICEM_E_UNSUPPORTED, nothing launched.  Staging / capture / ICEM_E_STATE rules of
+ * icem_rssm_rollout_cost. */
+int icem_rssm_rollout_cost_batch(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t cost_mode,
+                                 const void* params, const void* obs0, const void* actions, void* costs, void* stream);
 
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action
