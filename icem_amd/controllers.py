@@ -562,6 +562,10 @@ class MpcICemHip(MpcController):
             executed_action, self.last_min_cost = host[:-1], float(host[-1])
         else:
             executed_action = self._get_action_stagewise(obs, noise)
+        return self._finish_action(obs, executed_action)
+
+    def _finish_action(self, obs, executed_action):
+        """The tail of ``get_action`` behind the planning step (``self.last_min_cost`` is set), shared with ``get_action_batch``."""
         if self._new_mean_is_overridden(MpcICemHip):
             # icem.py:168-171: the device epilogue has shifted the mean and KEPT its last row (the default
             # compute_new_mean); a subclass decides that row from the best trajectory's last predicted observation
@@ -618,18 +622,7 @@ class MpcICemHip(MpcController):
         out = []
         for i, (c, ob) in enumerate(zip(ctrls, observations)):
             executed_action, c.last_min_cost = host[i, :-1].copy(), float(host[i, -1])
-            if c._new_mean_is_overridden(MpcICemHip):
-                best = c.elite_samples.as_array("actions")[0]
-                new_last = np.asarray(c.compute_new_mean(obs=c._last_predicted_observation(ob, best)), dtype=np.float64)
-                p = c.planner
-                p.mean[-1].copy_(torch.as_tensor(new_last.reshape(p.d), dtype=p.dt, device=p.device))
-            c.logger.log(c.last_min_cost, key="Expected_trajectory_cost")
-            if c.do_visualize_plan:
-                bt = c.best_trajectory(ob)
-                c.visualize_plan(obs=bt["observations"], state=c.forward_model_state, acts=bt["actions"])
-            if c.forward_model_state is not None:
-                _, c.forward_model_state, _ = c.forward_model.predict(observations=ob, states=c.forward_model_state, actions=executed_action)
-            out.append(executed_action)
+            out.append(c._finish_action(ob, executed_action))
         return out
 
     def compute_new_mean(self, obs):

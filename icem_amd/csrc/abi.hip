@@ -583,7 +583,7 @@ int icem_sample_clip(icem_handle* h, int32_t n, int64_t first_index, const void*
     if (t_begin < 0 || t_begin >= h->cfg.horizon) return fail(ICEM_E_INVALID, "t_begin out of range");
     hipStream_t st = (hipStream_t)stream;
     if (z_r == nullptr && t_begin == 0 && fast_sample_ok(h))
-        return launch_fast_sample(h, n, first_index, mean, std, low, high, offset, row0_mean, actions, st);
+        return launch_fast_sample(h, n, first_index, mean, std, low, high, offset, row0_mean, actions, LaunchCtx{st});
     return gk_sample(h, n, first_index, mean, std, low, high, z_r, z_i, offset, t_begin, row0_mean, actions, st);
 }
 
@@ -631,7 +631,7 @@ int icem_rollout_cost(icem_handle* h, int32_t n, const void* obs0, const void* a
     if (const char* e = wide_unsupported(h, 0, false, observations != nullptr)) return fail(ICEM_E_UNSUPPORTED, e);
     hipStream_t st = (hipStream_t)stream;
     if (observations == nullptr && n > 0 && fast_rollout_ok(h, 0))
-        return launch_fast_rollout(h, n, 0, 0, obs0, actions, costs, nullptr, nullptr, st, nullptr);
+        return launch_fast_rollout(h, n, 0, 0, obs0, actions, costs, nullptr, nullptr, LaunchCtx{st}, nullptr);
     return gk_rollout(h, n, obs0, actions, costs, observations, st);
 }
 

@@ -215,7 +215,7 @@ struct ProfScope {
     }
     ProfScope(const icem_handle* hc, int kind_, long long units_, hipStream_t st_)
         : h(const_cast<icem_handle*>(hc)), st(st_), kind(kind_), units(units_) {
-        if (!h->profiling || g_batch.rec) return;
+        if (!h->profiling) return;
         a = get(h);
         b = get(h);
         (void)hipEventRecord(a, st);
@@ -327,13 +327,13 @@ bool fast_rollout_ok(const icem_handle* h, int K);
 inline bool gemm_rollout(const icem_handle* h) { return h->wide || h->Of == 0; }
 bool fast_sample_ok(const icem_handle* h);
 int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const void* obs0, const void* actions,
-                        void* costs, float* part_c, int* part_i, hipStream_t st, int* lists_out,
+                        void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k = nullptr, int n_tail = 0, int* tail_out = nullptr);
 int refresh_act_mag(icem_handle* h, const void* low, const void* high, hipStream_t st, bool force);   // abi.hip
 void ahead_destroy(icem_handle* h);
-void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st);
+void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx);
 int launch_fast_sample(const icem_handle* h, int n, long long first_index, const void* mean, const void* std,
-                       const void* low, const void* high, uint64_t offset, int row0_mean, void* out, hipStream_t st,
+                       const void* low, const void* high, uint64_t offset, int row0_mean, void* out, const LaunchCtx& cx,
                        int n_shift = 0, const void* elites_src = nullptr, uint64_t offset2 = 0);
 
 }  // namespace icem

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstddef>
+#include <cstring>
 #include <vector>
 #include "cost_args.h"
 #include "options.h"
@@ -11,6 +13,8 @@
 namespace icem {
 
 constexpr int FAST_MAX_LISTS = 256;  // candidate lists (one per rollout workgroup) the merge accepts
+struct BatchHint;   // how many problems share the step's launches ...
+struct LaunchCtx;   // ... and stream + hint + recorder, what the step's launchers take (both below: "the step's launch context")
 
 // In-library elite exchange (exchange.hip): what a merge needs to wait for the ranks' records of one exchange.
 constexpr int XCHG_MAX_WORLD = 16;
@@ -187,11 +191,11 @@ struct MergeSingleArgs {
     int n_raw = 0;
     float xf_lo = 0.f, xf_hi = 0.f;
 };
-void launch_merge_single(const MergeSingleArgs& a, hipStream_t st);
+void launch_merge_single(const LaunchCtx& cx, const MergeSingleArgs& a);
 // ... with noise workgroups beside it (noise-ahead pipeline: z.n rows of raw colored noise -> z.out; see merge_noise_kernel)
 bool merge_noise_ok(const MergeSingleArgs& a, int rounds);
 // z2 (z2.n > 0): a second, small sampling call in one more workgroup (the next step's shifted elites' noise)
-void launch_merge_noise(const MergeSingleArgs& a, const FastSampleArgs& z, const FastSampleArgs& z2, hipStream_t st);
+void launch_merge_noise(const LaunchCtx& cx, const MergeSingleArgs& a, const FastSampleArgs& z, const FastSampleArgs& z2);
 // icem_update_distribution for small f32 pools (topk_small_ok(n + n_keep, K)): top-K over [costs | keep_costs], gather from
 // [pool | keep_actions], refit of mean / std in place -- one launch
 struct UpdateSmallArgs {
@@ -242,7 +246,7 @@ struct PackPrev {
 };
 // may the merge-prologue launch of an iteration with n_rows local rows carry the previous iteration's pack? (the
 // single-launch kernel or the sampler of the two-kernel path; the records must fit the workgroup's tile)
-bool sample_rollout_pack_ok(int h, int d, int O, int rounds, int n_rows, int K);
+bool sample_rollout_pack_ok(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int K);
 bool sample_folded_pack_ok(int h, int d, int rounds, int K);
 
 // ---- noise-ahead pipeline (large populations, world == 1; plan.hip::plan_step_ahead) -----------------------
@@ -278,9 +282,9 @@ struct IterAheadArgs {
     int n_roll, n_noise;  // workgroups per role (filled by the launcher)
     int dbg_slot = 0;     // development: which 16-word block of r.dbg this launch stamps (the iteration)
 };
-bool rollout_ahead_ok(int h, int d, int O, int K, int n_rows);
-int ahead_roll_workgroups(int n_rows);  // = candidate lists of that launch
-void launch_iter_ahead(const IterAheadArgs& a, int h, int d, int O, int kind, hipStream_t st);
+bool rollout_ahead_ok(const BatchHint& bh, int h, int d, int O, int K, int n_rows);
+int ahead_roll_workgroups(const BatchHint& bh, int n_rows);  // = candidate lists of that launch
+void launch_iter_ahead(const LaunchCtx& cx, const IterAheadArgs& a, int h, int d, int O, int kind);
 
 // K1 with the previous iteration's merge (last == 0) in its prologue, see sample_folded_merge_kernel
 struct FastSampleMergeArgs {
@@ -298,52 +302,120 @@ struct FastIterArgs {
     MergeSingleArgs m;  // merge prologue only: the PREVIOUS iteration's merge (last == 0), see sample_rollout_kernel
     PackPrev p;         // ... and its pack (sharded runs)
 };
-// ---- batched planners (icem_plan_step_batch; plan.hip) ----------------------------------------------------------------
+// ---- the step's launch context, and batched planners (icem_plan_step_batch; plan.hip) -----------------------------------
 // B independent MPC problems of the same configuration advance together: every launch of the small-population path
 // (sample_rollout_kernel x opt_iters, then the last merge) is ONE launch for all of them -- blockIdx.y = the problem, its
 // argument block read from an array in device memory instead of the kernel-argument segment.  The host side of every
-// handle runs as for a solo step, with the three launchers below RECORDING their arguments (g_batch.rec != nullptr) instead
-// of launching; plan.hip then issues the batched launches.  Same device code (the kernels' bodies are shared), same bits
-// per problem.
+// handle runs as for a solo step under a LaunchCtx that carries a recorder: a launcher computes its launch (LaunchKey: the
+// family's dispatch key and workgroup counts) and either issues it or, recording, appends key + argument block to the
+// recorder; plan.hip then issues one batched launch per recorded one.  Same device code (the kernels' bodies are shared),
+// same bits per problem.
 constexpr int ICEM_MAX_BATCH = 32;
 struct BatchBases {          // by value in the kernel-argument segment: the noise stream offset of this MPC step per problem
     unsigned long long v[ICEM_MAX_BATCH];   // (the offsets in the argument blocks are stored RELATIVE to it: the blocks of a
 };                                          //  steady-state step are the previous same-parity step's, and are not uploaded again)
-// which launcher recorded a BatchRecord (host side only: the batched kernels never see it)
-enum BatchKind : int { BATCH_NONE = 0, BATCH_SAMPLE_ROLLOUT = 1, BATCH_MERGE_SINGLE = 2, BATCH_MERGE_NOISE = 3, BATCH_ITER_AHEAD = 4 };
-struct BatchRecord {
-    BatchKind kind = BATCH_NONE;   // (iter_ahead: rw = waves per workgroup, grid = rollout workgroups)
-    // BATCH_SAMPLE_ROLLOUT
-    FastIterArgs it;
-    int h = 0, d = 0, O = 0, model_kind = 0, rw = 0, grid = 0;
-    bool prologue = false;
-    // BATCH_MERGE_SINGLE, BATCH_MERGE_NOISE
-    MergeSingleArgs m;
-    FastSampleArgs z1, z2;
-    // BATCH_ITER_AHEAD
-    IterAheadArgs ia;
+// How many problems share the step's launches: the shape rules choose launch shapes for mult x the rows ...
+struct BatchHint {
+    int mult = 1;
+    bool ahead = false;   // ... and the batch may take the noise-ahead launches where all its rows together fill them
 };
-struct BatchState {
-    int mult = 1;                       // problems in the running batch: launch shapes are chosen for mult x the rows
-    bool ahead = false;                 // ... and the batch may take the noise-ahead launches where all its rows together fill them
-    std::vector<BatchRecord>* rec = nullptr;   // != nullptr: the launchers record here instead of launching
-    bool unsupported = false;           // a launcher without a batched form was reached while recording
+// What a dispatch table maps to a compiled instantiation and a grid (all ints, no padding: compared as bytes)
+enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3 };
+struct LaunchKey {
+    int family = 0;
+    int h = 0, d = 0, O = 0, kind = 0, arith = 0;
+    int waves = 0;     // rollout waves per workgroup (sample_rollout: RW; iter_ahead: WAVES)
+    int form = 0;      // sample_rollout: 0 = plain, 1 = lists merge in the prologue, 2 = records merge; iter_ahead: PM; merge_noise: 1 = with noise
+    int wgs[3] = {0, 0, 0};   // workgroups per role; the grid is their sum
+    bool operator==(const LaunchKey& o) const { return std::memcmp(this, &o, sizeof(LaunchKey)) == 0; }
 };
-extern thread_local BatchState g_batch;     // (plan.hip)
 struct MergeNoiseBatchArgs {
     MergeSingleArgs a;
     FastSampleArgs z1, z2;
 };
-// the batched launches: args[n] in DEVICE memory (offsets relative to bases.v[problem])
-void launch_sample_rollout_batch(const BatchRecord& shape, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
-void launch_merge_batch(const BatchRecord& shape, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
-void launch_iter_ahead_batch(const BatchRecord& shape, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+// One recorded launch of one problem: the key and the family's argument block in its device-array form
+struct LaunchDesc {
+    LaunchKey key;
+    alignas(8) unsigned char block[sizeof(IterAheadArgs)];
+};
+static_assert(sizeof(FastIterArgs) <= sizeof(IterAheadArgs) && sizeof(MergeNoiseBatchArgs) <= sizeof(IterAheadArgs), "LaunchDesc::block");
+inline size_t launch_block_bytes(int family) {
+    return family == LAUNCH_SAMPLE_ROLLOUT ? sizeof(FastIterArgs) : family == LAUNCH_ITER_AHEAD ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
+}
+struct LaunchRecorder {
+    unsigned long long base = 0;        // noise stream base of the recorded problem's step (BatchBases::v)
+    std::vector<LaunchDesc> launches;
+    bool unsupported = false;           // a launch without a batched form was reached (nothing was launched for it)
+    void* add(const LaunchKey& key) {   // -> the new record's block, zeroed
+        launches.emplace_back();
+        launches.back().key = key;
+        std::memset(launches.back().block, 0, sizeof(launches.back().block));
+        return launches.back().block;
+    }
+};
+// What the MPC step's call tree passes down instead of a bare stream
+struct LaunchCtx {
+    hipStream_t st = nullptr;
+    BatchHint hint;
+    LaunchRecorder* rec = nullptr;      // != nullptr: launches are recorded, not issued
+};
+// A launcher's one exit: `issue` launches now; recording, `form(block, base)` writes the device-array form of the arguments
+template <class Form, class Issue>
+void submit(const LaunchCtx& cx, const LaunchKey& key, bool batched_form, Form&& form, Issue&& issue) {
+    if (!cx.rec) return issue();
+    if (!batched_form) cx.rec->unsupported = true;
+    else form(cx.rec->add(key), cx.rec->base);
+}
+// The device-array form of an argument block -> dst: sampling offsets relative to `base` (the kernels' add_base64, fused_dev.h,
+// undoes it), unused offsets and dbg zero, the struct's tail padding zero -- a steady-state step's blocks compare equal as bytes
+inline void sub_base(uint32_t& lo, uint32_t& hi, unsigned long long base) {
+    const unsigned long long v = (((unsigned long long)hi << 32) | lo) - base;
+    lo = (uint32_t)v;
+    hi = (uint32_t)(v >> 32);
+}
+inline void batch_form(const FastIterArgs& a, unsigned long long base, void* dst) {
+    std::memcpy(dst, &a, sizeof(a));
+    FastSampleArgs& s = ((FastIterArgs*)dst)->s;
+    if (s.n_shift == 0) s.off2_lo = s.off2_hi = 0;   // (unused)
+    else sub_base(s.off2_lo, s.off2_hi, base);
+    sub_base(s.off_lo, s.off_hi, base);
+}
+inline void batch_form(const IterAheadArgs& a, unsigned long long base, void* dst) {
+    constexpr size_t defined = offsetof(IterAheadArgs, dbg_slot) + sizeof(int);   // (copies do not carry the tail padding)
+    std::memcpy(dst, &a, defined);
+    IterAheadArgs& g = *(IterAheadArgs*)dst;
+    g.r.dbg = nullptr;
+    if (g.z.n > 0) sub_base(g.z.off_lo, g.z.off_hi, base);
+    else g.z.off_lo = g.z.off_hi = 0;
+    if (g.s.n_shift > 0) {
+        sub_base(g.s.off_lo, g.s.off_hi, base);
+        sub_base(g.s.off2_lo, g.s.off2_hi, base);
+    } else {
+        g.s.off_lo = g.s.off_hi = g.s.off2_lo = g.s.off2_hi = 0;
+    }
+}
+inline void batch_form(const MergeSingleArgs& a, const FastSampleArgs* z1, const FastSampleArgs* z2, unsigned long long base, void* dst) {
+    MergeNoiseBatchArgs& g = *(MergeNoiseBatchArgs*)dst;   // (zeroed: a merge alone has z1.n == z2.n == 0)
+    std::memcpy(&g.a, &a, sizeof(a));
+    if (!z1) return;
+    std::memcpy(&g.z1, z1, sizeof(*z1));
+    std::memcpy(&g.z2, z2, sizeof(*z2));
+    for (FastSampleArgs* z : {&g.z1, &g.z2}) {
+        if (z->n > 0) sub_base(z->off_lo, z->off_hi, base);
+        else z->off_lo = z->off_hi = 0;
+        z->off2_lo = z->off2_hi = 0;
+    }
+}
+// the batched launches: args[n] in DEVICE memory (the problems' keys are equal: plan.hip checked)
+void launch_sample_rollout_batch(const LaunchKey& key, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_merge_batch(const LaunchKey& key, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_iter_ahead_batch(const LaunchKey& key, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 
 // workgroups (= candidate lists) of that launch; 0 if this shape / generator / size has no single-launch kernel
 // (n_tail trailing shifted-elite rows; *tail_out > 0: that many rows behind the lists are scored through the cost array)
-int sample_rollout_lists(int h, int d, int O, int rounds, int n_rows, int n_tail = 0, int* tail_out = nullptr);
+int sample_rollout_lists(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int n_tail = 0, int* tail_out = nullptr);
 // may iteration `it >= 1` with n_rows rows fold the previous iteration's merge into its own launch?
-bool sample_rollout_merge_ok(int h, int d, int O, int rounds, int n_rows, int K);
-void launch_sample_rollout(const FastIterArgs& a, int h, int d, int O, int kind, bool merge_prologue, hipStream_t st);
+bool sample_rollout_merge_ok(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int K);
+void launch_sample_rollout(const LaunchCtx& cx, const FastIterArgs& a, int h, int d, int O, int kind, bool merge_prologue);
 
 }  // namespace icem

@@ -459,12 +459,12 @@ constexpr int single_launch_max_rw(int h, int d) {
 // extra candidates straight from the cost array (its kept-elite slot, free at iteration 0; *tail_out rows from pool row
 // n on).  Otherwise three shifted rows would push the launch over the list limit and onto twice the trajectories per
 // workgroup on half the CUs (N = 4 096: 15.5 instead of 12.5 us).
-static bool sample_rollout_shape(int h, int d, int O, int rounds, int n_rows, int n_tail, int* grid_out, int* rw_out,
+static bool sample_rollout_shape(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int n_tail, int* grid_out, int* rw_out,
                                  int* tail_out = nullptr) {
     const int max_rw = opt_i(OPT_FUSE_MAX_RW);  // read per call: the path-equivalence test flips it between planners
     int grid, rw, tail = 0;
     r16_shape(n_rows, &grid, &rw);
-    const int mult = g_batch.mult;
+    const int mult = bh.mult;
     if (mult > 1) {
         // a batch of `mult` problems of this size in one launch (icem_plan_step_batch): the slab size the chip would get for
         // all their rows together, the workgroup count of ONE problem (blockIdx.y is the problem); no tail shape
@@ -496,125 +496,92 @@ static bool sample_rollout_shape(int h, int d, int O, int rounds, int n_rows, in
     return true;
 }
 
-int sample_rollout_lists(int h, int d, int O, int rounds, int n_rows, int n_tail, int* tail_out) {
+int sample_rollout_lists(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int n_tail, int* tail_out) {
     int grid, rw, tail = 0;
-    if (!sample_rollout_shape(h, d, O, rounds, n_rows, n_tail, &grid, &rw, &tail)) return 0;
+    if (!sample_rollout_shape(bh, h, d, O, rounds, n_rows, n_tail, &grid, &rw, &tail)) return 0;
     if (tail_out) *tail_out = tail;
     return tail ? FAST_MAX_LISTS : grid;
 }
 
 // merge prologue: the selection wavefront joins the sampling waves (8 rollout waves: 13 waves share the register
 // file, the selection runs in its low-register form)
-bool sample_rollout_merge_ok(int h, int d, int O, int rounds, int n_rows, int K) {
+bool sample_rollout_merge_ok(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int K) {
     const int on = opt_i(OPT_MERGE_PROLOGUE);
     int grid, rw;
-    return on && K + 1 <= 12 && sample_rollout_shape(h, d, O, rounds, n_rows, 0, &grid, &rw);
+    return on && K + 1 <= 12 && sample_rollout_shape(bh, h, d, O, rounds, n_rows, 0, &grid, &rw);
 }
 
-bool sample_rollout_pack_ok(int h, int d, int O, int rounds, int n_rows, int K) {
+bool sample_rollout_pack_ok(const BatchHint& bh, int h, int d, int O, int rounds, int n_rows, int K) {
     const int on = opt_i(OPT_RIDING_PACK);
     int grid, rw;
-    return on && sample_rollout_merge_ok(h, d, O, rounds, n_rows, K) && sample_rollout_shape(h, d, O, rounds, n_rows, 0, &grid, &rw) &&
+    return on && sample_rollout_merge_ok(bh, h, d, O, rounds, n_rows, K) && sample_rollout_shape(bh, h, d, O, rounds, n_rows, 0, &grid, &rw) &&
            K * (h * d + 2) <= 16 * rw * h * d;
 }
 
-void launch_sample_rollout(const FastIterArgs& a, int h, int d, int O, int kind, bool merge_prologue, hipStream_t st) {
-    int grid, rw;
-    // (the tail shape only where the caller chose it -- it sets list_wgs then: the list count is the caller's contract)
-    if (!sample_rollout_shape(h, d, O, 10, a.r.n_rows, a.r.list_wgs > 0 ? a.s.n_shift : 0, &grid, &rw)) return;
-    if (g_batch.rec) {   // icem_plan_step_batch: recorded, launched for all problems at once (launch_sample_rollout_batch)
-        if (merge_prologue && a.m.records) {
-            g_batch.unsupported = true;
-            return;
+// The one table of the single-launch kernel: key -> compiled instantiation, handed to `f` as a tag that knows its two
+// launches; false: nothing compiled for this key.
+namespace {
+template <int H, int D, int O, int KIND, int RW, int KREG, bool REC, int ARITH>
+struct SrInst {
+    static constexpr int THREADS = sr_threads(D, RW) + (KREG > 0 ? 64 : 0);
+    static constexpr bool BATCHED = !REC;   // (the records merge is a sharded run's: not batched)
+    static void solo(int grid, hipStream_t st, const FastIterArgs& a) {
+        hipLaunchKernelGGL((sample_rollout_kernel<H, D, O, KIND, 10, RW, KREG, REC, ARITH>), dim3(grid), dim3(THREADS), 0, st, a);
+    }
+    static void batch(int grid, int n, hipStream_t st, const FastIterArgs* args_dev, const BatchBases& bases) {
+        hipLaunchKernelGGL((sample_rollout_batch_kernel<H, D, O, KIND, 10, RW, KREG, ARITH>), dim3(grid, n), dim3(THREADS), 0, st, args_dev, bases);
+    }
+};
+template <int H, int D, int O, int RW, class F>
+bool sample_rollout_pick(const LaunchKey& k, F& f) {
+    if constexpr (RW > single_launch_max_rw(H, D)) {
+        return false;
+    } else {
+        if (k.waves != RW) return false;
+        auto with = [&](auto kind, auto arith) {
+            constexpr int KK = decltype(kind)::value, AA = decltype(arith)::value;
+            if (k.form == 2) f(SrInst<H, D, O, KK, RW, 12, true, AA>{});
+            else if (k.form == 1) f(SrInst<H, D, O, KK, RW, 12, false, AA>{});
+            else f(SrInst<H, D, O, KK, RW, 0, false, AA>{});
+            return true;
+        };
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        if constexpr (O <= 20) {   // (the fp16-plane tile serves one-tile observation widths only)
+            if (k.arith == 1) return k.kind == 1 ? with(I1{}, I1{}) : with(I0{}, I1{});
         }
-        BatchRecord r;
-        r.kind = BATCH_SAMPLE_ROLLOUT;
-        r.it = a;
-        r.h = h, r.d = d, r.O = O, r.model_kind = kind, r.rw = rw, r.grid = grid;
-        r.prologue = merge_prologue;
-        g_batch.rec->push_back(r);
-        return;
+        return k.kind == 1 ? with(I1{}, I0{}) : with(I0{}, I0{});
     }
-    if (merge_prologue && a.m.records && a.p.part_k) grid += 1;  // workgroup 0: the riding pack
-#define XK(HH, DD, OO, WW, KR, RC)                                                                                      \
-    {                                                                                                                   \
-        constexpr int NT = sr_threads(DD, WW) + (KR > 0 ? 64 : 0);                                                     \
-        if constexpr (OO <= 20) {                                                                                       \
-            if (a.r.arith == 1) {                                                                                       \
-                if (kind == 1)                                                                                          \
-                    hipLaunchKernelGGL((sample_rollout_kernel<HH, DD, OO, 1, 10, WW, KR, RC, 1>), dim3(grid), dim3(NT), 0, st, a); \
-                else                                                                                                    \
-                    hipLaunchKernelGGL((sample_rollout_kernel<HH, DD, OO, 0, 10, WW, KR, RC, 1>), dim3(grid), dim3(NT), 0, st, a); \
-                return;                                                                                                 \
-            }                                                                                                           \
-        }                                                                                                               \
-        if (kind == 1)                                                                                                  \
-            hipLaunchKernelGGL((sample_rollout_kernel<HH, DD, OO, 1, 10, WW, KR, RC, 0>), dim3(grid), dim3(NT), 0, st, a); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((sample_rollout_kernel<HH, DD, OO, 0, 10, WW, KR, RC, 0>), dim3(grid), dim3(NT), 0, st, a); \
-        return;                                                                                                         \
-    }
-#define XW(HH, DD, OO, WW)                                                   \
-    if constexpr (WW <= single_launch_max_rw(HH, DD)) {                      \
-        if (rw == WW) {                                                      \
-            if (merge_prologue && a.m.records) XK(HH, DD, OO, WW, 12, true)  \
-            if (merge_prologue) XK(HH, DD, OO, WW, 12, false)                \
-            XK(HH, DD, OO, WW, 0, false)                                     \
-        }                                                                    \
-    }
-#define XR(HH, DD, OO)                   \
-    if (h == HH && d == DD && O == OO) { \
-        XW(HH, DD, OO, 1)                \
-        XW(HH, DD, OO, 2)                \
-        XW(HH, DD, OO, 4)                \
-        XW(HH, DD, OO, 8)                \
-    }
+}
+template <class F>
+bool sample_rollout_dispatch(const LaunchKey& k, F&& f) {
+#define XR(HH, DD, OO)                                                                                      \
+    if (k.h == HH && k.d == DD && k.O == OO)                                                                \
+        return sample_rollout_pick<HH, DD, OO, 1>(k, f) || sample_rollout_pick<HH, DD, OO, 2>(k, f) ||      \
+               sample_rollout_pick<HH, DD, OO, 4>(k, f) || sample_rollout_pick<HH, DD, OO, 8>(k, f);
     ICEM_FAST_SHAPES(XR)
 #undef XR
-#undef XW
-#undef XK
+    return false;
+}
+}  // namespace
+
+void launch_sample_rollout(const LaunchCtx& cx, const FastIterArgs& a, int h, int d, int O, int kind, bool merge_prologue) {
+    LaunchKey k;
+    // (the tail shape only where the caller chose it -- it sets list_wgs then: the list count is the caller's contract)
+    if (!sample_rollout_shape(cx.hint, h, d, O, 10, a.r.n_rows, a.r.list_wgs > 0 ? a.s.n_shift : 0, &k.wgs[0], &k.waves)) return;
+    k.family = LAUNCH_SAMPLE_ROLLOUT;
+    k.h = h, k.d = d, k.O = O, k.kind = kind, k.arith = a.r.arith;
+    k.form = !merge_prologue ? 0 : a.m.records ? 2 : 1;
+    k.wgs[1] = (k.form == 2 && a.p.part_k) ? 1 : 0;   // workgroup 0: the riding pack
+    submit(cx, k, k.form != 2, [&](void* dst, unsigned long long base) { batch_form(a, base, dst); },
+           [&] { sample_rollout_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0] + k.wgs[1], cx.st, a); }); });
 }
 
-// ... and the same launch for n problems (blockIdx.y): shape = one problem's record (all equal: plan.hip checked)
-void launch_sample_rollout_batch(const BatchRecord& s, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
-    const int h = s.h, d = s.d, O = s.O, kind = s.model_kind, rw = s.rw, arith = s.it.r.arith;
-    const dim3 grid(s.grid, n);
-#define XK(HH, DD, OO, WW, KR)                                                                                          \
-    {                                                                                                                   \
-        constexpr int NT = sr_threads(DD, WW) + (KR > 0 ? 64 : 0);                                                     \
-        if constexpr (OO <= 20) {                                                                                       \
-            if (arith == 1) {                                                                                           \
-                if (kind == 1)                                                                                          \
-                    hipLaunchKernelGGL((sample_rollout_batch_kernel<HH, DD, OO, 1, 10, WW, KR, 1>), grid, dim3(NT), 0, st, args_dev, bases); \
-                else                                                                                                    \
-                    hipLaunchKernelGGL((sample_rollout_batch_kernel<HH, DD, OO, 0, 10, WW, KR, 1>), grid, dim3(NT), 0, st, args_dev, bases); \
-                return;                                                                                                 \
-            }                                                                                                           \
-        }                                                                                                               \
-        if (kind == 1)                                                                                                  \
-            hipLaunchKernelGGL((sample_rollout_batch_kernel<HH, DD, OO, 1, 10, WW, KR, 0>), grid, dim3(NT), 0, st, args_dev, bases); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((sample_rollout_batch_kernel<HH, DD, OO, 0, 10, WW, KR, 0>), grid, dim3(NT), 0, st, args_dev, bases); \
-        return;                                                                                                         \
-    }
-#define XW(HH, DD, OO, WW)                                  \
-    if constexpr (WW <= single_launch_max_rw(HH, DD)) {     \
-        if (rw == WW) {                                     \
-            if (s.prologue) XK(HH, DD, OO, WW, 12)          \
-            XK(HH, DD, OO, WW, 0)                           \
-        }                                                   \
-    }
-#define XR(HH, DD, OO)                   \
-    if (h == HH && d == DD && O == OO) { \
-        XW(HH, DD, OO, 1)                \
-        XW(HH, DD, OO, 2)                \
-        XW(HH, DD, OO, 4)                \
-        XW(HH, DD, OO, 8)                \
-    }
-    ICEM_FAST_SHAPES(XR)
-#undef XR
-#undef XW
-#undef XK
+// ... and the same launch for n problems (blockIdx.y)
+void launch_sample_rollout_batch(const LaunchKey& k, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+    sample_rollout_dispatch(k, [&](auto inst) {
+        if constexpr (decltype(inst)::BATCHED) inst.batch(k.wgs[0], n, st, args_dev, bases);
+    });
 }
 
 }  // namespace icem

@@ -338,72 +338,64 @@ bool merge_noise_ok(const MergeSingleArgs& a, int rounds) {
     return a.records == nullptr && a.K + 1 <= 12 && rounds == 10 && fast_sample_supported(a.h, a.d);
 }
 
-void launch_merge_noise(const MergeSingleArgs& a, const FastSampleArgs& z, const FastSampleArgs& z2, hipStream_t st) {
-    if (g_batch.rec) {   // icem_plan_step_batch: recorded, launched for all problems at once (launch_merge_batch)
-        BatchRecord r;
-        r.kind = BATCH_MERGE_NOISE;
-        r.m = a;
-        r.z1 = z;
-        r.z2 = z2;
-        g_batch.rec->push_back(r);
-        return;
+// The last merge's launch, alone (wgs = {1, 0, 0}) or with noise workgroups beside it: key, and the one table of
+// merge_noise_kernel / merge_noise_batch_kernel -- the key's horizon -> `f(H, grid, lds)`; false: not a compiled horizon
+static LaunchKey merge_key(const MergeSingleArgs& a, const FastSampleArgs* z, const FastSampleArgs* z2) {
+    LaunchKey k;
+    k.family = LAUNCH_MERGE_NOISE;
+    k.h = a.h, k.d = a.d, k.form = z ? 1 : 0;
+    k.wgs[0] = 1;
+    if (z) {
+        const int tpw = MERGE_WG / z->d;
+        k.wgs[1] = (z->n + tpw - 1) / tpw;
+        k.wgs[2] = z2->n > 0 ? (z2->n + tpw - 1) / tpw : 0;
     }
-    const int tpw = MERGE_WG / z.d;
-    const int wgs1 = (z.n + tpw - 1) / tpw, wgs2 = z2.n > 0 ? (z2.n + tpw - 1) / tpw : 0;
-    const int grid = 1 + wgs1 + wgs2;
-    const size_t lds = std::max((size_t)a.h * a.d, (size_t)tpw * z.h * z.d) * sizeof(float);
-#define X(HH)                                                                                                    \
-    if (a.h == HH) {                                                                                             \
-        hipLaunchKernelGGL((merge_noise_kernel<HH, 12>), dim3(grid), dim3(MERGE_WG), lds, st, a, z, z2, wgs1);   \
-        return;                                                                                                  \
-    }
+    return k;
+}
+template <class F>
+static bool merge_noise_dispatch(const LaunchKey& k, F&& f) {
+    // workgroup 0 holds the new mean, a noise workgroup its [tpw, h, d] tile
+    const size_t lds = std::max((size_t)k.h * k.d, k.form ? (size_t)(MERGE_WG / k.d) * k.h * k.d : (size_t)0) * sizeof(float);
+    const int grid = k.wgs[0] + k.wgs[1] + k.wgs[2];
+#define X(HH) \
+    if (k.h == HH) return f(std::integral_constant<int, HH>{}, grid, lds), true;
     ICEM_FAST_HORIZONS(X)
 #undef X
+    return false;
 }
 
-// n problems' last merges (+ the next step's first noise, BATCH_MERGE_NOISE) in one launch; the lists form with K <= 11 only
-void launch_merge_batch(const BatchRecord& s, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
-    const MergeSingleArgs& a = s.m;
-    int wgs1 = 0, wgs2 = 0, tpw = 1;
-    if (s.kind == BATCH_MERGE_NOISE) {
-        tpw = MERGE_WG / s.z1.d;
-        wgs1 = (s.z1.n + tpw - 1) / tpw;
-        wgs2 = s.z2.n > 0 ? (s.z2.n + tpw - 1) / tpw : 0;
-    }
-    const dim3 grid(1 + wgs1 + wgs2, n);
-    const size_t lds = std::max((size_t)a.h * a.d, s.kind == BATCH_MERGE_NOISE ? (size_t)tpw * s.z1.h * s.z1.d : (size_t)0) * sizeof(float);
-#define X(HH)                                                                                                              \
-    if (a.h == HH) {                                                                                                       \
-        hipLaunchKernelGGL((merge_noise_batch_kernel<HH, 12>), grid, dim3(MERGE_WG), lds, st, args_dev, bases, wgs1);      \
-        return;                                                                                                            \
-    }
-    ICEM_FAST_HORIZONS(X)
-#undef X
+void launch_merge_noise(const LaunchCtx& cx, const MergeSingleArgs& a, const FastSampleArgs& z, const FastSampleArgs& z2) {
+    const LaunchKey k = merge_key(a, &z, &z2);
+    submit(cx, k, true, [&](void* dst, unsigned long long base) { batch_form(a, &z, &z2, base, dst); }, [&] {
+        merge_noise_dispatch(k, [&](auto H, int grid, size_t lds) {
+            hipLaunchKernelGGL((merge_noise_kernel<decltype(H)::value, 12>), dim3(grid), dim3(MERGE_WG), lds, cx.st, a, z, z2, k.wgs[1]);
+        });
+    });
 }
 
-void launch_merge_single(const MergeSingleArgs& a, hipStream_t st) {
-    if (g_batch.rec) {
-        if (a.records || a.K + 1 > 12) {
-            g_batch.unsupported = true;
-            return;
+// n problems' last merges (+ the next step's first noise) in one launch; the lists form with K <= 11 only
+void launch_merge_batch(const LaunchKey& k, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+    merge_noise_dispatch(k, [&](auto H, int grid, size_t lds) {
+        hipLaunchKernelGGL((merge_noise_batch_kernel<decltype(H)::value, 12>), dim3(grid, n), dim3(MERGE_WG), lds, st, args_dev, bases, k.wgs[1]);
+    });
+}
+
+// (alone, a solo step's merge is merge_single_kernel; a batch's is merge_noise_batch_kernel without noise workgroups)
+void launch_merge_single(const LaunchCtx& cx, const MergeSingleArgs& a) {
+    const LaunchKey k = merge_key(a, nullptr, nullptr);
+    submit(cx, k, !a.records && a.K + 1 <= 12, [&](void* dst, unsigned long long base) { batch_form(a, nullptr, nullptr, base, dst); }, [&] {
+        const size_t lds = (size_t)a.h * a.d * sizeof(float);
+        if (a.records) {
+            if (a.K + 1 <= 12)
+                hipLaunchKernelGGL((merge_single_kernel<12, true>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
+            else
+                hipLaunchKernelGGL((merge_single_kernel<34, true>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
+        } else if (a.K + 1 <= 12) {
+            hipLaunchKernelGGL((merge_single_kernel<12, false>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
+        } else {
+            hipLaunchKernelGGL((merge_single_kernel<34, false>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
         }
-        BatchRecord r;
-        r.kind = BATCH_MERGE_SINGLE;
-        r.m = a;
-        g_batch.rec->push_back(r);
-        return;
-    }
-    const size_t lds = (size_t)a.h * a.d * sizeof(float);
-    if (a.records) {
-        if (a.K + 1 <= 12)
-            hipLaunchKernelGGL((merge_single_kernel<12, true>), dim3(1), dim3(MERGE_WG), lds, st, a);
-        else
-            hipLaunchKernelGGL((merge_single_kernel<34, true>), dim3(1), dim3(MERGE_WG), lds, st, a);
-    } else if (a.K + 1 <= 12) {
-        hipLaunchKernelGGL((merge_single_kernel<12, false>), dim3(1), dim3(MERGE_WG), lds, st, a);
-    } else {
-        hipLaunchKernelGGL((merge_single_kernel<34, false>), dim3(1), dim3(MERGE_WG), lds, st, a);
-    }
+    });
 }
 
 }  // namespace icem

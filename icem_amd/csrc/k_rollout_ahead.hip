@@ -84,17 +84,57 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 8
 // Launch shape of the rollout role: rollout16's (one 16-trajectory tile per wave while they fit, at most FAST_MAX_LISTS
 // workgroups), but at most 8 wavefronts per workgroup -- two per SIMD, each taking its tiles one after the other: the
 // rollout leaves half of every SIMD's registers (and 100 of the CU's 160 KB of LDS) to a noise workgroup beside it.
-void ahead_shape(int n_rows, int* grid, int* waves) {
+void ahead_shape(const BatchHint& bh, int n_rows, int* grid, int* waves) {
     r16_shape(n_rows, grid, waves);
     if (*waves > 8) *waves = 8;
-    if (g_batch.mult > 1 && g_batch.ahead) {
+    if (bh.mult > 1 && bh.ahead) {
         // a batch of `mult` problems of this size in one launch (icem_plan_step_batch): waves per workgroup as for all their rows
         // together, the rollout workgroups of ONE problem (blockIdx.y is the problem)
         int g_all, w_all;
-        r16_shape(n_rows * g_batch.mult, &g_all, &w_all);
+        r16_shape(n_rows * bh.mult, &g_all, &w_all);
         *waves = std::max(*waves, std::min(w_all, 8));
         *grid = (std::max(1, (n_rows + 15) / 16) + *waves - 1) / *waves;
     }
+}
+
+// The one table of this launch: key -> compiled instantiation, handed to `f` as a tag that knows its two launches
+// (workgroups per role: key.wgs); false: nothing compiled for this key.
+template <int H, int D, int O, int KIND, int WAVES, int PM, int ARITH>
+struct AheadInst {
+    using L = AheadLds<H, D, O, KIND, WAVES>;
+    static constexpr bool BATCHED = PM != 2;   // (sharded launches are not batched)
+    static void solo(int grid, hipStream_t st, const IterAheadArgs& a) {
+        hipLaunchKernelGGL((iter_ahead_kernel<H, D, O, KIND, WAVES, PM, ARITH>), dim3(grid), dim3(64 * WAVES), L::FLOATS * sizeof(float), st, a);
+    }
+    static void batch(int grid, int n, hipStream_t st, const IterAheadArgs* args_dev, const BatchBases& bases) {
+        hipLaunchKernelGGL((iter_ahead_batch_kernel<H, D, O, KIND, WAVES, PM, ARITH>), dim3(grid, n), dim3(64 * WAVES), L::FLOATS * sizeof(float), st,
+                           args_dev, bases);
+    }
+};
+template <int H, int D, int O, int WAVES, class F>
+bool iter_ahead_pick(const LaunchKey& k, F& f) {
+    if (k.waves != WAVES) return false;
+    auto with = [&](auto kind, auto arith) {
+        constexpr int KK = decltype(kind)::value, AA = decltype(arith)::value;
+        if (k.form == 2) f(AheadInst<H, D, O, KK, WAVES, 2, AA>{});
+        else if (k.form) f(AheadInst<H, D, O, KK, WAVES, 1, AA>{});
+        else f(AheadInst<H, D, O, KK, WAVES, 0, AA>{});
+        return true;
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    if (k.arith == 1) return k.kind == 1 ? with(I1{}, I1{}) : with(I0{}, I1{});
+    return k.kind == 1 ? with(I1{}, I0{}) : with(I0{}, I0{});
+}
+template <class F>
+bool iter_ahead_dispatch(const LaunchKey& k, F&& f) {
+#define XR(HH, DD, OO)                                                                                        \
+    if constexpr (OO <= 20) {                                                                                 \
+        if (k.h == HH && k.d == DD && k.O == OO) return iter_ahead_pick<HH, DD, OO, 4>(k, f) || iter_ahead_pick<HH, DD, OO, 8>(k, f); \
+    }
+    ICEM_FAST_SHAPES(XR)
+#undef XR
+    return false;
 }
 
 }  // namespace
@@ -105,122 +145,37 @@ void ahead_shape(int n_rows, int* grid, int* waves) {
 // step) the rollout role does not fit the 128 registers it shares its SIMDs on -- 112-158 spilled VGPRs, and the launch
 // LOSES to the sampler + rollout16 pair: 236.1 vs 171.4 us per MPC step at N = 16 384 (d = 17, 3 iterations), 657.7 vs
 // 473.7 at 65 536 (EXPERIMENTS.md R4.6).  Those shapes are not instantiated.
-bool rollout_ahead_ok(int h, int d, int O, int K, int n_rows) {
+bool rollout_ahead_ok(const BatchHint& bh, int h, int d, int O, int K, int n_rows) {
     int grid, waves;
-    r16_shape(n_rows * ((g_batch.mult > 1 && g_batch.ahead) ? g_batch.mult : 1), &grid, &waves);   // (a batch: the rows of all its problems fill the chip)
+    r16_shape(n_rows * ((bh.mult > 1 && bh.ahead) ? bh.mult : 1), &grid, &waves);   // (a batch: the rows of all its problems fill the chip)
     return O <= 20 && K + 1 <= AHEAD_KREG && waves >= 4 && fast_rollout_supported(h, d, O, K) && fast_sample_supported(h, d);
 }
 
-int ahead_roll_workgroups(int n_rows) {
+int ahead_roll_workgroups(const BatchHint& bh, int n_rows) {
     int grid, waves;
-    ahead_shape(n_rows, &grid, &waves);
+    ahead_shape(bh, n_rows, &grid, &waves);
     return grid;
 }
 
-void launch_iter_ahead(const IterAheadArgs& a_in, int h, int d, int O, int kind, hipStream_t st) {
+void launch_iter_ahead(const LaunchCtx& cx, const IterAheadArgs& a_in, int h, int d, int O, int kind) {
     IterAheadArgs a = a_in;
-    int grid, waves;
-    ahead_shape(a.r.n_rows, &grid, &waves);
-    a.n_roll = grid;
-    if (g_batch.rec) {   // icem_plan_step_batch: recorded, launched for all problems at once (launch_iter_ahead_batch)
-        if (a.has_merge == 2 || O > 20 || (waves != 4 && waves != 8)) {
-            g_batch.unsupported = true;
-            return;
-        }
-        BatchRecord r;
-        r.kind = BATCH_ITER_AHEAD;
-        a.n_noise = a.z.n > 0 ? (a.z.n + (64 * waves) / d - 1) / ((64 * waves) / d) : 0;   // (AheadLds::TPW = threads / d)
-        r.ia = a;
-        r.h = h, r.d = d, r.O = O, r.model_kind = kind, r.rw = waves, r.grid = grid;
-        g_batch.rec->push_back(r);
-        return;
-    }
-#define XK(HH, DD, OO, KK, WW, PP)                                                                                         \
-    {                                                                                                                      \
-        using L = AheadLds<HH, DD, OO, KK, WW>;                                                                            \
-        a.n_noise = a.z.n > 0 ? (a.z.n + L::TPW - 1) / L::TPW : 0;                                                         \
-        const int total = grid + a.n_noise + (a.s.n_shift > 0 ? 1 : 0) + (PP == 2 ? 1 : 0);                                \
-        if (a.r.arith == 1)                                                                                                \
-            hipLaunchKernelGGL((iter_ahead_kernel<HH, DD, OO, KK, WW, PP, 1>), dim3(total), dim3(64 * WW), L::FLOATS * sizeof(float), st, a); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((iter_ahead_kernel<HH, DD, OO, KK, WW, PP, 0>), dim3(total), dim3(64 * WW), L::FLOATS * sizeof(float), st, a); \
-    }
-#define XW(HH, DD, OO, WW)                          \
-    if (waves == WW) {                              \
-        if (kind == 1) {                            \
-            if (a.has_merge == 2) {                 \
-                XK(HH, DD, OO, 1, WW, 2)            \
-            } else if (a.has_merge) {               \
-                XK(HH, DD, OO, 1, WW, 1)            \
-            } else {                                \
-                XK(HH, DD, OO, 1, WW, 0)            \
-            }                                       \
-        } else {                                    \
-            if (a.has_merge == 2) {                 \
-                XK(HH, DD, OO, 0, WW, 2)            \
-            } else if (a.has_merge) {               \
-                XK(HH, DD, OO, 0, WW, 1)            \
-            } else {                                \
-                XK(HH, DD, OO, 0, WW, 0)            \
-            }                                       \
-        }                                           \
-        return;                                     \
-    }
-#define XR(HH, DD, OO)                       \
-    if constexpr (OO <= 20) {                \
-        if (h == HH && d == DD && O == OO) { \
-            XW(HH, DD, OO, 4)                \
-            XW(HH, DD, OO, 8)                \
-        }                                    \
-    }
-    ICEM_FAST_SHAPES(XR)
-#undef XR
-#undef XW
-#undef XK
+    LaunchKey k;
+    ahead_shape(cx.hint, a.r.n_rows, &a.n_roll, &k.waves);
+    const int tpw = (64 * k.waves) / d;   // (AheadLds::TPW: rows of noise per workgroup)
+    a.n_noise = a.z.n > 0 ? (a.z.n + tpw - 1) / tpw : 0;
+    k.family = LAUNCH_ITER_AHEAD;
+    k.h = h, k.d = d, k.O = O, k.kind = kind, k.arith = a.r.arith, k.form = a.has_merge;
+    k.wgs[0] = a.n_roll, k.wgs[1] = a.n_noise, k.wgs[2] = (a.s.n_shift > 0 ? 1 : 0) + (a.has_merge == 2 ? 1 : 0);
+    const bool compiled = iter_ahead_dispatch(k, [](auto) {});
+    submit(cx, k, compiled && a.has_merge != 2, [&](void* dst, unsigned long long base) { batch_form(a, base, dst); },
+           [&] { iter_ahead_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0] + k.wgs[1] + k.wgs[2], cx.st, a); }); });
 }
 
-// ... and the same launch for n problems (blockIdx.y); shape = one problem's record (all equal: plan.hip checked)
-void launch_iter_ahead_batch(const BatchRecord& sr, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
-    const int h = sr.h, d = sr.d, O = sr.O, kind = sr.model_kind, waves = sr.rw;
-    const IterAheadArgs& a = sr.ia;
-#define XK(HH, DD, OO, KK, WW, PP)                                                                                         \
-    {                                                                                                                      \
-        using L = AheadLds<HH, DD, OO, KK, WW>;                                                                            \
-        const int n_noise = a.z.n > 0 ? (a.z.n + L::TPW - 1) / L::TPW : 0;                                                 \
-        const dim3 grid(a.n_roll + n_noise + (a.s.n_shift > 0 ? 1 : 0), n);                                                \
-        if (a.r.arith == 1)                                                                                                \
-            hipLaunchKernelGGL((iter_ahead_batch_kernel<HH, DD, OO, KK, WW, PP, 1>), grid, dim3(64 * WW), L::FLOATS * sizeof(float), st, args_dev, bases); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((iter_ahead_batch_kernel<HH, DD, OO, KK, WW, PP, 0>), grid, dim3(64 * WW), L::FLOATS * sizeof(float), st, args_dev, bases); \
-    }
-#define XW(HH, DD, OO, WW)                          \
-    if (waves == WW) {                              \
-        if (kind == 1) {                            \
-            if (a.has_merge) {                      \
-                XK(HH, DD, OO, 1, WW, 1)            \
-            } else {                                \
-                XK(HH, DD, OO, 1, WW, 0)            \
-            }                                       \
-        } else {                                    \
-            if (a.has_merge) {                      \
-                XK(HH, DD, OO, 0, WW, 1)            \
-            } else {                                \
-                XK(HH, DD, OO, 0, WW, 0)            \
-            }                                       \
-        }                                           \
-        return;                                     \
-    }
-#define XR(HH, DD, OO)                       \
-    if constexpr (OO <= 20) {                \
-        if (h == HH && d == DD && O == OO) { \
-            XW(HH, DD, OO, 4)                \
-            XW(HH, DD, OO, 8)                \
-        }                                    \
-    }
-    ICEM_FAST_SHAPES(XR)
-#undef XR
-#undef XW
-#undef XK
+// ... and the same launch for n problems (blockIdx.y)
+void launch_iter_ahead_batch(const LaunchKey& k, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+    iter_ahead_dispatch(k, [&](auto inst) {
+        if constexpr (decltype(inst)::BATCHED) inst.batch(k.wgs[0] + k.wgs[1] + k.wgs[2], n, st, args_dev, bases);
+    });
 }
 
 }  // namespace icem

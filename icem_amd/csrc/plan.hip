@@ -22,8 +22,6 @@ __global__ void publish_result_kernel(const float* executed, const float* best_c
 
 namespace icem {
 
-thread_local BatchState g_batch;   // icem_plan_step_batch: launch-shape hint + the recording launchers (icem_fused.h)
-
 // An argument block with EVERY byte defined (padding included): icem_plan_step_batch keeps the blocks of the previous
 // same-parity step and compares bytes to decide whether the device copy is still good.  (Members with a non-zero default:
 // MergeSingleArgs::keep_base, FastRolloutArgs::act_mag / m_scale / b_scale.)
@@ -187,20 +185,25 @@ FastRolloutArgs fast_rollout_args(const icem_handle* h, int n_rows, int n_cand, 
 // workgroups (= candidate lists) of the single-launch kernel for this handle, 0 where it has none.  (Its small slabs roll out on
 // Tile4, the VALU twin of the EXACT tile; a handle whose tile arithmetic is the fp16 planes gets the kernel's Tile16H
 // instantiation instead -- one arithmetic per handle, whatever a launch's row count.)
-static int one_launch_lists(const icem_handle* h, int n_rows, int n_tail = 0, int* tail_out = nullptr) {
+static int one_launch_lists(const icem_handle* h, const BatchHint& bh, int n_rows, int n_tail = 0, int* tail_out = nullptr) {
     if (tail_out) *tail_out = 0;
     const icem_config& c = h->cfg;
-    return sample_rollout_lists(c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, n_tail, tail_out);
+    return sample_rollout_lists(bh, c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, n_tail, tail_out);
+}
+
+// a launcher without a batched form, reached while recording (icem_plan_step_batch checks its configurations up front; belt
+// and braces): nothing is launched, the batch is refused
+static int no_batched_form(const LaunchCtx& cx, const char* what) {
+    cx.rec->unsupported = true;
+    return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_batch: ") + what);
 }
 
 // rows -> costs (+ one sorted candidate list per workgroup when K > 0); returns the number of candidate lists
 int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const void* obs0, const void* actions,
-                        void* costs, float* part_c, int* part_i, hipStream_t st, int* lists_out,
+                        void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k, int n_tail, int* tail_out) {
-    if (g_batch.rec) {   // (no batched form: icem_plan_step_batch checks its configurations up front; belt and braces)
-        g_batch.unsupported = true;
-        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: this configuration's rollout launch has no batched form");
-    }
+    if (cx.rec) return no_batched_form(cx, "this configuration's rollout launch has no batched form");
+    hipStream_t st = cx.st;
     int rc = ensure_fast_model(h);
     if (rc) return rc;
     if (tail_out) *tail_out = 0;
@@ -324,13 +327,11 @@ FastSampleArgs fast_sample_args(const icem_handle* h, int n, long long first_ind
 }
 
 int launch_fast_sample(const icem_handle* h, int n, long long first_index, const void* mean, const void* std,
-                       const void* low, const void* high, uint64_t offset, int row0_mean, void* out, hipStream_t st,
+                       const void* low, const void* high, uint64_t offset, int row0_mean, void* out, const LaunchCtx& cx,
                        int n_shift, const void* elites_src, uint64_t offset2) {
     if (n <= 0 && n_shift <= 0) return ICEM_OK;
-    if (g_batch.rec) {
-        g_batch.unsupported = true;
-        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: this configuration's sampling launch has no batched form");
-    }
+    if (cx.rec) return no_batched_form(cx, "this configuration's sampling launch has no batched form");
+    hipStream_t st = cx.st;
     const FastSampleArgs a = fast_sample_args(h, n, first_index, mean, std, low, high, offset, row0_mean, out, n_shift,
                                               elites_src, offset2);
     {
@@ -343,12 +344,12 @@ int launch_fast_sample(const icem_handle* h, int n, long long first_index, const
 
 // Can the f32 launch of an iteration with n_rows local rows (no shifted elites) carry a merge in its prologue?
 // (single-launch kernel with <= 4 rollout waves, or the sampler of the two-kernel path)
-bool prologue_possible(const icem_handle* h, int n_rows) {
+bool prologue_possible(const icem_handle* h, const BatchHint& bh, int n_rows) {
     const icem_config& c = h->cfg;
     const int K = c.num_elites;
     if (c.dtype != ICEM_F32 || !fast_rollout_ok(h, K) || !fast_sample_ok(h) || n_rows <= 0) return false;
-    if (one_launch_lists(h, n_rows) > 0)
-        return sample_rollout_merge_ok(c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, K);
+    if (one_launch_lists(h, bh, n_rows) > 0)
+        return sample_rollout_merge_ok(bh, c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, K);
     return sample_folded_merge_ok(c.horizon, c.act_dim, c.rng_rounds, K);
 }
 
@@ -566,31 +567,30 @@ static MergeSingleArgs pack_launch_args(const icem_handle* h, const PackPrev& pp
 }
 
 // a stashed merge that found no launch to ride in
-int launch_pending_merge(icem_handle* h, hipStream_t st) {
-    if (g_batch.rec) {
-        g_batch.unsupported = true;
-        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a merge found no launch to ride in");
-    }
+int launch_pending_merge(icem_handle* h, const LaunchCtx& cx) {
+    if (cx.rec) return no_batched_form(cx, "a merge found no launch to ride in");
+    hipStream_t st = cx.st;
     const MergeSingleArgs& m = h->ride.merge;
     if (m.records != nullptr) return gk_merge_refit(h, generic_from(m), st);
     {
         ProfScope prof(h, ICEM_K_MERGE_REFIT, m.n_lists * m.K + m.n_keep, st);
-        launch_merge_single(m, st);
+        launch_merge_single(cx, m);
     }
     ICEM_HIP_TRY(hipGetLastError());
     return ICEM_OK;
 }
 
 // will the merge-prologue launch of an iteration with n_rows local rows take the previous iteration's pack along?
-static bool next_launch_takes_pack(const icem_handle* h, int n_rows) {
+static bool next_launch_takes_pack(const icem_handle* h, const BatchHint& bh, int n_rows) {
     const icem_config& c = h->cfg;
-    if (one_launch_lists(h, n_rows) > 0)
-        return sample_rollout_pack_ok(c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, c.num_elites);
+    if (one_launch_lists(h, bh, n_rows) > 0)
+        return sample_rollout_pack_ok(bh, c.horizon, c.act_dim, h->Of, c.rng_rounds, n_rows, c.num_elites);
     return sample_folded_pack_ok(c.horizon, c.act_dim, c.rng_rounds, c.num_elites);
 }
 
 // a stashed pack that found no launch to ride in
-int launch_pending_pack(icem_handle* h, hipStream_t st) {
+int launch_pending_pack(icem_handle* h, const LaunchCtx& cx) {
+    hipStream_t st = cx.st;
     const PackPrev& pp = h->ride.pack;
     {
         ProfScope prof(h, ICEM_K_LOCAL_PACK, pp.n_lists * pp.K, st);
@@ -602,7 +602,8 @@ int launch_pending_pack(icem_handle* h, hipStream_t st) {
 }
 
 template <typename T>
-int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st) {
+int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, const LaunchCtx& cx) {
+    hipStream_t st = cx.st;
     const icem_config& c = h->cfg;
     const int hd = h->hd, K = c.num_elites;
     const int n_global = h->pop[it];
@@ -651,26 +652,26 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
             const int n_rows = n_loc + n_extra;
             int tail_rows = 0;  // shifted-elite rows scored through the cost array instead of a list (world 1 only)
             const int one = (!ext_z && fast_sample_ok(h) && (n_extra == 0 || shift_in_sampler))
-                                ? one_launch_lists(h, n_rows, shift_in_sampler ? n_extra : 0, &tail_rows) : 0;
+                                ? one_launch_lists(h, cx.hint, n_rows, shift_in_sampler ? n_extra : 0, &tail_rows) : 0;
             h->local.tail_rows = one > 0 ? tail_rows : 0;
             // the merge finds the lists' indices behind `lists * K` costs
             split_partial_ws<float>(b->workspace, one > 0 ? one : rollout_lists(c.horizon, c.act_dim, h->Of, n_rows), K, &pc, &pi);
             bool prologue = false, ride = false;
             if (h->ride.merge_pending) {
-                prologue = !ext_z && n_extra == 0 && prologue_possible(h, n_rows);
+                prologue = !ext_z && n_extra == 0 && prologue_possible(h, cx.hint, n_rows);
                 // a stashed pack rides with the merge whose records it produces, or runs now -- in front of that merge
-                ride = prologue && h->ride.pack_pending && next_launch_takes_pack(h, n_rows);
+                ride = prologue && h->ride.pack_pending && next_launch_takes_pack(h, cx.hint, n_rows);
                 if (h->ride.pack_pending && !ride) {
-                    rc = launch_pending_pack(h, st);
+                    rc = launch_pending_pack(h, cx);
                     if (rc) return rc;
                 }
                 if (!prologue) {  // cannot ride along after all: run it now
-                    rc = launch_pending_merge(h, st);
+                    rc = launch_pending_merge(h, cx);
                     if (rc) return rc;
                 }
                 h->ride.merge_pending = false;
             } else if (h->ride.pack_pending) {
-                rc = launch_pending_pack(h, st);
+                rc = launch_pending_pack(h, cx);
                 if (rc) return rc;
             }
             h->ride.pack_pending = false;
@@ -693,7 +694,7 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                 fa.r.list_wgs = tail_rows > 0 ? one : 0;
                 {
                     ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n_rows * c.horizon, st);
-                    launch_sample_rollout(fa, c.horizon, c.act_dim, h->Of, h->model_kind, prologue, st);
+                    launch_sample_rollout(cx, fa, c.horizon, c.act_dim, h->Of, h->model_kind, prologue);
                 }
                 ICEM_HIP_TRY(hipGetLastError());
                 lists = one;
@@ -722,14 +723,14 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                 } else if (ext_z) {
                     rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, off, 0, row0, actions, st);
                 } else if (fast_sample_ok(h)) {
-                    rc = launch_fast_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, st,
+                    rc = launch_fast_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, cx,
                                             shift_in_sampler ? n_extra : 0, shift_src, base + (uint64_t)c.opt_iters);
                 } else {
                     rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, nullptr, nullptr, off, 0, row0, actions, st);
                 }
                 if (rc) return rc;
                 int tail2 = 0;
-                rc = launch_fast_rollout(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi, st, &lists,
+                rc = launch_fast_rollout(h, n_rows, n_cand, K, b->obs0, actions, b->costs, pc, pi, cx, &lists,
                                          (unsigned long long*)b->workspace, (c.world == 1 && it == 0) ? n_extra : 0, &tail2);
                 if (rc) return rc;
                 h->local.tail_rows = tail2;
@@ -753,7 +754,7 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                 const bool rides_next = !last && it + 1 < c.opt_iters;
                 if (fold_push && xchg_concurrent_peers(h) && h->deferral && (rides_next || (last && fuse_last)) && lists > 0 && records_fit_prologue(h)) {
                     const int n_next = rides_next ? shard_of(h, it + 1).n_loc : 0;
-                    if (!rides_next || (prologue_possible(h, n_next) && next_launch_takes_pack(h, n_next))) {
+                    if (!rides_next || (prologue_possible(h, cx.hint, n_next) && next_launch_takes_pack(h, cx.hint, n_next))) {
                         h->ride.pack = make_pack(pk, sh, (float*)rec, px);
                         h->ride.pack_pending = true;
                         return ICEM_OK;
@@ -793,7 +794,8 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
 }
 
 template <typename T>
-int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, hipStream_t st, MergeRoute route = MergeRoute()) {
+int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, int it, const LaunchCtx& cx, MergeRoute route) {
+    hipStream_t st = cx.st;
     const icem_config& c = h->cfg;
     const int K = c.num_elites;
     const MergeArgsV a = merge_args<T>(h, b, mpc_step, it, route);
@@ -819,15 +821,15 @@ int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                 return ICEM_OK;
             }
             if (h->ride.pack_pending) {  // (cannot happen at world == 1; kept symmetrical)
-                const int rc = launch_pending_pack(h, st);
+                const int rc = launch_pending_pack(h, cx);
                 if (rc) return rc;
             }
             ProfScope prof(h, ICEM_K_MERGE_REFIT, h->local.lists * K + m.n_keep, st);
             if (h->ahead.tail_pending && merge_noise_ok(m, c.rng_rounds)) {
-                launch_merge_noise(m, h->ahead.tail_args, h->ahead.tail2_args, st);  // + (the rest of) the next step's first noise
+                launch_merge_noise(cx, m, h->ahead.tail_args, h->ahead.tail2_args);  // + (the rest of) the next step's first noise
                 h->ahead.tail_pending = false;
             } else {
-                launch_merge_single(m, st);
+                launch_merge_single(cx, m);
             }
             ICEM_HIP_TRY(hipGetLastError());
             return ICEM_OK;
@@ -855,17 +857,17 @@ int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                 return ICEM_OK;
             }
             if (h->ride.pack_pending) {  // (records gathered by a collective between the two: separate launches)
-                const int rc = launch_pending_pack(h, st);
+                const int rc = launch_pending_pack(h, cx);
                 if (rc) return rc;
             }
             ProfScope prof(h, ICEM_K_MERGE_REFIT, a.n_rec + a.n_keep, st);
-            launch_merge_single(m, st);
+            launch_merge_single(cx, m);
             ICEM_HIP_TRY(hipGetLastError());
             return ICEM_OK;
         }
     }
     if (h->ride.pack_pending) {
-        const int rc = launch_pending_pack(h, st);
+        const int rc = launch_pending_pack(h, cx);
         if (rc) return rc;
     }
     if (c.world == 1 && h->local.sel_cand > 0 && h->local.lists == 0) {
@@ -901,7 +903,7 @@ void ahead_destroy(icem_handle* h) {
     A = icem_handle::Ahead();
 }
 
-static bool ahead_eligible(icem_handle* h, const icem_plan_buffers* b, bool sharded = false) {
+static bool ahead_eligible(icem_handle* h, const icem_plan_buffers* b, const BatchHint& bh, bool sharded = false) {
     icem_handle::Ahead& A = h->ahead;
     const icem_config& c = h->cfg;
     if (A.disabled < 0) {
@@ -927,7 +929,7 @@ static bool ahead_eligible(icem_handle* h, const icem_plan_buffers* b, bool shar
     }
     for (size_t it = 0; it < h->pop.size(); ++it) {
         const int n = sharded ? shard_of(h, (int)it).n_loc : h->pop[it];
-        if (n < A.min_rows || !rollout_ahead_ok(c.horizon, c.act_dim, h->Of, c.num_elites, n)) return false;
+        if (n < A.min_rows || !rollout_ahead_ok(bh, c.horizon, c.act_dim, h->Of, c.num_elites, n)) return false;
     }
     if (c.shift_elites && h->n_reuse > 16) return false;  // (the shift role rolls its rows out as one 16-row tile)
     // the transform takes the bounds as two scalars: fetch them once per (low, high) buffer pair
@@ -963,7 +965,7 @@ struct AheadStep {
     icem_handle* h;
     const icem_plan_buffers* b;
     int mpc_step;
-    hipStream_t st;
+    LaunchCtx cx;
     const char* name;
     uint64_t base = 0;
     float* cur_mean = nullptr;  // where the current distribution lives
@@ -1001,12 +1003,12 @@ struct AheadStep {
     int first_noise(Shard sh, float* pool, bool* hit_out) {
         icem_handle::Ahead& A = h->ahead;
         const bool hit = A.next_valid && A.next_episode == h->episode && A.next_step == mpc_step && A.next_pool == pool &&
-                         A.next_stream == st;   // (another stream is not ordered behind the launch that drew it: a miss)
+                         A.next_stream == cx.st;   // (another stream is not ordered behind the launch that drew it: a miss)
         A.next_valid = false;
-        if (!hit) {
+        if (!hit) {   // (issued at once also while a batch records: it writes this handle's own pool, in front of the batch's launches)
             const FastSampleArgs za = noise_args(sh.n_loc, sh.lo, base, pool);
-            ProfScope prof(h, ICEM_K_SAMPLE, (long long)sh.n_loc * h->cfg.horizon, st);
-            launch_noise_rows(za, h->cfg.rng_rounds, st);
+            ProfScope prof(h, ICEM_K_SAMPLE, (long long)sh.n_loc * h->cfg.horizon, cx.st);
+            launch_noise_rows(za, h->cfg.rng_rounds, cx.st);
         }
         ICEM_HIP_TRY(hipGetLastError());
         *hit_out = hit;
@@ -1019,7 +1021,7 @@ struct AheadStep {
         A.next_episode = h->episode;
         A.next_step = mpc_step + 1;
         A.next_pool = np;
-        A.next_stream = st;
+        A.next_stream = cx.st;
     }
     // the rollout role of iteration `it`: map the shard's raw noise of bb.actions with the current distribution, roll out
     void roll_role(IterAheadArgs& ia, int it, Shard sh, const icem_plan_buffers& bb) const {
@@ -1045,17 +1047,17 @@ struct AheadStep {
     int launch(const IterAheadArgs& ia, int n) {
         const icem_config& c = h->cfg;
         {
-            ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n * c.horizon, st);
-            launch_iter_ahead(ia, c.horizon, c.act_dim, h->Of, h->model_kind, st);
+            ProfScope prof(h, ICEM_K_SAMPLE_ROLLOUT, (long long)n * c.horizon, cx.st);
+            launch_iter_ahead(cx, ia, c.horizon, c.act_dim, h->Of, h->model_kind);
         }
         ICEM_HIP_TRY(hipGetLastError());
-        h->local.lists = ahead_roll_workgroups(n);
+        h->local.lists = ahead_roll_workgroups(cx.hint, n);
         return ICEM_OK;
     }
     // iteration `it`'s merge: stashed for the next launch, its distribution going to the handle's ping-pong pair, or (last) launched
     int merge(const icem_plan_buffers& bb, int it) {
         const MergeRoute route = merge_route(h, b, it, true);
-        const int rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st, route);
+        const int rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, cx, route);
         if (rc || it == h->cfg.opt_iters - 1) return rc;
         if (!h->ride.merge_pending) return fail(ICEM_E_STATE, std::string(name) + ": the merge did not defer");
         cur_mean = route.mean_out;
@@ -1065,11 +1067,11 @@ struct AheadStep {
     void end() { h->ahead.ctr += (unsigned long long)(h->cfg.opt_iters - 1); }
 };
 
-static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
+static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx) {
     icem_handle::Ahead& A = h->ahead;
     const icem_config& c = h->cfg;
     const int iters = c.opt_iters, hd = h->hd;
-    AheadStep s{h, b, mpc_step, st, "noise-ahead"};
+    AheadStep s{h, b, mpc_step, cx, "noise-ahead"};
     int rc = s.begin();
     if (rc) return rc;
     const int n_extra = shift_rows(h, mpc_step, 0);
@@ -1137,9 +1139,9 @@ static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_s
         rc = s.merge(bb, it);
         if (rc) return rc;
         if (last && A.tail_pending) {  // (the merge could not take it along: launches of their own)
-            if (g_batch.rec) g_batch.unsupported = true;   // (icem_plan_step_batch: these would run AHEAD of the recorded launches)
-            launch_noise_rows(A.tail_args, c.rng_rounds, st);
-            if (A.tail2_args.n > 0) launch_noise_rows(A.tail2_args, c.rng_rounds, st);
+            if (cx.rec) return no_batched_form(cx, "the next step's noise found no merge to ride with");   // (they would run AHEAD of the recorded launches)
+            launch_noise_rows(A.tail_args, c.rng_rounds, cx.st);
+            if (A.tail2_args.n > 0) launch_noise_rows(A.tail2_args, c.rng_rounds, cx.st);
             ICEM_HIP_TRY(hipGetLastError());
             A.tail_pending = false;
         }
@@ -1159,13 +1161,13 @@ static int plan_step_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_s
 // roll out this rank's shard, the noise workgroups draw the shard's next noise; rank 0 alone builds and rolls out the
 // (replicated) shifted elites.  Every pool is written back (the record pack gathers actions).  The last iteration's
 // pack and merge share one launch of their own, as on the sampler + rollout path.
-static int plan_step_sharded_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
+static int plan_step_sharded_ahead(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx) {
     const icem_config& c = h->cfg;
     const int iters = c.opt_iters, K = c.num_elites, hd = h->hd;
-    AheadStep s{h, b, mpc_step, st, "noise-ahead (sharded)"};
+    AheadStep s{h, b, mpc_step, cx, "noise-ahead (sharded)"};
     int rc = s.begin();
     if (rc) return rc;
-    rc = ensure_pub(h, st);
+    rc = ensure_pub(h, cx.st);
     if (rc) return rc;
     const int n_extra = shift_rows(h, mpc_step, 0);
     float* rec = (float*)b->records + (size_t)c.rank * K * (hd + 2);
@@ -1234,7 +1236,7 @@ static int plan_step_sharded_ahead(icem_handle* h, const icem_plan_buffers* b, i
 // so it is drawn beside THIS step's last merge, the one launch that leaves 255 CUs idle (merge_noise_kernel), into a
 // buffer of the handle; iteration 0 of the next step then only maps it (FastSampleArgs::raw_src).  Same sample_row, same
 // map: same bits as sampling in place.  Arms h->ahead.tail_args for plan_iter_merge_t's last launch.
-void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, hipStream_t st) {
+void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx) {
     icem_handle::Ahead& A = h->ahead;
     const icem_config& c = h->cfg;
     const int on = opt_i(OPT_PREDRAW);
@@ -1249,7 +1251,7 @@ void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step,
     const int n_shift = shift_rows(h, mpc_step + 1, 0);
     if (n_shift * c.act_dim > 256) return;
     int tail_rows = 0;
-    if (one_launch_lists(h, n0 + n_shift, n_shift, &tail_rows) <= 0) return;
+    if (one_launch_lists(h, cx.hint, n0 + n_shift, n_shift, &tail_rows) <= 0) return;
     if (!A.pre_raw && hipMalloc(&A.pre_raw, (size_t)(n0 + h->n_reuse + 16) * h->hd * sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         A.pre_raw = nullptr;
@@ -1263,7 +1265,7 @@ void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step,
     A.pre_valid = true;
     A.pre_episode = h->episode;
     A.pre_step = mpc_step + 1;
-    A.pre_stream = st;
+    A.pre_stream = cx.st;
 }
 
 }  // namespace icem
@@ -1350,20 +1352,22 @@ int icem_plan_iter_local(icem_handle* h, const icem_plan_buffers* b, int32_t mpc
         bb.mean = h->cur_mean;
         bb.std = h->cur_std;
     }
-    return ICEM_DISPATCH(h, plan_iter_local_t<float>(h, &bb, mpc_step, it, st), plan_iter_local_t<double>(h, &bb, mpc_step, it, st));
+    const LaunchCtx cx{st};
+    return ICEM_DISPATCH(h, plan_iter_local_t<float>(h, &bb, mpc_step, it, cx), plan_iter_local_t<double>(h, &bb, mpc_step, it, cx));
 }
 
 // icem_plan_iter_merge with the merge's route given (icem_plan_step folds merges at world == 1 too)
-static int plan_iter_merge_routed(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, hipStream_t st, MergeRoute route) {
-    const int rc = check_plan(h, b, mpc_step, it, st);
+static int plan_iter_merge_routed(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, const LaunchCtx& cx, MergeRoute route) {
+    const int rc = check_plan(h, b, mpc_step, it, cx.st);
     if (rc) return rc;
-    return ICEM_DISPATCH(h, plan_iter_merge_t<float>(h, b, mpc_step, it, st, route), plan_iter_merge_t<double>(h, b, mpc_step, it, st, route));
+    return ICEM_DISPATCH(h, plan_iter_merge_t<float>(h, b, mpc_step, it, cx, route), plan_iter_merge_t<double>(h, b, mpc_step, it, cx, route));
 }
 
 int icem_plan_iter_merge(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, int32_t it, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool deferred = h && b && deferral_active(h, b) && h->cur_mean;
-    if (!deferred) return plan_iter_merge_routed(h, b, mpc_step, it, st, MergeRoute());  // launched now, in place
+    const LaunchCtx cx{st};
+    if (!deferred) return plan_iter_merge_routed(h, b, mpc_step, it, cx, MergeRoute());  // launched now, in place
     int rc = check_plan(h, b, mpc_step, it, st);
     if (rc) return rc;
     // sharded, deferral on: a non-last merge may ride in the next icem_plan_iter_local launch (mean / std / elites in
@@ -1371,12 +1375,12 @@ int icem_plan_iter_merge(icem_handle* h, const icem_plan_buffers* b, int32_t mpc
     rc = ensure_pp_stats(h);
     if (rc) return rc;
     const bool last = it == h->cfg.opt_iters - 1;
-    const bool fold = !last && h->local.lists > 0 && records_fit_prologue(h) && prologue_possible(h, shard_of(h, it + 1).n_loc);
+    const bool fold = !last && h->local.lists > 0 && records_fit_prologue(h) && prologue_possible(h, cx.hint, shard_of(h, it + 1).n_loc);
     icem_plan_buffers bb = *b;
     bb.mean = h->cur_mean;
     bb.std = h->cur_std;
     const MergeRoute route = merge_route(h, b, it, fold);
-    rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, st, route);
+    rc = plan_iter_merge_t<float>(h, &bb, mpc_step, it, cx, route);
     if (rc) return rc;
     if (fold && h->ride.merge_pending) {
         h->cur_mean = route.mean_out;
@@ -1410,8 +1414,8 @@ static int plan_step_sharded_body(icem_handle* h, const icem_plan_buffers* b, in
     if (xchg_status_peek(h) & 1u)
         return fail(ICEM_E_STATE, "in-library exchange: a wait for a peer's elite records timed out in an earlier MPC step "
                                   "(icem_exchange_status reads and clears the word); the plans since then are not valid");
-    if (b && check_plan(h, b, mpc_step, 0, (hipStream_t)stream) == ICEM_OK && !h->ride.merge_pending && !h->ride.pack_pending && ahead_eligible(h, b, true))
-        return plan_step_sharded_ahead(h, b, mpc_step, (hipStream_t)stream);
+    if (b && check_plan(h, b, mpc_step, 0, (hipStream_t)stream) == ICEM_OK && !h->ride.merge_pending && !h->ride.pack_pending && ahead_eligible(h, b, BatchHint(), true))
+        return plan_step_sharded_ahead(h, b, mpc_step, LaunchCtx{(hipStream_t)stream});
     const bool was = h->deferral;
     h->deferral = true;  // non-last merges ride in the next local launch
     int rc = ICEM_OK;
@@ -1430,13 +1434,13 @@ int icem_plan_step_sharded(icem_handle* h, const icem_plan_buffers* b, int32_t m
     return disarm_on_error(h, plan_step_sharded_body(h, b, mpc_step, stream));
 }
 
-static int plan_step_body(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, void* stream) {
+static int plan_step_body(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, const LaunchCtx& cx) {
     if (h->cfg.world != 1) return fail(ICEM_E_INVALID, "icem_plan_step is the world == 1 path; use iter_local/iter_merge");
-    int rc = check_plan(h, b, mpc_step, 0, (hipStream_t)stream);
+    int rc = check_plan(h, b, mpc_step, 0, cx.st);
     if (rc) return rc;
     const icem_config& c = h->cfg;
     const int iters = c.opt_iters;
-    if (ahead_eligible(h, b)) return plan_step_ahead(h, b, mpc_step, (hipStream_t)stream);
+    if (ahead_eligible(h, b, cx.hint)) return plan_step_ahead(h, b, mpc_step, cx);
     // f32, device noise: iteration it's merge may ride in the prologue of iteration it+1's launch.  That launch
     // reads pool / lists / distribution of iteration it while writing its own, so consecutive iterations alternate
     // between the caller's buffers and the handle's partners (the last iteration always uses the caller's).
@@ -1457,14 +1461,15 @@ static int plan_step_body(icem_handle* h, const icem_plan_buffers* b, int32_t mp
             bb.mean = cur_mean;
             bb.std = cur_std;
         }
-        rc = icem_plan_iter_local(h, &bb, mpc_step, it, stream);
+        // (world == 1: no deferral across calls, and check_plan above holds for every iteration of the step)
+        rc = ICEM_DISPATCH(h, plan_iter_local_t<float>(h, &bb, mpc_step, it, cx), plan_iter_local_t<double>(h, &bb, mpc_step, it, cx));
         if (rc) return rc;
         const bool last = it == iters - 1;
-        if (last) predraw_next_step(h, b, mpc_step, (hipStream_t)stream);  // small populations: the next step's first noise rides with the last merge
+        if (last) predraw_next_step(h, b, mpc_step, cx);  // small populations: the next step's first noise rides with the last merge
         bool fold = false;
-        if (pingpong && !last && h->local.lists > 0) fold = prologue_possible(h, h->pop[it + 1]);
+        if (pingpong && !last && h->local.lists > 0) fold = prologue_possible(h, cx.hint, h->pop[it + 1]);
         const MergeRoute route = merge_route(h, b, it, fold);
-        rc = plan_iter_merge_routed(h, &bb, mpc_step, it, (hipStream_t)stream, route);
+        rc = ICEM_DISPATCH(h, plan_iter_merge_t<float>(h, &bb, mpc_step, it, cx, route), plan_iter_merge_t<double>(h, &bb, mpc_step, it, cx, route));
         if (rc) return rc;
         if (last && h->ahead.tail_pending) {  // the merge that ran was not one that takes noise along: no noise was drawn
             h->ahead.tail_pending = false;
@@ -1480,7 +1485,7 @@ static int plan_step_body(icem_handle* h, const icem_plan_buffers* b, int32_t mp
 
 int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, void* stream) {
     if (check_handle(h)) return ICEM_E_INVALID;
-    return disarm_on_error(h, plan_step_body(h, b, mpc_step, stream));
+    return disarm_on_error(h, plan_step_body(h, b, mpc_step, LaunchCtx{(hipStream_t)stream}));
 }
 
 
@@ -1490,8 +1495,9 @@ int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step,
 // The reference runs several controllers side by side (parallel episodes: icem/misc/rollout_utils.py:46-58, 129-152), each
 // its own get_action (icem.py:106-189).  At the metric's population (N = 4096) one problem leaves the chip mostly empty and a
 // step is a chain of six launch latencies; B problems of one configuration share those six launches: the host side of
-// every handle runs exactly as for icem_plan_step -- same buffers, same ping-pong, same noise offsets -- with the launchers
-// recording their argument blocks (g_batch.rec), then every stage is ONE launch with blockIdx.y = the problem and the
+// every handle runs exactly as for icem_plan_step -- same buffers, same ping-pong, same noise offsets -- under a launch
+// context whose recorder takes every launch (key + argument block; a launcher without a batched form launches nothing and
+// has the batch refused), then every stage is ONE launch with blockIdx.y = the problem and the
 // blocks in a device array (one upload per step, skipped when nothing but the step number changed: the offsets are stored
 // relative to the step's base, which travels in the kernel arguments).  Slab sizes are chosen for all rows together.
 struct BatchCtx {
@@ -1510,20 +1516,9 @@ static void batch_ctx_free(void* p) {
     delete c;
 }
 
-// bytes of one problem's argument block in the device array of a recorded launch
-static size_t batch_block_bytes(BatchKind kind) {
-    return kind == BATCH_SAMPLE_ROLLOUT ? sizeof(FastIterArgs) : kind == BATCH_ITER_AHEAD ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
-}
-
-static void sub_base(uint32_t& lo, uint32_t& hi, unsigned long long base) {
-    const unsigned long long v = (((unsigned long long)hi << 32) | lo) - base;
-    lo = (uint32_t)v;
-    hi = (uint32_t)(v >> 32);
-}
-
 // does this handle's step consist of single-launch iterations with merge prologues and one last merge? (the path
 // decisions of plan_step_body / plan_iter_local_t / plan_iter_merge_t, evaluated without launching anything)
-static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step) {
+static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, const BatchHint& bh) {
     const icem_config& c = h->cfg;
     const int K = c.num_elites;
     if (c.world != 1) return "world must be 1";
@@ -1534,23 +1529,18 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     if (!fast_rollout_ok(h, K) || !fast_sample_ok(h) || K + 1 > 12 || c.rng_rounds != 10) return "shape outside the single-launch kernels";
     if (h->ride.merge_pending || h->ride.pack_pending) return "a deferred merge is pending: finish the MPC step first";
     if (c.opt_iters < 1) return "opt_iters";
-    // (g_batch.mult is set: the shapes below are the batch's.)  Where every iteration's rows of ALL problems together fill the
+    // (bh: the shapes below are the batch's.)  Where every iteration's rows of ALL problems together fill the
     // noise-ahead launch (>= 4 waves per rollout workgroup), the batch takes that path -- rollout, next noise and shifted elites
     // as roles of one launch (k_rollout_ahead.hip), 107 against 130 us per step at eight problems of 4096 rows -- provided a
     // problem ALONE does not take it (a population above 8192 rows fills the chip by itself: not batched)
-    {
-        const bool ah = g_batch.ahead;
-        g_batch.ahead = false;
-        const bool alone = ahead_eligible(h, b);
-        g_batch.ahead = ah;
-        if (alone) return "populations that take the noise-ahead launches alone (> 8192 rows per iteration) are not batched: they fill the chip by themselves";
-    }
-    if (ahead_eligible(h, b)) return nullptr;   // (false without g_batch.ahead: option batch_ahead = 0)
+    if (ahead_eligible(h, b, BatchHint()))
+        return "populations that take the noise-ahead launches alone (> 8192 rows per iteration) are not batched: they fill the chip by themselves";
+    if (ahead_eligible(h, b, bh)) return nullptr;   // (false without bh.ahead: option batch_ahead = 0)
     for (int it = 0; it < c.opt_iters; ++it) {
         const int n_extra = shift_rows(h, mpc_step, it, false);
         if (n_extra * c.act_dim > 256) return "too many shifted elites for the sampling launch";
-        if (one_launch_lists(h, h->pop[it] + n_extra, n_extra) <= 0) return "an iteration's population has no single-launch kernel";
-        if (it > 0 && !prologue_possible(h, h->pop[it])) return "an iteration cannot carry the previous merge in its prologue";
+        if (one_launch_lists(h, bh, h->pop[it] + n_extra, n_extra) <= 0) return "an iteration's population has no single-launch kernel";
+        if (it > 0 && !prologue_possible(h, bh, h->pop[it])) return "an iteration cannot carry the previous merge in its prologue";
     }
     return nullptr;
 }
@@ -1580,18 +1570,13 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         if (h->Of != h0->Of || h->model_kind != h0->model_kind || h->tile_arith != h0->tile_arith)
             return fail(ICEM_E_INVALID, "icem_plan_step_batch: the handles must share the model's width and kind and the tile arithmetic");
     }
-    struct MultGuard {
-        MultGuard(int m, long long rows0) {
-            g_batch.mult = m;
-            g_batch.unsupported = false;
-            // the noise-ahead launches from where they measure faster than the single-launch kernels: 12 problems of 4096 rows
-            // (160 against 161 us per step; 16: 194 against 212; 8: 129 against 128; 6: 115 against 100 -- EXPERIMENTS R6.3)
-            g_batch.ahead = opt_i(OPT_BATCH_AHEAD) != 0 && (double)m * (double)rows0 >= opt(OPT_BATCH_AHEAD_MIN_ROWS);
-        }
-        ~MultGuard() { g_batch.mult = 1; g_batch.rec = nullptr; g_batch.ahead = false; }
-    } guard(n, h0->pop.empty() ? 0 : h0->pop[0]);
+    // the batch's shape hint.  The noise-ahead launches from where they measure faster than the single-launch kernels: 12 problems
+    // of 4096 rows (160 against 161 us per step; 16: 194 against 212; 8: 129 against 128; 6: 115 against 100 -- EXPERIMENTS R6.3)
+    BatchHint hint;
+    hint.mult = n;
+    hint.ahead = opt_i(OPT_BATCH_AHEAD) != 0 && (double)n * (double)(h0->pop.empty() ? 0 : h0->pop[0]) >= opt(OPT_BATCH_AHEAD_MIN_ROWS);
     for (int i = 0; i < n; ++i)
-        if (const char* why = batch_ineligible(handles[i], &buffers[i], mpc_step))
+        if (const char* why = batch_ineligible(handles[i], &buffers[i], mpc_step, hint))
             return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_batch: ") + why);
     // ---- the host side of every problem's step, recorded ----
     // From here on the handles' host state runs ahead of the device: whatever return leaves before the last launch is
@@ -1604,87 +1589,37 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
             for (int i = 0; armed && i < n; ++i) disarm(handles[i]);
         }
     } disarm_all{handles, n};
-    std::vector<std::vector<BatchRecord>> recs(n);
+    BatchBases bases{};   // each problem's noise stream base of this step: the recorded blocks' offsets are relative to it
+    std::vector<LaunchRecorder> recs(n);
     int rc = ICEM_OK;
+    bool unsupported = false;
     for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        g_batch.rec = &recs[i];
-        rc = plan_step_body(handles[i], &buffers[i], mpc_step, stream);
+        recs[i].base = bases.v[i] = call_base(handles[i], mpc_step);
+        recs[i].launches.reserve(handles[i]->cfg.opt_iters + 1);
+        rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &recs[i]});
+        unsupported = unsupported || recs[i].unsupported;
     }
-    g_batch.rec = nullptr;
-    if (rc == ICEM_OK && g_batch.unsupported) rc = fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a launch without a batched form was reached");
-    const size_t L = recs[0].size();
+    if (rc == ICEM_OK && unsupported) rc = fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a launch without a batched form was reached");
+    const std::vector<LaunchDesc>& first = recs[0].launches;
+    const size_t L = first.size();
     for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        if (recs[i].size() != L || L == 0) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' steps took different launches");
-        for (size_t l = 0; l < L && rc == ICEM_OK; ++l) {
-            const BatchRecord &x = recs[i][l], &y = recs[0][l];
-            bool same = x.kind == y.kind;
-            if (same && x.kind == BATCH_SAMPLE_ROLLOUT)
-                same = x.h == y.h && x.d == y.d && x.O == y.O && x.model_kind == y.model_kind && x.rw == y.rw && x.grid == y.grid &&
-                       x.prologue == y.prologue && x.it.r.arith == y.it.r.arith;
-            if (same && x.kind == BATCH_ITER_AHEAD)
-                same = x.h == y.h && x.d == y.d && x.O == y.O && x.model_kind == y.model_kind && x.rw == y.rw && x.grid == y.grid &&
-                       x.ia.has_merge == y.ia.has_merge && x.ia.r.arith == y.ia.r.arith && x.ia.z.n == y.ia.z.n &&
-                       x.ia.s.n_shift == y.ia.s.n_shift && x.ia.n_noise == y.ia.n_noise;
-            if (same && x.kind != BATCH_SAMPLE_ROLLOUT && x.kind != BATCH_ITER_AHEAD)
-                same = x.m.h == y.m.h && x.m.d == y.m.d && (x.kind == BATCH_MERGE_SINGLE || (x.z1.n == y.z1.n && x.z2.n == y.z2.n && x.z1.d == y.z1.d && x.z1.h == y.z1.h));
-            if (!same) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' launches differ in shape");
-        }
+        if (recs[i].launches.size() != L || L == 0) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' steps took different launches");
+        for (size_t l = 0; l < L && rc == ICEM_OK; ++l)
+            if (!(recs[i].launches[l].key == first[l].key)) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' launches differ in shape");
     }
     if (rc != ICEM_OK) return rc;   // nothing was launched: the handles' half-armed state goes
-    // ---- argument blocks: offsets relative to each problem's base of this step, one array per launch ----
-    BatchBases bases{};
-    for (int i = 0; i < n; ++i)
-        bases.v[i] = call_base(handles[i], mpc_step);
+    // ---- argument blocks: one array per launch ----
     std::vector<size_t> at(L);
     size_t bytes = 0;
     for (size_t l = 0; l < L; ++l) {
         at[l] = bytes;
-        const size_t one = batch_block_bytes(recs[0][l].kind);
-        bytes += ((one * (size_t)n + 255) / 256) * 256;
+        bytes += ((launch_block_bytes(first[l].key.family) * (size_t)n + 255) / 256) * 256;
     }
     std::vector<unsigned char> blob(bytes, 0);
-    for (size_t l = 0; l < L; ++l)
-        for (int i = 0; i < n; ++i) {
-            BatchRecord& r = recs[i][l];
-            if (r.kind == BATCH_SAMPLE_ROLLOUT) {
-                FastIterArgs a = r.it;
-                if (a.s.n_shift == 0) a.s.off2_lo = (uint32_t)bases.v[i], a.s.off2_hi = (uint32_t)(bases.v[i] >> 32);   // (unused: kept at relative 0)
-                sub_base(a.s.off_lo, a.s.off_hi, bases.v[i]);
-                sub_base(a.s.off2_lo, a.s.off2_hi, bases.v[i]);
-                std::memcpy(blob.data() + at[l] + (size_t)i * sizeof(FastIterArgs), &a, sizeof(a));
-            } else if (r.kind == BATCH_ITER_AHEAD) {
-                IterAheadArgs a = r.ia;
-                a.r.dbg = nullptr;
-                if (a.z.n > 0) sub_base(a.z.off_lo, a.z.off_hi, bases.v[i]);
-                else a.z.off_lo = a.z.off_hi = 0;
-                if (a.s.n_shift > 0) {
-                    sub_base(a.s.off_lo, a.s.off_hi, bases.v[i]);
-                    sub_base(a.s.off2_lo, a.s.off2_hi, bases.v[i]);
-                } else {
-                    a.s.off_lo = a.s.off_hi = a.s.off2_lo = a.s.off2_hi = 0;
-                }
-                unsigned char* dst = blob.data() + at[l] + (size_t)i * sizeof(IterAheadArgs);
-                std::memcpy(dst, &a, sizeof(a));
-                // (the struct's tail padding is not carried by its copies: defined here, or every step's block "changes")
-                constexpr size_t tail = offsetof(IterAheadArgs, dbg_slot) + sizeof(int);
-                std::memset(dst + tail, 0, sizeof(IterAheadArgs) - tail);
-            } else {
-                MergeNoiseBatchArgs g{};
-                g.a = r.m;
-                if (r.kind == BATCH_MERGE_NOISE) {
-                    g.z1 = r.z1;
-                    g.z2 = r.z2;
-                    if (g.z1.n > 0) sub_base(g.z1.off_lo, g.z1.off_hi, bases.v[i]);
-                    else g.z1.off_lo = g.z1.off_hi = 0;
-                    if (g.z2.n > 0) sub_base(g.z2.off_lo, g.z2.off_hi, bases.v[i]);
-                    else g.z2.off_lo = g.z2.off_hi = 0;
-                    g.z1.off2_lo = g.z1.off2_hi = g.z2.off2_lo = g.z2.off2_hi = 0;
-                } else {
-                    g.z1.n = g.z2.n = 0;
-                }
-                std::memcpy(blob.data() + at[l] + (size_t)i * sizeof(MergeNoiseBatchArgs), &g, sizeof(g));
-            }
-        }
+    for (size_t l = 0; l < L; ++l) {
+        const size_t one = launch_block_bytes(first[l].key.family);
+        for (int i = 0; i < n; ++i) std::memcpy(blob.data() + at[l] + (size_t)i * one, recs[i].launches[l].block, one);
+    }
     icem_handle* owner = handles[0];
     BatchCtx* ctx = (BatchCtx*)owner->batch_ctx;
     if (!ctx) {
@@ -1708,10 +1643,10 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         if (opt_i(OPT_AHEAD_STAMPS) && ctx->shadow[slot].size() == bytes) {   // development: which bytes moved
             int shown = 0;
             for (size_t l = 0; l < L && shown < 12; ++l) {
-                const size_t one = batch_block_bytes(recs[0][l].kind);
+                const size_t one = launch_block_bytes(first[l].key.family);
                 for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
                     if (blob[at[l] + o] != ctx->shadow[slot][at[l] + o]) {
-                        std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, (int)recs[0][l].kind, o / one, o % one);
+                        std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
                         ++shown;
                         o = (o / 8 + 1) * 8 - 1;
                     }
@@ -1724,11 +1659,11 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
     }
     // ---- the launches ----
     for (size_t l = 0; l < L; ++l) {
-        const BatchRecord& s = recs[0][l];
+        const LaunchKey& k = first[l].key;
         const unsigned char* base = (const unsigned char*)ctx->dev[slot] + at[l];
-        if (s.kind == BATCH_SAMPLE_ROLLOUT) launch_sample_rollout_batch(s, (const FastIterArgs*)base, bases, n, st);
-        else if (s.kind == BATCH_ITER_AHEAD) launch_iter_ahead_batch(s, (const IterAheadArgs*)base, bases, n, st);
-        else launch_merge_batch(s, (const MergeNoiseBatchArgs*)base, bases, n, st);
+        if (k.family == LAUNCH_SAMPLE_ROLLOUT) launch_sample_rollout_batch(k, (const FastIterArgs*)base, bases, n, st);
+        else if (k.family == LAUNCH_ITER_AHEAD) launch_iter_ahead_batch(k, (const IterAheadArgs*)base, bases, n, st);
+        else launch_merge_batch(k, (const MergeNoiseBatchArgs*)base, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
     }
     disarm_all.armed = false;

@@ -84,6 +84,26 @@ def test_every_problem_of_a_batch_equals_its_solo_run_bit_for_bit(B, N, iters, k
         solo[i].mpc_step = batch[i].mpc_step
 
 
+def test_a_batch_whose_last_merge_draws_no_noise_equals_its_solo_runs():
+    """Option ``predraw = 0``: nothing rides with the step's last merge, which is then ``launch_merge_single`` -- for a batch
+    ``merge_noise_batch_kernel`` without noise workgroups, the one recorded launch no other case reaches.  A partial slab
+    (N = 300), and from the second step on the shifted and kept elites are in play.  (Options: reset by the suite's fixture.)"""
+    from icem_amd import IcemPlanner, _lib as L
+    L.set_option("predraw", 0)
+    B, N, iters, (h, d, o) = 3, 300, 2, (12, 6, 17)
+    solo = [_make(i, N, iters, h, d, o) for i in range(B)]
+    batch = [_make(i, N, iters, h, d, o) for i in range(B)]
+    for s in range(3):
+        obs = [0.1 * (1 + i) * np.random.RandomState(50 * s + i).randn(o) for i in range(B)]
+        for i in range(B):
+            solo[i].plan_step(obs[i])
+        IcemPlanner.plan_step_batch(batch, obs)
+        torch.cuda.synchronize()
+        for i in range(B):
+            for k, (x, y) in enumerate(zip(_state(batch[i]), _state(solo[i]))):
+                assert np.array_equal(x, y), (s, i, k)
+
+
 def test_a_batch_member_can_continue_alone_and_rejoin():
     from icem_amd import IcemPlanner
     B, N, iters, o = 3, 2048, 3, 17
