@@ -588,7 +588,7 @@ class MpcICemHip(MpcController):
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152) -- through ``icem_plan_step_batch``:
         every stage of the planning step is one launch for all of them.  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same hooks).  Device path with
-        device noise; or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
+        device noise (the HalfCheetah-sized tile shapes, and the Door / Relocate / FetchPickAndPlace envs at h = 30); or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
         one configuration: their populations are scored by ONE ``rollout_cost_batch`` launch per CEM iteration (sampling and
         the distribution update stay one launch per controller).  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)

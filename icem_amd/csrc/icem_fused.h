@@ -59,7 +59,7 @@ struct FastSampleArgs {
     const float* raw_src = nullptr;
 };
 bool fast_sample_supported(int h, int d);
-void launch_sample_folded(const FastSampleArgs& a, int rounds, hipStream_t st);
+void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int rounds);
 
 // K2+K3 fast: rollout on the matrix pipe (v_mfma_f32_16x16x4, exact f32), cost on the VALU, and a
 // sorted top-K per workgroup; one wavefront per 16 trajectories.
@@ -101,13 +101,29 @@ int rollout_lists(int h, int d, int O, int n_rows);
 // weights / act_mag, m_scale, b_scale.
 template <typename T> struct CostArgs;
 bool hn_rollout_supported(int h, int d, int o, int K);
-int hn_rollout_lists(int n_rows);
-int hn_tail_rows(int n_rows, int n_tail);   // trailing shifted-elite rows scored through the cost array (0: none)
+// (bh: a batch of bh.mult problems of this size in one launch -- waves per workgroup as for all their tiles together, the
+//  workgroups of ONE problem, always the one-wave-per-tile kernel, no tail workgroups)
+int hn_rollout_lists(const BatchHint& bh, int n_rows);
+int hn_tail_rows(const BatchHint& bh, int n_rows, int n_tail);   // trailing shifted-elite rows scored through the cost array (0: none)
+// the icem_cost_spec part of a step cost as the GEMM and TileHN kernels take it (wide_dev.h)
+struct WideCost {
+    int lin_idx, flip_idx;
+    float ctrl_w, lin_w, flip_pen, flip_th;
+};
+// the TileHN kernels' argument block: by value, or -- a batch -- one per problem in a device array
+struct HnArgs {
+    FastRolloutArgs r;           // n_rows, n_cand, K, o, cost_mode, obs0, actions, costs, part_*, ctrl_w, act_mag, m_scale, b_scale
+    const float* A;              // [o, lda] row-major f32
+    const float* B;              // [d, ldb]
+    int lda, ldb;
+    WideCost wc;
+    const CostArgs<float>* cs;   // device copy of the cost terms, nullptr: none
+};
 // cs: terms sorted into the program prog = (N32, N4, NP) and padded with null terms (kind -1): hn_cost_program says whether a
 // list of n32 long slices (5 .. 32 entries), n4 short ones and np point terms has a compiled program, and which
 bool hn_cost_program(int n32, int n4, int np, int* prog);
-void launch_rollout_hn(const FastRolloutArgs& r, int h, int d, int o, int kind, const float* A, int lda, const float* B, int ldb,
-                       int lin_idx, int flip_idx, const CostArgs<float>* cs, const int* prog, hipStream_t st);
+void launch_rollout_hn(const LaunchCtx& cx, const FastRolloutArgs& r, int h, int d, int o, int kind, const float* A, int lda, const float* B, int ldb,
+                       int lin_idx, int flip_idx, const CostArgs<float>* cs, const int* prog);
 
 // K2+K3 for wide observations (32 < o <= 384; k_rollout_wide.hip): the model step as an f32 matrix-pipe GEMM per
 // 16-trajectory tile, contraction vectors in LDS; same candidate-list outputs as the kernels above.
@@ -293,7 +309,7 @@ struct FastSampleMergeArgs {
     PackPrev p;        // sharded runs: the previous iteration's pack rides as workgroup 0
 };
 bool sample_folded_merge_ok(int h, int d, int rounds, int K);
-void launch_sample_folded_merge(const FastSampleMergeArgs& a, hipStream_t st);
+void launch_sample_folded_merge(const LaunchCtx& cx, const FastSampleMergeArgs& a);
 
 // K1+K2+K3 in one launch (small populations): r.actions == s.out, r.n_rows == s.n + s.n_shift.
 struct FastIterArgs {
@@ -320,13 +336,18 @@ struct BatchHint {
     bool ahead = false;   // ... and the batch may take the noise-ahead launches where all its rows together fill them
 };
 // What a dispatch table maps to a compiled instantiation and a grid (all ints, no padding: compared as bytes)
-enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3 };
+// (LAUNCH_SAMPLE / _SAMPLE_MERGE / _ROLLOUT_HN: the sampler, the sampler with the previous merge in its prologue and the TileHN
+//  rollout -- the two-kernel iterations of the Door / Relocate / FetchPickAndPlace shapes)
+enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3, LAUNCH_SAMPLE = 4, LAUNCH_SAMPLE_MERGE = 5,
+                          LAUNCH_ROLLOUT_HN = 6 };
 struct LaunchKey {
     int family = 0;
-    int h = 0, d = 0, O = 0, kind = 0, arith = 0;
-    int waves = 0;     // rollout waves per workgroup (sample_rollout: RW; iter_ahead: WAVES)
-    int form = 0;      // sample_rollout: 0 = plain, 1 = lists merge in the prologue, 2 = records merge; iter_ahead: PM; merge_noise: 1 = with noise
-    int wgs[3] = {0, 0, 0};   // workgroups per role; the grid is their sum
+    int h = 0, d = 0, O = 0, kind = 0, arith = 0;   // (rollout_hn: O = the observation width o)
+    int waves = 0;     // rollout waves per workgroup (sample_rollout: RW; iter_ahead, rollout_hn: WAVES)
+    // sample_rollout: 0 = plain, 1 = lists merge in the prologue, 2 = records merge; iter_ahead: PM; merge_noise: 1 = with noise;
+    // sample: the generator's rounds; sample_merge: 1 = lists merge, 2 = records merge; rollout_hn: the term program, N32 << 16 | N4 << 8 | NP
+    int form = 0;
+    int wgs[3] = {0, 0, 0};   // workgroups per role (of ONE problem); the grid is their sum
     bool operator==(const LaunchKey& o) const { return std::memcmp(this, &o, sizeof(LaunchKey)) == 0; }
 };
 struct MergeNoiseBatchArgs {
@@ -338,9 +359,17 @@ struct LaunchDesc {
     LaunchKey key;
     alignas(8) unsigned char block[sizeof(IterAheadArgs)];
 };
-static_assert(sizeof(FastIterArgs) <= sizeof(IterAheadArgs) && sizeof(MergeNoiseBatchArgs) <= sizeof(IterAheadArgs), "LaunchDesc::block");
+static_assert(sizeof(FastIterArgs) <= sizeof(IterAheadArgs) && sizeof(MergeNoiseBatchArgs) <= sizeof(IterAheadArgs) &&
+              sizeof(FastSampleMergeArgs) <= sizeof(IterAheadArgs) && sizeof(HnArgs) <= sizeof(IterAheadArgs), "LaunchDesc::block");
 inline size_t launch_block_bytes(int family) {
-    return family == LAUNCH_SAMPLE_ROLLOUT ? sizeof(FastIterArgs) : family == LAUNCH_ITER_AHEAD ? sizeof(IterAheadArgs) : sizeof(MergeNoiseBatchArgs);
+    switch (family) {
+        case LAUNCH_SAMPLE_ROLLOUT: return sizeof(FastIterArgs);
+        case LAUNCH_ITER_AHEAD: return sizeof(IterAheadArgs);
+        case LAUNCH_SAMPLE: return sizeof(FastSampleArgs);
+        case LAUNCH_SAMPLE_MERGE: return sizeof(FastSampleMergeArgs);
+        case LAUNCH_ROLLOUT_HN: return sizeof(HnArgs);
+        default: return sizeof(MergeNoiseBatchArgs);
+    }
 }
 struct LaunchRecorder {
     unsigned long long base = 0;        // noise stream base of the recorded problem's step (BatchBases::v)
@@ -406,7 +435,31 @@ inline void batch_form(const MergeSingleArgs& a, const FastSampleArgs* z1, const
         z->off2_lo = z->off2_hi = 0;
     }
 }
+// (dst is zeroed and the blocks are copied member by member: every byte of a recorded block is defined, whatever the padding of
+//  the launcher's own copy held)
+inline void batch_form(const FastSampleArgs& a, unsigned long long base, void* dst) {
+    std::memcpy(dst, &a, sizeof(a));
+    FastSampleArgs& s = *(FastSampleArgs*)dst;
+    if (s.n_shift == 0) s.off2_lo = s.off2_hi = 0;   // (unused)
+    else sub_base(s.off2_lo, s.off2_hi, base);
+    sub_base(s.off_lo, s.off_hi, base);
+}
+inline void batch_form(const FastSampleMergeArgs& a, unsigned long long base, void* dst) {   // (world 1: no riding pack, PackPrev stays zero)
+    FastSampleMergeArgs& g = *(FastSampleMergeArgs*)dst;
+    batch_form(a.s, base, &g.s);
+    std::memcpy(&g.m, &a.m, sizeof(a.m));
+    g.m.dbg = nullptr;
+}
+inline void batch_form(const HnArgs& a, void* dst) {
+    HnArgs& g = *(HnArgs*)dst;
+    std::memcpy(&g.r, &a.r, sizeof(a.r));
+    g.r.dbg = nullptr;
+    g.A = a.A, g.B = a.B, g.lda = a.lda, g.ldb = a.ldb, g.wc = a.wc, g.cs = a.cs;
+}
 // the batched launches: args[n] in DEVICE memory (the problems' keys are equal: plan.hip checked)
+void launch_sample_batch(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_sample_merge_batch(const LaunchKey& key, const FastSampleMergeArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_rollout_hn_batch(const LaunchKey& key, const HnArgs* args_dev, int n, hipStream_t st);
 void launch_sample_rollout_batch(const LaunchKey& key, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_merge_batch(const LaunchKey& key, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_iter_ahead_batch(const LaunchKey& key, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);

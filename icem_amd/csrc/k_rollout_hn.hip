@@ -332,17 +332,9 @@ struct TileHN {
     __device__ __forceinline__ float cost(const State& st) const { return cost_mode == 1 ? st.acc_b : st.acc_s; }
 };
 
-struct HnArgs {
-    FastRolloutArgs r;           // n_rows, n_cand, K, o, cost_mode, obs0, actions, costs, part_*, ctrl_w, act_mag, m_scale, b_scale
-    const float* A;              // [o, lda] row-major f32
-    const float* B;              // [d, ldb]
-    int lda, ldb;
-    WideCost wc;
-    const CostArgs<float>* cs;   // device copy of the cost terms, nullptr: none
-};
-
+// (the body of rollout_hn_kernel and of rollout_hn_batch_kernel: one device function, the same device code)
 template <int H, int D, int O, int KIND, int WAVES, int N32, int N4, int NP>
-__global__ __launch_bounds__(64 * WAVES) void rollout_hn_kernel(HnArgs a) {
+__device__ __forceinline__ void rollout_hn_body(const HnArgs& a) {
     using Tile = TileHN<H, D, O, KIND, N32, N4, NP>;
     using Stream = StreamT<Tile, H, D>;
     __shared__ __attribute__((aligned(16))) float stage[WAVES][Stream::STG];
@@ -371,6 +363,26 @@ __global__ __launch_bounds__(64 * WAVES) void rollout_hn_kernel(HnArgs a) {
         first = false;
     }
     if (a.r.K > 0) wg_merge_emit<WAVES>(wg_keys, run_key, a.r.K, lane, wave, a.r);
+}
+
+template <int H, int D, int O, int KIND, int WAVES, int N32, int N4, int NP>
+__global__ __launch_bounds__(64 * WAVES) void rollout_hn_kernel(HnArgs a) {
+    rollout_hn_body<H, D, O, KIND, WAVES, N32, N4, NP>(a);
+}
+
+// B problems in one launch (icem_plan_step_batch): blockIdx.y = the problem -- its own model, term list, scales, observation
+// and pool -- with its argument block read from an array in device memory (scalar loads: the index is uniform); H, D, O, KIND
+// and the term program are the launch's.  Workgroup blockIdx.x of gridDim.x walks the problem's tiles as in a launch of its own.
+__device__ __forceinline__ HnArgs from_device(const HnArgs& m) {
+    HnArgs a = m;
+    a.r = from_device(m.r);
+    a.A = gptr(m.A), a.B = gptr(m.B), a.cs = gptr(m.cs);
+    return a;
+}
+template <int H, int D, int O, int KIND, int WAVES, int N32, int N4, int NP>
+__global__ __launch_bounds__(64 * WAVES) void rollout_hn_batch_kernel(const HnArgs* __restrict__ args) {
+    const HnArgs a = from_device(args[blockIdx.y]);
+    rollout_hn_body<H, D, O, KIND, WAVES, N32, N4, NP>(a);
 }
 
 // The same rollout with TWO waves per tile for populations that leave the chip mostly empty (at most two tiles per CU): a lone
@@ -777,6 +789,17 @@ void hn_shape(int n_rows, int* grid, int* waves) {
     if (*waves > HN_MAX_WAVES) *waves = HN_MAX_WAVES;
 }
 
+// a batch of bh.mult problems of n_rows rows each in one launch (icem_plan_step_batch; blockIdx.y = the problem): the waves per
+// workgroup the chip would get for ALL their tiles in one population, the workgroups (= candidate lists) of ONE problem.  Always
+// rollout_hn_kernel's arrangement: at the benchmark's populations two problems together are past the pair form's range, four
+// put a lone wave on every SIMD; the few-tile batches it also serves: EXPERIMENTS R7.4, tools/hn_batch_bench.py.
+void hn_batch_shape(const BatchHint& bh, int n_rows, int* grid, int* waves) {
+    const int tiles = std::max(1, (n_rows + 15) / 16);
+    int g_all;
+    hn_shape(tiles * 16 * bh.mult, &g_all, waves);
+    *grid = std::min(FAST_MAX_LISTS, (tiles + *waves - 1) / *waves);
+}
+
 }  // namespace
 
 bool hn_rollout_supported(int h, int d, int o, int K) {
@@ -807,15 +830,20 @@ static bool hn_split_shape(int n_rows, int* grid) {
 
 // trailing shifted-elite rows of a launch whose sampled rows fill whole tiles: with the split form they get workgroups of
 // their own BEHIND the list-writing ones (no list: scored through the cost array) instead of a second round on workgroup 0
-int hn_tail_rows(int n_rows, int n_tail) {
+int hn_tail_rows(const BatchHint& bh, int n_rows, int n_tail) {
     int g;
+    if (bh.mult > 1) return 0;   // (a batch never takes the split form)
     if (n_tail <= 0 || n_tail > 64 || n_rows - n_tail <= 0 || (n_rows - n_tail) % 16 != 0) return 0;
     if (!hn_split_shape(n_rows - n_tail, &g) || (n_rows - n_tail) / 16 > FAST_MAX_LISTS) return 0;
     return n_tail;
 }
 
-int hn_rollout_lists(int n_rows) {
+int hn_rollout_lists(const BatchHint& bh, int n_rows) {
     int g, w;
+    if (bh.mult > 1) {
+        hn_batch_shape(bh, n_rows, &g, &w);
+        return g;
+    }
     if (hn_split_shape(n_rows, &g)) return g;
     if (hn_pair_shape(n_rows, &g, &w)) return g;
     hn_shape(n_rows, &g, &w);
@@ -835,11 +863,58 @@ bool hn_cost_program(int n32, int n4, int np, int* prog) {
     return false;
 }
 
-void launch_rollout_hn(const FastRolloutArgs& r, int h, int d, int o, int kind, const float* A, int lda, const float* B, int ldb,
-                       int lin_idx, int flip_idx, const CostArgs<float>* cs, const int* prog, hipStream_t st) {
+// The one table of the one-wave-per-tile kernel: key -> compiled instantiation, handed to `f` as a tag that knows its two launches
+namespace {
+template <int H, int D, int O, int KIND, int WAVES, int N32, int N4, int NP>
+struct HnInst {
+    static void solo(int grid, hipStream_t st, const HnArgs& a) {
+        hipLaunchKernelGGL((rollout_hn_kernel<H, D, O, KIND, WAVES, N32, N4, NP>), dim3(grid), dim3(64 * WAVES), 0, st, a);
+    }
+    static void batch(int grid, int n, hipStream_t st, const HnArgs* args_dev) {
+        hipLaunchKernelGGL((rollout_hn_batch_kernel<H, D, O, KIND, WAVES, N32, N4, NP>), dim3(grid, n), dim3(64 * WAVES), 0, st, args_dev);
+    }
+};
+constexpr int hn_form(int n32, int n4, int np) { return n32 << 16 | n4 << 8 | np; }
+template <class F>
+bool hn_dispatch(const LaunchKey& k, F&& f) {
+#define XP(HH, DD, OO, KK, WW, A32, A4, AP) \
+    if (k.form == hn_form(A32, A4, AP)) return f(HnInst<HH, DD, OO, KK, WW, A32, A4, AP>{}), true;
+#define XK(HH, DD, OO, KK, WW) XP(HH, DD, OO, KK, WW, 0, 0, 0) XP(HH, DD, OO, KK, WW, 0, 2, 0) XP(HH, DD, OO, KK, WW, 0, 4, 1) XP(HH, DD, OO, KK, WW, 1, 1, 4)
+#define XW(HH, DD, OO, WW)                  \
+    if (k.waves == WW) {                    \
+        if (k.kind == 1) {                  \
+            XK(HH, DD, OO, 1, WW)           \
+        } else {                            \
+            XK(HH, DD, OO, 0, WW)           \
+        }                                   \
+        return false;                       \
+    }
+#define XR(HH, DD, OO)                           \
+    if (k.h == HH && k.d == DD && k.O == OO) {   \
+        XW(HH, DD, OO, 1)                        \
+        XW(HH, DD, OO, 2)                        \
+        XW(HH, DD, OO, 4)                        \
+    }
+    ICEM_HN_SHAPES(XR)
+#undef XR
+#undef XW
+#undef XK
+#undef XP
+    return false;
+}
+}  // namespace
+
+void launch_rollout_hn(const LaunchCtx& cx, const FastRolloutArgs& r, int h, int d, int o, int kind, const float* A, int lda, const float* B, int ldb,
+                       int lin_idx, int flip_idx, const CostArgs<float>* cs, const int* prog) {
     HnArgs a{r, A, B, lda, ldb, WideCost{lin_idx, flip_idx, r.ctrl_w, r.lin_w, r.flip_pen, r.flip_th}, cs};
+    hipStream_t st = cx.st;
+    const bool batch = cx.hint.mult > 1;   // (a batch's launches are recorded, and always the one-wave-per-tile kernel's)
+    if (cx.rec && !batch) {
+        cx.rec->unsupported = true;
+        return;
+    }
     int grid, waves;
-    if (hn_split_shape(r.n_rows, &grid)) {
+    if (!batch && hn_split_shape(r.n_rows, &grid)) {
         if (r.list_wgs > 0) grid = (r.n_rows + 15) / 16;   // list workgroups + the tail's (hn_tail_rows)
 #define SP(HH, DD, OO, KK, A32, A4, AP)                                                                                             \
     if (prog[0] == A32 && prog[1] == A4 && prog[2] == AP) {                                                                         \
@@ -864,7 +939,7 @@ void launch_rollout_hn(const FastRolloutArgs& r, int h, int d, int o, int kind, 
 #undef SP
         return;
     }
-    if (hn_pair_shape(r.n_rows, &grid, &waves)) {
+    if (!batch && hn_pair_shape(r.n_rows, &grid, &waves)) {
         const int pairs = waves;
 #define PP(HH, DD, OO, KK, PPV, A32, A4, AP)                                                                                       \
     if (prog[0] == A32 && prog[1] == A4 && prog[2] == AP) {                                                                        \
@@ -893,33 +968,19 @@ void launch_rollout_hn(const FastRolloutArgs& r, int h, int d, int o, int kind, 
 #undef PP
         return;
     }
-    hn_shape(r.n_rows, &grid, &waves);
-#define XP(HH, DD, OO, KK, WW, A32, A4, AP)                                                                                   \
-    if (prog[0] == A32 && prog[1] == A4 && prog[2] == AP) {                                                                   \
-        hipLaunchKernelGGL((rollout_hn_kernel<HH, DD, OO, KK, WW, A32, A4, AP>), dim3(grid), dim3(64 * WW), 0, st, a);        \
-        return;                                                                                                               \
-    }
-#define XK(HH, DD, OO, KK, WW) XP(HH, DD, OO, KK, WW, 0, 0, 0) XP(HH, DD, OO, KK, WW, 0, 2, 0) XP(HH, DD, OO, KK, WW, 0, 4, 1) XP(HH, DD, OO, KK, WW, 1, 1, 4)
-#define XW(HH, DD, OO, WW)                  \
-    if (waves == WW) {                      \
-        if (kind == 1) {                    \
-            XK(HH, DD, OO, 1, WW)           \
-        } else {                            \
-            XK(HH, DD, OO, 0, WW)           \
-        }                                   \
-        return;                             \
-    }
-#define XR(HH, DD, OO)                   \
-    if (h == HH && d == DD && o == OO) { \
-        XW(HH, DD, OO, 1)                \
-        XW(HH, DD, OO, 2)                \
-        XW(HH, DD, OO, 4)                \
-    }
-    ICEM_HN_SHAPES(XR)
-#undef XR
-#undef XW
-#undef XK
-#undef XP
+    LaunchKey k;
+    k.family = LAUNCH_ROLLOUT_HN;
+    k.h = h, k.d = d, k.O = o, k.kind = kind, k.arith = 1;
+    k.form = hn_form(prog[0], prog[1], prog[2]);
+    if (batch) hn_batch_shape(cx.hint, r.n_rows, &k.wgs[0], &k.waves);
+    else hn_shape(r.n_rows, &k.wgs[0], &k.waves);
+    submit(cx, k, batch, [&](void* dst, unsigned long long) { batch_form(a, dst); },
+           [&] { hn_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0], st, a); }); });
+}
+
+// ... and the same launch for n problems (blockIdx.y)
+void launch_rollout_hn_batch(const LaunchKey& k, const HnArgs* args_dev, int n, hipStream_t st) {
+    hn_dispatch(k, [&](auto inst) { inst.batch(k.wgs[0], n, st, args_dev); });
 }
 
 }  // namespace icem

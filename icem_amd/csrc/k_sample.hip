@@ -12,8 +12,9 @@ namespace icem {
 
 namespace {
 
+// (the body of sample_folded_kernel and of sample_folded_batch_kernel: one device function, the same device code)
 template <int H, int ROUNDS>
-__global__ __launch_bounds__(SWG) void sample_folded_kernel(FastSampleArgs a) {
+__device__ __forceinline__ void sample_folded_body(const FastSampleArgs& a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int d = a.d;
     const int hd = H * d;
@@ -100,6 +101,23 @@ __global__ __launch_bounds__(SWG) void sample_folded_kernel(FastSampleArgs a) {
     }
 }
 
+template <int H, int ROUNDS>
+__global__ __launch_bounds__(SWG) void sample_folded_kernel(FastSampleArgs a) {
+    sample_folded_body<H, ROUNDS>(a);
+}
+
+// B problems in one launch (icem_plan_step_batch, the two-kernel iterations of the TileHN shapes): blockIdx.y = the problem, its
+// argument block in device memory (scalar loads: the index is uniform), the sampling calls' stream offsets stored relative to
+// the step's base of that problem (BatchBases)
+template <int H, int ROUNDS>
+__global__ __launch_bounds__(SWG) void sample_folded_batch_kernel(const FastSampleArgs* __restrict__ args, BatchBases bases) {
+    FastSampleArgs s = from_device(args[blockIdx.y]);
+    const unsigned long long base = bases.v[blockIdx.y];
+    add_base64(s.off_lo, s.off_hi, base);
+    add_base64(s.off2_lo, s.off2_hi, base);
+    sample_folded_body<H, ROUNDS>(s);
+}
+
 // -------------------------------------------------------------------------------------------------
 // K1 without the distribution ("noise ahead"): the raw colored samples y [n, h, d] of one sampling call
 // -------------------------------------------------------------------------------------------------
@@ -146,15 +164,14 @@ __global__ __launch_bounds__(SWG) void noise_rows_kernel(FastSampleArgs a) {
 // into the LDS tile; then all 5 waves gather the K elite rows and refit, the affine map + clip is applied to the
 // tile and the tile leaves as before.  Every workgroup redoes the same merge (L2 serves the 20 KB of keys and 7 KB
 // of elite rows), workgroup 0 publishes it.  Saves the merge launch (8.6 + 2.6 us) for ~3 us more sampler time.
+// (the body of sample_folded_merge_kernel and of sample_folded_merge_batch_kernel)
 template <int H, int ROUNDS, int KREG, bool REC>
-__global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampleMergeArgs args) {
+__device__ __forceinline__ void sample_folded_merge_body(const FastSampleArgs& a, const MergeSingleArgs& m, const PackPrev& p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ unsigned long long sel[64];
     __shared__ unsigned long long cand[64];
     __shared__ int slot[64];
     constexpr int NTT = SWG + 64;
-    const FastSampleArgs& a = args.s;
-    const MergeSingleArgs& m = args.m;
     const int d = a.d;
     const int hd = H * d;
     const int tpw = SWG / d;
@@ -164,27 +181,27 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
     const int lane = tid & 63;
     // riding pack (sharded runs, PackPrev): workgroup 0 packs + pushes the previous iteration's records while the others
     // draw their noise; the launch has one workgroup more
-    const bool has_pack = REC && args.p.part_k != nullptr;
+    const bool has_pack = REC && p.part_k != nullptr;
     if constexpr (REC) {
         if (has_pack && blockIdx.x == 0) {
             MergeSingleArgs pk{};
-            pk.n_lists = args.p.n_lists;
-            pk.n_pool = args.p.n_pool;
-            pk.n_global = args.p.n_global;
-            pk.K = args.p.K;
+            pk.n_lists = p.n_lists;
+            pk.n_pool = p.n_pool;
+            pk.n_global = p.n_global;
+            pk.K = p.K;
             pk.h = H;
             pk.d = d;
-            pk.part_k = args.p.part_k;
-            pk.actions = args.p.actions;
-            pk.n_keep = args.p.n_keep;
-            pk.elites_cost_cur = args.p.keep_costs;
-            pk.keep_base = args.p.n_loc;
+            pk.part_k = p.part_k;
+            pk.actions = p.actions;
+            pk.n_keep = p.n_keep;
+            pk.elites_cost_cur = p.keep_costs;
+            pk.keep_base = p.n_loc;
             // everybody else's prologue waits for this workgroup's push: its waves go first on their SIMDs
             __builtin_amdgcn_s_setprio(3);
             if (tid >= SWG) merge_select_shallow<3>(pk, lane, cand, sel);
             __syncthreads();
-            pack_records_body<KREG>(pk, args.p.n_loc, args.p.shard_lo, args.p.records, args.p.px, smem, sel, tid, NTT);
-            if (args.p.pub != nullptr) {
+            pack_records_body<KREG>(pk, p.n_loc, p.shard_lo, p.records, p.px, smem, sel, tid, NTT);
+            if (p.pub != nullptr) {
                 // Published merge: this workgroup also runs THE merge of the launch -- waits for every rank's records,
                 // selects, gathers, refits -- and publishes the new mean | std to all the others (written through: the
                 // XCDs' L2s are not coherent inside a launch; then one agent-scope flag).  Hundreds of workgroups each
@@ -199,8 +216,8 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
                     for (int r = 0; r < KREG; ++r) xs[r] = rows[r][e];
                     float nm, ns;
                     refit_element_regs<float, KREG>(m.K, m.alpha, m.mean[e], m.std[e], xs, nm, ns);
-                    __hip_atomic_store(args.p.pub + e, nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(args.p.pub + hd + e, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(p.pub + e, nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(p.pub + hd + e, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     m.mean_out[e] = nm;
                     m.std_out[e] = ns;
 #pragma unroll
@@ -210,12 +227,12 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
                 if (tid < m.K) m.elites_cost_next[tid] = key_cost(sel[tid]);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-                if (tid == 0) __hip_atomic_store(args.p.pub_flag, args.p.pub_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tid == 0) __hip_atomic_store(p.pub_flag, p.pub_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             return;
         }
     }
-    const bool published = REC && has_pack && args.p.pub != nullptr;
+    const bool published = REC && has_pack && p.pub != nullptr;
     const int wg = blockIdx.x - (has_pack ? 1 : 0);
     const int n_base = wg * tpw;
     const int n_here = cmin(tpw, a.n - n_base);
@@ -226,11 +243,11 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
     if (tid >= SWG) {
         if (published) {  // workgroup 0 merges for everybody: wait for its flag (bounded like every exchange wait)
             unsigned polls = 0;
-            while (__hip_atomic_load(args.p.pub_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != args.p.pub_seq &&
-                   ++polls <= args.m.xw.max_polls)
+            while (__hip_atomic_load(p.pub_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.pub_seq &&
+                   ++polls <= m.xw.max_polls)
                 __builtin_amdgcn_s_sleep(16);
-            if (polls > args.m.xw.max_polls && lane == 0 && args.m.xw.status)
-                __hip_atomic_store(args.m.xw.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (polls > m.xw.max_polls && lane == 0 && m.xw.status)
+                __hip_atomic_store(m.xw.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         } else if constexpr (!REC) {
             merge_select_shallow<3>(m, lane, cand, sel);
         }
@@ -241,7 +258,7 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
     if (REC && !published) merge_select_records_wg(m, tid >= SWG, lane, tid, NTT, sel, slot);   // (the records' keys ranked by all threads)
     else __syncthreads();
     if (published) {
-        for (int e = tid; e < 2 * hd; e += NTT) ms[e] = __hip_atomic_load(args.p.pub + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int e = tid; e < 2 * hd; e += NTT) ms[e] = __hip_atomic_load(p.pub + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
         const float* rows[KREG];
         merge_rows<KREG, REC>(m, sel, slot, rows);
@@ -288,6 +305,21 @@ __global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampl
     }
 }
 
+template <int H, int ROUNDS, int KREG, bool REC>
+__global__ __launch_bounds__(SWG + 64) void sample_folded_merge_kernel(FastSampleMergeArgs args) {
+    sample_folded_merge_body<H, ROUNDS, KREG, REC>(args.s, args.m, args.p);
+}
+
+// ... and for B problems (the lists merge: world 1, no riding pack -- the block's PackPrev is all zero)
+template <int H, int ROUNDS, int KREG>
+__global__ __launch_bounds__(SWG + 64) void sample_folded_merge_batch_kernel(const FastSampleMergeArgs* __restrict__ args, BatchBases bases) {
+    const FastSampleMergeArgs& g = args[blockIdx.y];
+    FastSampleArgs s = from_device(g.s);
+    add_base64(s.off_lo, s.off_hi, bases.v[blockIdx.y]);
+    const MergeSingleArgs m = from_device(g.m);
+    sample_folded_merge_body<H, ROUNDS, KREG, false>(s, m, g.p);
+}
+
 }  // namespace
 
 bool fast_sample_supported(int h, int d) {
@@ -311,10 +343,29 @@ bool sample_folded_pack_ok(int h, int d, int rounds, int K) {
     return on && sample_folded_merge_ok(h, d, rounds, K) && K * (h * d + 2) <= (2 + tpw) * h * d;
 }
 
-void launch_sample_folded_merge(const FastSampleMergeArgs& a, hipStream_t st) {
+// horizons with a batched sampler: what a batch of TileHN handles reaches (ICEM_HN_SHAPES are all h = 30)
+#define ICEM_SAMPLE_BATCH_HORIZONS(X) X(30)
+static bool sample_batch_compiled(int h) {
+#define X(HH) \
+    if (h == HH) return true;
+    ICEM_SAMPLE_BATCH_HORIZONS(X)
+#undef X
+    return false;
+}
+static size_t sample_lds(int h, int d) { return ((size_t)2 * h * d + (size_t)(SWG / d) * h * d) * sizeof(float); }
+
+void launch_sample_folded_merge(const LaunchCtx& cx, const FastSampleMergeArgs& a) {
     const int tpw = SWG / a.s.d;
-    const int grid = (a.s.n + tpw - 1) / tpw + (a.m.records && a.p.part_k ? 1 : 0);  // + workgroup 0: the riding pack
-    const size_t lds = ((size_t)2 * a.s.h * a.s.d + (size_t)tpw * a.s.h * a.s.d) * sizeof(float);
+    const bool pack = a.m.records && a.p.part_k;
+    LaunchKey k;
+    k.family = LAUNCH_SAMPLE_MERGE;
+    k.h = a.s.h, k.d = a.s.d, k.form = a.m.records ? 2 : 1;
+    k.wgs[0] = (a.s.n + tpw - 1) / tpw;
+    k.wgs[1] = pack ? 1 : 0;   // + workgroup 0: the riding pack
+    const int grid = k.wgs[0] + k.wgs[1];
+    const size_t lds = sample_lds(a.s.h, a.s.d);
+    hipStream_t st = cx.st;
+    submit(cx, k, k.form == 1 && sample_batch_compiled(k.h), [&](void* dst, unsigned long long base) { batch_form(a, base, dst); }, [&] {
 #define X(HH)                                                                                                  \
     if (a.s.h == HH) {                                                                                         \
         if (a.m.records)                                                                                       \
@@ -323,7 +374,19 @@ void launch_sample_folded_merge(const FastSampleMergeArgs& a, hipStream_t st) {
             hipLaunchKernelGGL((sample_folded_merge_kernel<HH, 10, 12, false>), dim3(grid), dim3(SWG + 64), lds, st, a); \
         return;                                                                                                \
     }
-    ICEM_FAST_HORIZONS(X)
+        ICEM_FAST_HORIZONS(X)
+#undef X
+    });
+}
+
+void launch_sample_merge_batch(const LaunchKey& k, const FastSampleMergeArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+#define X(HH)                                                                                                                   \
+    if (k.h == HH) {                                                                                                            \
+        hipLaunchKernelGGL((sample_folded_merge_batch_kernel<HH, 10, 12>), dim3(k.wgs[0], n), dim3(SWG + 64), sample_lds(k.h, k.d), st, \
+                           args_dev, bases);                                                                                    \
+        return;                                                                                                                 \
+    }
+    ICEM_SAMPLE_BATCH_HORIZONS(X)
 #undef X
 }
 
@@ -354,10 +417,17 @@ void launch_noise_rows(const FastSampleArgs& a, int rounds, hipStream_t st) {
 #undef X
 }
 
-void launch_sample_folded(const FastSampleArgs& a, int rounds, hipStream_t st) {
+void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int rounds) {
     const int tpw = SWG / a.d;
-    const int grid = (a.n + tpw - 1) / tpw + (a.n_shift > 0 ? 1 : 0);
-    const size_t lds = ((size_t)2 * a.h * a.d + (size_t)tpw * a.h * a.d) * sizeof(float);
+    LaunchKey k;
+    k.family = LAUNCH_SAMPLE;
+    k.h = a.h, k.d = a.d, k.form = rounds;
+    k.wgs[0] = (a.n + tpw - 1) / tpw;
+    k.wgs[1] = a.n_shift > 0 ? 1 : 0;   // the last workgroup: the shifted elites
+    const int grid = k.wgs[0] + k.wgs[1];
+    const size_t lds = sample_lds(a.h, a.d);
+    hipStream_t st = cx.st;
+    submit(cx, k, rounds == 10 && sample_batch_compiled(k.h), [&](void* dst, unsigned long long base) { batch_form(a, base, dst); }, [&] {
 #define X(HH)                                                                                        \
     if (a.h == HH) {                                                                                 \
         if (rounds == 7)                                                                             \
@@ -366,7 +436,19 @@ void launch_sample_folded(const FastSampleArgs& a, int rounds, hipStream_t st) {
             hipLaunchKernelGGL((sample_folded_kernel<HH, 10>), dim3(grid), dim3(SWG), lds, st, a);   \
         return;                                                                                      \
     }
-    ICEM_FAST_HORIZONS(X)
+        ICEM_FAST_HORIZONS(X)
+#undef X
+    });
+}
+
+void launch_sample_batch(const LaunchKey& k, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+#define X(HH)                                                                                                                       \
+    if (k.h == HH) {                                                                                                                \
+        hipLaunchKernelGGL((sample_folded_batch_kernel<HH, 10>), dim3(k.wgs[0] + k.wgs[1], n), dim3(SWG), sample_lds(k.h, k.d), st, \
+                           args_dev, bases);                                                                                        \
+        return;                                                                                                                     \
+    }
+    ICEM_SAMPLE_BATCH_HORIZONS(X)
 #undef X
 }
 

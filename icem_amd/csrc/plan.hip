@@ -202,15 +202,15 @@ static int no_batched_form(const LaunchCtx& cx, const char* what) {
 int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const void* obs0, const void* actions,
                         void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k, int n_tail, int* tail_out) {
-    if (cx.rec) return no_batched_form(cx, "this configuration's rollout launch has no batched form");
+    if (cx.rec && !h->hn_tile) return no_batched_form(cx, "this configuration's rollout launch has no batched form");
     hipStream_t st = cx.st;
-    int rc = ensure_fast_model(h);
+    int rc = ensure_fast_model(h);   // (per handle, also ahead of a batch's recorded launches: uploads only)
     if (rc) return rc;
     if (tail_out) *tail_out = 0;
     if (h->hn_tile) {   // Door / Relocate / FetchPickAndPlace shapes: TileHN (k_rollout_hn.hip)
         // trailing shifted elites that would open a second round of tiles: workgroups of their own, no list (tail_out rows: the
         // caller's merge takes them as extra candidates through the cost array)
-        const int tail = (tail_out && n_cand == n_rows && K > 0) ? hn_tail_rows(n_rows, n_tail) : 0;
+        const int tail = (tail_out && n_cand == n_rows && K > 0) ? hn_tail_rows(cx.hint, n_rows, n_tail) : 0;
         FastRolloutArgs a = fast_rollout_args(h, n_rows, tail ? n_rows - tail : n_cand, K, obs0, actions, costs, part_c, part_i);
         a.part_k = part_k;
         a.arith = 1;
@@ -219,11 +219,11 @@ int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const voi
         const int ld = h->wide ? h->obs_dim : h->O;   // A_dev / B_dev: row-major f32, unpadded at o > 32, padded to O below
         {
             ProfScope prof(h, ICEM_K_ROLLOUT, (long long)n_rows * h->cfg.horizon, st);
-            launch_rollout_hn(a, h->cfg.horizon, h->cfg.act_dim, h->obs_dim, h->model_kind, (const float*)h->A_dev, ld, (const float*)h->B_dev, ld,
-                              h->cost.lin_idx, h->cost.flip_idx, h->has_terms ? (const CostArgs<float>*)h->hn_cs_dev : nullptr, h->hn_prog, st);
+            launch_rollout_hn(cx, a, h->cfg.horizon, h->cfg.act_dim, h->obs_dim, h->model_kind, (const float*)h->A_dev, ld, (const float*)h->B_dev, ld,
+                              h->cost.lin_idx, h->cost.flip_idx, h->has_terms ? (const CostArgs<float>*)h->hn_cs_dev : nullptr, h->hn_prog);
         }
         ICEM_HIP_TRY(hipGetLastError());
-        if (lists_out) *lists_out = tail ? a.list_wgs : hn_rollout_lists(n_rows);
+        if (lists_out) *lists_out = tail ? a.list_wgs : hn_rollout_lists(cx.hint, n_rows);
         return ICEM_OK;
     }
     if (gemm_rollout(h)) {
@@ -330,13 +330,12 @@ int launch_fast_sample(const icem_handle* h, int n, long long first_index, const
                        const void* low, const void* high, uint64_t offset, int row0_mean, void* out, const LaunchCtx& cx,
                        int n_shift, const void* elites_src, uint64_t offset2) {
     if (n <= 0 && n_shift <= 0) return ICEM_OK;
-    if (cx.rec) return no_batched_form(cx, "this configuration's sampling launch has no batched form");
     hipStream_t st = cx.st;
     const FastSampleArgs a = fast_sample_args(h, n, first_index, mean, std, low, high, offset, row0_mean, out, n_shift,
                                               elites_src, offset2);
     {
         ProfScope prof(h, ICEM_K_SAMPLE, (long long)n * a.h, st);
-        launch_sample_folded(a, h->cfg.rng_rounds, st);
+        launch_sample_folded(cx, a, h->cfg.rng_rounds);
     }
     ICEM_HIP_TRY(hipGetLastError());
     return ICEM_OK;
@@ -701,7 +700,7 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
             }
             if (one == 0) {
                 if (prologue) {
-                    FastSampleMergeArgs sm;
+                    FastSampleMergeArgs sm = zeroed_args<FastSampleMergeArgs>();
                     sm.s = fast_sample_args(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, 0, nullptr, 0);
                     sm.m = h->ride.merge;
                     if (ride) {
@@ -716,7 +715,7 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                     }
                     {
                         ProfScope prof(h, ICEM_K_SAMPLE, (long long)n_loc * c.horizon, st);
-                        launch_sample_folded_merge(sm, st);
+                        launch_sample_folded_merge(cx, sm);
                     }
                     ICEM_HIP_TRY(hipGetLastError());
                     rc = ICEM_OK;
@@ -1525,10 +1524,21 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     if (c.dtype != ICEM_F32 || !h->use_fast) return "dtype f32 on the throughput kernels only";
     if (b->z_r || b->z_i || b->z_r_shift || b->z_i_shift) return "external noise is not batched";
     if (h->profiling || h->dbg) return "per-kernel profiling / debug stamps are per handle: switch them off";
-    if (gemm_rollout(h) || h->hn_tile || h->Of == 0) return "only the 16-trajectory tile kernels (o <= 20 shapes) are batched";
-    if (!fast_rollout_ok(h, K) || !fast_sample_ok(h) || K + 1 > 12 || c.rng_rounds != 10) return "shape outside the single-launch kernels";
+    if (gemm_rollout(h) && !h->hn_tile)
+        return "only the 16-trajectory tile kernels (o <= 20 shapes) and the TileHN kernel (the Door / Relocate / FetchPickAndPlace shapes) are batched";
+    if (!fast_rollout_ok(h, K) || !fast_sample_ok(h) || K + 1 > 12 || c.rng_rounds != 10)
+        return h->hn_tile ? "the merge cannot ride in the sampler's prologue (num_elites <= 11, the default generator)" : "shape outside the single-launch kernels";
     if (h->ride.merge_pending || h->ride.pack_pending) return "a deferred merge is pending: finish the MPC step first";
     if (c.opt_iters < 1) return "opt_iters";
+    if (h->hn_tile) {
+        // sampler (shifted elites in its extra workgroup; from iteration 1 on the previous merge in its prologue) + TileHN rollout
+        // per iteration, then the last merge: the path decisions of plan_iter_local_t for these handles
+        if (h->pop.empty() || h->pop[0] > 8192) return "populations above 8192 rows per iteration are not batched: they fill the chip by themselves";
+        if (shift_rows(h, mpc_step, 0, false) * c.act_dim > 256) return "too many shifted elites for the sampling launch";
+        if (c.opt_iters > 1 && !sample_folded_merge_ok(c.horizon, c.act_dim, c.rng_rounds, K))
+            return "an iteration cannot carry the previous merge in its prologue";
+        return nullptr;
+    }
     // (bh: the shapes below are the batch's.)  Where every iteration's rows of ALL problems together fill the
     // noise-ahead launch (>= 4 waves per rollout workgroup), the batch takes that path -- rollout, next noise and shifted elites
     // as roles of one launch (k_rollout_ahead.hip), 107 against 130 us per step at eight problems of 4096 rows -- provided a
@@ -1569,6 +1579,9 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         if (rc) return rc;
         if (h->Of != h0->Of || h->model_kind != h0->model_kind || h->tile_arith != h0->tile_arith)
             return fail(ICEM_E_INVALID, "icem_plan_step_batch: the handles must share the model's width and kind and the tile arithmetic");
+        // (a handle that is not on the TileHN kernel beside one that is: refused below, as unsupported)
+        if (h->hn_tile && h0->hn_tile && (h->obs_dim != h0->obs_dim || std::memcmp(h->hn_prog, h0->hn_prog, sizeof(h->hn_prog)) != 0))
+            return fail(ICEM_E_INVALID, "icem_plan_step_batch: TileHN handles must share the observation width and the compiled term program");
     }
     // the batch's shape hint.  The noise-ahead launches from where they measure faster than the single-launch kernels: 12 problems
     // of 4096 rows (160 against 161 us per step; 16: 194 against 212; 8: 129 against 128; 6: 115 against 100 -- EXPERIMENTS R6.3)
@@ -1595,7 +1608,7 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
     bool unsupported = false;
     for (int i = 0; i < n && rc == ICEM_OK; ++i) {
         recs[i].base = bases.v[i] = call_base(handles[i], mpc_step);
-        recs[i].launches.reserve(handles[i]->cfg.opt_iters + 1);
+        recs[i].launches.reserve(2 * handles[i]->cfg.opt_iters + 1);
         rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &recs[i]});
         unsupported = unsupported || recs[i].unsupported;
     }
@@ -1663,6 +1676,9 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         const unsigned char* base = (const unsigned char*)ctx->dev[slot] + at[l];
         if (k.family == LAUNCH_SAMPLE_ROLLOUT) launch_sample_rollout_batch(k, (const FastIterArgs*)base, bases, n, st);
         else if (k.family == LAUNCH_ITER_AHEAD) launch_iter_ahead_batch(k, (const IterAheadArgs*)base, bases, n, st);
+        else if (k.family == LAUNCH_SAMPLE) launch_sample_batch(k, (const FastSampleArgs*)base, bases, n, st);
+        else if (k.family == LAUNCH_SAMPLE_MERGE) launch_sample_merge_batch(k, (const FastSampleMergeArgs*)base, bases, n, st);
+        else if (k.family == LAUNCH_ROLLOUT_HN) launch_rollout_hn_batch(k, (const HnArgs*)base, n, st);
         else launch_merge_batch(k, (const MergeNoiseBatchArgs*)base, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
     }

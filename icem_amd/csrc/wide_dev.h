@@ -3,6 +3,7 @@
 // Anonymous namespace: every translation unit gets its own copy (same bits).
 #pragma once
 #include "cost_terms_dev.h"
+#include "icem_fused.h"   // WideCost
 
 namespace icem {
 namespace {
@@ -23,10 +24,6 @@ __device__ __forceinline__ void wide_stage_terms(CostArgs<float>& dst, const Cos
             reinterpret_cast<int*>(&dst)[e] = reinterpret_cast<const int*>(src)[e];
     __syncthreads();
 }
-struct WideCost {
-    int lin_idx, flip_idx;
-    float ctrl_w, lin_w, flip_pen, flip_th;
-};
 __device__ __forceinline__ float wide_step_cost(const WideCost& b, bool ext, const CostArgs<float>& cs, const float* x, int o, int d,
                                                 bool bad, float& dold) {
     float c = 0.f;

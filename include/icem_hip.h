@@ -392,16 +392,29 @@ int icem_plan_step_sharded(icem_handle* h, const icem_plan_buffers* b, int32_t m
 int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, void* stream);
 
 /* B independent planners of ONE configuration -- the reference's parallel episodes, each its own get_action
- * (icem/misc/rollout_utils.py:46-58, 129-152; icem.py:106-189) -- advanced by one MPC step together: every stage of the
- * small-population path is one launch for all of them (grid.y = the problem), so the step's chain of launch latencies is paid
- * once per batch instead of once per problem.  handles[i] with buffers[i]: exactly the arguments icem_plan_step takes; every
- * problem's outputs (executed action, best cost, mean, std, elites, pool, costs) are bit for bit those of its own
- * icem_plan_step.  The handles must share horizon, act_dim, populations, elites, flags, model width / kind and tile
- * arithmetic; models, costs, seeds, bounds and observations are per problem.  world == 1, f32, device noise, o <= 20 tile
- * shapes, populations that take the single-launch kernel alone (<= 8192 rows per iteration): otherwise ICEM_E_UNSUPPORTED and
- * nothing is launched.  (From 49 152 rows of all problems together the batch takes the noise-ahead launches of large
- * populations -- k_rollout_ahead.hip -- instead of the single-launch kernels: measured faster from there on.)  n in [1, 32]; n == 1 is icem_plan_step.  No host synchronisation; one small host-to-device copy
- * on `stream` when the argument blocks changed (the first steps). */
+ * (icem/misc/rollout_utils.py:46-58, 129-152; icem.py:106-189) -- advanced by one MPC step together: every launch of the step
+ * is one launch for all of them (grid.y = the problem, the argument blocks in a device array), so the step's chain of launch
+ * latencies is paid once per batch instead of once per problem.  handles[i] with buffers[i]: exactly the arguments
+ * icem_plan_step takes; every problem's outputs (executed action, best cost, mean, std, elites, pool, costs) are bit for bit
+ * those of its own icem_plan_step.  The handles must share horizon, act_dim, populations, elites, flags, model width / kind and
+ * tile arithmetic (else ICEM_E_INVALID); models, costs, seeds, bounds and observations are per problem.  Served, at world == 1,
+ * f32, device noise and at most 8192 rows per iteration:
+ *   - the o <= 20 tile shapes (HalfCheetah ...), whose iterations are the single-launch kernel.  (From 49 152 rows of all
+ *     problems together the batch takes the noise-ahead launches of large populations -- k_rollout_ahead.hip -- instead:
+ *     measured faster from there on.)
+ *   - the TileHN shapes -- Door (d = 28, o = 39), Relocate (d = 30, o = 39), FetchPickAndPlace (d = 4, o = 28) at h = 30 --
+ *     whose iterations are a sampler (from the second iteration on with the previous merge in its prologue: num_elites <= 11
+ *     and the default generator, rng_rounds = 10) and a rollout.  The handles must also share the observation width and the
+ *     compiled term program of their icem_cost_terms (a Door planner beside one without its term list: ICEM_E_INVALID).  A
+ *     batch's rollout is always the one-wave-per-tile arrangement (rollout_hn_kernel's), with the waves per workgroup chosen
+ *     for the tiles of all problems together: the two- and several-waves-per-tile arrangements that serve one small
+ *     population alone are not batched.  At the benchmark's populations that is the arrangement that fills the chip from four
+ *     problems on; for where a batch pays against stepping alone see EXPERIMENTS.md R7.4 (tools/hn_batch_bench.py).
+ * Anything else -- handles on the GEMM kernels (wide observations; a term list outside the compiled programs; ICEM_TILE_F32 on
+ * a TileHN shape), f64, external noise, sharded handles, populations above 8192 rows per iteration (they fill the chip
+ * alone), profiling switched on -- is ICEM_E_UNSUPPORTED.  Whatever is refused is refused before anything is launched, and
+ * every handle is left as it was.  n in [1, 32]; n == 1 is icem_plan_step.  No host synchronisation; one small host-to-device
+ * copy on `stream` when the argument blocks changed (the first steps: the blocks of step s are those of step s - 6). */
 int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream);
 int64_t icem_batch_uploads(const icem_handle* h); /* how often handles[0]'s argument array was (re)written (measurement) */
 
