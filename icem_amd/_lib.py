@@ -140,6 +140,10 @@ SYMBOLS = [
     ("icem_profile_overhead", C.c_int, [_VP, _I32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icem_plan_step_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, _VP]),
     ("icem_batch_uploads", C.c_int64, [_H]),
+    ("icem_plan_step_learned_ok", C.c_int, [_H]),
+    ("icem_plan_step_learned", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _VP, _I32, _VP]),
+    ("icem_plan_step_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _VP, C.POINTER(_I32), _VP, _VP]),
+    ("icem_learned_step_launches", C.c_int64, [_H]),
     ("icem_tile_growth", C.c_double, [_H]),
     ("icem_nonfinite_costs", C.c_int, [_H, C.POINTER(C.c_int64), _VP]),
     ("icem_set_option", C.c_int, [C.c_char_p, C.c_double]),
@@ -151,6 +155,7 @@ SYMBOLS = [
 
 IPC_HANDLE_BYTES = 64
 RCCL_ID_BYTES = 128
+RSSM_OBS_DIM = 230   # include/icem_hip.h: ICEM_RSSM_OBS_DIM
 ABI_VERSION = 6   # include/icem_hip.h: ICEM_ABI_VERSION
 
 

@@ -503,8 +503,12 @@ class MpcICemHip(MpcController):
             self.planner.reset()
         else:
             p = self.planner
-            self._mean = torch.empty((p.h, p.d), dtype=p.dt, device=p.device)
-            self._std = torch.empty_like(self._mean)
+            if self.rssm_path:   # the learned-dynamics step works in the planner's own buffers: the same ones every episode
+                p._ensure_buffers(learned=True)
+                self._mean, self._std = p.mean, p.std
+            else:
+                self._mean = torch.empty((p.h, p.d), dtype=p.dt, device=p.device)
+                self._std = torch.empty_like(self._mean)
             p.reset_distribution(self._mean, self._std)
             p.mean, p.std = self._mean, self._std
             p.mpc_step = 0
@@ -560,6 +564,8 @@ class MpcICemHip(MpcController):
             executed_dev = self.planner.plan_step(obs, noise=noise)
             host = torch.cat([executed_dev, self.planner.best_cost]).cpu().numpy().astype(np.float64)  # one D2H sync
             executed_action, self.last_min_cost = host[:-1], float(host[-1])
+        elif self._learned_step_ok(noise):
+            executed_action = self._get_action_learned(obs)   # the whole step one library call (icem_plan_step_learned)
         else:
             executed_action = self._get_action_stagewise(obs, noise)
         return self._finish_action(obs, executed_action)
@@ -589,8 +595,10 @@ class MpcICemHip(MpcController):
         every stage of the planning step is one launch for all of them.  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same hooks).  Device path with
         device noise (the HalfCheetah-sized tile shapes, and the Door / Relocate / FetchPickAndPlace envs at h = 30); or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
-        one configuration: their populations are scored by ONE ``rollout_cost_batch`` launch per CEM iteration (sampling and
-        the distribution update stay one launch per controller).  Anything else: call ``get_action`` per controller."""
+        one configuration: the whole step is ``icem_plan_step_learned_batch``, every stage one launch for all of them (where
+        that entry does not serve them -- another horizon, f64 ... -- ONE ``rollout_cost_batch`` launch per CEM iteration scores
+        their populations and sampling and the distribution update stay one launch per controller).  Anything else: call
+        ``get_action`` per controller."""
         ctrls = list(controllers)
         n = len(ctrls)
         states = [None] * n if states is None else list(states)
@@ -607,7 +615,9 @@ class MpcICemHip(MpcController):
         for c, ob, stt in zip(ctrls, observations, states):
             c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
                 observation=ob, env_state=stt, model_state=c.forward_model_state)
-        if rssm:
+        if rssm and all(c._learned_step_ok(None) for c in ctrls):
+            host = MpcICemHip._get_action_batch_learned(ctrls, observations)
+        elif rssm:
             host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
         else:
             IcemPlanner.plan_step_batch([c.planner for c in ctrls], observations)
@@ -738,6 +748,61 @@ class MpcICemHip(MpcController):
         host = self._stage_finish().cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
         self.last_min_cost = float(host[-1])
         return host[:-1]
+
+    # -- the learned-dynamics step as one library call (icem_plan_step_learned / _batch): same bits as the stage-wise loop
+    def _learned_step_ok(self, noise) -> bool:
+        return bool(self.rssm_path and not self.device_path and noise is None and self.planner.cfg.world == 1
+                    and not self.verbose and self._model_is_the_library_rssm() and self.planner.learned_step_ok())
+
+    def _model_is_the_library_rssm(self) -> bool:
+        """The library's step rolls out through the declared RSSM itself.  ``rssm_path`` is duck-typed (``rollout_cost`` +
+        ``params``): a model whose ``rollout_cost`` / ``rollout_cost_batch`` is not ``DeviceRSSMModel``'s own -- a subclass's,
+        or one replaced on the instance to time or count the rollouts -- is called stage by stage, as it asks to be."""
+        from .models import DeviceRSSMModel
+        m = self.forward_model
+        return (isinstance(m, DeviceRSSMModel) and type(m).rollout_cost is DeviceRSSMModel.rollout_cost
+                and type(m).rollout_cost_batch is DeviceRSSMModel.rollout_cost_batch
+                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
+                and m.params.device == self.planner.device)
+
+    def _elites_into_planner(self):
+        """A fused step reads the kept / shifted elites from the planner's current elite half: behind a stage-wise step
+        they are the controller's own tensors and go there first (behind a fused step they already are that half)."""
+        if self._elite_actions is None:
+            return
+        a, c = self.planner.current_elites()
+        if self._elite_actions.data_ptr() != a.data_ptr():
+            a.copy_(self._elite_actions)
+            c.copy_(self._elite_costs)
+
+    def _elites_from_planner(self):
+        self._elite_actions, self._elite_costs = self.planner.current_elites()
+
+    def _get_action_learned(self, obs):
+        p = self.planner
+        self._elites_into_planner()
+        p.plan_step_learned(self.forward_model, obs)
+        self._elites_from_planner()
+        host = torch.cat([p.executed, p.best_cost]).cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+        self.last_min_cost = float(host[-1])
+        return host[:-1]
+
+    @staticmethod
+    def _get_action_batch_learned(ctrls, observations):
+        """-> [B, d + 1] host array of executed actions and best costs (one device-to-host copy, one synchronisation); a
+        batch the entry does not serve as a whole (all tiles together beyond the rollout's limit) steps stage-wise."""
+        from ._lib import IcemError, ICEM_E_UNSUPPORTED
+        for c in ctrls:
+            c._elites_into_planner()
+        try:
+            results = IcemPlanner.plan_step_learned_batch([c.planner for c in ctrls], ctrls[0].forward_model, observations)
+        except IcemError as e:
+            if e.code != ICEM_E_UNSUPPORTED:
+                raise
+            return MpcICemHip._get_action_batch_rssm(ctrls, observations)   # (refused before anything ran)
+        for c in ctrls:
+            c._elites_from_planner()
+        return results.cpu().numpy().astype(np.float64)
 
     @staticmethod
     def _rssm_batch_refusal(ctrls):

@@ -157,6 +157,20 @@ int refresh_act_mag(icem_handle* h, const void* low, const void* high, hipStream
     h->am_hi = high;
     return ICEM_OK;
 }
+// what a learned-dynamics launch's HIP result means to the caller (every entry point that launches it)
+int rssm_launch_result(hipError_t e) {
+    if (e == hipErrorStreamCaptureUnsupported)
+        return fail(ICEM_E_STATE, "learned-dynamics rollout: the stream is capturing and this call would have to synchronise it (a larger "
+                                  "population or horizon than the staging area holds, or recovery from a timed-out wait): make one call "
+                                  "of this size outside the capture first");
+    if (e == hipErrorLaunchTimeOut)
+        return fail(ICEM_E_STATE, "learned-dynamics rollout: a reward workgroup of an EARLIER launch on this stream gave up waiting "
+                                  "for its recurrence (that launch's costs are NaN); the staging flags were reset, nothing was "
+                                  "launched by this call -- call again");
+    ICEM_HIP_TRY(e);
+    return ICEM_OK;
+}
+
 }  // namespace icem
 
 // what icem_profile_overhead times: one wave that spins for `ticks` of the 100 MHz wall clock and reports how long it
@@ -261,6 +275,7 @@ int icem_destroy(icem_handle* h) {
     if (h->W_dev) (void)hipFree(h->W_dev);
     if (h->nonfinite_dev) (void)hipFree(h->nonfinite_dev);
     if (h->batch_ctx && h->batch_ctx_free) h->batch_ctx_free(h->batch_ctx);
+    if (h->learned_ctx && h->learned_ctx_free) h->learned_ctx_free(h->learned_ctx);
     if (h->actions_alt) (void)hipFree(h->actions_alt);
     if (h->host_stage) (void)hipHostFree(h->host_stage);
     if (h->ws_alt) (void)hipFree(h->ws_alt);
@@ -824,20 +839,6 @@ size_t icem_rssm_param_elems(void) { return rssm::TOTAL; }
 
 int icem_rssm_trim(void) {
     rssm_split_trim();
-    return ICEM_OK;
-}
-
-// what a learned-dynamics launch's HIP result means to the caller (both entry points)
-static int rssm_launch_result(hipError_t e) {
-    if (e == hipErrorStreamCaptureUnsupported)
-        return fail(ICEM_E_STATE, "learned-dynamics rollout: the stream is capturing and this call would have to synchronise it (a larger "
-                                  "population or horizon than the staging area holds, or recovery from a timed-out wait): make one call "
-                                  "of this size outside the capture first");
-    if (e == hipErrorLaunchTimeOut)
-        return fail(ICEM_E_STATE, "learned-dynamics rollout: a reward workgroup of an EARLIER launch on this stream gave up waiting "
-                                  "for its recurrence (that launch's costs are NaN); the staging flags were reset, nothing was "
-                                  "launched by this call -- call again");
-    ICEM_HIP_TRY(e);
     return ICEM_OK;
 }
 

@@ -57,6 +57,10 @@ struct SampleArgs {
     int white;  // noise_beta <= 0 (icem.py:77): zr is randn[n, h, d], zi unused; W is the identity
     T* out;
 };
+struct ShiftSampleArgs {
+    SampleArgs<float> s;        // n = the shifted rows, t_begin = h - 1, out = their first row, offset relative to the step's base
+    const float* elites_src;    // [>= n, h, d]
+};
 
 template <typename T, int HMAX, int ROUNDS>
 __device__ __forceinline__ void white_row(const SampleArgs<T>& a, int row_local, long long gi, int j, T (&g)[HMAX]) {
@@ -89,8 +93,9 @@ __device__ __forceinline__ void white_row(const SampleArgs<T>& a, int row_local,
     }
 }
 
+// (the body of sample_clip_kernel and of the thread form of shift_sample_batch_kernel: one device function, the same device code)
 template <typename T, int HMAX, int ROUNDS>
-__global__ __launch_bounds__(WG) void sample_clip_kernel(SampleArgs<T> a) {
+__device__ __forceinline__ void sample_clip_body(const SampleArgs<T>& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* tile = reinterpret_cast<T*>(smem_raw);
     const int tid = threadIdx.x;
@@ -128,6 +133,11 @@ __global__ __launch_bounds__(WG) void sample_clip_kernel(SampleArgs<T> a) {
     }
 }
 
+template <typename T, int HMAX, int ROUNDS>
+__global__ __launch_bounds__(WG) void sample_clip_kernel(SampleArgs<T> a) {
+    sample_clip_body<T, HMAX, ROUNDS>(a);
+}
+
 // The same sampler with FOUR lanes per (trajectory, dim) row (WG / 4 rows per workgroup): in float64 a row is one thread's chain of
 // HMAX / 2 libm-grade Box-Muller transforms and h x HMAX dependent fused multiply-adds -- 19 us per launch at N = 4096 with the
 // chip all but empty.  Lane q of a row's quad runs the row's generator like the others (integer work: cheap), transforms only
@@ -147,7 +157,7 @@ __device__ __forceinline__ double quad_swap(double x) {
 }
 
 template <typename T, int HMAX, int ROUNDS>
-__global__ __launch_bounds__(WG) void sample_clip_quad_kernel(SampleArgs<T> a) {
+__device__ __forceinline__ void sample_clip_quad_body(const SampleArgs<T>& a) {
     constexpr int PAIRS = HMAX / 8;   // Box-Muller pairs per lane
     typedef T T2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -245,6 +255,36 @@ __global__ __launch_bounds__(WG) void sample_clip_quad_kernel(SampleArgs<T> a) {
     for (int e = tid; e < total; e += WG) {
         if (e_begin == 0 || (e % hd) >= e_begin) a.out[base + e] = tile[e];
     }
+}
+
+template <typename T, int HMAX, int ROUNDS>
+__global__ __launch_bounds__(WG) void sample_clip_quad_kernel(SampleArgs<T> a) {
+    sample_clip_quad_body<T, HMAX, ROUNDS>(a);
+}
+
+// The shifted elites of B problems in one launch (icem_plan_step_learned*, learned_step.hip): blockIdx.y = the problem, its
+// argument block in device memory, the stream offset stored relative to the step's base of that problem (BatchBases).  Rows
+// [0, s.n) of s.out <- elites_src[e, 1:, :] (icem.py:97-100) and, behind them, the freshly drawn last action: the sampling
+// call icem_sample_clip(t_begin = h - 1) makes for these rows -- the same body, so the same bits -- which writes the last
+// time step only.  A problem without shifted elites (s.n == 0: its first MPC step) and surplus workgroups exit.
+template <int HMAX, int ROUNDS, bool QUAD>
+__global__ __launch_bounds__(WG) void shift_sample_batch_kernel(const ShiftSampleArgs* __restrict__ args, BatchBases bases) {
+    ShiftSampleArgs g = args[blockIdx.y];
+    SampleArgs<float>& a = g.s;
+    const int n_base = blockIdx.x * a.tpw;
+    if (n_base >= a.n) return;
+    const unsigned long long off = (((unsigned long long)a.off_hi << 32) | a.off_lo) + bases.v[blockIdx.y];
+    a.off_lo = (uint32_t)off;
+    a.off_hi = (uint32_t)(off >> 32);
+    const int hd = a.h * a.d;
+    const int n_here = min(a.tpw, a.n - n_base);
+    const int keep = hd - a.d;
+    for (int x = threadIdx.x; x < n_here * keep; x += WG) {
+        const int e = x / keep, r = x - e * keep;
+        a.out[(size_t)(n_base + e) * hd + r] = g.elites_src[(size_t)(n_base + e) * hd + a.d + r];
+    }
+    if (QUAD) sample_clip_quad_body<float, HMAX, ROUNDS>(a);
+    else sample_clip_body<float, HMAX, ROUNDS>(a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1474,6 +1514,45 @@ int launch_topk(int n, int K, const void* costs, void* out_c, int* out_i, void* 
 }
 
 // ---- dtype-erased entry points (host_common.h) ---------------------------------------------------------------------
+
+// ---- icem_plan_step_learned* (learned_step.hip): the shifted elites of n problems, one launch ----
+size_t gk_shift_sample_block_bytes() { return sizeof(ShiftSampleArgs); }
+
+// the argument block of one problem (every byte defined: the blocks are compared with the previous step's)
+void gk_shift_sample_block(const icem_handle* h, int n_shift, const void* mean, const void* std, const void* low, const void* high,
+                           uint64_t offset_rel, const void* elites_src, void* out, void* dst) {
+    std::memset(dst, 0, sizeof(ShiftSampleArgs));
+    ShiftSampleArgs& g = *(ShiftSampleArgs*)dst;
+    const SampleArgs<float> a = make_sample_args<float>(h, n_shift, 0, mean, std, low, high, nullptr, nullptr, offset_rel, h->cfg.horizon - 1, 0, out);
+    g.s.n = a.n, g.s.h = a.h, g.s.d = a.d, g.s.F = a.F;
+    g.s.tpw = gk_shift_sample_quad(h) ? std::max(1, (WG / 4) / a.d) : a.tpw;
+    g.s.first_index = 0;
+    g.s.W = a.W, g.s.mean = a.mean, g.s.std = a.std, g.s.low = a.low, g.s.high = a.high, g.s.zr = nullptr, g.s.zi = nullptr;
+    g.s.seed_lo = a.seed_lo, g.s.seed_hi = a.seed_hi, g.s.off_lo = a.off_lo, g.s.off_hi = a.off_hi;
+    g.s.t_begin = a.t_begin, g.s.row0_mean = 0, g.s.white = a.white, g.s.out = a.out;
+    g.elites_src = (const float*)elites_src;
+}
+
+// launch_sample's choice between its two forms (one summation order per handle)
+bool gk_shift_sample_quad(const icem_handle* h) {
+    return opt_i(OPT_GK_SAMPLE) != 0 && h->cfg.act_dim <= WG / 4 && (long long)h->cfg.num_traj * h->cfg.act_dim <= 262144;
+}
+
+// f32, HMAX = 32 (h <= 32), rng_rounds = 10: what icem_plan_step_learned_ok admits
+int gk_shift_sample_batch(const icem_handle* h, int n_problems, int n_shift_max, const void* args_dev, const BatchBases& bases, hipStream_t st) {
+    const bool quad = gk_shift_sample_quad(h);
+    const int d = h->cfg.act_dim, hh = h->cfg.horizon;
+    const int tpw = quad ? std::max(1, (WG / 4) / d) : std::max(1, WG / d);
+    const dim3 grid((n_shift_max + tpw - 1) / tpw, n_problems);
+    if (quad)
+        hipLaunchKernelGGL((shift_sample_batch_kernel<32, 10, true>), grid, dim3(WG),
+                           ((((size_t)tpw * hh * d + 1) & ~(size_t)1) + (size_t)hh * 32) * sizeof(float), st, (const ShiftSampleArgs*)args_dev, bases);
+    else
+        hipLaunchKernelGGL((shift_sample_batch_kernel<32, 10, false>), grid, dim3(WG), (size_t)tpw * hh * d * sizeof(float), st,
+                           (const ShiftSampleArgs*)args_dev, bases);
+    ICEM_HIP_TRY(hipGetLastError());
+    return ICEM_OK;
+}
 
 int gk_sample(const icem_handle* h, int n, long long first_index, const void* mean, const void* std, const void* low,
               const void* high, const void* zr, const void* zi, uint64_t offset, int t_begin, int row0_mean, void* out,

@@ -191,6 +191,10 @@ struct icem_handle {
     void* batch_ctx = nullptr;
     void (*batch_ctx_free)(void*) = nullptr;
     unsigned long long batch_uploads = 0;   // how often that array was (re)written (steady state: never)
+    // icem_plan_step_learned* (learned_step.hip): argument arrays and the batch's contiguous pool live with the step's FIRST handle
+    void* learned_ctx = nullptr;
+    void (*learned_ctx_free)(void*) = nullptr;
+    long long learned_launches = 0;         // kernel launches of the last learned step this handle led
     void* rccl_comm = nullptr;       // collective.hip: the RCCL communicator of icem_allgather_elites (world > 1)
     bool rccl_owned = false;         // ... created by icem_rccl_connect (destroyed with the handle) or adopted
 };
@@ -267,6 +271,14 @@ int gk_gather_refit(const icem_handle* h, const void* actions, const int32_t* id
 int gk_shift(const icem_handle* h, void* mean, void* std, const void* low, const void* high, hipStream_t st);
 int gk_reset(const icem_handle* h, void* mean, void* std, const void* low, const void* high, hipStream_t st);
 int gk_shift_elites(const icem_handle* h, int n_extra, const void* elites, void* dst, hipStream_t st);
+// icem_plan_step_learned* (learned_step.hip): the shifted elites of n problems in one launch -- the copy of elites[e, 1:, :] and
+// icem_sample_clip(t_begin = h - 1)'s draw of the last action (f32, h <= 32, rng_rounds 10).  One argument block per problem
+// in a device array (gk_shift_sample_block writes the host form, stream offset relative to the step's base).
+size_t gk_shift_sample_block_bytes();
+bool gk_shift_sample_quad(const icem_handle* h);
+void gk_shift_sample_block(const icem_handle* h, int n_shift, const void* mean, const void* std, const void* low, const void* high,
+                           uint64_t offset_rel, const void* elites_src, void* out, void* dst);
+int gk_shift_sample_batch(const icem_handle* h, int n_problems, int n_shift_max, const void* args_dev, const BatchBases& bases, hipStream_t st);
 // merge of the all-gathered records (+ kept elites): arguments of merge_refit_kernel, dtype-erased
 struct MergeArgsV {
     int n_rec, n_keep, K, h, d, n_global, last;
@@ -329,6 +341,7 @@ bool fast_sample_ok(const icem_handle* h);
 int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const void* obs0, const void* actions,
                         void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k = nullptr, int n_tail = 0, int* tail_out = nullptr);
+int rssm_launch_result(hipError_t e);   // abi.hip: a learned-dynamics launch's HIP result as an ICEM_* code (+ message)
 int refresh_act_mag(icem_handle* h, const void* low, const void* high, hipStream_t st, bool force);   // abi.hip
 void ahead_destroy(icem_handle* h);
 void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx);

@@ -228,6 +228,21 @@ struct UpdateSmallArgs {
     int* idx_out;               // [K] indices into [pool | kept elites]
 };
 void launch_update_small(const UpdateSmallArgs& a, hipStream_t st);
+// ... for B problems in one launch (one workgroup each, args[n] in DEVICE memory), and -- finish -- with the MPC step's
+// epilogue behind the refit: shift of the new mean, reset of std (icem_shift's arithmetic), executed = elites[0, 0, :],
+// best_cost = elite_costs[0], both also as `result` [d + 1] (nullptr: not wanted).  hd <= UPDATE_FINISH_MAX_HD.
+constexpr int UPDATE_FINISH_MAX_HD = 256;
+struct UpdateFinishArgs {
+    UpdateSmallArgs u;
+    int d;
+    float init_std;
+    const float* low;
+    const float* high;
+    float* executed;
+    float* best_cost;
+    float* result;
+};
+void launch_update_small_batch(const UpdateFinishArgs* args_dev, int n, bool finish, hipStream_t st);
 // sorted top-K of a small f32 cost array in one launch (icem_topk_sorted's fast path)
 bool topk_small_ok(int n, int K);
 void launch_topk_small(const float* costs, int n, int K, float* out_c, int* out_i, hipStream_t st);
@@ -457,6 +472,16 @@ inline void batch_form(const HnArgs& a, void* dst) {
     g.A = a.A, g.B = a.B, g.lda = a.lda, g.ldb = a.ldb, g.wc = a.wc, g.cs = a.cs;
 }
 // the batched launches: args[n] in DEVICE memory (the problems' keys are equal: plan.hip checked)
+// the learned-dynamics step's sampler (icem_plan_step_learned*): problem p draws args[p].n rows (ragged; n_max = the largest),
+// rng_rounds 10, any horizon fast_sample_supported admits; og.dst != nullptr: problem p's observation og.src[p] [og.width]
+// is also copied to og.dst + p * og.width
+struct ObsGather {
+    const float* src[ICEM_MAX_BATCH];
+    float* dst;
+    int width;
+};
+void launch_sample_learned(int h, int d, int n_max, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n,
+                           hipStream_t st);
 void launch_sample_batch(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_sample_merge_batch(const LaunchKey& key, const FastSampleMergeArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_rollout_hn_batch(const LaunchKey& key, const HnArgs* args_dev, int n, hipStream_t st);

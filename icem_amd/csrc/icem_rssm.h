@@ -49,6 +49,7 @@ hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned s
 // one a launch of its problem alone gives, bit for bit.  tiles = the sum of the problems' tile counts.
 int rssm_batch_tiles(int n_problems, const int* rows);   // (-1: more than the staging bookkeeping could ever hold)
 bool rssm_split_batch_ok(int tiles, int horizon);
+hipError_t rssm_split_prepare(int tiles, int horizon, hipStream_t st);   // staging + status check of such a launch, no kernel
 hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int cost_mode, const unsigned short* params,
                                    const float* obs0, const float* actions, float* costs, hipStream_t st);
 }  // namespace icem

@@ -769,6 +769,14 @@ Arrangement arrangement(int tiles) {
 }
 }  // namespace
 
+// what a launch of `tiles` tiles would do in front of its kernel, without the kernel: the caller learns of a timed-out wait
+// (hipErrorLaunchTimeOut: flags reset, nothing launched) or a capture that forbids growing BEFORE it launches anything else
+hipError_t rssm_split_prepare(int tiles, int horizon, hipStream_t st) {
+    std::unique_lock<std::mutex> lk;
+    const Staging* sg = nullptr;
+    return staging_for(tiles, horizon, st, lk, sg);
+}
+
 hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
                              const float* actions, float* costs, hipStream_t st) {
     const int tiles = (n + 15) / 16;

@@ -259,9 +259,14 @@ __global__ __launch_bounds__(1024) void topk_small_kernel(const float* costs, in
 // over the pool's costs and the kept elites' (icem.py:143-145: appended behind the pool, index n + e), the gather of the
 // K elite rows from pool / kept elites, the refit (refit.h: the arithmetic of gather_refit_kernel).  Phase 1 + 2 are
 // topk_small_kernel's; the selection lands in LDS (wg_merge_emit's list 0 of 1, through a generic pointer).
-__global__ __launch_bounds__(1024) void update_small_kernel(UpdateSmallArgs a) {
+// (the body of update_small_kernel and of update_small_batch_kernel: one device function.  FINISH: the step's epilogue behind
+//  the refit -- the new mean goes through LDS and leaves shifted, std is reset (shift_kernel's arithmetic, icem.py:167-175),
+//  executed = elites[0, 0, :], best_cost = elite_costs[0], and both once more as the problem's row of `results`.)
+template <bool FINISH>
+__device__ __forceinline__ void update_small_body(const UpdateSmallArgs& a, const UpdateFinishArgs* f) {
     __shared__ unsigned long long wg_keys[2][16][32];
     __shared__ unsigned long long sel[32];
+    __shared__ float shifted[FINISH ? UPDATE_FINISH_MAX_HD : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_all = a.n + a.n_keep;
     unsigned long long run = KEY_SENTINEL;
@@ -297,15 +302,55 @@ __global__ __launch_bounds__(1024) void update_small_kernel(UpdateSmallArgs a) {
         for (int r = 0; r < a.K; ++r) a.elites_out[(size_t)r * a.hd + e] = row(r)[e];
         float nm, ns;
         refit_element<float>(a.K, a.alpha, a.mean[e], a.std[e], [&](int r) { return row(r)[e]; }, nm, ns);
-        a.mean[e] = nm;
-        a.std[e] = ns;
+        if (FINISH) {
+            shifted[e] = nm;
+        } else {
+            a.mean[e] = nm;
+            a.std[e] = ns;
+        }
     }
+    if (FINISH) {
+        __syncthreads();
+        const int d = f->d;
+        for (int e = tid; e < a.hd; e += 1024) {
+            const int j = e % d;
+            a.mean[e] = (e + d < a.hd) ? shifted[e + d] : shifted[e];
+            a.std[e] = (f->high[j] - f->low[j]) / 2.f * f->init_std;
+        }
+        if (tid < d) {
+            const float x = row(0)[tid];
+            f->executed[tid] = x;
+            if (f->result) f->result[tid] = x;
+        }
+        if (tid == 0) {
+            const float c = key_cost(sel[0]);
+            f->best_cost[0] = c;
+            if (f->result) f->result[d] = c;
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void update_small_kernel(UpdateSmallArgs a) {
+    update_small_body<false>(a, nullptr);
+}
+
+// B problems in one launch (icem_plan_step_learned*): one workgroup per problem, its argument block in device memory; the
+// step's last update carries the epilogue
+template <bool FINISH>
+__global__ __launch_bounds__(1024) void update_small_batch_kernel(const UpdateFinishArgs* __restrict__ args) {
+    const UpdateFinishArgs g = args[blockIdx.x];
+    update_small_body<FINISH>(g.u, &g);
 }
 
 }  // namespace
 
 void launch_update_small(const UpdateSmallArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(update_small_kernel, dim3(1), dim3(1024), 0, st, a);
+}
+
+void launch_update_small_batch(const UpdateFinishArgs* args_dev, int n, bool finish, hipStream_t st) {
+    if (finish) hipLaunchKernelGGL(update_small_batch_kernel<true>, dim3(n), dim3(1024), 0, st, args_dev);
+    else hipLaunchKernelGGL(update_small_batch_kernel<false>, dim3(n), dim3(1024), 0, st, args_dev);
 }
 
 bool topk_small_ok(int n, int K) { return n >= 1 && n <= 16384 && K >= 1 && K <= 32; }

@@ -118,6 +118,21 @@ __global__ __launch_bounds__(SWG) void sample_folded_batch_kernel(const FastSamp
     sample_folded_body<H, ROUNDS>(s);
 }
 
+// ... and for the learned-dynamics step (icem_plan_step_learned*, learned_step.hip), at every horizon of the folded sampler:
+// ragged row counts (the grid's x extent is the largest problem's; surplus workgroups exit), and workgroup 0 of a problem also
+// copies its observation into the batch's contiguous [n, 230] array (og.dst; nullptr: a step of one problem reads its own)
+template <int H, int ROUNDS>
+__global__ __launch_bounds__(SWG) void sample_folded_learned_kernel(const FastSampleArgs* __restrict__ args, BatchBases bases, ObsGather og) {
+    FastSampleArgs s = from_device(args[blockIdx.y]);
+    if (og.dst != nullptr && blockIdx.x == 0) {
+        const float* src = og.src[blockIdx.y];
+        for (int e = threadIdx.x; e < og.width; e += SWG) og.dst[(size_t)blockIdx.y * og.width + e] = src[e];
+    }
+    if ((int)blockIdx.x * (SWG / s.d) >= s.n) return;
+    add_base64(s.off_lo, s.off_hi, bases.v[blockIdx.y]);
+    sample_folded_body<H, ROUNDS>(s);
+}
+
 // -------------------------------------------------------------------------------------------------
 // K1 without the distribution ("noise ahead"): the raw colored samples y [n, h, d] of one sampling call
 // -------------------------------------------------------------------------------------------------
@@ -439,6 +454,20 @@ void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int roun
         ICEM_FAST_HORIZONS(X)
 #undef X
     });
+}
+
+// (args[p].n_shift == 0: the learned step's shifted elites are a launch of their own, gk_shift_sample_batch)
+void launch_sample_learned(int h, int d, int n_max, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n,
+                           hipStream_t st) {
+    const int tpw = SWG / d;
+#define X(HH)                                                                                                                          \
+    if (h == HH) {                                                                                                                     \
+        hipLaunchKernelGGL((sample_folded_learned_kernel<HH, 10>), dim3((n_max + tpw - 1) / tpw, n), dim3(SWG), sample_lds(h, d), st,  \
+                           args_dev, bases, og);                                                                                       \
+        return;                                                                                                                        \
+    }
+    ICEM_FAST_HORIZONS(X)
+#undef X
 }
 
 void launch_sample_batch(const LaunchKey& k, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {

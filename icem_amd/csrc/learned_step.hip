@@ -1,0 +1,279 @@
+// learned_step.hip -- the MPC step of the learned-dynamics configuration (BASELINE configs[4]: the declared RSSM) as one C
+// call, for one planner or for B planners at once: icem_plan_step_learned / icem_plan_step_learned_batch.
+//
+// The step is the stage-wise loop of the controllers (icem_amd/controllers.py::_get_action_stagewise + _stage_finish) with
+// every stage ONE launch for all problems:
+//   sample   sample_folded_learned_kernel (k_sample.hip): icem_sample_clip's folded sampler, blockIdx.y = the problem
+//   shift    iteration 0 of a step > 0: shift_sample_batch_kernel (generic_kernels.hip) -- the copy of elites[e, 1:, :] and
+//            icem_sample_clip(t_begin = h - 1)'s draw of the last action, the operator's own arithmetic
+//   rollout  launch_rssm_rollout (one problem) / launch_rssm_split_batch (several)
+//   update   update_small_batch_kernel (k_merge.hip): icem_update_distribution's body, one workgroup per problem; the last
+//            one carries the epilogue (icem_shift's arithmetic, executed, best_cost, the results row)
+// i.e. 3 launches per iteration, + 1 in the steps that shift elites.  The argument blocks live in a device array with the
+// step's first handle, stream offsets relative to each problem's base (BatchBases), uploaded only when a byte changed
+// (icem_plan_step_batch's scheme): the steady state uploads nothing.  A batch's rows sit back to back in a pool of that
+// handle's (the batched rollout wants them contiguous); one problem alone uses its own actions / costs buffers.
+#include "host_common.h"
+#include "icem_rssm.h"
+
+using namespace icem;
+
+namespace {
+
+struct LearnedCtx {
+    static constexpr int SLOTS = 2;          // by the first handle's step parity: the elite halves alternate per iteration
+    void* dev[SLOTS] = {nullptr, nullptr};
+    size_t cap[SLOTS] = {0, 0};
+    std::vector<unsigned char> shadow[SLOTS];
+    float* pool = nullptr;                   // a batch's [rows, hd] actions | [rows] costs | [n, 230] observations
+    size_t pool_rows = 0;
+    int pool_n = 0;
+    int* idx = nullptr;                      // [ICEM_MAX_BATCH, ICEM_MAX_ELITES]: the updates' index output (not kept)
+};
+
+void learned_ctx_free(void* p) {
+    LearnedCtx* c = (LearnedCtx*)p;
+    if (!c) return;
+    for (void* d : c->dev)
+        if (d) (void)hipFree(d);
+    if (c->pool) (void)hipFree(c->pool);
+    if (c->idx) (void)hipFree(c->idx);
+    delete c;
+}
+
+int max_rows(const icem_handle* h) {
+    int m = 0;
+    for (size_t it = 0; it < h->pop.size(); ++it) m = std::max(m, h->pop[it] + (it == 0 ? std::max(0, h->n_reuse) : 0));
+    return m;
+}
+
+// the per-handle part of "who is served" (nullptr: this handle is)
+const char* learned_unserved(const icem_handle* h) {
+    const icem_config& c = h->cfg;
+    if (opt_i(OPT_LEARNED_STEP) == 0) return "option learned_step is 0";
+    if (c.dtype != ICEM_F32) return "dtype f32 only";
+    if (c.world != 1) return "world must be 1";
+    if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
+    if (!h->use_fast) return "the handle's fast path is off";
+    if (h->profiling) return "per-kernel profiling is per launch of one handle: switch it off";
+    if (!fast_sample_supported(c.horizon, c.act_dim) || c.horizon > 32 || h->hd > UPDATE_FINISH_MAX_HD)
+        return "the horizon is outside the folded sampler's list (30, 12, 13, 10)";
+    if (c.rng_rounds != 10) return "the batched sampler is compiled for the default generator (rng_rounds 10)";
+    if ((int)h->pop.size() != c.opt_iters || c.opt_iters < 1) return "opt_iters";
+    if (!topk_small_ok(max_rows(h) + std::max(0, h->n_reuse), c.num_elites)) return "the one-launch update does not take this pool / num_elites (<= 16384 candidates, <= 32 elites)";
+    if (!rssm_split_ok(max_rows(h), c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
+    return nullptr;
+}
+
+bool same_config(const icem_config& a, const icem_config& r) {
+    return a.horizon == r.horizon && a.act_dim == r.act_dim && a.num_traj == r.num_traj && a.num_elites == r.num_elites &&
+           a.elites_size == r.elites_size && a.opt_iters == r.opt_iters && a.cost_mode == r.cost_mode &&
+           a.use_mean_actions == r.use_mean_actions && a.keep_previous_elites == r.keep_previous_elites &&
+           a.shift_elites == r.shift_elites && a.factor_decrease == r.factor_decrease && a.fraction_reused == r.fraction_reused &&
+           a.rng_rounds == r.rng_rounds && a.dtype == r.dtype && a.world == r.world && a.rank == r.rank && a.alpha == r.alpha &&
+           a.init_std == r.init_std && a.noise_beta == r.noise_beta;
+}
+
+int shifted(const icem_handle* h, int mpc_step, int it) {
+    return (it == 0 && h->cfg.shift_elites && mpc_step > 0 && h->n_reuse > 0) ? h->n_reuse : 0;
+}
+
+size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
+                 void* results, hipStream_t st) {
+    icem_handle* h0 = handles[0];
+    const icem_config& c = h0->cfg;
+    const int H = c.horizon, d = c.act_dim, hd = h0->hd, K = c.num_elites, iters = c.opt_iters, n_reuse = std::max(0, h0->n_reuse);
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (handles[i] == handles[j]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: the same handle twice in one batch");
+    for (int i = 0; i < n; ++i) {
+        if (!same_config(handles[i]->cfg, c) || handles[i]->pop != h0->pop || handles[i]->n_reuse != h0->n_reuse)
+            return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: the handles must share one configuration (everything but the seed)");
+        if (steps[i] < 0) return fail(ICEM_E_INVALID, "icem_plan_step_learned: negative mpc_step");
+        const icem_plan_buffers& b = buffers[i];
+        if (!b.mean || !b.std || !b.low || !b.high || !b.obs0 || !b.actions || !b.costs || !b.elites || !b.executed || !b.best_cost)
+            return fail(ICEM_E_INVALID, "icem_plan_step_learned: null buffer (mean, std, low, high, obs0, actions, costs, elites, executed, best_cost)");
+    }
+    for (int i = 0; i < n; ++i) {
+        if (const char* why = learned_unserved(handles[i])) return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_learned: ") + why);
+        const icem_plan_buffers& b = buffers[i];
+        if (b.z_r || b.z_i || b.z_r_shift || b.z_i_shift) return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned: external noise (z_*) is not served");
+    }
+    // rows of every problem and iteration; the largest launch's tiles
+    std::vector<int> rows((size_t)iters * n);
+    int tiles_max = 0, shift_max = 0;
+    size_t rows_max = 0;
+    for (int it = 0; it < iters; ++it) {
+        size_t all = 0;
+        for (int p = 0; p < n; ++p) {
+            rows[(size_t)it * n + p] = h0->pop[it] + shifted(handles[p], steps[p], it);
+            all += rows[(size_t)it * n + p];
+            shift_max = std::max(shift_max, shifted(handles[p], steps[p], it));
+        }
+        const int tiles = rssm_batch_tiles(n, &rows[(size_t)it * n]);
+        if (tiles < 0 || !rssm_split_batch_ok(tiles, H))
+            return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_batch: the batch's tiles (the sum over the problems of ceil(rows / 16)) exceed "
+                                            "the split launch's limit; nothing was launched");
+        tiles_max = std::max(tiles_max, tiles);
+        rows_max = std::max(rows_max, all);
+    }
+    // the rollout's staging area and its host-visible status word, BEFORE the first launch: a refused step leaves everything as it was
+    if (int rc = rssm_launch_result(rssm_split_prepare(tiles_max, H, st))) return rc;
+    // ---- the step's own memory (first call, or a larger batch than before) ----
+    LearnedCtx* ctx = (LearnedCtx*)h0->learned_ctx;
+    if (!ctx) {
+        ctx = new LearnedCtx();
+        h0->learned_ctx = ctx;
+        h0->learned_ctx_free = learned_ctx_free;
+    }
+    if (!ctx->idx) ICEM_HIP_TRY(hipMalloc((void**)&ctx->idx, (size_t)ICEM_MAX_BATCH * ICEM_MAX_ELITES * sizeof(int)));
+    const size_t cap_rows = (size_t)n * (size_t)max_rows(h0);   // (what any mix of steps of this batch size needs)
+    if (n > 1 && (ctx->pool_rows < cap_rows || ctx->pool_n < n)) {
+        if (ctx->pool) {
+            ICEM_HIP_TRY(hipStreamSynchronize(st));   // (an earlier step's launches may still use the old pool)
+            (void)hipFree(ctx->pool);
+            ctx->pool = nullptr;
+            ctx->pool_rows = 0;
+        }
+        const size_t rws = std::max(cap_rows, ctx->pool_rows);
+        const int pn = std::max(n, ctx->pool_n);
+        ICEM_HIP_TRY(hipMalloc((void**)&ctx->pool, (rws * (size_t)(hd + 1) + (size_t)pn * (rssm::DET + rssm::STOCH)) * sizeof(float)));
+        ctx->pool_rows = rws;
+        ctx->pool_n = pn;
+    }
+    float* pool_a = ctx->pool;
+    float* pool_c = ctx->pool ? ctx->pool + ctx->pool_rows * (size_t)hd : nullptr;
+    float* pool_o = ctx->pool ? pool_c + ctx->pool_rows : nullptr;
+    // ---- argument blocks: per iteration [sample x n | update x n], then [shift x n] ----
+    const size_t sb = sizeof(FastSampleArgs), ub = sizeof(UpdateFinishArgs), hb = gk_shift_sample_block_bytes();
+    const size_t per_it = padded(sb * n) + padded(ub * n);
+    const size_t bytes = per_it * iters + padded(hb * n);
+    std::vector<unsigned char> blob(bytes, 0);
+    BatchBases bases{};
+    for (int p = 0; p < n; ++p) bases.v[p] = (handles[p]->episode << 32) + (uint64_t)steps[p] * (uint64_t)(iters + 1);
+    for (int it = 0; it < iters; ++it) {
+        size_t row0 = 0;
+        for (int p = 0; p < n; ++p) {
+            const icem_handle* h = handles[p];
+            const icem_plan_buffers& b = buffers[p];
+            const int n_it = h0->pop[it], n_shift = shifted(h, steps[p], it), n_rows = n_it + n_shift;
+            float* acts = n == 1 ? (float*)b.actions : pool_a + row0 * hd;
+            float* csts = n == 1 ? (float*)b.costs : pool_c + row0;
+            row0 += n_rows;
+            // iteration `it` of step s writes elite half (s * iters + it + 1) & 1 and reads the other one
+            const int w = (int)(((long long)steps[p] * iters + it + 1) & 1), r = w ^ 1;
+            float* el = (float*)b.elites;
+            float* el_w = el + (size_t)w * K * hd;
+            const float* el_r = el + (size_t)r * K * hd;
+            float* ec_w = el + (size_t)2 * K * hd + (size_t)w * K;
+            const float* ec_r = el + (size_t)2 * K * hd + (size_t)r * K;
+            FastSampleArgs& s = *(FastSampleArgs*)(blob.data() + per_it * it + sb * p);
+            s.n = n_it, s.h = H, s.d = d, s.first_index = 0;
+            s.W = (const float*)h->W_dev;
+            s.mean = (const float*)b.mean, s.std = (const float*)b.std, s.low = (const float*)b.low, s.high = (const float*)b.high;
+            s.seed_lo = (uint32_t)h->cfg.seed, s.seed_hi = (uint32_t)(h->cfg.seed >> 32);
+            s.off_lo = (uint32_t)it, s.off_hi = 0;   // (relative to bases.v[p])
+            s.row0_mean = (c.use_mean_actions && it == iters - 1) ? 1 : 0;
+            s.out = acts;
+            s.white = c.noise_beta <= 0 ? 1 : 0;
+            if (it == 0)
+                gk_shift_sample_block(h, n_shift, b.mean, b.std, b.low, b.high, (uint64_t)iters, el_r, acts + (size_t)n_it * hd,
+                                      blob.data() + per_it * iters + hb * p);
+            UpdateFinishArgs& u = *(UpdateFinishArgs*)(blob.data() + per_it * it + padded(sb * n) + ub * p);
+            const bool keep = it > 0 && c.keep_previous_elites && n_reuse > 0;
+            u.u.costs = csts, u.u.pool = acts;
+            u.u.keep_costs = keep ? ec_r : nullptr, u.u.keep_actions = keep ? el_r : nullptr;
+            u.u.n = n_rows, u.u.n_keep = keep ? n_reuse : 0, u.u.K = K, u.u.hd = hd;
+            u.u.alpha = (float)c.alpha;
+            u.u.mean = (float*)b.mean, u.u.std = (float*)b.std;
+            u.u.elites_out = el_w, u.u.elite_costs_out = ec_w;
+            u.u.idx_out = ctx->idx + (size_t)p * ICEM_MAX_ELITES;
+            if (it == iters - 1) {
+                u.d = d;
+                u.init_std = (float)c.init_std;
+                u.low = (const float*)b.low, u.high = (const float*)b.high;
+                u.executed = (float*)b.executed, u.best_cost = (float*)b.best_cost;
+                u.result = results ? (float*)results + (size_t)p * (d + 1) : nullptr;
+            }
+        }
+    }
+    const int slot = steps[0] & 1;
+    if (ctx->cap[slot] < bytes) {
+        if (ctx->dev[slot]) {
+            ICEM_HIP_TRY(hipStreamSynchronize(st));   // (launches of an earlier step may still read the old array)
+            (void)hipFree(ctx->dev[slot]);
+        }
+        ctx->dev[slot] = nullptr;
+        ctx->cap[slot] = 0;
+        ctx->shadow[slot].clear();
+        // (room for the largest batch: a batch that grows later allocates nothing)
+        const size_t room = (padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH)) * iters + padded(hb * ICEM_MAX_BATCH);
+        ICEM_HIP_TRY(hipMalloc(&ctx->dev[slot], room));
+        ctx->cap[slot] = room;
+    }
+    if (ctx->shadow[slot].size() != bytes || std::memcmp(ctx->shadow[slot].data(), blob.data(), bytes) != 0) {
+        // (pageable source: the runtime stages it before returning; ordered behind the earlier steps' launches on `st`)
+        ICEM_HIP_TRY(hipMemcpyAsync(ctx->dev[slot], blob.data(), bytes, hipMemcpyHostToDevice, st));
+        ctx->shadow[slot] = blob;
+        ++h0->batch_uploads;
+    }
+    // ---- the launches ----
+    const unsigned char* dev = (const unsigned char*)ctx->dev[slot];
+    long long launches = 0;
+    h0->learned_launches = 0;
+    for (int it = 0; it < iters; ++it) {
+        ObsGather og{};
+        if (n > 1 && it == 0) {
+            for (int p = 0; p < n; ++p) og.src[p] = (const float*)buffers[p].obs0;
+            og.dst = pool_o;
+            og.width = rssm::DET + rssm::STOCH;
+        }
+        launch_sample_learned(H, d, h0->pop[it], (const FastSampleArgs*)(dev + per_it * it), bases, og, n, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+        if (it == 0 && shift_max > 0) {
+            if (int rc = gk_shift_sample_batch(h0, n, shift_max, dev + per_it * iters, bases, st)) return rc;
+            ++launches;
+        }
+        hipError_t e;
+        if (n == 1)
+            e = launch_rssm_rollout(rows[it], H, c.cost_mode, (const unsigned short*)params, (const float*)buffers[0].obs0,
+                                    (const float*)buffers[0].actions, (float*)buffers[0].costs, st);
+        else
+            e = launch_rssm_split_batch(n, &rows[(size_t)it * n], H, c.cost_mode, (const unsigned short*)params, pool_o, pool_a, pool_c, st);
+        if (int rc = rssm_launch_result(e)) return rc;
+        ++launches;
+        launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + padded(sb * n)), n, it == iters - 1, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    h0->learned_launches = launches;
+    return ICEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icem_plan_step_learned_ok(const icem_handle* h) { return (h && learned_unserved(h) == nullptr) ? 1 : 0; }
+
+int icem_plan_step_learned_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const void* params,
+                                 const int32_t* mpc_steps_host, void* results, void* stream) {
+    if (!handles || !buffers || !params || !mpc_steps_host || n < 1 || n > ICEM_MAX_BATCH)
+        return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: null argument / n outside [1, 32]");
+    for (int i = 0; i < n; ++i)
+        if (!handles[i]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: null handle");
+    return learned_step(handles, n, buffers, params, mpc_steps_host, results, (hipStream_t)stream);
+}
+
+int icem_plan_step_learned(icem_handle* h, const icem_plan_buffers* b, const void* params, int32_t mpc_step, void* stream) {
+    if (!h || !b || !params) return fail(ICEM_E_INVALID, "icem_plan_step_learned: null handle, buffers or params");
+    return learned_step(&h, 1, b, params, &mpc_step, nullptr, (hipStream_t)stream);
+}
+
+int64_t icem_learned_step_launches(const icem_handle* h) { return h ? (int64_t)h->learned_launches : 0; }
+
+}  // extern "C"

@@ -477,6 +477,67 @@ class IcemPlanner:
     def batch_uploads(self) -> int:
         return int(self.lib.icem_batch_uploads(self._h))
 
+    # ------------------------------------------------------------------ the learned-dynamics step (declared RSSM)
+    def learned_step_ok(self) -> bool:
+        """Does ``icem_plan_step_learned`` serve THIS handle?  (f32, one GPU, six action dimensions, a horizon of the folded
+        sampler, the default generator, option ``learned_step`` on ...: asked of the handle.)"""
+        return bool(self.lib.icem_plan_step_learned_ok(self._h))
+
+    @property
+    def learned_step_launches(self) -> int:
+        """Kernel launches of the last learned step this planner led (``icem_learned_step_launches``)."""
+        return int(self.lib.icem_learned_step_launches(self._h))
+
+    def _learned_buffers(self, obs0_ptr) -> "L.IcemPlanBuffersC":
+        self._ensure_buffers(learned=True)
+        cb = L.IcemPlanBuffersC.from_buffer_copy(self._cb)
+        cb.mean, cb.std = self.mean.data_ptr(), self.std.data_ptr()   # (the controller owns them between episodes)
+        cb.obs0 = obs0_ptr
+        cb.z_r = cb.z_i = cb.z_r_shift = cb.z_i_shift = None
+        return cb
+
+    def plan_step_learned(self, model, obs) -> torch.Tensor:
+        """One MPC step through ``model`` (a ``DeviceRSSMModel``: its packed ``params``) as ``icem_plan_step_learned``: every
+        CEM iteration's sampling, rollout and update and the step's epilogue inside the library, no host synchronisation.
+        ``obs``: the observation ``[230]``.  Afterwards ``mean`` / ``std`` are shifted, :meth:`current_elites` is the step's
+        elite set, ``executed`` / ``best_cost`` hold the step's result.  Returns ``executed`` (device tensor, no host sync).
+        Raises ``IcemError`` (``ICEM_E_UNSUPPORTED``) before anything runs where :meth:`learned_step_ok` is false."""
+        self._ensure_buffers(learned=True)
+        ob = np.ascontiguousarray(obs, dtype=np.float32).reshape(-1)
+        if ob.shape != (L.RSSM_OBS_DIM,):
+            raise ValueError(f"expected an observation of shape ({L.RSSM_OBS_DIM},)")
+        self.obs_rssm.copy_(torch.as_tensor(ob), non_blocking=False)
+        cb = self._learned_buffers(self.obs_rssm.data_ptr())
+        L.check(self.lib.icem_plan_step_learned(self._h, C.byref(cb), C.c_void_p(model.params.data_ptr()), self.mpc_step,
+                                                self._stream()))
+        self.mpc_step += 1
+        return self.executed
+
+    @staticmethod
+    def plan_step_learned_batch(planners: Sequence["IcemPlanner"], model, observations) -> torch.Tensor:
+        """One MPC step of every planner of ``planners`` (one configuration; seeds, episodes, step counts and observations
+        of their own) through ``model`` as ``icem_plan_step_learned_batch``: every stage one launch for all of them.  Each
+        planner's buffers afterwards are bit for bit those of its own :meth:`plan_step_learned`.  Returns the results
+        ``[B, d + 1]`` (executed action | best cost per planner; device tensor, no host sync).  Raises ``IcemError`` before
+        anything runs -- and before any planner has advanced -- where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_learned_batch(None, 0, None, None, None, None, None))
+        p0 = pls[0]
+        obs = np.ascontiguousarray(np.asarray(observations, dtype=np.float32).reshape(n, -1))
+        if obs.shape[1] != L.RSSM_OBS_DIM:
+            raise ValueError(f"expected observations of shape ({n}, {L.RSSM_OBS_DIM})")
+        obs_dev = torch.as_tensor(obs, device=p0.device)   # one host-to-device copy for the whole batch
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemPlanBuffersC * n)(*[pl._learned_buffers(obs_dev[i].data_ptr()) for i, pl in enumerate(pls)])
+        steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
+        results = torch.empty((n, p0.d + 1), dtype=torch.float32, device=p0.device)
+        L.check(p0.lib.icem_plan_step_learned_batch(hs, n, bs, C.c_void_p(model.params.data_ptr()), steps, _ptr(results), p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        return results
+
     # ------------------------------------------------------------------ in-library elite exchange (world > 1)
     def connect_exchange(self, group=None):
         """Set up the in-library elite exchange between the ranks' processes (``icem_exchange_create`` /
@@ -658,10 +719,14 @@ class IcemPlanner:
             self._deferral = on
 
     # ------------------------------------------------------------------ fused MPC step
-    def _ensure_buffers(self):
+    def _ensure_buffers(self, learned: bool = False):
+        """``learned``: for the learned-dynamics step, which needs no built-in model (``obs0`` then stays empty; the step's
+        observation lives in ``obs_rssm``, 230 f32)."""
+        if learned and getattr(self, "obs_rssm", None) is None:
+            self.obs_rssm = torch.zeros((L.RSSM_OBS_DIM,), dtype=torch.float32, device=self.device)
         if self._bufs is not None:
             return
-        if self.obs_dim == 0:
+        if self.obs_dim == 0 and not learned:
             raise RuntimeError("set_model()/set_cost() must be called before planning")
         names = ["mean", "std", "low", "high", "obs0", "actions", "costs", "elites", "records", "workspace",
                  "executed", "best_cost"]

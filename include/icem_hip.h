@@ -3,6 +3,8 @@
  *
  * This is the drop-in boundary for ONE hot path of martius-lab/iCEM: everything inside the
  * `for i in range(opt_iter)` loop of MpcICem.get_action (reference icem/controllers/icem.py:106-189).
+ * The whole loop is one call for the built-in models (icem_plan_step, icem_plan_step_batch, icem_get_action) and for the
+ * learned-dynamics model (icem_plan_step_learned, icem_plan_step_learned_batch); its stages are calls of their own too.
  * The reference is pure Python/NumPy and has no FFI; each entry point below names the reference
  * call site (file:line, relative to /root/reference) whose arithmetic it replaces.  The binding a
  * reference maintainer would add is a ctypes stub -- see INTEGRATION.md.
@@ -31,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ICEM_ABI_VERSION 6 /* 6: icem_step_status removed (icem_rssm_rollout_cost_batch was added without a new number: an added symbol breaks no caller); 5: ICEM_TILE_AUTO serves the fp16 planes only where no state can leave their range (icem_tile_growth), icem_nonfinite_costs / ICEM_E_RANGE, icem_set_option (the library reads no environment variable), icem_plan_step_batch; 2: icem_build_hash, icem_allgather_elites / icem_rccl_*, noise-ahead planning; ICEM_MAX_OBS_DIM 384; 3: icem_set_tile_arith; 4: icem_set_wide_arith (default AUTO), ICEM_TILE_AUTO = planes at every population */
+#define ICEM_ABI_VERSION 6 /* 6: icem_step_status removed (icem_rssm_rollout_cost_batch and the learned-dynamics step -- icem_plan_step_learned, icem_plan_step_learned_batch, icem_plan_step_learned_ok, icem_learned_step_launches -- were added without a new number: an added symbol breaks no caller); 5: ICEM_TILE_AUTO serves the fp16 planes only where no state can leave their range (icem_tile_growth), icem_nonfinite_costs / ICEM_E_RANGE, icem_set_option (the library reads no environment variable), icem_plan_step_batch; 2: icem_build_hash, icem_allgather_elites / icem_rccl_*, noise-ahead planning; ICEM_MAX_OBS_DIM 384; 3: icem_set_tile_arith; 4: icem_set_wide_arith (default AUTO), ICEM_TILE_AUTO = planes at every population */
 
 enum { ICEM_F32 = 0, ICEM_F64 = 1 };
 enum { ICEM_COST_SUM = 0, ICEM_COST_BEST = 1, ICEM_COST_FINAL = 2 }; /* abstract_controller.py:82-87 */
@@ -417,6 +419,41 @@ int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step,
  * copy on `stream` when the argument blocks changed (the first steps: the blocks of step s are those of step s - 6). */
 int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream);
 int64_t icem_batch_uploads(const icem_handle* h); /* how often handles[0]'s argument array was (re)written (measurement) */
+
+/* The MPC step of the learned-dynamics configuration (the declared RSSM of the learned-dynamics rollout below; BASELINE
+ * configs[4]) as ONE call, for one planner or for n planners at once: the loop a caller would otherwise drive operator by
+ * operator.  Per CEM iteration i of MPC step s: sample population_sizes[i] rows at stream offset
+ * (episode << 32) + s * (opt_iters + 1) + i (row 0 = the mean on the last iteration under use_mean_actions); at i == 0, with
+ * shift_elites, s > 0 and n_reuse > 0, append the n_reuse shifted elites, their last action drawn at offset ... + opt_iters with
+ * the arithmetic of the sampling operator at t_begin = h - 1; roll all rows out through the RSSM under the handle's cost_mode; select the
+ * top K over [pool | kept elites] (kept for i > 0 under keep_previous_elites), gather, refit; behind the last iteration shift
+ * mean and std and write executed = elites[0, 0, :] and best_cost = elite_costs[0].  Every stage is one launch for all
+ * problems: 3 launches per iteration, one more in a step that shifts elites.
+ *   Buffers: b->obs0 is [ICEM_RSSM_OBS_DIM] f32 and the CALLER sizes it (the buffer-size query knows no model width for a
+ * handle without a built-in model); mean, std, low, high, actions, costs, elites, executed, best_cost as the fused step uses them
+ * (actions / costs are scratch; a batch scores its rows in a pool of handles[0]'s instead).  records, workspace: unused.
+ * A non-NULL z_*: ICEM_E_UNSUPPORTED.  Elite halves: iteration i of step s writes half (s * opt_iters + i + 1) & 1 of
+ * `elites` and reads the other one, so the current set behind step s is half ((s + 1) * opt_iters) & 1.
+ *   params: the packed parameter buffer of the learned-dynamics rollout, shared by all problems.  mpc_step is the caller's
+ * count since the last reset -- per problem in a batch (mpc_steps_host[n], host memory): a planner reset later than its peers
+ * has no shifted elites and fewer rows.  results (device, may be NULL): [n, act_dim + 1] f32, row p = problem p's executed
+ * action | best cost.
+ *   Served: f32, world == 1, act_dim == 6, the handle's fast path on, profiling off, rng_rounds 10, a horizon of the folded
+ * sampler (30, 12, 13, 10), at most 16 384 candidates and 32 elites per update, and all problems' 16-row tiles together within
+ * the split launch's limit; development option learned_step = 0 switches the entries off.  Anything else is
+ * ICEM_E_UNSUPPORTED; mismatched configurations (everything but the seed must agree), the same handle twice, n outside
+ * [1, 32] or a NULL argument ICEM_E_INVALID.  Whatever is refused is refused before anything is launched.  The staging,
+ * first-call-not-under-capture and ICEM_E_STATE rules of the learned-dynamics rollout apply; its host-visible status word is
+ * looked at BEFORE the step's first launch, so a step refused with ICEM_E_STATE has launched nothing.  No host
+ * synchronisation; no allocation after the first call of a batch size on a stream; one small host-to-device copy when the
+ * argument blocks changed (the first steps).  Each problem's outputs in a batch are bit for bit those of its own solo step;
+ * n == 1 is the solo entry. */
+#define ICEM_RSSM_OBS_DIM 230
+int icem_plan_step_learned_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
+int icem_plan_step_learned(icem_handle* h, const icem_plan_buffers* b, const void* params, int32_t mpc_step, void* stream);
+int icem_plan_step_learned_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const void* params,
+                                 const int32_t* mpc_steps_host, void* results, void* stream);
+int64_t icem_learned_step_launches(const icem_handle* h); /* kernel launches of the last learned step this handle led (handles[0]); measurement */
 
 /* Wide observations (32 < obs_dim <= 384; HumanoidStandup's o = 378, environments/mujoco.py:241-277): which matrix-pipe
  * arithmetic the rollout's model step (the GEMM of abstract_models.py:31-53's predict at this width) runs in.  The modes
