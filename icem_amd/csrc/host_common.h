@@ -1,7 +1,9 @@
 // host_common.h -- what the host-side translation units of libicem_hip.so share: the handle, error plumbing,
-// per-kernel timing scopes, and the launcher interfaces between them.
+// per-kernel timing scopes, the launcher interfaces between them, and what the batched steps of plan.hip and learned_step.hip
+// share (arg_array.h, admit_batch, call_base / shift_rows / elite_parity).
 //   generic_kernels.hip  the generic (f32 / f64, any shape) kernels + their launchers (gk_*)
 //   plan.hip             the fused MPC step: icem_plan_* / icem_get_action and the f32 throughput-path orchestration
+//   learned_step.hip     the learned-dynamics MPC step: icem_plan_step_learned*
 //   exchange.hip         the in-library elite exchange between GPUs (icem_exchange_*)
 //   abi.hip              handle life cycle and the stateless operators of include/icem_hip.h
 // Internal; not part of the public ABI.
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "../../include/icem_hip.h"
+#include "arg_array.h"
 #include "icem_fused.h"
 #include "options.h"
 
@@ -44,6 +47,22 @@ constexpr int WG = 256;          // 4 wavefronts of 64
 constexpr int TOPK_CHUNK = 1024; // costs per workgroup in the block-level top-k
 
 struct Exchange;  // exchange.hip
+
+// icem_plan_step_learned* (learned_step.hip): what the step keeps with its FIRST handle
+struct LearnedCtx {
+    // argument arrays by the first handle's step parity: the elite halves alternate per iteration.  Each has room for the
+    // largest batch: a batch that grows later allocates nothing
+    DeviceArgArray<2> args;
+    float* pool = nullptr;                   // a batch's [rows, hd] actions | [rows] costs | [n, 230] observations
+    size_t pool_rows = 0;
+    int pool_n = 0;
+    int* idx = nullptr;                      // [ICEM_MAX_BATCH, ICEM_MAX_ELITES]: the updates' index output (not kept)
+    long long launches = 0;                  // kernel launches of the last learned step this handle led
+    ~LearnedCtx() {
+        if (pool) (void)hipFree(pool);
+        if (idx) (void)hipFree(idx);
+    }
+};
 
 }  // namespace icem
 
@@ -187,14 +206,12 @@ struct icem_handle {
         int disabled = -1;                   // ICEM_NOISE_AHEAD (latched at first use)
         int min_rows = 0;                    // ICEM_NOISE_AHEAD_MIN_ROWS
     } ahead;
-    // icem_plan_step_batch (plan.hip): the device array of the batch's argument blocks lives with the batch's FIRST handle
-    void* batch_ctx = nullptr;
-    void (*batch_ctx_free)(void*) = nullptr;
-    unsigned long long batch_uploads = 0;   // how often that array was (re)written (steady state: never)
-    // icem_plan_step_learned* (learned_step.hip): argument arrays and the batch's contiguous pool live with the step's FIRST handle
-    void* learned_ctx = nullptr;
-    void (*learned_ctx_free)(void*) = nullptr;
-    long long learned_launches = 0;         // kernel launches of the last learned step this handle led
+    // icem_plan_step_batch (plan.hip): the device arrays of the batch's argument blocks live with the batch's FIRST handle.
+    // Six, by the MPC step modulo 6: the elite buffers ping-pong per ITERATION (with an odd iteration count every second
+    // step's blocks are the same again), the noise-ahead launches rotate three pools per step: 2 x 3 steps close every cycle
+    icem::DeviceArgArray<6> batch_args;
+    unsigned long long batch_uploads = 0;   // how often a batched step of either kind (re)wrote its array (steady state: never)
+    icem::LearnedCtx learned;               // icem_plan_step_learned* (learned_step.hip)
     void* rccl_comm = nullptr;       // collective.hip: the RCCL communicator of icem_allgather_elites (world > 1)
     bool rccl_owned = false;         // ... created by icem_rccl_connect (destroyed with the handle) or adopted
 };
@@ -232,6 +249,53 @@ struct ProfScope {
 };
 
 inline int shard_chunk(int n_global, int world) { return (n_global + world - 1) / world; }
+
+// ---- rules that every path of a step must agree on (a controller may alternate icem_plan_step* and _learned*), each written once ----
+
+// Noise stream offset of an MPC step's sampling calls: episode in the high word (icem_set_episode; the reference's
+// np.random stream runs on across episodes, icem.py:73), sampling call number of the episode in the low one --
+// iteration `it` draws at call_base + it, the shifted elites at call_base + opt_iters.
+inline uint64_t call_base(const icem_handle* h, int mpc_step) {
+    return (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(h->cfg.opt_iters + 1);
+}
+
+// shifted elites, simulated at iteration 0 of every MPC step but the first (icem.py:131-137): rows behind the sampled ones.
+// (icem_create does not refuse a negative fraction_reused, which makes n_reuse negative: the launches then build no such
+// rows, while the lists merge's pool size and the batch's dry run have always taken the count as it is -- at_least_0 = false.)
+inline int shift_rows(const icem_handle* h, int mpc_step, int it, bool at_least_0 = true) {
+    if (it != 0 || !h->cfg.shift_elites || mpc_step <= 0) return 0;
+    return at_least_0 ? std::max(0, h->n_reuse) : h->n_reuse;
+}
+
+// which of the two elite buffers iteration `it` of step `mpc_step` reads (it writes the other): the global iteration's parity
+inline int elite_parity(const icem_handle* h, int mpc_step, int it) { return (int)(((long long)mpc_step * h->cfg.opt_iters + it) & 1); }
+
+// Do two handles share the configuration a batched step needs?  Every launch shape and template instantiation of a batch is
+// shared, so everything that decides one is compared (the populations and n_reuse are functions of these fields); seeds differ.
+// exact: the learned step also reads the cost mode, the momentum, the initial deviation and the noise exponent from its FIRST
+// handle, so there they must be equal too; the recorded steps of icem_plan_step_batch carry each handle's own.
+inline bool same_batch_config(const icem_config& a, const icem_config& r, bool exact) {
+    return a.horizon == r.horizon && a.act_dim == r.act_dim && a.num_traj == r.num_traj && a.num_elites == r.num_elites &&
+           a.elites_size == r.elites_size && a.opt_iters == r.opt_iters && a.use_mean_actions == r.use_mean_actions &&
+           a.keep_previous_elites == r.keep_previous_elites && a.shift_elites == r.shift_elites && a.factor_decrease == r.factor_decrease &&
+           a.fraction_reused == r.fraction_reused && a.rng_rounds == r.rng_rounds && a.dtype == r.dtype && a.world == r.world &&
+           (a.noise_beta > 0) == (r.noise_beta > 0) &&
+           (!exact || (a.cost_mode == r.cost_mode && a.rank == r.rank && a.alpha == r.alpha && a.init_std == r.init_std && a.noise_beta == r.noise_beta));
+}
+
+// Admission of a batch, before any handle is touched: n in [1, ICEM_MAX_BATCH], no null handle, no handle twice, one
+// configuration.  who: prefix of the first three messages; config_msg: the whole text of the fourth.
+inline int admit_batch(icem_handle* const* handles, int n, bool other_args, bool exact, const char* who, const char* config_msg) {
+    if (!handles || !other_args || n < 1 || n > ICEM_MAX_BATCH) return fail(ICEM_E_INVALID, std::string(who) + "null argument / n outside [1, 32]");
+    for (int i = 0; i < n; ++i)
+        if (!handles[i]) return fail(ICEM_E_INVALID, std::string(who) + "null handle");
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (handles[i] == handles[j]) return fail(ICEM_E_INVALID, std::string(who) + "the same handle twice in one batch");
+    for (int i = 1; i < n; ++i)
+        if (!same_batch_config(handles[i]->cfg, handles[0]->cfg, exact)) return fail(ICEM_E_INVALID, config_msg);
+    return ICEM_OK;
+}
 inline int topk_blocks(int n) { return (n + TOPK_CHUNK - 1) / TOPK_CHUNK; }
 
 template <typename T>

@@ -1,6 +1,7 @@
 // icem_fused.h -- interface between the host-side translation units (plan.hip, abi.hip) and the f32 throughput
 // kernels (k_sample.hip, k_rollout.hip, k_rollout_ahead.hip, k_rollout_wide.hip, k_iter_small.hip, k_merge.hip):
-// argument blocks and launchers.  Internal; not part of the public ABI.
+// argument blocks and launchers; the launch context of a step and what a batched step (icem_plan_step_batch, and for its sampler
+// icem_plan_step_learned*) needs of a launch family -- LAUNCH_FAMILIES, one row per family.  Internal; not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +60,7 @@ struct FastSampleArgs {
     const float* raw_src = nullptr;
 };
 bool fast_sample_supported(int h, int d);
+int sample_row_workgroups(int n, int d);   // workgroups of the folded sampler that draw n rows
 void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int rounds);
 
 // K2+K3 fast: rollout on the matrix pipe (v_mfma_f32_16x16x4, exact f32), cost on the VALU, and a
@@ -374,18 +376,6 @@ struct LaunchDesc {
     LaunchKey key;
     alignas(8) unsigned char block[sizeof(IterAheadArgs)];
 };
-static_assert(sizeof(FastIterArgs) <= sizeof(IterAheadArgs) && sizeof(MergeNoiseBatchArgs) <= sizeof(IterAheadArgs) &&
-              sizeof(FastSampleMergeArgs) <= sizeof(IterAheadArgs) && sizeof(HnArgs) <= sizeof(IterAheadArgs), "LaunchDesc::block");
-inline size_t launch_block_bytes(int family) {
-    switch (family) {
-        case LAUNCH_SAMPLE_ROLLOUT: return sizeof(FastIterArgs);
-        case LAUNCH_ITER_AHEAD: return sizeof(IterAheadArgs);
-        case LAUNCH_SAMPLE: return sizeof(FastSampleArgs);
-        case LAUNCH_SAMPLE_MERGE: return sizeof(FastSampleMergeArgs);
-        case LAUNCH_ROLLOUT_HN: return sizeof(HnArgs);
-        default: return sizeof(MergeNoiseBatchArgs);
-    }
-}
 struct LaunchRecorder {
     unsigned long long base = 0;        // noise stream base of the recorded problem's step (BatchBases::v)
     std::vector<LaunchDesc> launches;
@@ -472,22 +462,54 @@ inline void batch_form(const HnArgs& a, void* dst) {
     g.A = a.A, g.B = a.B, g.lda = a.lda, g.ldb = a.ldb, g.wc = a.wc, g.cs = a.cs;
 }
 // the batched launches: args[n] in DEVICE memory (the problems' keys are equal: plan.hip checked)
-// the learned-dynamics step's sampler (icem_plan_step_learned*): problem p draws args[p].n rows (ragged; n_max = the largest),
-// rng_rounds 10, any horizon fast_sample_supported admits; og.dst != nullptr: problem p's observation og.src[p] [og.width]
-// is also copied to og.dst + p * og.width
+// The batched sampler also serves the learned-dynamics step (icem_plan_step_learned*), which builds its key itself (family
+// LAUNCH_SAMPLE, form 10, wgs[0] for the LARGEST problem, wgs[1] = 0) at any horizon fast_sample_supported admits: problem p
+// draws args[p].n rows, surplus workgroups exit -- ragged row counts require n_shift == 0 in every block.  og.dst != nullptr:
+// problem p's observation og.src[p] [og.width] is also copied to og.dst + p * og.width
 struct ObsGather {
     const float* src[ICEM_MAX_BATCH];
     float* dst;
     int width;
 };
-void launch_sample_learned(int h, int d, int n_max, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n,
-                           hipStream_t st);
-void launch_sample_batch(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_sample_batch(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n, hipStream_t st);
 void launch_sample_merge_batch(const LaunchKey& key, const FastSampleMergeArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
-void launch_rollout_hn_batch(const LaunchKey& key, const HnArgs* args_dev, int n, hipStream_t st);
+void launch_rollout_hn_batch(const LaunchKey& key, const HnArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);   // (draws nothing: bases unused)
 void launch_sample_rollout_batch(const LaunchKey& key, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_merge_batch(const LaunchKey& key, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_iter_ahead_batch(const LaunchKey& key, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+inline void launch_sample_batch_recorded(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+    launch_sample_batch(key, args_dev, bases, ObsGather{}, n, st);
+}
+
+// The launch families, each written once: the size of the family's argument block and its batched launch.  A recorded launch
+// whose family has no row here is refused by icem_plan_step_batch (launch_family -> nullptr).
+struct LaunchFamilyRow {
+    int family;
+    size_t block_bytes;
+    void (*launch)(const LaunchKey& key, const void* args_dev, const BatchBases& bases, int n, hipStream_t st);
+};
+template <class Args, void (*Fn)(const LaunchKey&, const Args*, const BatchBases&, int, hipStream_t)>
+void launch_typed(const LaunchKey& key, const void* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+    Fn(key, (const Args*)args_dev, bases, n, st);
+}
+template <class Args, void (*Fn)(const LaunchKey&, const Args*, const BatchBases&, int, hipStream_t)>
+constexpr LaunchFamilyRow family_row(int family) {
+    static_assert(sizeof(Args) <= sizeof(LaunchDesc::block), "LaunchDesc::block");
+    return {family, sizeof(Args), &launch_typed<Args, Fn>};
+}
+constexpr LaunchFamilyRow LAUNCH_FAMILIES[] = {
+    family_row<FastIterArgs, launch_sample_rollout_batch>(LAUNCH_SAMPLE_ROLLOUT),
+    family_row<IterAheadArgs, launch_iter_ahead_batch>(LAUNCH_ITER_AHEAD),
+    family_row<MergeNoiseBatchArgs, launch_merge_batch>(LAUNCH_MERGE_NOISE),
+    family_row<FastSampleArgs, launch_sample_batch_recorded>(LAUNCH_SAMPLE),
+    family_row<FastSampleMergeArgs, launch_sample_merge_batch>(LAUNCH_SAMPLE_MERGE),
+    family_row<HnArgs, launch_rollout_hn_batch>(LAUNCH_ROLLOUT_HN),
+};
+inline const LaunchFamilyRow* launch_family(int family) {
+    for (const LaunchFamilyRow& r : LAUNCH_FAMILIES)
+        if (r.family == family) return &r;
+    return nullptr;
+}
 
 // workgroups (= candidate lists) of that launch; 0 if this shape / generator / size has no single-launch kernel
 // (n_tail trailing shifted-elite rows; *tail_out > 0: that many rows behind the lists are scored through the cost array)

@@ -979,7 +979,7 @@ void launch_rollout_hn(const LaunchCtx& cx, const FastRolloutArgs& r, int h, int
 }
 
 // ... and the same launch for n problems (blockIdx.y)
-void launch_rollout_hn_batch(const LaunchKey& k, const HnArgs* args_dev, int n, hipStream_t st) {
+void launch_rollout_hn_batch(const LaunchKey& k, const HnArgs* args_dev, const BatchBases&, int n, hipStream_t st) {
     hn_dispatch(k, [&](auto inst) { inst.batch(k.wgs[0], n, st, args_dev); });
 }
 

@@ -106,30 +106,26 @@ __global__ __launch_bounds__(SWG) void sample_folded_kernel(FastSampleArgs a) {
     sample_folded_body<H, ROUNDS>(a);
 }
 
-// B problems in one launch (icem_plan_step_batch, the two-kernel iterations of the TileHN shapes): blockIdx.y = the problem, its
-// argument block in device memory (scalar loads: the index is uniform), the sampling calls' stream offsets stored relative to
-// the step's base of that problem (BatchBases)
+// B problems in one launch (icem_plan_step_batch's two-kernel iterations of the TileHN shapes; icem_plan_step_learned*):
+// blockIdx.y = the problem, its argument block in device memory (scalar loads: the index is uniform), the sampling calls'
+// stream offsets stored relative to the step's base of that problem (BatchBases; the second offset is unused where
+// n_shift == 0).  The grid's x extent is the largest problem's: a workgroup beyond its problem's rows that is not its shift
+// workgroup (the launch's last, n_shift > 0) exits.  CONTRACT: ragged row counts require n_shift == 0 in every block -- else the
+// last workgroup of a smaller problem would be a row workgroup and the shift workgroup at once (icem_plan_step_batch's problems
+// have equal LaunchKeys, so equal row counts; the learned step's shifted elites are a launch of their own).  og.dst != nullptr:
+// workgroup 0 of a problem also copies its observation into the batch's contiguous [n, og.width] array.
 template <int H, int ROUNDS>
-__global__ __launch_bounds__(SWG) void sample_folded_batch_kernel(const FastSampleArgs* __restrict__ args, BatchBases bases) {
-    FastSampleArgs s = from_device(args[blockIdx.y]);
-    const unsigned long long base = bases.v[blockIdx.y];
-    add_base64(s.off_lo, s.off_hi, base);
-    add_base64(s.off2_lo, s.off2_hi, base);
-    sample_folded_body<H, ROUNDS>(s);
-}
-
-// ... and for the learned-dynamics step (icem_plan_step_learned*, learned_step.hip), at every horizon of the folded sampler:
-// ragged row counts (the grid's x extent is the largest problem's; surplus workgroups exit), and workgroup 0 of a problem also
-// copies its observation into the batch's contiguous [n, 230] array (og.dst; nullptr: a step of one problem reads its own)
-template <int H, int ROUNDS>
-__global__ __launch_bounds__(SWG) void sample_folded_learned_kernel(const FastSampleArgs* __restrict__ args, BatchBases bases, ObsGather og) {
+__global__ __launch_bounds__(SWG) void sample_folded_batch_kernel(const FastSampleArgs* __restrict__ args, BatchBases bases, ObsGather og) {
     FastSampleArgs s = from_device(args[blockIdx.y]);
     if (og.dst != nullptr && blockIdx.x == 0) {
         const float* src = og.src[blockIdx.y];
         for (int e = threadIdx.x; e < og.width; e += SWG) og.dst[(size_t)blockIdx.y * og.width + e] = src[e];
     }
-    if ((int)blockIdx.x * (SWG / s.d) >= s.n) return;
-    add_base64(s.off_lo, s.off_hi, bases.v[blockIdx.y]);
+    const bool shift_wg = s.n_shift > 0 && blockIdx.x == gridDim.x - 1;
+    if ((int)blockIdx.x * (SWG / s.d) >= s.n && !shift_wg) return;
+    const unsigned long long base = bases.v[blockIdx.y];
+    add_base64(s.off_lo, s.off_hi, base);
+    add_base64(s.off2_lo, s.off2_hi, base);
     sample_folded_body<H, ROUNDS>(s);
 }
 
@@ -358,7 +354,9 @@ bool sample_folded_pack_ok(int h, int d, int rounds, int K) {
     return on && sample_folded_merge_ok(h, d, rounds, K) && K * (h * d + 2) <= (2 + tpw) * h * d;
 }
 
-// horizons with a batched sampler: what a batch of TileHN handles reaches (ICEM_HN_SHAPES are all h = 30)
+// horizons at which a recorded sampling launch has a batched form: what a batch of TileHN handles reaches (ICEM_HN_SHAPES are
+// all h = 30).  sample_folded_merge_batch_kernel is compiled for these only; sample_folded_batch_kernel for every horizon of
+// the folded sampler (the learned step's), but icem_plan_step_batch records a sampler only where BOTH exist
 #define ICEM_SAMPLE_BATCH_HORIZONS(X) X(30)
 static bool sample_batch_compiled(int h) {
 #define X(HH) \
@@ -367,6 +365,7 @@ static bool sample_batch_compiled(int h) {
 #undef X
     return false;
 }
+int sample_row_workgroups(int n, int d) { return (n + SWG / d - 1) / (SWG / d); }
 static size_t sample_lds(int h, int d) { return ((size_t)2 * h * d + (size_t)(SWG / d) * h * d) * sizeof(float); }
 
 void launch_sample_folded_merge(const LaunchCtx& cx, const FastSampleMergeArgs& a) {
@@ -433,11 +432,10 @@ void launch_noise_rows(const FastSampleArgs& a, int rounds, hipStream_t st) {
 }
 
 void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int rounds) {
-    const int tpw = SWG / a.d;
     LaunchKey k;
     k.family = LAUNCH_SAMPLE;
     k.h = a.h, k.d = a.d, k.form = rounds;
-    k.wgs[0] = (a.n + tpw - 1) / tpw;
+    k.wgs[0] = sample_row_workgroups(a.n, a.d);
     k.wgs[1] = a.n_shift > 0 ? 1 : 0;   // the last workgroup: the shifted elites
     const int grid = k.wgs[0] + k.wgs[1];
     const size_t lds = sample_lds(a.h, a.d);
@@ -456,28 +454,14 @@ void launch_sample_folded(const LaunchCtx& cx, const FastSampleArgs& a, int roun
     });
 }
 
-// (args[p].n_shift == 0: the learned step's shifted elites are a launch of their own, gk_shift_sample_batch)
-void launch_sample_learned(int h, int d, int n_max, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n,
-                           hipStream_t st) {
-    const int tpw = SWG / d;
-#define X(HH)                                                                                                                          \
-    if (h == HH) {                                                                                                                     \
-        hipLaunchKernelGGL((sample_folded_learned_kernel<HH, 10>), dim3((n_max + tpw - 1) / tpw, n), dim3(SWG), sample_lds(h, d), st,  \
-                           args_dev, bases, og);                                                                                       \
-        return;                                                                                                                        \
-    }
-    ICEM_FAST_HORIZONS(X)
-#undef X
-}
-
-void launch_sample_batch(const LaunchKey& k, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
+void launch_sample_batch(const LaunchKey& k, const FastSampleArgs* args_dev, const BatchBases& bases, const ObsGather& og, int n, hipStream_t st) {
 #define X(HH)                                                                                                                       \
     if (k.h == HH) {                                                                                                                \
         hipLaunchKernelGGL((sample_folded_batch_kernel<HH, 10>), dim3(k.wgs[0] + k.wgs[1], n), dim3(SWG), sample_lds(k.h, k.d), st, \
-                           args_dev, bases);                                                                                        \
+                           args_dev, bases, og);                                                                                    \
         return;                                                                                                                     \
     }
-    ICEM_SAMPLE_BATCH_HORIZONS(X)
+    ICEM_FAST_HORIZONS(X)
 #undef X
 }
 

@@ -3,43 +3,25 @@
 //
 // The step is the stage-wise loop of the controllers (icem_amd/controllers.py::_get_action_stagewise + _stage_finish) with
 // every stage ONE launch for all problems:
-//   sample   sample_folded_learned_kernel (k_sample.hip): icem_sample_clip's folded sampler, blockIdx.y = the problem
+//   sample   sample_folded_batch_kernel (k_sample.hip), icem_plan_step_batch's batched sampler: icem_sample_clip's folded sampler,
+//            blockIdx.y = the problem, ragged row counts (so never with shifted rows: they are the next launch)
 //   shift    iteration 0 of a step > 0: shift_sample_batch_kernel (generic_kernels.hip) -- the copy of elites[e, 1:, :] and
 //            icem_sample_clip(t_begin = h - 1)'s draw of the last action, the operator's own arithmetic
 //   rollout  launch_rssm_rollout (one problem) / launch_rssm_split_batch (several)
 //   update   update_small_batch_kernel (k_merge.hip): icem_update_distribution's body, one workgroup per problem; the last
 //            one carries the epilogue (icem_shift's arithmetic, executed, best_cost, the results row)
-// i.e. 3 launches per iteration, + 1 in the steps that shift elites.  The argument blocks live in a device array with the
-// step's first handle, stream offsets relative to each problem's base (BatchBases), uploaded only when a byte changed
-// (icem_plan_step_batch's scheme): the steady state uploads nothing.  A batch's rows sit back to back in a pool of that
-// handle's (the batched rollout wants them contiguous); one problem alone uses its own actions / costs buffers.
+// i.e. 3 launches per iteration, + 1 in the steps that shift elites.  The step shares icem_plan_step_batch's plumbing rather
+// than restating it: the argument blocks live in a DeviceArgArray (arg_array.h) with the step's first handle, stream offsets
+// relative to each problem's base (BatchBases, call_base), uploaded only when a byte changed -- the steady state uploads
+// nothing; a batch is admitted by admit_batch; noise offsets, shifted rows and elite halves are host_common.h's call_base,
+// shift_rows and elite_parity, so a controller may alternate between the two steps.  A batch's rows sit back to back in a
+// pool of the first handle's (the batched rollout wants them contiguous); one problem alone uses its own actions / costs buffers.
 #include "host_common.h"
 #include "icem_rssm.h"
 
 using namespace icem;
 
 namespace {
-
-struct LearnedCtx {
-    static constexpr int SLOTS = 2;          // by the first handle's step parity: the elite halves alternate per iteration
-    void* dev[SLOTS] = {nullptr, nullptr};
-    size_t cap[SLOTS] = {0, 0};
-    std::vector<unsigned char> shadow[SLOTS];
-    float* pool = nullptr;                   // a batch's [rows, hd] actions | [rows] costs | [n, 230] observations
-    size_t pool_rows = 0;
-    int pool_n = 0;
-    int* idx = nullptr;                      // [ICEM_MAX_BATCH, ICEM_MAX_ELITES]: the updates' index output (not kept)
-};
-
-void learned_ctx_free(void* p) {
-    LearnedCtx* c = (LearnedCtx*)p;
-    if (!c) return;
-    for (void* d : c->dev)
-        if (d) (void)hipFree(d);
-    if (c->pool) (void)hipFree(c->pool);
-    if (c->idx) (void)hipFree(c->idx);
-    delete c;
-}
 
 int max_rows(const icem_handle* h) {
     int m = 0;
@@ -65,19 +47,6 @@ const char* learned_unserved(const icem_handle* h) {
     return nullptr;
 }
 
-bool same_config(const icem_config& a, const icem_config& r) {
-    return a.horizon == r.horizon && a.act_dim == r.act_dim && a.num_traj == r.num_traj && a.num_elites == r.num_elites &&
-           a.elites_size == r.elites_size && a.opt_iters == r.opt_iters && a.cost_mode == r.cost_mode &&
-           a.use_mean_actions == r.use_mean_actions && a.keep_previous_elites == r.keep_previous_elites &&
-           a.shift_elites == r.shift_elites && a.factor_decrease == r.factor_decrease && a.fraction_reused == r.fraction_reused &&
-           a.rng_rounds == r.rng_rounds && a.dtype == r.dtype && a.world == r.world && a.rank == r.rank && a.alpha == r.alpha &&
-           a.init_std == r.init_std && a.noise_beta == r.noise_beta;
-}
-
-int shifted(const icem_handle* h, int mpc_step, int it) {
-    return (it == 0 && h->cfg.shift_elites && mpc_step > 0 && h->n_reuse > 0) ? h->n_reuse : 0;
-}
-
 size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
@@ -86,12 +55,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     const icem_config& c = h0->cfg;
     const int H = c.horizon, d = c.act_dim, hd = h0->hd, K = c.num_elites, iters = c.opt_iters, n_reuse = std::max(0, h0->n_reuse);
     // ---- refusals: all of them before anything is launched or any handle touched ----
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j)
-            if (handles[i] == handles[j]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: the same handle twice in one batch");
     for (int i = 0; i < n; ++i) {
-        if (!same_config(handles[i]->cfg, c) || handles[i]->pop != h0->pop || handles[i]->n_reuse != h0->n_reuse)
-            return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: the handles must share one configuration (everything but the seed)");
         if (steps[i] < 0) return fail(ICEM_E_INVALID, "icem_plan_step_learned: negative mpc_step");
         const icem_plan_buffers& b = buffers[i];
         if (!b.mean || !b.std || !b.low || !b.high || !b.obs0 || !b.actions || !b.costs || !b.elites || !b.executed || !b.best_cost)
@@ -109,9 +73,9 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     for (int it = 0; it < iters; ++it) {
         size_t all = 0;
         for (int p = 0; p < n; ++p) {
-            rows[(size_t)it * n + p] = h0->pop[it] + shifted(handles[p], steps[p], it);
+            rows[(size_t)it * n + p] = h0->pop[it] + shift_rows(handles[p], steps[p], it);
             all += rows[(size_t)it * n + p];
-            shift_max = std::max(shift_max, shifted(handles[p], steps[p], it));
+            shift_max = std::max(shift_max, shift_rows(handles[p], steps[p], it));
         }
         const int tiles = rssm_batch_tiles(n, &rows[(size_t)it * n]);
         if (tiles < 0 || !rssm_split_batch_ok(tiles, H))
@@ -123,12 +87,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     // the rollout's staging area and its host-visible status word, BEFORE the first launch: a refused step leaves everything as it was
     if (int rc = rssm_launch_result(rssm_split_prepare(tiles_max, H, st))) return rc;
     // ---- the step's own memory (first call, or a larger batch than before) ----
-    LearnedCtx* ctx = (LearnedCtx*)h0->learned_ctx;
-    if (!ctx) {
-        ctx = new LearnedCtx();
-        h0->learned_ctx = ctx;
-        h0->learned_ctx_free = learned_ctx_free;
-    }
+    LearnedCtx* ctx = &h0->learned;
     if (!ctx->idx) ICEM_HIP_TRY(hipMalloc((void**)&ctx->idx, (size_t)ICEM_MAX_BATCH * ICEM_MAX_ELITES * sizeof(int)));
     const size_t cap_rows = (size_t)n * (size_t)max_rows(h0);   // (what any mix of steps of this batch size needs)
     if (n > 1 && (ctx->pool_rows < cap_rows || ctx->pool_n < n)) {
@@ -153,18 +112,17 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     const size_t bytes = per_it * iters + padded(hb * n);
     std::vector<unsigned char> blob(bytes, 0);
     BatchBases bases{};
-    for (int p = 0; p < n; ++p) bases.v[p] = (handles[p]->episode << 32) + (uint64_t)steps[p] * (uint64_t)(iters + 1);
+    for (int p = 0; p < n; ++p) bases.v[p] = call_base(handles[p], steps[p]);
     for (int it = 0; it < iters; ++it) {
         size_t row0 = 0;
         for (int p = 0; p < n; ++p) {
             const icem_handle* h = handles[p];
             const icem_plan_buffers& b = buffers[p];
-            const int n_it = h0->pop[it], n_shift = shifted(h, steps[p], it), n_rows = n_it + n_shift;
+            const int n_it = h0->pop[it], n_shift = shift_rows(h, steps[p], it), n_rows = n_it + n_shift;
             float* acts = n == 1 ? (float*)b.actions : pool_a + row0 * hd;
             float* csts = n == 1 ? (float*)b.costs : pool_c + row0;
             row0 += n_rows;
-            // iteration `it` of step s writes elite half (s * iters + it + 1) & 1 and reads the other one
-            const int w = (int)(((long long)steps[p] * iters + it + 1) & 1), r = w ^ 1;
+            const int r = elite_parity(h, steps[p], it), w = r ^ 1;
             float* el = (float*)b.elites;
             float* el_w = el + (size_t)w * K * hd;
             const float* el_r = el + (size_t)r * K * hd;
@@ -201,29 +159,14 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         }
     }
     const int slot = steps[0] & 1;
-    if (ctx->cap[slot] < bytes) {
-        if (ctx->dev[slot]) {
-            ICEM_HIP_TRY(hipStreamSynchronize(st));   // (launches of an earlier step may still read the old array)
-            (void)hipFree(ctx->dev[slot]);
-        }
-        ctx->dev[slot] = nullptr;
-        ctx->cap[slot] = 0;
-        ctx->shadow[slot].clear();
-        // (room for the largest batch: a batch that grows later allocates nothing)
-        const size_t room = (padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH)) * iters + padded(hb * ICEM_MAX_BATCH);
-        ICEM_HIP_TRY(hipMalloc(&ctx->dev[slot], room));
-        ctx->cap[slot] = room;
-    }
-    if (ctx->shadow[slot].size() != bytes || std::memcmp(ctx->shadow[slot].data(), blob.data(), bytes) != 0) {
-        // (pageable source: the runtime stages it before returning; ordered behind the earlier steps' launches on `st`)
-        ICEM_HIP_TRY(hipMemcpyAsync(ctx->dev[slot], blob.data(), bytes, hipMemcpyHostToDevice, st));
-        ctx->shadow[slot] = blob;
-        ++h0->batch_uploads;
-    }
+    const size_t room = (padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH)) * iters + padded(hb * ICEM_MAX_BATCH);
+    ICEM_HIP_TRY(ctx->args.put(slot, blob, room, st, &h0->batch_uploads));
     // ---- the launches ----
-    const unsigned char* dev = (const unsigned char*)ctx->dev[slot];
+    const unsigned char* dev = (const unsigned char*)ctx->args.dev(slot);
     long long launches = 0;
-    h0->learned_launches = 0;
+    ctx->launches = 0;
+    LaunchKey sk;   // the sampler's: the grid's x extent is the largest problem's (all of them draw pop[it] rows)
+    sk.family = LAUNCH_SAMPLE, sk.h = H, sk.d = d, sk.form = 10;
     for (int it = 0; it < iters; ++it) {
         ObsGather og{};
         if (n > 1 && it == 0) {
@@ -231,7 +174,8 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             og.dst = pool_o;
             og.width = rssm::DET + rssm::STOCH;
         }
-        launch_sample_learned(H, d, h0->pop[it], (const FastSampleArgs*)(dev + per_it * it), bases, og, n, st);
+        sk.wgs[0] = sample_row_workgroups(h0->pop[it], d);
+        launch_sample_batch(sk, (const FastSampleArgs*)(dev + per_it * it), bases, og, n, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
         if (it == 0 && shift_max > 0) {
@@ -250,7 +194,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
     }
-    h0->learned_launches = launches;
+    ctx->launches = launches;
     return ICEM_OK;
 }
 
@@ -262,10 +206,9 @@ int icem_plan_step_learned_ok(const icem_handle* h) { return (h && learned_unser
 
 int icem_plan_step_learned_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const void* params,
                                  const int32_t* mpc_steps_host, void* results, void* stream) {
-    if (!handles || !buffers || !params || !mpc_steps_host || n < 1 || n > ICEM_MAX_BATCH)
-        return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: null argument / n outside [1, 32]");
-    for (int i = 0; i < n; ++i)
-        if (!handles[i]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_batch: null handle");
+    if (int rc = admit_batch(handles, n, buffers && params && mpc_steps_host, true, "icem_plan_step_learned_batch: ",
+                             "icem_plan_step_learned_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
     return learned_step(handles, n, buffers, params, mpc_steps_host, results, (hipStream_t)stream);
 }
 
@@ -274,6 +217,6 @@ int icem_plan_step_learned(icem_handle* h, const icem_plan_buffers* b, const voi
     return learned_step(&h, 1, b, params, &mpc_step, nullptr, (hipStream_t)stream);
 }
 
-int64_t icem_learned_step_launches(const icem_handle* h) { return h ? (int64_t)h->learned_launches : 0; }
+int64_t icem_learned_step_launches(const icem_handle* h) { return h ? (int64_t)h->learned.launches : 0; }
 
 }  // extern "C"

@@ -352,26 +352,6 @@ bool prologue_possible(const icem_handle* h, const BatchHint& bh, int n_rows) {
     return sample_folded_merge_ok(c.horizon, c.act_dim, c.rng_rounds, K);
 }
 
-// ---- rules that every path of a step must agree on, each written once ---------------------------------------------------
-
-// Noise stream offset of an MPC step's sampling calls: episode in the high word (icem_set_episode; the reference's
-// np.random stream runs on across episodes, icem.py:73), sampling call number of the episode in the low one --
-// iteration `it` draws at call_base + it, the shifted elites at call_base + opt_iters.
-static uint64_t call_base(const icem_handle* h, int mpc_step) {
-    return (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)(h->cfg.opt_iters + 1);
-}
-
-// shifted elites, simulated at iteration 0 of every MPC step but the first (icem.py:131-137): rows behind the sampled ones.
-// (icem_create does not refuse a negative fraction_reused, which makes n_reuse negative: the launches then build no such
-// rows, while the lists merge's pool size and the batch's dry run have always taken the count as it is -- at_least_0 = false.)
-static int shift_rows(const icem_handle* h, int mpc_step, int it, bool at_least_0 = true) {
-    if (it != 0 || !h->cfg.shift_elites || mpc_step <= 0) return 0;
-    return at_least_0 ? std::max(0, h->n_reuse) : h->n_reuse;
-}
-
-// which of the two elite buffers iteration `it` of step `mpc_step` reads (it writes the other): the global iteration's parity
-static int elite_parity(const icem_handle* h, int mpc_step, int it) { return (int)(((long long)mpc_step * h->cfg.opt_iters + it) & 1); }
-
 // this rank's shard of iteration `it`: rows [lo, lo + n_loc) of the population (world 1: all of it)
 struct Shard {
     int lo, n_loc;
@@ -1499,22 +1479,6 @@ int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step,
 // has the batch refused), then every stage is ONE launch with blockIdx.y = the problem and the
 // blocks in a device array (one upload per step, skipped when nothing but the step number changed: the offsets are stored
 // relative to the step's base, which travels in the kernel arguments).  Slab sizes are chosen for all rows together.
-struct BatchCtx {
-    // six arrays, by the MPC step modulo 6: the elite buffers ping-pong per ITERATION (with an odd iteration count every second
-    // step's blocks are the same again), the noise-ahead launches rotate three pools per step: 2 x 3 steps close every cycle
-    static constexpr int SLOTS = 6;
-    void* dev[SLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[SLOTS] = {0, 0, 0, 0, 0, 0};
-    std::vector<unsigned char> shadow[SLOTS];   // what each device array holds
-};
-static void batch_ctx_free(void* p) {
-    BatchCtx* c = (BatchCtx*)p;
-    if (!c) return;
-    for (void* d : c->dev)
-        if (d) (void)hipFree(d);
-    delete c;
-}
-
 // does this handle's step consist of single-launch iterations with merge prologues and one last merge? (the path
 // decisions of plan_step_body / plan_iter_local_t / plan_iter_merge_t, evaluated without launching anything)
 static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step, const BatchHint& bh) {
@@ -1556,25 +1520,15 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
 }
 
 extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream) {
-    if (!handles || !buffers || n < 1 || n > ICEM_MAX_BATCH) return fail(ICEM_E_INVALID, "null argument / n outside [1, 32]");
-    for (int i = 0; i < n; ++i)
-        if (!handles[i]) return fail(ICEM_E_INVALID, "null handle");
+    if (int rc = admit_batch(handles, n, buffers != nullptr, false, "",
+                             "icem_plan_step_batch: the handles must share one configuration (horizon, act_dim, populations, elites, flags)"))
+        return rc;
     if (n == 1) return icem_plan_step(handles[0], &buffers[0], mpc_step, stream);
     hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j)
-            if (handles[i] == handles[j]) return fail(ICEM_E_INVALID, "the same handle twice in one batch");
-    // one configuration (every launch shape and template instantiation is shared); models, costs, seeds, bounds, observations differ
+    // (one configuration; models, costs, seeds, bounds, observations differ)
     const icem_handle* h0 = handles[0];
     for (int i = 0; i < n; ++i) {
         icem_handle* h = handles[i];
-        const icem_config &a = h->cfg, &r = h0->cfg;
-        if (a.horizon != r.horizon || a.act_dim != r.act_dim || a.num_traj != r.num_traj || a.num_elites != r.num_elites ||
-            a.elites_size != r.elites_size || a.opt_iters != r.opt_iters || a.use_mean_actions != r.use_mean_actions ||
-            a.keep_previous_elites != r.keep_previous_elites || a.shift_elites != r.shift_elites || a.factor_decrease != r.factor_decrease ||
-            a.fraction_reused != r.fraction_reused || a.rng_rounds != r.rng_rounds || a.dtype != r.dtype || a.world != r.world ||
-            (a.noise_beta > 0) != (r.noise_beta > 0))
-            return fail(ICEM_E_INVALID, "icem_plan_step_batch: the handles must share one configuration (horizon, act_dim, populations, elites, flags)");
         int rc = check_plan(h, &buffers[i], mpc_step, 0, st);
         if (rc) return rc;
         if (h->Of != h0->Of || h->model_kind != h0->model_kind || h->tile_arith != h0->tile_arith)
@@ -1626,60 +1580,33 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
     size_t bytes = 0;
     for (size_t l = 0; l < L; ++l) {
         at[l] = bytes;
-        bytes += ((launch_block_bytes(first[l].key.family) * (size_t)n + 255) / 256) * 256;
+        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, "icem_plan_step_batch: a recorded launch's family has no batched launch");
+        bytes += ((launch_family(first[l].key.family)->block_bytes * (size_t)n + 255) / 256) * 256;
     }
     std::vector<unsigned char> blob(bytes, 0);
     for (size_t l = 0; l < L; ++l) {
-        const size_t one = launch_block_bytes(first[l].key.family);
+        const size_t one = launch_family(first[l].key.family)->block_bytes;
         for (int i = 0; i < n; ++i) std::memcpy(blob.data() + at[l] + (size_t)i * one, recs[i].launches[l].block, one);
     }
     icem_handle* owner = handles[0];
-    BatchCtx* ctx = (BatchCtx*)owner->batch_ctx;
-    if (!ctx) {
-        ctx = new BatchCtx();
-        owner->batch_ctx = ctx;
-        owner->batch_ctx_free = batch_ctx_free;
-    }
-    const int slot = mpc_step % BatchCtx::SLOTS;
-    if (ctx->cap[slot] < bytes) {
-        if (ctx->dev[slot]) {
-            ICEM_HIP_TRY(hipStreamSynchronize(st));   // (launches of an earlier step may still read the old array)
-            (void)hipFree(ctx->dev[slot]);
+    const int slot = mpc_step % 6;
+    if (opt_i(OPT_AHEAD_STAMPS) && owner->batch_args.holds(slot).size() == bytes) {   // development: which bytes moved
+        const std::vector<unsigned char>& held = owner->batch_args.holds(slot);
+        int shown = 0;
+        for (size_t l = 0; l < L && shown < 12; ++l) {
+            const size_t one = launch_family(first[l].key.family)->block_bytes;
+            for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
+                if (blob[at[l] + o] != held[at[l] + o]) {
+                    std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
+                    ++shown;
+                    o = (o / 8 + 1) * 8 - 1;
+                }
         }
-        ctx->dev[slot] = nullptr;
-        ctx->cap[slot] = 0;
-        ctx->shadow[slot].clear();
-        ICEM_HIP_TRY(hipMalloc(&ctx->dev[slot], bytes + 4096));
-        ctx->cap[slot] = bytes + 4096;
     }
-    if (ctx->shadow[slot].size() != bytes || std::memcmp(ctx->shadow[slot].data(), blob.data(), bytes) != 0) {
-        if (opt_i(OPT_AHEAD_STAMPS) && ctx->shadow[slot].size() == bytes) {   // development: which bytes moved
-            int shown = 0;
-            for (size_t l = 0; l < L && shown < 12; ++l) {
-                const size_t one = launch_block_bytes(first[l].key.family);
-                for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
-                    if (blob[at[l] + o] != ctx->shadow[slot][at[l] + o]) {
-                        std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
-                        ++shown;
-                        o = (o / 8 + 1) * 8 - 1;
-                    }
-            }
-        }
-        // (pageable source: the runtime stages it before returning; ordered behind the earlier steps' launches on `st`)
-        ICEM_HIP_TRY(hipMemcpyAsync(ctx->dev[slot], blob.data(), bytes, hipMemcpyHostToDevice, st));
-        ctx->shadow[slot] = blob;
-        ++owner->batch_uploads;
-    }
+    ICEM_HIP_TRY(owner->batch_args.put(slot, blob, bytes + 4096, st, &owner->batch_uploads));
     // ---- the launches ----
     for (size_t l = 0; l < L; ++l) {
-        const LaunchKey& k = first[l].key;
-        const unsigned char* base = (const unsigned char*)ctx->dev[slot] + at[l];
-        if (k.family == LAUNCH_SAMPLE_ROLLOUT) launch_sample_rollout_batch(k, (const FastIterArgs*)base, bases, n, st);
-        else if (k.family == LAUNCH_ITER_AHEAD) launch_iter_ahead_batch(k, (const IterAheadArgs*)base, bases, n, st);
-        else if (k.family == LAUNCH_SAMPLE) launch_sample_batch(k, (const FastSampleArgs*)base, bases, n, st);
-        else if (k.family == LAUNCH_SAMPLE_MERGE) launch_sample_merge_batch(k, (const FastSampleMergeArgs*)base, bases, n, st);
-        else if (k.family == LAUNCH_ROLLOUT_HN) launch_rollout_hn_batch(k, (const HnArgs*)base, n, st);
-        else launch_merge_batch(k, (const MergeNoiseBatchArgs*)base, bases, n, st);
+        launch_family(first[l].key.family)->launch(first[l].key, (const unsigned char*)owner->batch_args.dev(slot) + at[l], bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
     }
     disarm_all.armed = false;

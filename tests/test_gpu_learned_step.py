@@ -6,7 +6,8 @@ comparison in this file is ``np.array_equal``: no tolerance appears.
 Shapes: one shared DeviceRSSMModel(seed=3), N = 128, factor_decrease_num = 1.25, elites_size = 10, 3 iterations -- rows
 128 (+ 3 shifted elites from the second step on), 102, 81: the last 16-row tile of every rollout is ragged, the sampler's
 last workgroup (42 rows at d = 6) is partial (N = 126 fills it exactly), a batch's problems start off a multiple of 16 rows.
-h = 12 and h = 10 are two of the folded sampler's horizons; h = 4 is none of them (refused, the controller falls back)."""
+h = 12 and h = 10 are two of the folded sampler's horizons, h = 30 the one at which its batched kernel also serves
+icem_plan_step_batch; h = 4 is none of them (refused, the controller falls back)."""
 import contextlib
 import ctypes as C
 
@@ -187,7 +188,7 @@ def test_raw_entry_against_the_operators():
 
 
 # ---- 3. batch equals solo ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("horizon", [12, 10])
+@pytest.mark.parametrize("horizon", [12, 10, 30])
 def test_batch_equals_solo_and_stagewise(horizon):
     """B = 3 (distinct seeds and observations) through get_action_batch against twins stepping alone on the new entry and
     twins on the stage-wise path: 3 steps; 2 more after controller 1 alone was reset (128 rows against its peers' 131, its
@@ -293,7 +294,52 @@ def test_launch_count_does_not_grow_with_the_batch():
     assert counts[1] == counts[3] == counts[8], counts
 
 
-# ---- 6. refusals --------------------------------------------------------------------------------------------------------------
+# ---- 6. steady state ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 3])
+def test_the_steady_state_uploads_nothing(B):
+    """learned_step.hip's claim: the argument blocks of a step are those of the step two before it (the elite halves alternate
+    per iteration, 3 iterations: per step), the stream offsets travel in the kernel arguments.  The blocks change at step 0,
+    at step 1 and at step 2 (shifted elites first appear in slot 0); after 4 warm-up steps 4 more upload nothing.
+    B = 1: a controller.  B = 3: the raw entry on planners stepped by hand, with ONE results tensor and ONE observation
+    array for all steps -- both pointers sit inside the blocks."""
+    m = model()
+    if B == 1:
+        c = controller(5)
+        ob0 = observations(1)[0]
+        begin(c, ob0)
+        lead = c.planner
+
+        def step(k):
+            c.get_action(ob0 + 0.01 * k, None)
+            assert lead.learned_step_launches > 0
+    else:
+        from icem_amd import _lib as L
+        pls = [planner(31 + i) for i in range(B)]
+        lead = pls[0]
+        obs = torch.as_tensor(np.stack(observations(B, seed=7)), dtype=torch.float32, device="cuda")
+        res = torch.zeros((B, 7), dtype=torch.float32, device="cuda")
+        hs = (C.c_void_p * B)(*[pl._h for pl in pls])
+
+        def step(k):
+            obs.add_(0.01)
+            bs = (L.IcemPlanBuffersC * B)(*[pl._learned_buffers(obs[i].data_ptr()) for i, pl in enumerate(pls)])
+            st = (C.c_int32 * B)(*[pl.mpc_step for pl in pls])
+            L.check(lead.lib.icem_plan_step_learned_batch(hs, B, bs, C.c_void_p(m.params.data_ptr()), st, C.c_void_p(res.data_ptr()),
+                                                          lead._stream()))
+            for pl in pls:
+                pl.mpc_step += 1
+    for k in range(4):
+        step(k)
+    before = lead.batch_uploads
+    assert before > 0
+    for k in range(4, 8):
+        step(k)
+    torch.cuda.synchronize()
+    print("argument uploads: %d in 4 warm-up steps, %d in the 4 steps behind them" % (before, lead.batch_uploads - before))
+    assert lead.batch_uploads == before, (before, lead.batch_uploads)
+
+
+# ---- 7. refusals --------------------------------------------------------------------------------------------------------------
 def snapshot(p):
     return [p.mpc_step] + [np_(x).copy() for x in (p.mean, p.std, p.elites_actions, p.elites_costs, p.executed, p.best_cost)]
 
