@@ -140,6 +140,8 @@ SYMBOLS = [
     ("icem_profile_overhead", C.c_int, [_VP, _I32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icem_plan_step_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, _VP]),
     ("icem_batch_uploads", C.c_int64, [_H]),
+    ("icem_plan_step_batch_f64", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, _VP]),
+    ("icem_batch_f64_launches", C.c_int64, [_H]),
     ("icem_plan_step_learned_ok", C.c_int, [_H]),
     ("icem_plan_step_learned", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _VP, _I32, _VP]),
     ("icem_plan_step_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _VP, C.POINTER(_I32), _VP, _VP]),

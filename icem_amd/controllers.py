@@ -620,7 +620,9 @@ class MpcICemHip(MpcController):
         elif rssm:
             host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
         else:
-            IcemPlanner.plan_step_batch([c.planner for c in ctrls], observations)
+            # strict-parity controllers (every planner f64): the generic kernels' batched step, icem_plan_step_batch_f64
+            f64 = all(c.planner.cfg.dtype == "f64" for c in ctrls)
+            (IcemPlanner.plan_step_batch_f64 if f64 else IcemPlanner.plan_step_batch)([c.planner for c in ctrls], observations)
             host = torch.stack([torch.cat([c.planner.executed, c.planner.best_cost]) for c in ctrls]).cpu().numpy().astype(np.float64)  # one D2H sync
             # what icem_get_action reports for a solo step: non-finite costs out of a finite observation (ICEM_E_RANGE)
             from ._lib import IcemError, ICEM_E_RANGE

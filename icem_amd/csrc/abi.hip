@@ -597,7 +597,7 @@ int icem_sample_clip(icem_handle* h, int32_t n, int64_t first_index, const void*
     hipStream_t st = (hipStream_t)stream;
     if (z_r == nullptr && t_begin == 0 && fast_sample_ok(h))
         return launch_fast_sample(h, n, first_index, mean, std, low, high, offset, row0_mean, actions, LaunchCtx{st});
-    return gk_sample(h, n, first_index, mean, std, low, high, z_r, z_i, offset, t_begin, row0_mean, actions, st);
+    return gk_sample(h, n, first_index, mean, std, low, high, z_r, z_i, offset, t_begin, row0_mean, actions, LaunchCtx{st});
 }
 
 int icem_sample_truncnorm(icem_handle* h, int32_t n, int64_t first_index, const void* mean, const void* std,
@@ -645,7 +645,7 @@ int icem_rollout_cost(icem_handle* h, int32_t n, const void* obs0, const void* a
     hipStream_t st = (hipStream_t)stream;
     if (observations == nullptr && n > 0 && fast_rollout_ok(h, 0))
         return launch_fast_rollout(h, n, 0, 0, obs0, actions, costs, nullptr, nullptr, LaunchCtx{st}, nullptr);
-    return gk_rollout(h, n, obs0, actions, costs, observations, st);
+    return gk_rollout(h, n, obs0, actions, costs, observations, LaunchCtx{st});
 }
 
 int icem_cost_reduce(icem_handle* h, int32_t n, const void* step_costs, void* costs, void* stream) {

@@ -211,6 +211,7 @@ struct icem_handle {
     // step's blocks are the same again), the noise-ahead launches rotate three pools per step: 2 x 3 steps close every cycle
     icem::DeviceArgArray<6> batch_args;
     unsigned long long batch_uploads = 0;   // how often a batched step of either kind (re)wrote its array (steady state: never)
+    long long batch_f64_launches = 0;       // kernel launches of the last icem_plan_step_batch_f64 this handle led
     icem::LearnedCtx learned;               // icem_plan_step_learned* (learned_step.hip)
     void* rccl_comm = nullptr;       // collective.hip: the RCCL communicator of icem_allgather_elites (world > 1)
     bool rccl_owned = false;         // ... created by icem_rccl_connect (destroyed with the handle) or adopted
@@ -312,7 +313,8 @@ inline int check_handle(const icem_handle* h) {
 // ---- generic_kernels.hip: launchers of the generic kernels; pointers are of the handle's dtype ------------------
 int gk_sample(const icem_handle* h, int n, long long first_index, const void* mean, const void* std, const void* low,
               const void* high, const void* zr, const void* zi, uint64_t offset, int t_begin, int row0_mean, void* out,
-              hipStream_t st);
+              const LaunchCtx& cx);   // (cx: the step's launch context -- under a recorder the launch is recorded, not issued; also gk_rollout,
+                                      //  gk_shift_elites, gk_select_refit: the launches of a float64 step, icem_plan_step_batch_f64)
 int gk_sample_truncnorm(const icem_handle* h, int n, long long first_index, const void* mean, const void* std,
                         const void* lower, const void* upper, const void* u, uint64_t offset, void* actions, hipStream_t st);
 int gk_sample_piecewise(const icem_handle* h, int n, long long call_offset, int change_freq, long long first_block,
@@ -322,7 +324,7 @@ int gk_cem_bounds(const icem_handle* h, int like_levine, const void* mean, void*
 int gk_philox_normals(const icem_handle* h, int n, long long first_index, uint64_t offset, void* z_r, void* z_i,
                       hipStream_t st);
 int gk_rollout(const icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations,
-               hipStream_t st);
+               const LaunchCtx& cx);
 int gk_trajectory_cost(const icem_handle* h, int n, int o, const void* obs, const void* nxt, long long ts, long long ss,
                        const void* actions, void* costs, hipStream_t st);
 int gk_cost_reduce(const icem_handle* h, int n, const void* step_costs, void* costs, hipStream_t st);
@@ -334,7 +336,7 @@ int gk_gather_refit(const icem_handle* h, const void* actions, const int32_t* id
                     void* elites_out, hipStream_t st);
 int gk_shift(const icem_handle* h, void* mean, void* std, const void* low, const void* high, hipStream_t st);
 int gk_reset(const icem_handle* h, void* mean, void* std, const void* low, const void* high, hipStream_t st);
-int gk_shift_elites(const icem_handle* h, int n_extra, const void* elites, void* dst, hipStream_t st);
+int gk_shift_elites(const icem_handle* h, int n_extra, const void* elites, void* dst, const LaunchCtx& cx);
 // icem_plan_step_learned* (learned_step.hip): the shifted elites of n problems in one launch -- the copy of elites[e, 1:, :] and
 // icem_sample_clip(t_begin = h - 1)'s draw of the last action (f32, h <= 32, rng_rounds 10).  One argument block per problem
 // in a device array (gk_shift_sample_block writes the host form, stream offset relative to the step's base).
@@ -366,7 +368,7 @@ int gk_merge_refit(const icem_handle* h, const MergeArgsV& a, hipStream_t st);
 // world == 1: top-K over the pool's costs (+ kept elites) + gather + refit in ONE launch (a.records / a.n_rec unused)
 bool gk_select_ok(const icem_handle* h, int n_cand, int n_keep, int K);
 int gk_select_refit(const icem_handle* h, int n_cand, int n_loc, const void* costs, const void* actions, const MergeArgsV& a,
-                    hipStream_t st);
+                    const LaunchCtx& cx);
 // every index a cost term reads lies inside an observation of width o (nullptr = fine)
 const char* cost_indices_error(const icem_handle* h, int o);
 

@@ -335,7 +335,10 @@ struct FastIterArgs {
     MergeSingleArgs m;  // merge prologue only: the PREVIOUS iteration's merge (last == 0), see sample_rollout_kernel
     PackPrev p;         // ... and its pack (sharded runs)
 };
-// ---- the step's launch context, and batched planners (icem_plan_step_batch; plan.hip) -----------------------------------
+}  // namespace icem
+#include "generic_args.h"   // the generic kernels' argument blocks (MergeArgs holds an XchgWait): families 7-11 below
+namespace icem {
+// ---- the step's launch context, and batched planners (icem_plan_step_batch, icem_plan_step_batch_f64; plan.hip) ------------
 // B independent MPC problems of the same configuration advance together: every launch of the small-population path
 // (sample_rollout_kernel x opt_iters, then the last merge) is ONE launch for all of them -- blockIdx.y = the problem, its
 // argument block read from an array in device memory instead of the kernel-argument segment.  The host side of every
@@ -355,14 +358,18 @@ struct BatchHint {
 // What a dispatch table maps to a compiled instantiation and a grid (all ints, no padding: compared as bytes)
 // (LAUNCH_SAMPLE / _SAMPLE_MERGE / _ROLLOUT_HN: the sampler, the sampler with the previous merge in its prologue and the TileHN
 //  rollout -- the two-kernel iterations of the Door / Relocate / FetchPickAndPlace shapes)
+// (LAUNCH_GK_*: the generic kernels of a float64 step, icem_plan_step_batch_f64 -- the quad sampler, the shifted elites' copy, the
+//  rollout with a row of lanes / a thread per trajectory, the one-launch selection + refit; generic_kernels.hip, k_generic_batch.hip)
 enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3, LAUNCH_SAMPLE = 4, LAUNCH_SAMPLE_MERGE = 5,
-                          LAUNCH_ROLLOUT_HN = 6 };
+                          LAUNCH_ROLLOUT_HN = 6, LAUNCH_GK_SAMPLE = 7, LAUNCH_GK_SHIFT = 8, LAUNCH_GK_ROLLOUT_ROWS = 9, LAUNCH_GK_ROLLOUT_THREAD = 10,
+                          LAUNCH_GK_SELECT = 11 };
 struct LaunchKey {
     int family = 0;
     int h = 0, d = 0, O = 0, kind = 0, arith = 0;   // (rollout_hn: O = the observation width o)
     int waves = 0;     // rollout waves per workgroup (sample_rollout: RW; iter_ahead, rollout_hn: WAVES)
     // sample_rollout: 0 = plain, 1 = lists merge in the prologue, 2 = records merge; iter_ahead: PM; merge_noise: 1 = with noise;
     // sample: the generator's rounds; sample_merge: 1 = lists merge, 2 = records merge; rollout_hn: the term program, N32 << 16 | N4 << 8 | NP
+    // gk_sample: O = HMAX, waves = trajectories per workgroup, form = the generator's rounds; gk_rollout_*: O = the padded width
     int form = 0;
     int wgs[3] = {0, 0, 0};   // workgroups per role (of ONE problem); the grid is their sum
     bool operator==(const LaunchKey& o) const { return std::memcmp(this, &o, sizeof(LaunchKey)) == 0; }
@@ -374,12 +381,15 @@ struct MergeNoiseBatchArgs {
 // One recorded launch of one problem: the key and the family's argument block in its device-array form
 struct LaunchDesc {
     LaunchKey key;
-    alignas(8) unsigned char block[sizeof(IterAheadArgs)];
+    static constexpr size_t BLOCK = sizeof(IterAheadArgs) > sizeof(RolloutArgs<double>) ? sizeof(IterAheadArgs) : sizeof(RolloutArgs<double>);
+    static_assert(sizeof(SelectArgs<double>) <= BLOCK && sizeof(SampleArgs<double>) <= BLOCK, "LaunchDesc::block");
+    alignas(8) unsigned char block[BLOCK];
 };
 struct LaunchRecorder {
     unsigned long long base = 0;        // noise stream base of the recorded problem's step (BatchBases::v)
     std::vector<LaunchDesc> launches;
     bool unsupported = false;           // a launch without a batched form was reached (nothing was launched for it)
+    const char* who = "icem_plan_step_batch: ";   // the recording entry's name, for the message of such a refusal
     void* add(const LaunchKey& key) {   // -> the new record's block, zeroed
         launches.emplace_back();
         launches.back().key = key;
@@ -461,6 +471,27 @@ inline void batch_form(const HnArgs& a, void* dst) {
     g.r.dbg = nullptr;
     g.A = a.A, g.B = a.B, g.lda = a.lda, g.ldb = a.ldb, g.wc = a.wc, g.cs = a.cs;
 }
+// The generic kernels' blocks (float64).  Their launchers fill a ZEROED block member by member (generic_kernels.hip), so a copy
+// carries defined bytes throughout; the sampler's offset goes relative to the step's base, external noise and dbg are never batched
+inline void batch_form(const SampleArgs<double>& a, unsigned long long base, void* dst) {
+    SampleArgs<double>& g = *(SampleArgs<double>*)dst;   // (dst is zeroed)
+    g.n = a.n, g.h = a.h, g.d = a.d, g.F = a.F, g.tpw = a.tpw;
+    g.first_index = a.first_index;
+    g.W = a.W, g.mean = a.mean, g.std = a.std, g.low = a.low, g.high = a.high;
+    g.zr = nullptr, g.zi = nullptr;
+    g.seed_lo = a.seed_lo, g.seed_hi = a.seed_hi, g.off_lo = a.off_lo, g.off_hi = a.off_hi;
+    sub_base(g.off_lo, g.off_hi, base);
+    g.t_begin = a.t_begin, g.row0_mean = a.row0_mean, g.white = a.white;
+    g.out = a.out;
+}
+inline void batch_form(const RolloutArgs<double>& a, void* dst) {
+    std::memcpy(dst, &a, sizeof(a));
+    ((RolloutArgs<double>*)dst)->dbg = nullptr;
+}
+inline void batch_form(const SelectArgs<double>& a, void* dst) {
+    std::memcpy(dst, &a, sizeof(a));
+    ((SelectArgs<double>*)dst)->dbg = nullptr;
+}
 // the batched launches: args[n] in DEVICE memory (the problems' keys are equal: plan.hip checked)
 // The batched sampler also serves the learned-dynamics step (icem_plan_step_learned*), which builds its key itself (family
 // LAUNCH_SAMPLE, form 10, wgs[0] for the LARGEST problem, wgs[1] = 0) at any horizon fast_sample_supported admits: problem p
@@ -477,6 +508,28 @@ void launch_rollout_hn_batch(const LaunchKey& key, const HnArgs* args_dev, const
 void launch_sample_rollout_batch(const LaunchKey& key, const FastIterArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_merge_batch(const LaunchKey& key, const MergeNoiseBatchArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_iter_ahead_batch(const LaunchKey& key, const IterAheadArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+// k_generic_batch.hip (float64; gk_sample_batch adds each problem's base to its block's offset, the others draw nothing)
+void launch_gk_sample_batch(const LaunchKey& key, const SampleArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_gk_shift_batch(const LaunchKey& key, const ShiftElitesArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_gk_rollout_rows_batch(const LaunchKey& key, const RolloutArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_gk_rollout_thread_batch(const LaunchKey& key, const RolloutArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_gk_select_batch(const LaunchKey& key, const SelectArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+// is there a batched instantiation of the thread-form rollout at this width and model kind?  (rollout_cost_kernel<double, 32, tanh>
+// spills registers -- tests/test_register_hygiene_cpu.py carries it -- and gets no twin)
+inline bool gk_rollout_thread_batched(int O, int kind) { return !(O == 32 && kind == ICEM_MODEL_TANH); }
+// LDS of the row-of-lanes rollout and the steps of actions it stages at a time: one rule for the solo and the batched launch
+inline int gk_rollout_rows_ch(int O, int h, int d, size_t tsize) {
+    const int tpw = 256 / (O <= 16 ? 16 : 32), ds = d <= 8 ? 8 : ((d + 1) & ~1);
+    const int ch = (int)(32768 / ((size_t)tpw * ds * tsize));   /* at most 32 KB of actions */
+    return ch < 1 ? 1 : (ch > h ? h : ch);
+}
+inline size_t gk_rollout_rows_lds(int O, int h, int d, size_t tsize) {
+    const int tpw = 256 / (O <= 16 ? 16 : 32), os = (O + 1) & ~1, ds = d <= 8 ? 8 : ((d + 1) & ~1);
+    return ((size_t)2 * tpw * os + (size_t)d * os + (size_t)tpw * gk_rollout_rows_ch(O, h, d, tsize) * ds) * tsize;
+}
+inline size_t gk_sample_quad_lds(int tpw, int h, int d, int hmax, size_t tsize) {
+    return ((((size_t)tpw * h * d + 1) & ~(size_t)1) + (size_t)h * hmax) * tsize;
+}
 inline void launch_sample_batch_recorded(const LaunchKey& key, const FastSampleArgs* args_dev, const BatchBases& bases, int n, hipStream_t st) {
     launch_sample_batch(key, args_dev, bases, ObsGather{}, n, st);
 }
@@ -504,6 +557,11 @@ constexpr LaunchFamilyRow LAUNCH_FAMILIES[] = {
     family_row<FastSampleArgs, launch_sample_batch_recorded>(LAUNCH_SAMPLE),
     family_row<FastSampleMergeArgs, launch_sample_merge_batch>(LAUNCH_SAMPLE_MERGE),
     family_row<HnArgs, launch_rollout_hn_batch>(LAUNCH_ROLLOUT_HN),
+    family_row<SampleArgs<double>, launch_gk_sample_batch>(LAUNCH_GK_SAMPLE),
+    family_row<ShiftElitesArgs<double>, launch_gk_shift_batch>(LAUNCH_GK_SHIFT),
+    family_row<RolloutArgs<double>, launch_gk_rollout_rows_batch>(LAUNCH_GK_ROLLOUT_ROWS),
+    family_row<RolloutArgs<double>, launch_gk_rollout_thread_batch>(LAUNCH_GK_ROLLOUT_THREAD),
+    family_row<SelectArgs<double>, launch_gk_select_batch>(LAUNCH_GK_SELECT),
 };
 inline const LaunchFamilyRow* launch_family(int family) {
     for (const LaunchFamilyRow& r : LAUNCH_FAMILIES)

@@ -195,7 +195,7 @@ static int one_launch_lists(const icem_handle* h, const BatchHint& bh, int n_row
 // and braces): nothing is launched, the batch is refused
 static int no_batched_form(const LaunchCtx& cx, const char* what) {
     cx.rec->unsupported = true;
-    return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_batch: ") + what);
+    return fail(ICEM_E_UNSUPPORTED, std::string(cx.rec->who) + what);
 }
 
 // rows -> costs (+ one sorted candidate list per workgroup when K > 0); returns the number of candidate lists
@@ -602,10 +602,10 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                            n_extra * c.act_dim <= 256;
         if (!shift_in_sampler) {
             T* dst = actions + (size_t)n_loc * hd;
-            int rc = gk_shift_elites(h, n_extra, shift_src, dst, st);
+            int rc = gk_shift_elites(h, n_extra, shift_src, dst, cx);
             if (rc) return rc;
             rc = gk_sample(h, n_extra, 0, b->mean, b->std, b->low, b->high, b->z_r_shift, b->z_i_shift,
-                           base + (uint64_t)c.opt_iters, c.horizon - 1, 0, dst, st);
+                           base + (uint64_t)c.opt_iters, c.horizon - 1, 0, dst, cx);
             if (rc) return rc;
         }
     }
@@ -700,12 +700,12 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
                     ICEM_HIP_TRY(hipGetLastError());
                     rc = ICEM_OK;
                 } else if (ext_z) {
-                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, off, 0, row0, actions, st);
+                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, off, 0, row0, actions, cx);
                 } else if (fast_sample_ok(h)) {
                     rc = launch_fast_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, off, row0, actions, cx,
                                             shift_in_sampler ? n_extra : 0, shift_src, base + (uint64_t)c.opt_iters);
                 } else {
-                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, nullptr, nullptr, off, 0, row0, actions, st);
+                    rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, nullptr, nullptr, off, 0, row0, actions, cx);
                 }
                 if (rc) return rc;
                 int tail2 = 0;
@@ -752,9 +752,9 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
     }
     // generic path (f64, external noise, shapes outside the fast list): one kernel per stage
     int rc = gk_sample(h, n_loc, lo, b->mean, b->std, b->low, b->high, b->z_r, b->z_i, base + (uint64_t)it, 0, row0,
-                       actions, st);
+                       actions, cx);
     if (rc) return rc;
-    rc = gk_rollout(h, n_loc + n_extra, b->obs0, actions, b->costs, nullptr, st);
+    rc = gk_rollout(h, n_loc + n_extra, b->obs0, actions, b->costs, nullptr, cx);
     if (rc) return rc;
     h->local.sel_cand = 0;
     if (c.world == 1 && gk_select_ok(h, n_cand, h->n_reuse, K)) {
@@ -763,6 +763,7 @@ int plan_iter_local_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
         h->local.sel_loc = n_loc;
         return ICEM_OK;
     }
+    if (cx.rec) return no_batched_form(cx, "the three-launch selection has no batched form");
     const int nblk = std::max(1, topk_blocks(n_cand));
     rc = gk_topk_partial(h, n_cand, K, b->costs, b->workspace, nblk, st);
     if (rc) return rc;
@@ -852,8 +853,9 @@ int plan_iter_merge_t(icem_handle* h, const icem_plan_buffers* b, int mpc_step, 
     if (c.world == 1 && h->local.sel_cand > 0 && h->local.lists == 0) {
         const int n_cand = h->local.sel_cand;
         h->local.sel_cand = 0;
-        return gk_select_refit(h, n_cand, h->local.sel_loc, b->costs, b->actions, a, st);
+        return gk_select_refit(h, n_cand, h->local.sel_loc, b->costs, b->actions, a, cx);
     }
+    if (cx.rec) return no_batched_form(cx, "the records merge has no batched form");
     return gk_merge_refit(h, a, st);
 }
 
@@ -1519,6 +1521,82 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     return nullptr;
 }
 
+// What the batched entries share behind their admission: the host side of every problem's step under a recorder, the
+// comparison of the problems' launch keys, the argument blob in handles[0]'s six-slot array (uploaded only when a byte changed),
+// one launch per recorded launch.  who: the entry's name for messages; spare: room a new array gets beyond the first blob (a later
+// step's blob may be larger: shifted elites); *launches_out: the kernel launches issued.
+static int run_recorded_batch(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, int32_t mpc_step, hipStream_t st,
+                              const BatchHint& hint, const std::string& who, size_t spare, long long* launches_out) {
+    // ---- the host side of every problem's step, recorded ----
+    // From here on the handles' host state runs ahead of the device: whatever return leaves before the last launch is
+    // enqueued takes every handle's armed state with it.
+    struct DisarmGuard {
+        icem_handle* const* handles;
+        int n;
+        bool armed = true;
+        ~DisarmGuard() {
+            for (int i = 0; armed && i < n; ++i) disarm(handles[i]);
+        }
+    } disarm_all{handles, n};
+    BatchBases bases{};   // each problem's noise stream base of this step: the recorded blocks' offsets are relative to it
+    std::vector<LaunchRecorder> recs(n);
+    int rc = ICEM_OK;
+    bool unsupported = false;
+    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
+        recs[i].base = bases.v[i] = call_base(handles[i], mpc_step);
+        recs[i].who = who.c_str();
+        recs[i].launches.reserve(3 * handles[i]->cfg.opt_iters + 2);   // (the float64 step's count; the f32 plans record 2 * iters + 1)
+        rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &recs[i]});
+        unsupported = unsupported || recs[i].unsupported;
+    }
+    if (rc == ICEM_OK && unsupported) rc = fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached");
+    const std::vector<LaunchDesc>& first = recs[0].launches;
+    const size_t L = first.size();
+    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
+        if (recs[i].launches.size() != L || L == 0) rc = fail(ICEM_E_STATE, who + "the problems' steps took different launches");
+        for (size_t l = 0; l < L && rc == ICEM_OK; ++l)
+            if (!(recs[i].launches[l].key == first[l].key)) rc = fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
+    }
+    if (rc != ICEM_OK) return rc;   // nothing was launched: the handles' half-armed state goes
+    // ---- argument blocks: one array per launch ----
+    std::vector<size_t> at(L);
+    size_t bytes = 0;
+    for (size_t l = 0; l < L; ++l) {
+        at[l] = bytes;
+        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
+        bytes += ((launch_family(first[l].key.family)->block_bytes * (size_t)n + 255) / 256) * 256;
+    }
+    std::vector<unsigned char> blob(bytes, 0);
+    for (size_t l = 0; l < L; ++l) {
+        const size_t one = launch_family(first[l].key.family)->block_bytes;
+        for (int i = 0; i < n; ++i) std::memcpy(blob.data() + at[l] + (size_t)i * one, recs[i].launches[l].block, one);
+    }
+    icem_handle* owner = handles[0];
+    const int slot = mpc_step % 6;
+    if (opt_i(OPT_AHEAD_STAMPS) && owner->batch_args.holds(slot).size() == bytes) {   // development: which bytes moved
+        const std::vector<unsigned char>& held = owner->batch_args.holds(slot);
+        int shown = 0;
+        for (size_t l = 0; l < L && shown < 12; ++l) {
+            const size_t one = launch_family(first[l].key.family)->block_bytes;
+            for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
+                if (blob[at[l] + o] != held[at[l] + o]) {
+                    std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
+                    ++shown;
+                    o = (o / 8 + 1) * 8 - 1;
+                }
+        }
+    }
+    ICEM_HIP_TRY(owner->batch_args.put(slot, blob, bytes + spare, st, &owner->batch_uploads));
+    // ---- the launches ----
+    for (size_t l = 0; l < L; ++l) {
+        launch_family(first[l].key.family)->launch(first[l].key, (const unsigned char*)owner->batch_args.dev(slot) + at[l], bases, n, st);
+        ICEM_HIP_TRY(hipGetLastError());
+    }
+    disarm_all.armed = false;
+    if (launches_out) *launches_out = (long long)L;
+    return ICEM_OK;
+}
+
 extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream) {
     if (int rc = admit_batch(handles, n, buffers != nullptr, false, "",
                              "icem_plan_step_batch: the handles must share one configuration (horizon, act_dim, populations, elites, flags)"))
@@ -1545,75 +1623,69 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
     for (int i = 0; i < n; ++i)
         if (const char* why = batch_ineligible(handles[i], &buffers[i], mpc_step, hint))
             return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_batch: ") + why);
-    // ---- the host side of every problem's step, recorded ----
-    // From here on the handles' host state runs ahead of the device: whatever return leaves before the last launch is
-    // enqueued takes every handle's armed state with it.
-    struct DisarmGuard {
-        icem_handle* const* handles;
-        int n;
-        bool armed = true;
-        ~DisarmGuard() {
-            for (int i = 0; armed && i < n; ++i) disarm(handles[i]);
-        }
-    } disarm_all{handles, n};
-    BatchBases bases{};   // each problem's noise stream base of this step: the recorded blocks' offsets are relative to it
-    std::vector<LaunchRecorder> recs(n);
-    int rc = ICEM_OK;
-    bool unsupported = false;
-    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        recs[i].base = bases.v[i] = call_base(handles[i], mpc_step);
-        recs[i].launches.reserve(2 * handles[i]->cfg.opt_iters + 1);
-        rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &recs[i]});
-        unsupported = unsupported || recs[i].unsupported;
-    }
-    if (rc == ICEM_OK && unsupported) rc = fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a launch without a batched form was reached");
-    const std::vector<LaunchDesc>& first = recs[0].launches;
-    const size_t L = first.size();
-    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        if (recs[i].launches.size() != L || L == 0) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' steps took different launches");
-        for (size_t l = 0; l < L && rc == ICEM_OK; ++l)
-            if (!(recs[i].launches[l].key == first[l].key)) rc = fail(ICEM_E_STATE, "icem_plan_step_batch: the problems' launches differ in shape");
-    }
-    if (rc != ICEM_OK) return rc;   // nothing was launched: the handles' half-armed state goes
-    // ---- argument blocks: one array per launch ----
-    std::vector<size_t> at(L);
-    size_t bytes = 0;
-    for (size_t l = 0; l < L; ++l) {
-        at[l] = bytes;
-        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, "icem_plan_step_batch: a recorded launch's family has no batched launch");
-        bytes += ((launch_family(first[l].key.family)->block_bytes * (size_t)n + 255) / 256) * 256;
-    }
-    std::vector<unsigned char> blob(bytes, 0);
-    for (size_t l = 0; l < L; ++l) {
-        const size_t one = launch_family(first[l].key.family)->block_bytes;
-        for (int i = 0; i < n; ++i) std::memcpy(blob.data() + at[l] + (size_t)i * one, recs[i].launches[l].block, one);
-    }
-    icem_handle* owner = handles[0];
-    const int slot = mpc_step % 6;
-    if (opt_i(OPT_AHEAD_STAMPS) && owner->batch_args.holds(slot).size() == bytes) {   // development: which bytes moved
-        const std::vector<unsigned char>& held = owner->batch_args.holds(slot);
-        int shown = 0;
-        for (size_t l = 0; l < L && shown < 12; ++l) {
-            const size_t one = launch_family(first[l].key.family)->block_bytes;
-            for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
-                if (blob[at[l] + o] != held[at[l] + o]) {
-                    std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
-                    ++shown;
-                    o = (o / 8 + 1) * 8 - 1;
-                }
-        }
-    }
-    ICEM_HIP_TRY(owner->batch_args.put(slot, blob, bytes + 4096, st, &owner->batch_uploads));
-    // ---- the launches ----
-    for (size_t l = 0; l < L; ++l) {
-        launch_family(first[l].key.family)->launch(first[l].key, (const unsigned char*)owner->batch_args.dev(slot) + at[l], bases, n, st);
-        ICEM_HIP_TRY(hipGetLastError());
-    }
-    disarm_all.armed = false;
-    return ICEM_OK;
+    return run_recorded_batch(handles, n, buffers, mpc_step, st, hint, "icem_plan_step_batch: ", 4096, nullptr);
 }
 
 extern "C" int64_t icem_batch_uploads(const icem_handle* h) { return h ? (int64_t)h->batch_uploads : 0; }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// icem_plan_step_batch_f64: the same for planners in the strict-parity arithmetic (the generic kernels)
+// ---------------------------------------------------------------------------------------------------------------------
+// A world-1 float64 step is, per iteration, gk_sample + gk_rollout + gk_select_refit, and in a step with shifted elites
+// gk_shift_elites + the t_begin = h - 1 sampler in front of iteration 0: seventeen dependent launches at five iterations, two of
+// them a single workgroup.  Their launchers record under a LaunchCtx like the f32 ones (families LAUNCH_GK_*), the batched kernels
+// (k_generic_batch.hip) run the solo kernels' bodies (generic_dev.h) on the block of problem blockIdx.y.
+// The path decisions of plan_iter_local_t / plan_iter_merge_t and of the generic launchers for a float64 handle, evaluated without
+// launching anything: does every launch of this handle's step have a batched twin?
+static const char* batch_f64_ineligible(const icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step) {
+    const icem_config& c = h->cfg;
+    if (c.world != 1) return "world must be 1 (sharded handles are not batched)";
+    if (b->z_r || b->z_i || b->z_r_shift || b->z_i_shift) return "external noise is not batched";
+    if (h->profiling || h->dbg) return "per-kernel profiling / debug stamps are per handle: switch them off";
+    if (opt_i(OPT_GK_SAMPLE) == 0 || opt_i(OPT_GK_ROLLOUT_THREAD) != 0 || opt_i(OPT_GK_SELECT) == 0)
+        return "the development options gk_sample / gk_rollout_thread / gk_select must be at their defaults: the batch mirrors the default kernels";
+    if (c.act_dim > WG / 4 || (long long)c.num_traj * c.act_dim > 262144) return "the sampler's one-thread-per-row form (num_traj * act_dim > 262144) is not batched";
+    if (c.opt_iters < 1 || h->pop.empty()) return "opt_iters";
+    if (!(h->O == 8 || h->O == 16 || h->O == 17 || h->O == 18 || h->O == 24 || h->O == 32)) return "the generic rollout is compiled for padded observation widths 8, 16, 17, 18, 24, 32 only";
+    if (h->has_terms && !gk_rollout_thread_batched(h->O, h->model_kind))
+        return "the thread-form rollout at padded width 32 with a tanh model has no batched instantiation (register budget)";
+    for (int it = 0; it < c.opt_iters; ++it) {
+        if (h->pop[it] > 8192) return "populations above 8192 rows per iteration are not batched";
+        if (!gk_select_ok(h, h->pop[it] + shift_rows(h, mpc_step, it), h->n_reuse, c.num_elites))
+            return "an iteration's pool takes the three-launch selection, which is not batched";
+    }
+    return nullptr;
+}
+
+extern "C" int icem_plan_step_batch_f64(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream) {
+    const std::string who = "icem_plan_step_batch_f64: ";
+    if (int rc = admit_batch(handles, n, buffers != nullptr, false, "",
+                             "icem_plan_step_batch_f64: the handles must share one configuration (horizon, act_dim, populations, elites, flags, dtype)"))
+        return rc;
+    if (handles[0]->cfg.dtype != ICEM_F64) return fail(ICEM_E_UNSUPPORTED, who + "dtype f64 only (f32 handles: icem_plan_step_batch)");
+    if (n == 1) return icem_plan_step(handles[0], &buffers[0], mpc_step, stream);
+    hipStream_t st = (hipStream_t)stream;
+    const icem_handle* h0 = handles[0];
+    for (int i = 0; i < n; ++i) {
+        icem_handle* h = handles[i];
+        if (h->cfg.world != 1) return fail(ICEM_E_UNSUPPORTED, who + "world must be 1 (sharded handles are not batched)");
+        int rc = check_plan(h, &buffers[i], mpc_step, 0, st);
+        if (rc) return rc;
+        if (h->O != h0->O || h->model_kind != h0->model_kind || h->has_terms != h0->has_terms)
+            return fail(ICEM_E_INVALID, who + "the handles must share the model's padded width and kind, and all or none carry icem_cost_terms "
+                                              "(the term list decides the rollout kernel)");
+    }
+    for (int i = 0; i < n; ++i)
+        if (const char* why = batch_f64_ineligible(handles[i], &buffers[i], mpc_step)) return fail(ICEM_E_UNSUPPORTED, who + why);
+    BatchHint hint;
+    hint.mult = n;
+    long long launches = 0;
+    const int rc = run_recorded_batch(handles, n, buffers, mpc_step, st, hint, who, 8192, &launches);
+    if (rc == ICEM_OK) handles[0]->batch_f64_launches = launches;
+    return rc;
+}
+
+extern "C" int64_t icem_batch_f64_launches(const icem_handle* h) { return h ? (int64_t)h->batch_f64_launches : 0; }
 
 // MpcICem.get_action as one call for a host caller: observation in, executed action (+ its pool's best cost) out.
 // The handle owns a small pinned, device-mapped block [obs | action, best cost | flag].  On the f32 fast path the first

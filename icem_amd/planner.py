@@ -453,6 +453,11 @@ class IcemPlanner:
         anything runs.  ``observations``: one per planner (``None``: already in ``planner.obs0``).
         Each planner's buffers afterwards are bit for bit those of its own :meth:`plan_step`.  Returns the executed actions
         (device tensors, no host sync)."""
+        return IcemPlanner._step_batch("icem_plan_step_batch", planners, observations)
+
+    @staticmethod
+    def _step_batch(entry: str, planners, observations):
+        """The host side the batched plan entries share: buffers, one ``mpc_step``, observations, the C call ``entry``."""
         pls = list(planners)
         n = len(pls)
         if n == 0:
@@ -468,14 +473,30 @@ class IcemPlanner:
                 pl.obs0.copy_(torch.as_tensor(np.asarray(observations[i], dtype=np.float64), dtype=pl.dt), non_blocking=False)
         hs = (C.c_void_p * n)(*[pl._h for pl in pls])
         bs = (L.IcemPlanBuffersC * n)(*[pl._cb for pl in pls])
-        L.check(lib.icem_plan_step_batch(hs, n, bs, step, pls[0]._stream()))
+        L.check(getattr(lib, entry)(hs, n, bs, step, pls[0]._stream()))
         for pl in pls:
             pl.mpc_step += 1
         return [pl.executed for pl in pls]
 
+    @staticmethod
+    def plan_step_batch_f64(planners: Sequence["IcemPlanner"], observations=None):
+        """:meth:`plan_step_batch` for planners in the strict-parity arithmetic (``dtype="f64"``), as
+        ``icem_plan_step_batch_f64``: the generic kernels' sampler, rollout and one-launch selection, each ONE launch for all
+        planners -- 3 launches per iteration, 2 more in a step with shifted elites, whatever the number of planners.  Served:
+        one GPU, device noise, at most 8192 rows per iteration, the default arrangement of the generic kernels; anything else
+        raises ``IcemError`` (``ICEM_E_UNSUPPORTED`` / ``ICEM_E_INVALID``) before anything runs.  Each planner's buffers
+        afterwards are bit for bit those of its own :meth:`plan_step`.  Returns the executed actions (device tensors, no host
+        sync)."""
+        return IcemPlanner._step_batch("icem_plan_step_batch_f64", planners, observations)
+
     @property
     def batch_uploads(self) -> int:
         return int(self.lib.icem_batch_uploads(self._h))
+
+    @property
+    def batch_f64_launches(self) -> int:
+        """Kernel launches of the last float64 batch step this planner led (``icem_batch_f64_launches``)."""
+        return int(self.lib.icem_batch_f64_launches(self._h))
 
     # ------------------------------------------------------------------ the learned-dynamics step (declared RSSM)
     def learned_step_ok(self) -> bool:

@@ -420,6 +420,30 @@ int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step,
 int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream);
 int64_t icem_batch_uploads(const icem_handle* h); /* how often handles[0]'s argument array was (re)written (measurement) */
 
+/* The same for planners in the strict-parity arithmetic (dtype f64, the generic kernels): arguments and contract are those of
+ * icem_plan_step_batch -- n in [1, 32] (n == 1 is icem_plan_step), one configuration, and also one padded model width, one model
+ * kind, and either every handle with icem_cost_terms or none (else ICEM_E_INVALID: the term list decides the rollout kernel, so a
+ * planner with a term list beside one without is refused); models, costs (the parametric spec and the term lists), seeds, bounds,
+ * episodes and observations are per problem.  Every problem's outputs -- executed action, best cost, mean, std, both elite halves
+ * and their costs, the last pool and its costs -- are bit for bit those of its own icem_plan_step: the batched kernels run the
+ * solo kernels' bodies (csrc/generic_dev.h) on the argument block of problem blockIdx.y.  A step launches what a solo step
+ * launches, whatever n: sampler, rollout and the one-launch selection + refit per iteration (3 * opt_iters), and in a step with
+ * shifted elites their copy and their last action's sampler in front (2 more).  No host synchronisation; no allocation after
+ * the first call of a batch size; one small host-to-device copy on `stream` when the argument blocks changed (the first steps;
+ * icem_batch_uploads counts them for this entry too).
+ *   Served: dtype f64, world == 1, device noise (colored, and white at noise_beta <= 0), rng_rounds 7 and 10, every horizon,
+ * act_dim, cost mode and flag combination of the generic path, padded observation widths 8 / 16 / 17 / 18 / 24 / 32 (linear and
+ * tanh), at most 8192 rows per iteration: the row-of-lanes rollout for the parametric cost, the thread-per-trajectory rollout
+ * where the handles carry icem_cost_terms.
+ *   ICEM_E_UNSUPPORTED, before anything is launched and with every handle left as it was: f32 handles (icem_plan_step_batch is
+ * theirs), a non-NULL z_*, sharded handles, profiling or debug stamps switched on, a population above 8192 rows, an iteration
+ * whose pool the one-launch selection does not admit (it would take the three-launch selection), a development option
+ * gk_sample / gk_rollout_thread / gk_select away from its default, num_traj * act_dim > 262144 (the sampler's one-thread-per-row
+ * form), and icem_cost_terms on a tanh model of padded width 32 (that instantiation of the thread-form rollout spills registers
+ * and has no batched twin).  Where a batch pays against stepping alone: EXPERIMENTS.md R8.1 (tools/f64_batch_bench.py). */
+int icem_plan_step_batch_f64(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream);
+int64_t icem_batch_f64_launches(const icem_handle* h); /* kernel launches of the last f64 batch step this handle led (handles[0]); measurement */
+
 /* The MPC step of the learned-dynamics configuration (the declared RSSM of the learned-dynamics rollout below; BASELINE
  * configs[4]) as ONE call, for one planner or for n planners at once: the loop a caller would otherwise drive operator by
  * operator.  Per CEM iteration i of MPC step s: sample population_sizes[i] rows at stream offset
