@@ -594,7 +594,8 @@ class MpcICemHip(MpcController):
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152) -- through ``icem_plan_step_batch``:
         every stage of the planning step is one launch for all of them.  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same hooks).  Device path with
-        device noise (the HalfCheetah-sized tile shapes, and the Door / Relocate / FetchPickAndPlace envs at h = 30); or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
+        device noise (the HalfCheetah-sized tile shapes, the Door / Relocate / FetchPickAndPlace envs at h = 30, and the envs on the
+        GEMM kernels at h = 30: HumanoidStandup at o = 378, Humanoid, Ant, Hopper, Reacher, FetchReach); or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
         one configuration: the whole step is ``icem_plan_step_learned_batch``, every stage one launch for all of them (where
         that entry does not serve them -- another horizon, f64 ... -- ONE ``rollout_cost_batch`` launch per CEM iteration scores
         their populations and sampling and the distribution update stay one launch per controller).  Anything else: call

@@ -157,7 +157,7 @@ int wide_rollout_lists(int n_rows);
 int wide_kb(int o, int d);
 int wide_xs(int o, int d);
 void pack_wide_model(int o, int d, const double* A, const double* B, std::vector<float>& Mp);
-void launch_rollout_wide(const WideRolloutArgs& a, int kind, hipStream_t st);
+void launch_rollout_wide(const LaunchCtx& cx, const WideRolloutArgs& a, int kind);
 // ... the same on the bf16 matrix cores (k_rollout_wide_split.hip): every f32 operand as three bf16 planes, six products
 // per MAC, up to 80 trajectories per workgroup; a.Mp = pack_wide_model_split's planes, a.kb / a.xs = wide_split_kb / _xs
 int wide_split_kb(int o, int d);
@@ -167,10 +167,19 @@ bool wide_split_fits(int o, int d);   // the workgroup's rows + planes in 160 KB
 int wide_model_imbalance_log2(int o, int d, const double* A, const double* B);   // ICEM_WIDE_AUTO's criterion (k_rollout_wide_split.hip)
 void pack_wide_model_split(int o, int d, const double* A, const double* B, int planes, std::vector<unsigned short>& Mb, float* minv,
                            std::vector<float>* ksc, std::vector<float>* csc, float* sbound);
-void launch_rollout_wide_split(const WideRolloutArgs& a, int kind, hipStream_t st);
+void launch_rollout_wide_split(const LaunchCtx& cx, const WideRolloutArgs& a, int kind);
 // rows [row0, row0 + n_tail) of the same pool one workgroup each, from the row-major f32 model (A [o, o], B [d, o]); costs only
-void launch_rollout_rows_wide(const WideRolloutArgs& a, int row0, int n_tail, const float* A, const float* B, int kind,
-                              hipStream_t st);
+struct WideRowsArgs {
+    int row0, n_tail, o, d, h, cost_mode;
+    WideCost wc;
+    const CostArgs<float>* cs;
+    const float* A;  // [o, o] row-major
+    const float* B;  // [d, o]
+    const float* obs0;
+    const float* actions;
+    float* costs;
+};
+void launch_rollout_rows_wide(const LaunchCtx& cx, const WideRolloutArgs& a, int row0, int n_tail, const float* A, const float* B, int kind);
 
 // world == 1: global sorted top-K straight from the waves' candidate lists (+ kept elites), gather of
 // the elite rows from the pool, refit, and the last-iteration epilogue.
@@ -327,6 +336,7 @@ struct FastSampleMergeArgs {
 };
 bool sample_folded_merge_ok(int h, int d, int rounds, int K);
 void launch_sample_folded_merge(const LaunchCtx& cx, const FastSampleMergeArgs& a);
+bool sample_batch_compiled(int h);   // do the batched forms of BOTH sampling launches exist at this horizon? (ICEM_SAMPLE_BATCH_HORIZONS)
 
 // K1+K2+K3 in one launch (small populations): r.actions == s.out, r.n_rows == s.n + s.n_shift.
 struct FastIterArgs {
@@ -360,9 +370,11 @@ struct BatchHint {
 //  rollout -- the two-kernel iterations of the Door / Relocate / FetchPickAndPlace shapes)
 // (LAUNCH_GK_*: the generic kernels of a float64 step, icem_plan_step_batch_f64 -- the quad sampler, the shifted elites' copy, the
 //  rollout with a row of lanes / a thread per trajectory, the one-launch selection + refit; generic_kernels.hip, k_generic_batch.hip)
+// (LAUNCH_ROLLOUT_WIDE / _WIDE_SPLIT / _ROWS_WIDE: the GEMM-path rollouts -- exact f32 tiles, the 16-bit planes, the row-by-row tail
+//  behind the exact kernel; k_rollout_wide_batch.hip, k_rollout_wide_split_batch.hip.  A batch keeps each problem's SOLO launch shape)
 enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3, LAUNCH_SAMPLE = 4, LAUNCH_SAMPLE_MERGE = 5,
                           LAUNCH_ROLLOUT_HN = 6, LAUNCH_GK_SAMPLE = 7, LAUNCH_GK_SHIFT = 8, LAUNCH_GK_ROLLOUT_ROWS = 9, LAUNCH_GK_ROLLOUT_THREAD = 10,
-                          LAUNCH_GK_SELECT = 11 };
+                          LAUNCH_GK_SELECT = 11, LAUNCH_ROLLOUT_WIDE = 12, LAUNCH_ROLLOUT_WIDE_SPLIT = 13, LAUNCH_ROLLOUT_ROWS_WIDE = 14 };
 struct LaunchKey {
     int family = 0;
     int h = 0, d = 0, O = 0, kind = 0, arith = 0;   // (rollout_hn: O = the observation width o)
@@ -370,6 +382,8 @@ struct LaunchKey {
     // sample_rollout: 0 = plain, 1 = lists merge in the prologue, 2 = records merge; iter_ahead: PM; merge_noise: 1 = with noise;
     // sample: the generator's rounds; sample_merge: 1 = lists merge, 2 = records merge; rollout_hn: the term program, N32 << 16 | N4 << 8 | NP
     // gk_sample: O = HMAX, waves = trajectories per workgroup, form = the generator's rounds; gk_rollout_*: O = the padded width
+    // rollout_wide: O = o, arith = 1 (exact f32), waves = NT, form = EXT; rollout_wide_split: arith = 2 (fp16 planes) / 3 (bf16),
+    // waves = NCT, form = EXT | FIVE << 1; rollout_rows_wide: O = o, form = EXT, wgs[0] = the tail's rows
     int form = 0;
     int wgs[3] = {0, 0, 0};   // workgroups per role (of ONE problem); the grid is their sum
     bool operator==(const LaunchKey& o) const { return std::memcmp(this, &o, sizeof(LaunchKey)) == 0; }
@@ -383,6 +397,7 @@ struct LaunchDesc {
     LaunchKey key;
     static constexpr size_t BLOCK = sizeof(IterAheadArgs) > sizeof(RolloutArgs<double>) ? sizeof(IterAheadArgs) : sizeof(RolloutArgs<double>);
     static_assert(sizeof(SelectArgs<double>) <= BLOCK && sizeof(SampleArgs<double>) <= BLOCK, "LaunchDesc::block");
+    // (every family's block is held to BLOCK by family_row's static_assert below: WideRolloutArgs, WideRowsArgs included)
     alignas(8) unsigned char block[BLOCK];
 };
 struct LaunchRecorder {
@@ -465,6 +480,20 @@ inline void batch_form(const FastSampleMergeArgs& a, unsigned long long base, vo
     std::memcpy(&g.m, &a.m, sizeof(a.m));
     g.m.dbg = nullptr;
 }
+// (member by member into the zeroed block: the padding behind planes / sbound / flip_th stays zero)
+inline void batch_form(const WideRolloutArgs& a, void* dst) {
+    WideRolloutArgs& g = *(WideRolloutArgs*)dst;
+    g.n_rows = a.n_rows, g.n_cand = a.n_cand, g.K = a.K, g.o = a.o, g.d = a.d, g.h = a.h, g.kb = a.kb, g.xs = a.xs;
+    g.planes = a.planes, g.minv = a.minv, g.ksc = a.ksc, g.csc = a.csc, g.sbound = a.sbound, g.cost_mode = a.cost_mode;
+    g.lin_idx = a.lin_idx, g.flip_idx = a.flip_idx, g.ctrl_w = a.ctrl_w, g.lin_w = a.lin_w, g.flip_pen = a.flip_pen, g.flip_th = a.flip_th;
+    g.cs = a.cs, g.dbg = nullptr, g.Mp = a.Mp, g.obs0 = a.obs0, g.actions = a.actions, g.costs = a.costs;
+    g.part_c = a.part_c, g.part_i = a.part_i, g.part_k = a.part_k;
+}
+inline void batch_form(const WideRowsArgs& a, void* dst) {
+    WideRowsArgs& g = *(WideRowsArgs*)dst;
+    g.row0 = a.row0, g.n_tail = a.n_tail, g.o = a.o, g.d = a.d, g.h = a.h, g.cost_mode = a.cost_mode, g.wc = a.wc;
+    g.cs = a.cs, g.A = a.A, g.B = a.B, g.obs0 = a.obs0, g.actions = a.actions, g.costs = a.costs;
+}
 inline void batch_form(const HnArgs& a, void* dst) {
     HnArgs& g = *(HnArgs*)dst;
     std::memcpy(&g.r, &a.r, sizeof(a.r));
@@ -514,6 +543,10 @@ void launch_gk_shift_batch(const LaunchKey& key, const ShiftElitesArgs<double>* 
 void launch_gk_rollout_rows_batch(const LaunchKey& key, const RolloutArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_gk_rollout_thread_batch(const LaunchKey& key, const RolloutArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_gk_select_batch(const LaunchKey& key, const SelectArgs<double>* args_dev, const BatchBases& bases, int n, hipStream_t st);
+// k_rollout_wide_batch.hip, k_rollout_wide_split_batch.hip (draw nothing: bases unused; grid = key.wgs[0] x n, the problem's own)
+void launch_rollout_wide_batch(const LaunchKey& key, const WideRolloutArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_rollout_wide_split_batch(const LaunchKey& key, const WideRolloutArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+void launch_rollout_rows_wide_batch(const LaunchKey& key, const WideRowsArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 // is there a batched instantiation of the thread-form rollout at this width and model kind?  (rollout_cost_kernel<double, 32, tanh>
 // spills registers -- tests/test_register_hygiene_cpu.py carries it -- and gets no twin)
 inline bool gk_rollout_thread_batched(int O, int kind) { return !(O == 32 && kind == ICEM_MODEL_TANH); }
@@ -562,6 +595,9 @@ constexpr LaunchFamilyRow LAUNCH_FAMILIES[] = {
     family_row<RolloutArgs<double>, launch_gk_rollout_rows_batch>(LAUNCH_GK_ROLLOUT_ROWS),
     family_row<RolloutArgs<double>, launch_gk_rollout_thread_batch>(LAUNCH_GK_ROLLOUT_THREAD),
     family_row<SelectArgs<double>, launch_gk_select_batch>(LAUNCH_GK_SELECT),
+    family_row<WideRolloutArgs, launch_rollout_wide_batch>(LAUNCH_ROLLOUT_WIDE),
+    family_row<WideRolloutArgs, launch_rollout_wide_split_batch>(LAUNCH_ROLLOUT_WIDE_SPLIT),
+    family_row<WideRowsArgs, launch_rollout_rows_wide_batch>(LAUNCH_ROLLOUT_ROWS_WIDE),
 };
 inline const LaunchFamilyRow* launch_family(int family) {
     for (const LaunchFamilyRow& r : LAUNCH_FAMILIES)

@@ -355,10 +355,11 @@ bool sample_folded_pack_ok(int h, int d, int rounds, int K) {
 }
 
 // horizons at which a recorded sampling launch has a batched form: what a batch of TileHN handles reaches (ICEM_HN_SHAPES are
-// all h = 30).  sample_folded_merge_batch_kernel is compiled for these only; sample_folded_batch_kernel for every horizon of
-// the folded sampler (the learned step's), but icem_plan_step_batch records a sampler only where BOTH exist
+// all h = 30), and what a batch of GEMM-kernel handles is admitted at (plan.hip: batch_ineligible).
+// sample_folded_merge_batch_kernel is compiled for these only; sample_folded_batch_kernel for every horizon of the folded sampler
+// (the learned step's), but icem_plan_step_batch records a sampler only where BOTH exist
 #define ICEM_SAMPLE_BATCH_HORIZONS(X) X(30)
-static bool sample_batch_compiled(int h) {
+bool sample_batch_compiled(int h) {
 #define X(HH) \
     if (h == HH) return true;
     ICEM_SAMPLE_BATCH_HORIZONS(X)

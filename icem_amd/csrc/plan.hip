@@ -202,7 +202,6 @@ static int no_batched_form(const LaunchCtx& cx, const char* what) {
 int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const void* obs0, const void* actions,
                         void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k, int n_tail, int* tail_out) {
-    if (cx.rec && !h->hn_tile) return no_batched_form(cx, "this configuration's rollout launch has no batched form");
     hipStream_t st = cx.st;
     int rc = ensure_fast_model(h);   // (per handle, also ahead of a batch's recorded launches: uploads only)
     if (rc) return rc;
@@ -271,17 +270,18 @@ int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const voi
         w.part_k = part_k;
         {
             ProfScope prof(h, ICEM_K_ROLLOUT, (long long)n_rows * h->cfg.horizon, st);
-            if (exact) launch_rollout_wide(w, h->model_kind, st);
-            else launch_rollout_wide_split(w, h->model_kind, st);
+            if (exact) launch_rollout_wide(cx, w, h->model_kind);
+            else launch_rollout_wide_split(cx, w, h->model_kind);
             // (the row-wise kernel BESIDE the tile kernel on a second stream instead of behind it was measured: 4.70
             //  instead of 4.15 ms per MPC step -- the three CUs that host a row workgroup finish their tile workgroup
             //  late, and the launch waits for its slowest workgroup; EXPERIMENTS.md R3.7)
-            if (split_tail) launch_rollout_rows_wide(w, n_rows, n_tail, (const float*)h->A_dev, (const float*)h->B_dev, h->model_kind, st);
+            if (split_tail) launch_rollout_rows_wide(cx, w, n_rows, n_tail, (const float*)h->A_dev, (const float*)h->B_dev, h->model_kind);
         }
         ICEM_HIP_TRY(hipGetLastError());
         if (lists_out) *lists_out = exact ? wide_rollout_lists(n_rows) : wide_split_lists(n_rows);
         return ICEM_OK;
     }
+    if (cx.rec) return no_batched_form(cx, "this configuration's rollout launch has no batched form");   // (rollout16 alone: a tile shape's two-kernel iteration)
     FastRolloutArgs a = fast_rollout_args(h, n_rows, n_cand, K, obs0, actions, costs, part_c, part_i);
     a.part_k = part_k;
     const int grid = rollout_lists(h->cfg.horizon, h->cfg.act_dim, h->Of, n_rows);
@@ -1490,15 +1490,17 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     if (c.dtype != ICEM_F32 || !h->use_fast) return "dtype f32 on the throughput kernels only";
     if (b->z_r || b->z_i || b->z_r_shift || b->z_i_shift) return "external noise is not batched";
     if (h->profiling || h->dbg) return "per-kernel profiling / debug stamps are per handle: switch them off";
-    if (gemm_rollout(h) && !h->hn_tile)
-        return "only the 16-trajectory tile kernels (o <= 20 shapes) and the TileHN kernel (the Door / Relocate / FetchPickAndPlace shapes) are batched";
+    const bool gemm = gemm_rollout(h) && !h->hn_tile;   // the GEMM-kernel shapes: wide observations, and the narrow ones no tile kernel serves
     if (!fast_rollout_ok(h, K) || !fast_sample_ok(h) || K + 1 > 12 || c.rng_rounds != 10)
-        return h->hn_tile ? "the merge cannot ride in the sampler's prologue (num_elites <= 11, the default generator)" : "shape outside the single-launch kernels";
+        return (h->hn_tile || gemm) ? "the merge cannot ride in the sampler's prologue (num_elites <= 11, the default generator)" : "shape outside the single-launch kernels";
     if (h->ride.merge_pending || h->ride.pack_pending) return "a deferred merge is pending: finish the MPC step first";
     if (c.opt_iters < 1) return "opt_iters";
-    if (h->hn_tile) {
-        // sampler (shifted elites in its extra workgroup; from iteration 1 on the previous merge in its prologue) + TileHN rollout
-        // per iteration, then the last merge: the path decisions of plan_iter_local_t for these handles
+    // (TileHN shapes are compiled at h = 30; the GEMM kernels take any horizon, the batched merge-prologue sampler does not)
+    if (gemm && !sample_batch_compiled(c.horizon)) return "the batched samplers of a GEMM-kernel shape are compiled for horizon 30 only";
+    if (h->hn_tile || gemm) {
+        // sampler (shifted elites in its extra workgroup; from iteration 1 on the previous merge in its prologue) + TileHN or GEMM
+        // rollout (exact f32 tiles with the row-by-row tail behind them, or the 16-bit planes) per iteration, then the last merge:
+        // the path decisions of plan_iter_local_t for these handles
         if (h->pop.empty() || h->pop[0] > 8192) return "populations above 8192 rows per iteration are not batched: they fill the chip by themselves";
         if (shift_rows(h, mpc_step, 0, false) * c.act_dim > 256) return "too many shifted elites for the sampling launch";
         if (c.opt_iters > 1 && !sample_folded_merge_ok(c.horizon, c.act_dim, c.rng_rounds, K))
@@ -1614,6 +1616,13 @@ extern "C" int icem_plan_step_batch(icem_handle* const* handles, int32_t n, cons
         // (a handle that is not on the TileHN kernel beside one that is: refused below, as unsupported)
         if (h->hn_tile && h0->hn_tile && (h->obs_dim != h0->obs_dim || std::memcmp(h->hn_prog, h0->hn_prog, sizeof(h->hn_prog)) != 0))
             return fail(ICEM_E_INVALID, "icem_plan_step_batch: TileHN handles must share the observation width and the compiled term program");
+        // GEMM-kernel handles: one launch serves all problems, so one instantiation -- width, kind (above), arithmetic in effect, term list or none
+        const bool g = gemm_rollout(h) && !h->hn_tile, g0 = gemm_rollout(h0) && !h0->hn_tile;
+        if (g && g0 && (h->obs_dim != h0->obs_dim || h->wide_eff != h0->wide_eff || h->has_terms != h0->has_terms))
+            return fail(ICEM_E_INVALID, "icem_plan_step_batch: GEMM-kernel handles must share the observation width, the wide arithmetic in effect "
+                                        "(icem_wide_arith) and all or none carry icem_cost_terms");
+        if ((g && h0->hn_tile) || (h->hn_tile && g0))
+            return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_batch: a TileHN handle and a GEMM-kernel handle take different rollout launches and cannot share a batch");
     }
     // the batch's shape hint.  The noise-ahead launches from where they measure faster than the single-launch kernels: 12 problems
     // of 4096 rows (160 against 161 us per step; 16: 194 against 212; 8: 129 against 128; 6: 115 against 100 -- EXPERIMENTS R6.3)

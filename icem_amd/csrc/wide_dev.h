@@ -3,6 +3,7 @@
 // Anonymous namespace: every translation unit gets its own copy (same bits).
 #pragma once
 #include "cost_terms_dev.h"
+#include "fused_dev.h"    // gptr
 #include "icem_fused.h"   // WideCost
 
 namespace icem {
@@ -88,6 +89,20 @@ __device__ __forceinline__ float wide_accumulate(float acc, float c, int t, int 
     if (t == 0 || cost_mode == 2) return c;
     if (cost_mode == 0) return acc + c;
     return (c < acc || c != c) ? c : acc;
+}
+
+// The GEMM kernels' argument blocks read from DEVICE memory (a batch's launches: blockIdx.y = the problem): the pointers re-read as
+// global addresses (fused_dev.h: gptr), the development stamps off -- they are per handle and never batched
+__device__ __forceinline__ WideRolloutArgs from_device(const WideRolloutArgs& m) {
+    WideRolloutArgs a = m;
+    a.ksc = gptr(m.ksc), a.csc = gptr(m.csc), a.cs = gptr(m.cs), a.dbg = nullptr, a.Mp = gptr(m.Mp), a.obs0 = gptr(m.obs0);
+    a.actions = gptr(m.actions), a.costs = gptr(m.costs), a.part_c = gptr(m.part_c), a.part_i = gptr(m.part_i), a.part_k = gptr(m.part_k);
+    return a;
+}
+__device__ __forceinline__ WideRowsArgs from_device(const WideRowsArgs& m) {
+    WideRowsArgs a = m;
+    a.cs = gptr(m.cs), a.A = gptr(m.A), a.B = gptr(m.B), a.obs0 = gptr(m.obs0), a.actions = gptr(m.actions), a.costs = gptr(m.costs);
+    return a;
 }
 
 }  // namespace

@@ -447,8 +447,10 @@ class IcemPlanner:
     def plan_step_batch(planners: Sequence["IcemPlanner"], observations=None):
         """One MPC step of every planner of ``planners`` (one configuration; models, costs, seeds and observations of their
         own) as ``icem_plan_step_batch``: the reference's parallel episodes (icem/misc/rollout_utils.py:46-58, 129-152),
-        every stage one launch for all of them.  Served: the o <= 20 tile shapes (HalfCheetah ...) and the TileHN shapes -- Door,
-        Relocate, FetchPickAndPlace at h = 30, planners that share the compiled term program of their cost terms -- at up to
+        every stage one launch for all of them.  Served: the o <= 20 tile shapes (HalfCheetah ...), the TileHN shapes -- Door,
+        Relocate, FetchPickAndPlace at h = 30, planners that share the compiled term program of their cost terms -- and the
+        GEMM-kernel shapes at h = 30 -- HumanoidStandup (o = 378), Humanoid, Ant, Hopper, Reacher, FetchReach: planners that share
+        the observation width, the wide arithmetic in effect (:attr:`wide_arith`) and all or none carry cost terms -- at up to
         8192 rows per iteration; anything else raises ``IcemError`` (``ICEM_E_UNSUPPORTED`` / ``ICEM_E_INVALID``) before
         anything runs.  ``observations``: one per planner (``None``: already in ``planner.obs0``).
         Each planner's buffers afterwards are bit for bit those of its own :meth:`plan_step`.  Returns the executed actions

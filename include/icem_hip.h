@@ -412,11 +412,23 @@ int icem_plan_step(icem_handle* h, const icem_plan_buffers* b, int32_t mpc_step,
  *     for the tiles of all problems together: the two- and several-waves-per-tile arrangements that serve one small
  *     population alone are not batched.  At the benchmark's populations that is the arrangement that fills the chip from four
  *     problems on; for where a batch pays against stepping alone see EXPERIMENTS.md R7.4 (tools/hn_batch_bench.py).
- * Anything else -- handles on the GEMM kernels (wide observations; a term list outside the compiled programs; ICEM_TILE_F32 on
- * a TileHN shape), f64, external noise, sharded handles, populations above 8192 rows per iteration (they fill the chip
- * alone), profiling switched on -- is ICEM_E_UNSUPPORTED.  Whatever is refused is refused before anything is launched, and
- * every handle is left as it was.  n in [1, 32]; n == 1 is icem_plan_step.  No host synchronisation; one small host-to-device
- * copy on `stream` when the argument blocks changed (the first steps: the blocks of step s are those of step s - 6). */
+ *   - the GEMM-kernel shapes at h = 30 -- wide observations (HumanoidStandup o = 378, Humanoid o = 376, Ant o = 113 with its term
+ *     list, any 32 < o <= 384) on the 16-bit planes or the exact-f32 kernel, and the narrow shapes no tile kernel serves (Hopper,
+ *     Reacher, FetchReach; a term list outside the compiled programs; ICEM_TILE_F32 on a TileHN shape) on the exact-f32 kernel --
+ *     whose iterations are the same sampler pair and a GEMM rollout (rollout_wide_split_kernel, or rollout_wide_kernel with
+ *     rollout_rows_wide_kernel behind it for trailing shifted elites): num_elites <= 11, rng_rounds = 10, shifted elites that fit
+ *     the sampling launch (rows * act_dim <= 256).  Every problem keeps the launch shape it has alone (grid.x = its own
+ *     workgroups, grid.y = the problem), so one problem's four or sixteen workgroups become 4 n or 16 n on the chip's 256 CUs.
+ *     The handles must also share the observation width, the wide arithmetic IN EFFECT (icem_wide_arith: a model that
+ *     ICEM_WIDE_AUTO sends to the bf16 planes beside one on the fp16 planes is refused) and all or none carry icem_cost_terms
+ *     (else ICEM_E_INVALID).  Not served (ICEM_E_UNSUPPORTED): another horizon (the batched merge-prologue sampler is compiled
+ *     for h = 30); a TileHN handle beside a GEMM-kernel handle.  (Every instantiation of the three rollout kernels has its
+ *     batched twin: none had to be left out for its registers.)  Where a batch pays, per population and n: EXPERIMENTS.md R9.1 (tools/wide_batch_bench.py).
+ * Anything else -- f64, external noise, sharded handles, num_elites > 11, other generators, populations above 8192 rows per
+ * iteration (they fill the chip alone), profiling or debug stamps switched on -- is ICEM_E_UNSUPPORTED.  Whatever is refused is
+ * refused before anything is launched, and every handle is left as it was.  n in [1, 32]; n == 1 is icem_plan_step.  No host
+ * synchronisation; one small host-to-device copy on `stream` when the argument blocks changed (the first steps: the blocks of
+ * step s are those of step s - 6).  Solo and batched steps may alternate on a handle. */
 int icem_plan_step_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t mpc_step, void* stream);
 int64_t icem_batch_uploads(const icem_handle* h); /* how often handles[0]'s argument array was (re)written (measurement) */
 
