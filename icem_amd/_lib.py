@@ -137,6 +137,8 @@ SYMBOLS = [
     ("icem_wide_model_imbalance_log2", C.c_int, [_I32, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icem_set_tile_arith", C.c_int, [_H, _I32]),
     ("icem_tile_arith", C.c_int, [_H]),
+    ("icem_set_f64_arith", C.c_int, [_H, _I32]),
+    ("icem_f64_arith", C.c_int, [_H]),
     ("icem_profile_overhead", C.c_int, [_VP, _I32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("icem_plan_step_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, _VP]),
     ("icem_batch_uploads", C.c_int64, [_H]),

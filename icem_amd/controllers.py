@@ -413,12 +413,14 @@ class MpcICemHip(MpcController):
     ``dtype`` ("f32" | "f64"), ``seed``, ``rng_rounds`` (10 | 7), ``device``,
     ``noise_source`` ("philox": device counter RNG; "numpy_legacy": the reference's draws from
     the global ``np.random`` stream, in the reference's order -- parity mode; or a callable
-    ``noise(num) -> (z_r, z_i)``), ``process_group`` / ``rank`` / ``world`` to shard N over GPUs.
+    ``noise(num) -> (z_r, z_i)``), ``process_group`` / ``rank`` / ``world`` to shard N over GPUs,
+    ``f64_arith`` ("chain" | "mfma", with ``dtype="f64"``: ``IcemPlanner.set_f64_arith`` -- "mfma" serves observations
+    wider than 32 in float64).
     """
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
                  noise_source: Union[str, Callable] = "philox", process_group=None, rank=0, world=1,
-                 deterministic_replay=False, **kwargs):
+                 deterministic_replay=False, f64_arith=None, **kwargs):
         super().__init__(**kwargs)
         self._parse_action_sampler_params(**dict(action_sampler_params))
         self._check_validity_parameters()
@@ -439,6 +441,8 @@ class MpcICemHip(MpcController):
                 "Implement method {} to compute cost along trajectory".format(cfg.cost_mode))
         self.planner = IcemPlanner(cfg, self.env.action_space.low, self.env.action_space.high, device=device,
                                    process_group=process_group)
+        if f64_arith is not None:
+            self.planner.set_f64_arith(f64_arith)
         self._bind_models(world)
         self._elite_costs = None
         self._elite_actions = None

@@ -286,6 +286,8 @@ int icem_destroy(icem_handle* h) {
     if (h->Mwh_dev) (void)hipFree(h->Mwh_dev);
     if (h->Mwh_ksc_dev) (void)hipFree(h->Mwh_ksc_dev);
     if (h->wide_cs_dev) (void)hipFree(h->wide_cs_dev);
+    if (h->M64_dev) (void)hipFree(h->M64_dev);
+    if (h->f64_cs_dev) (void)hipFree(h->f64_cs_dev);
     if (h->hn_cs_dev) (void)hipFree(h->hn_cs_dev);
     if (h->pub_dev) (void)hipFree(h->pub_dev);
     if (h->perm_dev) (void)hipFree(h->perm_dev);
@@ -407,6 +409,7 @@ static void update_paths(icem_handle* h) {
 }
 
 static int sync_wide_cost(icem_handle* h);
+static int sync_f64_mfma(icem_handle* h);
 
 int icem_set_tile_arith(icem_handle* h, int32_t mode) {
     if (check_handle(h)) return ICEM_E_INVALID;
@@ -467,10 +470,30 @@ int icem_set_model(icem_handle* h, int32_t kind, int32_t obs_dim, const double* 
     if (!h || !A_host || !B_host) return fail(ICEM_E_INVALID, "null argument");
     if (kind != ICEM_MODEL_LINEAR && kind != ICEM_MODEL_TANH) return fail(ICEM_E_INVALID, "model kind");
     const int d = h->cfg.act_dim;
+    if (obs_dim > 32 && h->cfg.dtype == ICEM_F64 && h->f64_arith == ICEM_F64_MFMA) {
+        // float64 on the f64 matrix cores (k_rollout_f64.hip): the model lives in M64_dev only; `wide` stays the f32 GEMM path's
+        if (obs_dim > ICEM_MAX_OBS_DIM || f64_mfma_lds_bytes(obs_dim, d) > 160 * 1024)
+            return fail(ICEM_E_UNSUPPORTED, "obs_dim must be in [1, 384]");
+        if (h->A_dev) (void)hipFree(h->A_dev);
+        if (h->B_dev) (void)hipFree(h->B_dev);
+        h->A_dev = h->B_dev = nullptr;
+        h->model_kind = kind;
+        h->obs_dim = obs_dim;
+        h->O = 0;
+        h->wide = false;
+        h->has_model = true;
+        h->A_host.assign(A_host, A_host + (size_t)obs_dim * obs_dim);
+        h->B_host.assign(B_host, B_host + (size_t)d * obs_dim);
+        h->fast_model_ready = false;
+        h->f64_model_ready = false;
+        update_paths(h);
+        return sync_wide_cost(h);
+    }
     if (obs_dim > 32) {
         // wide observations (HumanoidStandup's real o = 378, mujoco.py:241-252): the f32 GEMM rollout only
         if (h->cfg.dtype != ICEM_F32 || !wide_rollout_supported(obs_dim, d, 1))
-            return fail(ICEM_E_UNSUPPORTED, "obs_dim in (32, 384] needs dtype f32 (k_rollout_wide); beyond 384 is not compiled");
+            return fail(ICEM_E_UNSUPPORTED, "obs_dim in (32, 384] needs dtype f32 (k_rollout_wide) or, on an f64 handle, "
+                                            "icem_set_f64_arith(ICEM_F64_MFMA); beyond 384 is not compiled");
         if (h->cfg.num_elites > 32) return fail(ICEM_E_UNSUPPORTED, "obs_dim > 32 needs num_elites <= 32 (candidate lists of k_rollout_wide)");
         if (h->A_dev) (void)hipFree(h->A_dev);
         if (h->B_dev) (void)hipFree(h->B_dev);
@@ -507,13 +530,41 @@ int icem_set_model(icem_handle* h, int32_t kind, int32_t obs_dim, const double* 
     h->A_host.assign(A_host, A_host + (size_t)obs_dim * obs_dim);
     h->B_host.assign(B_host, B_host + (size_t)d * obs_dim);
     h->fast_model_ready = false;
+    h->f64_model_ready = false;
     update_paths(h);
     return sync_wide_cost(h);
+}
+
+// ICEM_F64_MFMA (k_rollout_f64.hip): the device copies its kernel reads -- the model [A ; B] as f64, zero-padded to
+// [ceil4(o + d)][ceil16(o)], and the cost (spec + terms) as a CostArgs<double>.  Called behind EVERY setter (through
+// sync_wide_cost), so the copies are current whichever of icem_set_cost* / icem_set_model / icem_set_f64_arith came last.
+static int sync_f64_mfma(icem_handle* h) {
+    if (h->cfg.dtype != ICEM_F64 || h->f64_arith != ICEM_F64_MFMA) return ICEM_OK;
+    if (h->has_model && !h->f64_model_ready) {
+        const int o = h->obs_dim, d = h->cfg.act_dim, Op = (o + 15) & ~15, Kp = (o + d + 3) & ~3;
+        std::vector<double> M((size_t)Kp * Op, 0.0);
+        for (int k = 0; k < o; ++k)
+            for (int i = 0; i < o; ++i) M[(size_t)k * Op + i] = h->A_host[(size_t)k * o + i];
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i < o; ++i) M[(size_t)(o + j) * Op + i] = h->B_host[(size_t)j * o + i];
+        const int rc = upload<double>(&h->M64_dev, M);
+        if (rc) return rc;
+        h->f64_model_ready = true;
+    }
+    if (h->has_cost) {
+        CostArgs<double> cs;
+        std::memset((void*)&cs, 0, sizeof(cs));
+        fill_cost_args_f64(h, cs);
+        if (!h->f64_cs_dev) ICEM_HIP_TRY(hipMalloc(&h->f64_cs_dev, sizeof(cs)));
+        ICEM_HIP_TRY(hipMemcpy(h->f64_cs_dev, &cs, sizeof(cs), hipMemcpyHostToDevice));
+    }
+    return ICEM_OK;
 }
 
 // the device copy of the cost the wide rollout kernels read when cost terms are on (by value in the argument block it
 // costs them 200 spilled scalar registers -- and 9 % of a launch -- whether a term is on or not)
 static int sync_wide_cost(icem_handle* h) {
+    if (const int rc = sync_f64_mfma(h)) return rc;
     if (!h->has_terms) return ICEM_OK;
     CostArgs<float> cs;
     fill_cost_args_f32(h, cs);
@@ -555,7 +606,7 @@ int icem_set_cost_terms(icem_handle* h, const icem_cost_terms* terms) {
     if (terms == nullptr) {
         h->has_terms = false;
         update_paths(h);
-        return ICEM_OK;
+        return sync_wide_cost(h);
     }
     if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return fail(ICEM_E_INVALID, "n_terms must be in [0, 8]");
     for (int j = 0; j < terms->n_terms; ++j) {
@@ -747,6 +798,19 @@ int icem_set_wide_arith(icem_handle* h, int32_t mode) {
 
 // (a TileHN handle -- Door / Relocate at o = 39 -- launches the fp16 planes of icem_set_tile_arith, whatever wide_eff says)
 int icem_wide_arith(const icem_handle* h) { return h ? (h->hn_tile ? ICEM_WIDE_F16X2 : h->wide_eff) : 0; }
+
+int icem_set_f64_arith(icem_handle* h, int32_t mode) {
+    if (check_handle(h)) return ICEM_E_INVALID;
+    if (mode != ICEM_F64_CHAIN && mode != ICEM_F64_MFMA)
+        return fail(ICEM_E_INVALID, "f64 arithmetic: ICEM_F64_CHAIN (0, the fma chain) or ICEM_F64_MFMA (1, the f64 matrix cores)");
+    if (h->cfg.dtype != ICEM_F64) return fail(ICEM_E_UNSUPPORTED, "icem_set_f64_arith: the handle's dtype is f32");
+    if (mode == ICEM_F64_CHAIN && h->has_model && h->obs_dim > 32)
+        return fail(ICEM_E_UNSUPPORTED, "icem_set_f64_arith: the handle's model is wider than 32, which only ICEM_F64_MFMA serves");
+    h->f64_arith = mode;
+    return sync_wide_cost(h);
+}
+
+int icem_f64_arith(const icem_handle* h) { return (h && h->cfg.dtype == ICEM_F64) ? h->f64_arith : ICEM_F64_CHAIN; }
 
 int icem_wide_imbalance_log2(const icem_handle* h) { return h ? h->wide_imbalance : 0; }
 

@@ -68,5 +68,6 @@ __device__ __forceinline__ T cost_terms(const CostArgs<T>& cs, bool bad, Obs obs
 
 // host side (generic_kernels.hip): the handle's cost spec + terms in kernel-argument form
 void fill_cost_args_f32(const icem_handle* h, CostArgs<float>& cs);
+void fill_cost_args_f64(const icem_handle* h, CostArgs<double>& cs);
 
 }  // namespace icem

@@ -671,6 +671,15 @@ int launch_rollout_k(const icem_handle* h, const RolloutArgs<T>& a, const Launch
     hipStream_t st = cx.st;
     const int grid = (a.n + WG - 1) / WG;
     ProfScope prof(h, ICEM_K_ROLLOUT, (long long)a.n * a.h, st);
+    if constexpr (std::is_same<T, double>::value) {
+        if (h->f64_arith == ICEM_F64_MFMA) {   // the f64 matrix-core rollout (k_rollout_f64.hip): any width; no batched twin
+            if (cx.rec) {
+                cx.rec->unsupported = true;
+                return ICEM_OK;
+            }
+            return launch_rollout_f64_mfma(h, a.n, a.obs0, a.actions, a.costs, a.observations, st);
+        }
+    }
     const bool thread_form = opt_i(OPT_GK_ROLLOUT_THREAD) != 0;   // read per call: the path-equivalence test flips it between planners
     const bool widths = h->O == 8 || h->O == 16 || h->O == 17 || h->O == 18 || h->O == 24 || h->O == 32;
     if (cx.rec) {   // a batched step: the float64 rollouts' batched twins (k_generic_batch.hip), costs only
@@ -768,6 +777,7 @@ void fill_cost_args(const icem_handle* h, CostArgs<T>& cs) {
 }
 
 void fill_cost_args_f32(const icem_handle* h, CostArgs<float>& cs) { fill_cost_args<float>(h, cs); }
+void fill_cost_args_f64(const icem_handle* h, CostArgs<double>& cs) { fill_cost_args<double>(h, cs); }
 
 // every index a cost term reads lies inside an observation of width o
 const char* cost_indices_error(const icem_handle* h, int o) {

@@ -160,6 +160,13 @@ struct icem_handle {
     int wide_packed = -2;        // which arithmetic Mw_dev / Mwh_dev / Mws_dev currently hold the model for (-2: none)
                                  // (k_rollout_wide.hip + its row kernel), 2 = bf16 planes (6 products)
     void* wide_cs_dev = nullptr; // CostArgs<float> (cost spec + terms) for k_rollout_wide, refreshed by the cost setters
+    // float64 handles (icem_set_f64_arith): ICEM_F64_CHAIN = the generic kernels' fma chain (o <= 32), ICEM_F64_MFMA = the f64
+    // matrix-core rollout of k_rollout_f64.hip (o <= 384).  `wide` above stays "the f32 GEMM path": an f64 handle wider than
+    // 32 has wide == false, O == 0 and its model only in M64_dev
+    int f64_arith = 0;
+    void* M64_dev = nullptr;     // [A ; B] as f64, row-major, zero-padded to [ceil4(o + d)][ceil16(o)] (abi.hip: sync_f64_mfma)
+    bool f64_model_ready = false;   // M64_dev holds the current model
+    void* f64_cs_dev = nullptr;  // CostArgs<double> (cost spec + terms) of k_rollout_f64.hip, refreshed by every setter
     void* Mp_dev = nullptr;
     void* perm_dev = nullptr;
     int flip_col = -1;
@@ -371,6 +378,11 @@ int gk_select_refit(const icem_handle* h, int n_cand, int n_loc, const void* cos
                     const LaunchCtx& cx);
 // every index a cost term reads lies inside an observation of width o (nullptr = fine)
 const char* cost_indices_error(const icem_handle* h, int o);
+
+// ---- k_rollout_f64.hip: the float64 rollout on the f64 matrix cores (icem_set_f64_arith(ICEM_F64_MFMA)) ----------------
+size_t f64_mfma_lds_bytes(int o, int d);   // dynamic LDS of a launch (two buffers of 16 padded rows)
+int launch_rollout_f64_mfma(const icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations,
+                            hipStream_t st);
 
 // ---- exchange.hip: the in-library elite exchange --------------------------------------------------------------------
 bool xchg_connected(const icem_handle* h);

@@ -1678,6 +1678,8 @@ extern "C" int icem_plan_step_batch_f64(icem_handle* const* handles, int32_t n, 
     for (int i = 0; i < n; ++i) {
         icem_handle* h = handles[i];
         if (h->cfg.world != 1) return fail(ICEM_E_UNSUPPORTED, who + "world must be 1 (sharded handles are not batched)");
+        if (h->f64_arith == ICEM_F64_MFMA)
+            return fail(ICEM_E_UNSUPPORTED, who + "handles on ICEM_F64_MFMA are not batched (the f64 matrix-core rollout has no batched twin)");
         int rc = check_plan(h, &buffers[i], mpc_step, 0, st);
         if (rc) return rc;
         if (h->O != h0->O || h->model_kind != h0->model_kind || h->has_terms != h0->has_terms)

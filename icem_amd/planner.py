@@ -357,6 +357,22 @@ class IcemPlanner:
         L.check(self.lib.icem_nonfinite_costs(self._h, C.byref(n), self._stream()))
         return int(n.value)
 
+    F64_ARITH = {"chain": 0, "mfma": 1}
+
+    def set_f64_arith(self, mode="chain"):
+        """dtype f64: which arithmetic the rollout's model step runs in (``icem_set_f64_arith``), by NAME: ``"chain"`` / 0 the
+        generic kernels' fma chain (obs_dim <= 32, the default), ``"mfma"`` / 1 the f64 matrix cores -- sixteen trajectories
+        per workgroup, every obs_dim up to 384, float64 rounding in blocks of four (not the chain's bits).  Set it BEFORE
+        ``set_model`` for a model wider than 32.  Returns the arithmetic now in effect (a name)."""
+        m = self.F64_ARITH.get(mode, mode)
+        L.check(self.lib.icem_set_f64_arith(self._h, int(m)))
+        return self.f64_arith
+
+    @property
+    def f64_arith(self):
+        """The float64 arithmetic in effect: ``"chain"`` / ``"mfma"`` (``"chain"`` on an f32 planner)."""
+        return {0: "chain", 1: "mfma"}[int(self.lib.icem_f64_arith(self._h))]
+
     WIDE_ARITH = {"auto": -1, "f16x2": 0, "fp16x2": 0, "f32": 1, "bf16x3": 2}
 
     def set_wide_arith(self, mode="auto"):

@@ -553,6 +553,26 @@ int icem_set_tile_arith(icem_handle* h, int32_t mode);
 int icem_tile_arith(const icem_handle* h); /* the arithmetic in effect: ICEM_TILE_F32 or ICEM_TILE_F16X2 */
 double icem_tile_growth(const icem_handle* h); /* reachable max of |state| / max(|obs0|, action bound) over the horizon (1: tanh) */
 
+/* Float64 handles (dtype ICEM_F64, the reference's own arithmetic): which arithmetic the model step of the rollout
+ * (abstract_models.py:17-26's predict) runs in.
+ *   ICEM_F64_CHAIN (0, the default): one fma chain per output (k = 0 .. o - 1, then the actions) on the vector ALU, the
+ *     generic kernels; observation widths up to 32.
+ *   ICEM_F64_MFMA (1): v_mfma_f64_16x16x4_f64 -- sixteen trajectories per workgroup, the contraction over [state | actions]
+ *     summed in blocks of four on the f64 matrix cores: float64 rounding in another summation order, NOT the chain's bits
+ *     (the float64 oracle's bar, 1e-10 relative, holds with a factor 100 in hand at every shipped cost).  Under it
+ *     icem_set_model accepts 1 <= obs_dim <= 384 with either model kind, the num_elites <= 32 limit of the f32 wide
+ *     kernels does not apply (selection runs on the cost array), external noise (z_r / z_i) works at every width and
+ *     icem_rollout_cost returns `observations` at every width.  One kernel serves the stand-alone operator, icem_plan_step,
+ *     icem_plan_iter_local (sharded or not) and icem_get_action; it has no batched twin: icem_plan_step_batch_f64 refuses
+ *     such handles with ICEM_E_UNSUPPORTED, nothing launched.  The development option gk_rollout_thread does not apply.
+ * Other values: ICEM_E_INVALID.  An f32 handle: ICEM_E_UNSUPPORTED.  Back to ICEM_F64_CHAIN while the handle's model is
+ * wider than 32: ICEM_E_UNSUPPORTED.  A refused call leaves the handle as it was.  Takes effect at the next launch (not
+ * between icem_plan_iter_local and its merge).  icem_f64_arith: the arithmetic in effect (ICEM_F64_CHAIN on an f32
+ * handle).  No reference counterpart. */
+enum { ICEM_F64_CHAIN = 0, ICEM_F64_MFMA = 1 };
+int icem_set_f64_arith(icem_handle* h, int32_t mode);
+int icem_f64_arith(const icem_handle* h);
+
 /* Status word of the tile rollouts (every launch of the o <= 48 kernels counts into it): the number of trajectories since
  * icem_create whose cost came out NaN -- a state that left the arithmetic's range (f32's; the fp16 planes' for actions
  * outside the bounds their scale was taken from) or non-finite inputs.  Such a trajectory ranks last, as a NaN does under
