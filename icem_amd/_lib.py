@@ -70,6 +70,18 @@ class IcemPlanBuffersC(C.Structure):
         "executed", "best_cost", "z_r", "z_i", "z_r_shift", "z_i_shift")]
 
 
+class IcemCemParamsC(C.Structure):
+    """include/icem_hip.h: struct icem_cem_params."""
+    _fields_ = [("like_levine", C.c_int32), ("shift_means", C.c_int32), ("execute_best_elite", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IcemCemBuffersC(C.Structure):
+    """include/icem_hip.h: struct icem_cem_buffers."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "mean", "std", "lower", "upper", "low", "high", "obs0", "actions", "costs", "elites", "elite_costs", "elite_idx",
+        "executed", "best_cost", "workspace")]
+
+
 # every symbol include/icem_hip.h declares: (name, restype, argtypes)
 _VP, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 _H = C.c_void_p
@@ -121,6 +133,9 @@ SYMBOLS = [
     ("icem_sample_truncnorm", C.c_int, [_H, C.c_int32, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
     ("icem_cem_bounds", C.c_int, [_H, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("icem_update_distribution_ok", C.c_int, [_H, C.c_int32, C.c_int32]),
+    ("icem_plan_step_cem_ok", C.c_int, [_H]),
+    ("icem_plan_step_cem", C.c_int, [_H, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _I32, _VP]),
+    ("icem_cem_step_launches", C.c_int64, [_H]),
     ("icem_rccl_load", C.c_int, [C.c_char_p]),
     ("icem_rccl_library", C.c_char_p, []),
     ("icem_rccl_unique_id", C.c_int, [_VP]),

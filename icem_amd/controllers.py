@@ -858,11 +858,20 @@ class MpcCemStdHip(MpcController):
     against -- with sampling, rollout (built-in model), top-K, refit and bounds on the device.  Same constructor as the
     reference; extra optional keywords ``dtype``, ``seed``, ``rng_rounds``, ``device`` and ``noise_source``
     ("philox": device uniforms; "numpy_legacy": scipy's draws from the global ``np.random`` stream -- parity mode; or
-    a callable ``uniforms(num) -> [num, h, d]``)."""
+    a callable ``uniforms(num) -> [num, h, d]``).
+
+    ``get_action`` is one library call (``icem_plan_step_cem``: a chain of launches, no host round trip, one
+    device-to-host copy of the result) where the model is the device's built-in one, the noise is the device's, no
+    subclass overrides ``compute_new_mean``, the controller is not verbose and ``IcemPlanner.cem_step_ok()``; everywhere
+    else it is the stage-wise loop over the operators -- the same bits.  ``fused_step``: None (the rule above), False
+    (always the loop) or True (raise where the fused step is not served)."""
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
-                 noise_source: Union[str, Callable] = "philox", deterministic_replay=False, **kwargs):
+                 noise_source: Union[str, Callable] = "philox", deterministic_replay=False, fused_step=None, **kwargs):
         super().__init__(**kwargs)
+        if fused_step not in (None, True, False):
+            raise ValueError("fused_step must be None (where served), True (or raise) or False (the stage-wise loop)")
+        self.fused_step = fused_step
         self._parse_action_sampler_params(**dict(action_sampler_params))
         self._check_validity_parameters()
         self.logger = _get_logger(self.__class__.__name__)
@@ -949,6 +958,47 @@ class MpcCemStdHip(MpcController):
             raise AttributeError("beginning_of_rollout() needs to be called before")
         self.forward_model_state = self.forward_model.got_actual_observation_and_env_state(
             observation=obs, env_state=state, model_state=self.forward_model_state)
+        executed_action = self._step_fused(obs) if self._takes_fused_step() else self._step_stagewise(obs)
+        self.logger.log(self.last_min_cost / self.horizon if self.cost_along_trajectory == "sum" else self.last_min_cost,
+                        key="Expected_trajectory_cost")
+        if self.forward_model_state is not None:
+            _, self.forward_model_state, _ = self.forward_model.predict(
+                observations=obs, states=self.forward_model_state, actions=executed_action)
+        return executed_action
+
+    def _fused_step_refusal(self):
+        """Why ``icem_plan_step_cem`` cannot run this controller's step (None: it can)."""
+        if not self.device_path:
+            return "the model is not the device's built-in one"
+        if self.noise_source != "philox":
+            return "the noise source is not the device's (external uniforms keep the operator loop)"
+        if self._new_mean_is_overridden(MpcCemStdHip):
+            return "compute_new_mean is overridden"
+        if self.verbose:
+            return "the controller is verbose"
+        if not self.planner.cem_step_ok():
+            return "the library does not serve this handle (IcemPlanner.cem_step_ok)"
+        return None
+
+    def _takes_fused_step(self) -> bool:
+        if self.fused_step is False:
+            return False
+        why = self._fused_step_refusal()
+        if why is not None and self.fused_step is True:
+            raise RuntimeError(f"fused_step=True, but the fused CEM step is not served: {why}")
+        return why is None
+
+    def _step_fused(self, obs):
+        """The whole step in the library (``icem_plan_step_cem``); one device-to-host copy of ``[executed | best_cost]``."""
+        p = self.planner
+        p.plan_step_cem(obs, self._mean, self._std, self._lower, self._upper, like_levine=self.like_levine,
+                        shift_means=self.shift_means, execute_best_elite=self.execute_best_elite)
+        host = p.cem_result.cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+        self._elite_actions, self._elite_costs = p.cem_elites, p.cem_elite_costs
+        self.last_min_cost = float(host[-1])
+        return host[:-1]
+
+    def _step_stagewise(self, obs):
         p, uniforms = self.planner, self._uniform_fn()
         actions = costs_sorted = idx = None
         for i in range(self.opt_iter):
@@ -979,12 +1029,7 @@ class MpcCemStdHip(MpcController):
             self._mean.zero_()
         self._reset_std()                                                  # mpc.py:244-245
         self.last_min_cost = float(costs_sorted[0])
-        self.logger.log(self.last_min_cost / self.horizon if self.cost_along_trajectory == "sum" else self.last_min_cost,
-                        key="Expected_trajectory_cost")
         p.mpc_step += 1
-        if self.forward_model_state is not None:
-            _, self.forward_model_state, _ = self.forward_model.predict(
-                observations=obs, states=self.forward_model_state, actions=executed_action)
         return executed_action
 
 

@@ -482,8 +482,9 @@ __device__ __forceinline__ unsigned long long wave_min_u64_shfl(unsigned long lo
     return x;
 }
 
+// idx_out (icem_plan_step_cem, k_cem.hip): where the K selected global indices go as well; the step kernels pass none.
 template <typename T>
-__device__ __forceinline__ void select_refit_body(const SelectArgs<T>& s) {
+__device__ __forceinline__ void select_refit_body(const SelectArgs<T>& s, int* idx_out = nullptr) {
     constexpr int NW = SELECT_NT / 64;
     __shared__ unsigned long long wave_T[NW];
     __shared__ unsigned long long wave_best[NW][64];
@@ -656,6 +657,7 @@ __device__ __forceinline__ void select_refit_body(const SelectArgs<T>& s) {
         }
     }
     if (tid < a.K) a.elites_cost_next[tid] = sel_c[tid];
+    if (idx_out != nullptr && tid < a.K) idx_out[tid] = sel_i[tid];
     if (s.dbg && tid == 0) s.dbg[21] = wall_clock64();
     if (a.last) {
         __syncthreads();

@@ -15,6 +15,7 @@
 #include "host_common.h"
 #include "cost_terms_dev.h"
 #include "exchange_dev.h"
+#include "cem_dev.h"       // the CEM baseline's quantile, bounds and step tail (k_cem.hip)
 #include "generic_dev.h"   // the bodies a batched float64 step shares (k_generic_batch.hip)
 #include "philox.h"
 #include "refit.h"
@@ -146,11 +147,7 @@ __global__ __launch_bounds__(WG) void shift_sample_batch_kernel(const ShiftSampl
 // ---------------------------------------------------------------------------------------------
 // MpcCemStd (the CEM baseline, icem/controllers/mpc.py:142-327): truncated-normal sampling and its bounds
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double std_normal_cdf(double x) { return normcdf(x); }
-__device__ __forceinline__ float std_normal_cdf(float x) { return normcdff(x); }
-__device__ __forceinline__ double std_normal_icdf(double p) { return normcdfinv(p); }
-__device__ __forceinline__ float std_normal_icdf(float p) { return normcdfinvf(p); }
-
+// (the quantile and _update_bounds of one element: cem_dev.h, shared with the kernels of icem_plan_step_cem)
 // actions[i, t, j] = mean[t, j] + std[t, j] * ppf(u; lower[t, j], upper[t, j]) with the truncated standard normal's
 // inverse CDF ppf(u; a, b) = Phi^-1(Phi(a) + u (Phi(b) - Phi(a)))  (scipy.stats.truncnorm.rvs, mpc.py:188-198).
 // u: the caller's uniforms [n, h, d] (parity: scipy draws exactly that array), or, if null, word t of row (i, j)'s
@@ -167,14 +164,9 @@ __global__ __launch_bounds__(WG) void sample_truncnorm_kernel(int n, int h, int 
     for (int t = 0; t < h; ++t) {
         const size_t e = ((size_t)i * h + t) * d + j;
         const uint32_t x = rng.next();
-        const T uu = u ? u[e] : ((T)x + (T)0.5) * (T)2.3283064365386963e-10;
+        const T uu = u ? u[e] : word_uniform<T>(x);
         const T pa = std_normal_cdf(lower[t * d + j]), pb = std_normal_cdf(upper[t * d + j]);
-        // the quantile lies in [lower, upper] by definition; in f32 a uniform that rounds to 1 or an interval deep in
-        // one tail (pa == pb) would otherwise come back as +-inf
-        T z = std_normal_icdf(fmad(uu, pb - pa, pa));
-        const T lo_z = lower[t * d + j], hi_z = upper[t * d + j];
-        z = z < lo_z ? lo_z : z;
-        z = z > hi_z ? hi_z : z;
+        const T z = truncnorm_quantile<T>(uu, pa, pb - pa, lower[t * d + j], upper[t * d + j]);
         out[e] = fmad(z, std[t * d + j], mean[t * d + j]);
     }
 }
@@ -209,18 +201,7 @@ __global__ __launch_bounds__(WG) void cem_bounds_kernel(int hd, int d, int like_
                                                        const T* high, T* lower, T* upper) {
     const int e = blockIdx.x * WG + threadIdx.x;
     if (e >= hd) return;
-    const int j = e % d;
-    if (like_levine) {
-        const T lb = (mean[e] - low[j]) / (T)2, ub = (high[j] - mean[e]) / (T)2;
-        T s = lb < ub ? lb : ub;
-        s = s < std[e] ? s : std[e];
-        std[e] = s > (T)1e-8 ? s : (T)1e-8;
-        lower[e] = (T)-2;
-        upper[e] = (T)2;
-    } else {
-        lower[e] = (low[j] - mean[e]) / (std[e] + (T)1e-8);
-        upper[e] = (high[j] - mean[e]) / (std[e] + (T)1e-8);
-    }
+    cem_bounds_element<T>(e, e % d, like_levine, mean, std, low, high, lower, upper);
 }
 
 // Raw Philox white noise in the reference's [n, d, F] x 2 layout (RNG known-answer tests).

@@ -3,6 +3,7 @@
 // pack_records_kernel (sharded runs: this rank's K best as records for the exchange).
 #include "fused_dev.h"
 #include "refit.h"
+#include "update_small_body.h"
 
 namespace icem {
 
@@ -255,81 +256,7 @@ __global__ __launch_bounds__(1024) void topk_small_kernel(const float* costs, in
     wg_merge_emit<16>(wg_keys, run, K, lane, wave, fr, 0, 1);
 }
 
-// icem_update_distribution: the reference's update_distributions in ONE launch for small f32 pools -- the sorted top-K
-// over the pool's costs and the kept elites' (icem.py:143-145: appended behind the pool, index n + e), the gather of the
-// K elite rows from pool / kept elites, the refit (refit.h: the arithmetic of gather_refit_kernel).  Phase 1 + 2 are
-// topk_small_kernel's; the selection lands in LDS (wg_merge_emit's list 0 of 1, through a generic pointer).
-// (the body of update_small_kernel and of update_small_batch_kernel: one device function.  FINISH: the step's epilogue behind
-//  the refit -- the new mean goes through LDS and leaves shifted, std is reset (shift_kernel's arithmetic, icem.py:167-175),
-//  executed = elites[0, 0, :], best_cost = elite_costs[0], and both once more as the problem's row of `results`.)
-template <bool FINISH>
-__device__ __forceinline__ void update_small_body(const UpdateSmallArgs& a, const UpdateFinishArgs* f) {
-    __shared__ unsigned long long wg_keys[2][16][32];
-    __shared__ unsigned long long sel[32];
-    __shared__ float shifted[FINISH ? UPDATE_FINISH_MAX_HD : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_all = a.n + a.n_keep;
-    unsigned long long run = KEY_SENTINEL;
-    bool first = true;
-    for (int base = wave * 64; base < n_all; base += 1024) {
-        const int i = base + lane;
-        unsigned long long key = KEY_SENTINEL;
-        if (i < n_all) key = make_key(i < a.n ? a.costs[i] : a.keep_costs[i - a.n], i);
-        key = wave_sort64(key, lane);
-        if (!first) {
-            const unsigned long long prev = __shfl(run, lane - 32, 64);
-            key = (lane >= 32 && lane < 32 + a.K) ? prev : (lane < a.K ? key : KEY_SENTINEL);
-            key = wave_sort64(key, lane);
-        }
-        run = key;
-        first = false;
-    }
-    FastRolloutArgs fr{};
-    fr.part_k = sel;
-    wg_merge_emit<16>(wg_keys, run, a.K, lane, wave, fr, 0, 1);
-    __syncthreads();
-    if (tid < a.K) {
-        a.elite_costs_out[tid] = key_cost(sel[tid]);
-        a.idx_out[tid] = key_idx(sel[tid]);
-    }
-    // a padded selection (fewer than K candidates: (+inf, INT_MAX)) repeats its best row, as icem_gather_refit does
-    auto row = [&](int r) -> const float* {
-        int i = key_idx(sel[r]);
-        if (i < 0 || i == INT_MAX) i = key_idx(sel[0]);
-        return i < a.n ? a.pool + (size_t)i * a.hd : a.keep_actions + (size_t)(i - a.n) * a.hd;
-    };
-    for (int e = tid; e < a.hd; e += 1024) {
-        for (int r = 0; r < a.K; ++r) a.elites_out[(size_t)r * a.hd + e] = row(r)[e];
-        float nm, ns;
-        refit_element<float>(a.K, a.alpha, a.mean[e], a.std[e], [&](int r) { return row(r)[e]; }, nm, ns);
-        if (FINISH) {
-            shifted[e] = nm;
-        } else {
-            a.mean[e] = nm;
-            a.std[e] = ns;
-        }
-    }
-    if (FINISH) {
-        __syncthreads();
-        const int d = f->d;
-        for (int e = tid; e < a.hd; e += 1024) {
-            const int j = e % d;
-            a.mean[e] = (e + d < a.hd) ? shifted[e + d] : shifted[e];
-            a.std[e] = (f->high[j] - f->low[j]) / 2.f * f->init_std;
-        }
-        if (tid < d) {
-            const float x = row(0)[tid];
-            f->executed[tid] = x;
-            if (f->result) f->result[tid] = x;
-        }
-        if (tid == 0) {
-            const float c = key_cost(sel[0]);
-            f->best_cost[0] = c;
-            if (f->result) f->result[d] = c;
-        }
-    }
-}
-
+// icem_update_distribution: update_small_body.h (the body is shared with the f32 update kernel of icem_plan_step_cem, k_cem.hip)
 __global__ __launch_bounds__(1024) void update_small_kernel(UpdateSmallArgs a) {
     update_small_body<false>(a, nullptr);
 }

@@ -131,6 +131,7 @@ class IcemPlanner:
                                         B.ctypes.data_as(C.POINTER(C.c_double))))
         self.obs_dim = o
         self._bufs = None
+        self._cem = None
 
     def set_cost(self, ctrl_weight=0.1, lin_idx=8, lin_weight=-1.0, flip_idx=1, flip_penalty=10.0,
                  flip_thresh=float(np.pi / 2)):
@@ -576,6 +577,69 @@ class IcemPlanner:
         for pl in pls:
             pl.mpc_step += 1
         return results
+
+    # ------------------------------------------------------------------ the CEM baseline's step (MpcCemStd)
+    def cem_step_ok(self) -> bool:
+        """Does ``icem_plan_step_cem`` serve THIS handle?  (One GPU, profiling off, ``factor_decrease == 1``, no kept or
+        shifted elites, a pool the one-launch update / selection of the handle's dtype admits, option ``cem_step`` on:
+        asked of the handle.)"""
+        return bool(self.lib.icem_plan_step_cem_ok(self._h))
+
+    @property
+    def cem_step_launches(self) -> int:
+        """Kernel launches of the last CEM step of this planner (``icem_cem_step_launches``): 3 per iteration."""
+        return int(self.lib.icem_cem_step_launches(self._h))
+
+    def _cem_buffers(self):
+        """The step's buffers, owned by the planner: the last pool and its costs, the elite set, its costs and indices,
+        the observation, and ``[executed | best_cost]`` as one tensor (one device-to-host copy fetches both)."""
+        b = getattr(self, "_cem", None)
+        if b is None:
+            if self.obs_dim == 0:
+                raise RuntimeError("set_model()/set_cost() must be called before planning")
+            n, new = self.cfg.num_traj, lambda *shape, dt=self.dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+            b = self._cem = dict(actions=new(n, self.h, self.d), costs=new(n), elites=new(self.K, self.h, self.d),
+                                 elite_costs=new(self.K), elite_idx=new(self.K, dt=torch.int32), obs0=new(self.obs_dim),
+                                 result=new(self.d + 1), cb=None, key=None)
+        return b
+
+    def plan_step_cem(self, obs, mean: torch.Tensor, std: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, *,
+                      like_levine: bool, shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
+        """One MPC step of the truncated-normal CEM (``MpcCemStd.get_action``, icem/controllers/mpc.py:200-262) as
+        ``icem_plan_step_cem``: every iteration's sampling, rollout, update and bounds and the step's epilogue inside the
+        library, no host synchronisation.  ``mean`` / ``std`` / ``lower`` / ``upper`` ``[h, d]`` are the caller's and are
+        updated in place (afterwards: shifted / reset for the next step).  The planner's ``cem_elites`` / ``cem_elite_costs``
+        / ``cem_elite_idx`` / ``cem_actions`` / ``cem_costs`` hold the last iteration's elite set and pool, ``cem_result``
+        is ``[executed | best_cost]``.  Returns ``executed`` (device tensor, no host sync) and advances ``mpc_step``.
+        Raises ``IcemError`` (``ICEM_E_UNSUPPORTED``) before anything runs where :meth:`cem_step_ok` is false."""
+        b = self._cem_buffers()
+        for t in (mean, std, lower, upper):
+            if t.dtype != self.dt or t.device != self.device or tuple(t.shape) != (self.h, self.d) or not t.is_contiguous():
+                raise ValueError("mean / std / lower / upper must be contiguous [h, d] device tensors of the planner dtype")
+        if isinstance(obs, torch.Tensor) and obs.device == self.device:
+            b["obs0"].copy_(obs.reshape(-1))
+        else:
+            b["obs0"].copy_(torch.as_tensor(np.asarray(obs, dtype=np.float64).reshape(self.obs_dim), dtype=self.dt))
+        key = (mean.data_ptr(), std.data_ptr(), lower.data_ptr(), upper.data_ptr())
+        if b["key"] != key:
+            r = b["result"]
+            b["cb"] = L.IcemCemBuffersC(
+                mean=key[0], std=key[1], lower=key[2], upper=key[3], low=self.low.data_ptr(), high=self.high.data_ptr(),
+                obs0=b["obs0"].data_ptr(), actions=b["actions"].data_ptr(), costs=b["costs"].data_ptr(),
+                elites=b["elites"].data_ptr(), elite_costs=b["elite_costs"].data_ptr(), elite_idx=b["elite_idx"].data_ptr(),
+                executed=r.data_ptr(), best_cost=r[self.d:].data_ptr(), workspace=None)
+            b["key"] = key
+        prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        L.check(self.lib.icem_plan_step_cem(self._h, C.byref(b["cb"]), C.byref(prm), self.mpc_step, self._stream()))
+        self.mpc_step += 1
+        return b["result"][:self.d]
+
+    cem_actions = property(lambda self: self._cem_buffers()["actions"])
+    cem_costs = property(lambda self: self._cem_buffers()["costs"])
+    cem_elites = property(lambda self: self._cem_buffers()["elites"])
+    cem_elite_costs = property(lambda self: self._cem_buffers()["elite_costs"])
+    cem_elite_idx = property(lambda self: self._cem_buffers()["elite_idx"])
+    cem_result = property(lambda self: self._cem_buffers()["result"])
 
     # ------------------------------------------------------------------ in-library elite exchange (world > 1)
     def connect_exchange(self, group=None):

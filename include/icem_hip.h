@@ -212,6 +212,42 @@ int icem_sample_truncnorm(icem_handle* h, int32_t n, int64_t first_index, const 
 int icem_cem_bounds(icem_handle* h, int32_t like_levine, const void* mean, void* std, const void* low, const void* high,
                     void* lower, void* upper, void* stream);
 
+/* MpcCemStd.get_action (mpc.py:200-262) as ONE call: the loop a caller would otherwise drive operator by operator
+ * (icem_sample_truncnorm, icem_rollout_cost, icem_update_distribution or icem_topk_sorted + icem_gather_refit,
+ * icem_cem_bounds), a chain of launches with no host round trip.  Per CEM iteration i of MPC step s (mpc.py:207-228):
+ *   - cfg.num_traj rows are drawn with icem_sample_truncnorm's arithmetic from (mean, std, lower, upper) at stream offset
+ *     (episode << 32) + s * opt_iters + i (mpc.py:188-198; device uniforms);
+ *   - they are rolled out by the launch icem_rollout_cost picks for this handle (mpc.py:56-67: every model width, tile / wide /
+ *     f64 arithmetic and cost-term list the operator serves);
+ *   - the K = cfg.num_elites best rows in (cost, index) order go to elites / elite_costs / elite_idx and mean / std are
+ *     refitted with cfg.alpha (mpc.py:270-281), then lower / upper -- and std under like_levine -- follow as icem_cem_bounds
+ *     writes them (_update_bounds, mpc.py:290-301).
+ * Behind the last iteration: executed = elites[0, 0, :] under execute_best_elite, else mean[0, :] as refitted and before the
+ * shift (mpc.py:230-233); best_cost = elite_costs[0]; with shift_means the mean's rows move up one and the last row keeps its
+ * value, or is zero under like_levine (mpc.py:236-243 with the default compute_new_mean, mpc.py:265-269), without it the
+ * mean is set to 0; std is reset to what icem_reset_distribution writes and lower / upper follow once more (mpc.py:244-245).
+ * actions / costs hold the last iteration's pool afterwards.  3 launches per iteration, none in between; no host
+ * synchronisation; no allocation after the first call.  Every output is bit for bit what the operators give.
+ *   Served: f32 handles where icem_update_distribution_ok(num_traj, K); f64 handles whose pool the one-launch selection
+ * admits; world == 1, rng_rounds 7 and 10, profiling off, factor_decrease == 1, keep_previous_elites and shift_elites off
+ * (MpcCemStd has neither, mpc.py:142-327); development option cem_step = 0 switches the entry off.  Anything else is
+ * ICEM_E_UNSUPPORTED; a NULL argument or a negative mpc_step ICEM_E_INVALID; no model or cost set ICEM_E_STATE.  Whatever
+ * is refused is refused before anything is launched. */
+typedef struct icem_cem_params { int32_t like_levine, shift_means, execute_best_elite, reserved; } icem_cem_params; /* mpc.py:303-327 */
+typedef struct icem_cem_buffers {   /* all device, handle dtype */
+    void *mean, *std;        /* [h,d] in/out, persistent (mpc.py:158-170)      */
+    void *lower, *upper;     /* [h,d] in/out, standard-normal units (mpc.py:290-301) */
+    void *low, *high;        /* [d]                                            */
+    void *obs0;              /* [obs_dim]                                      */
+    void *actions, *costs;   /* [N,h,d], [N]: the last iteration's pool        */
+    void *elites, *elite_costs; int32_t* elite_idx;   /* [K,h,d], [K], [K] (mpc.py:270-271) */
+    void *executed, *best_cost;                        /* [d], [1] (mpc.py:230-233) */
+    void *workspace;         /* icem_topk_workspace_bytes(N, K), may be unused */
+} icem_cem_buffers;
+int     icem_plan_step_cem_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
+int     icem_plan_step_cem(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, int32_t mpc_step, void* stream);
+int64_t icem_cem_step_launches(const icem_handle* h);  /* kernel launches of the last such step of this handle; measurement */
+
 /* MpcRandom.sample_action_sequences (icem/controllers/mpc.py:96-109, random shooting): actions[i, t, :] = low +
  * (high - low) * U(block), uniform draws held for consecutive calls of MpcRandom.sample() (mpc.py:96-102) -- one call
  * per (trajectory, step) pair in row-major order, the call counter running on across MPC steps: call c =
