@@ -32,6 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-fun
 UNIT_FLAGS = {}   # (measured for TileHN: no gain, 30 more registers)
 if os.environ.get("ICEM_DEV_SHAPES"):   # development builds: compile the matrix-pipe kernels for ONE shape, e.g. "30,6,17" (4x faster)
     FLAGS.append(f"-DICEM_FAST_SHAPES(X)=X({os.environ['ICEM_DEV_SHAPES']})")
+if os.environ.get("ICEM_WAVE_CENSUS"):   # development builds: the single-launch kernel records where its waves run (tools/dbg/stamps.py --census)
+    FLAGS.append("-DICEM_WAVE_CENSUS")
 
 
 def _hipcc() -> str:

@@ -1504,7 +1504,7 @@ __device__ __forceinline__ void merge_select_stream(const MergeSingleArgs& a, in
 // Same result as merge_select (the K smallest keys, ascending; keys are all different).
 template <int DEPTH>
 __device__ __forceinline__ void merge_select_shallow(const MergeSingleArgs& a, int lane, unsigned long long* cand,
-                                                     unsigned long long* sel) {
+                                                     unsigned long long* sel, long long* keys_stamp = nullptr) {
     const int K = a.K, nl = a.n_lists;
     const float keep_cost = merge_keep_cost(a, lane);
     unsigned long long k[LPL][DEPTH];
@@ -1514,6 +1514,15 @@ __device__ __forceinline__ void merge_select_shallow(const MergeSingleArgs& a, i
 #pragma unroll
         for (int i = 0; i < DEPTH; ++i) k[l][i] = a.part_k[(size_t)(i < K ? i : 0) * nl + (list < nl ? list : 0)];
     }
+#ifdef ICEM_WAVE_CENSUS
+    if (keys_stamp) {   // development build: "keys loaded" -- the wait for every key of the one load round, then the clock
+#pragma unroll
+        for (int l = 0; l < LPL; ++l)
+#pragma unroll
+            for (int i = 0; i < DEPTH; ++i) asm volatile("" : "+v"(k[l][i]));
+        if (lane == 0) *keys_stamp = wall_clock64();
+    }
+#endif
 #pragma unroll
     for (int l = 0; l < LPL; ++l) {
         const bool has_list = lane + l * 64 < nl;

@@ -109,6 +109,19 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
     const int base = wg * TPB;          // one slab of TPB trajectories per workgroup (launch_sample_rollout)
     if (base >= n_rows) return;
     if (ra.dbg && tid == 0 && wg == 0) ra.dbg[8] = wall_clock64();
+#ifdef ICEM_WAVE_CENSUS
+    // Development build (-DICEM_WAVE_CENSUS; tools/dbg/stamps.py --census, whose stamp buffer has the 64 words): where the
+    // waves of the first and of the last workgroup of a merge-prologue launch run, and how the selection wave's time into the
+    // first barrier splits.  Per workgroup 24 words behind the 16 stamps: [0..6] HW_ID of wave w (SIMD_ID = bits 5:4),
+    // [8] the workgroup's first stamp, [9] selection wave's first instruction, [10] its keys loaded, [11] selected,
+    // [12 + w] wave w at the first barrier, [19] wave 0 behind it.
+    const int cen_wg = wg == 0 ? 0 : (base + TPB >= n_rows ? 1 : -1);
+    long long* const cen = (PM && !REC && ra.dbg && cen_wg >= 0) ? ra.dbg + 16 + 24 * cen_wg : nullptr;
+    if (cen && lane == 0) cen[wave] = (long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID, all 32 bits
+    if (cen && tid == 0) cen[8] = wall_clock64();
+#else
+    long long* const cen = nullptr;
+#endif
     // Order matters at this size, and a load whose data the previous launch wrote is a memory round trip nothing overlaps,
     // so every load whose address is known here is requested here and waited for ONCE:
     //  * iteration 0 (no prologue): distribution, start observation, model operands, bounds and -- with the noise drawn
@@ -264,9 +277,13 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             }
             else if constexpr (RW >= 8)  // 13 waves share the register file: the low-register selection
                 merge_select_stream(am, lane, cand, sel);
-            else
-                merge_select_shallow<3>(am, lane, cand, sel);
+            else {
+                if (cen && lane == 0) cen[9] = wall_clock64();
+                merge_select_shallow<3>(am, lane, cand, sel, cen ? cen + 10 : nullptr);
+                if (cen && lane == 0) cen[11] = wall_clock64();
+            }
         }
+        if (!REC && cen && lane == 0) cen[12 + wave] = wall_clock64();
     }
     if (PM) {  // now the rest of the inputs: in flight across the barriers below
         obs_reg = ra.obs0[(tid < 32 && tid < ra.o) ? tid : 0];
@@ -281,6 +298,7 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             if (ra.dbg && tid == 0 && wg == 0) ra.dbg[4] = wall_clock64();
         } else {
             __syncthreads();
+            if (cen && tid == 0) cen[19] = wall_clock64();
         }
         if (ra.dbg && tid == 0 && wg == 0) ra.dbg[5] = wall_clock64();
         // (stamps 5 / 6 are overwritten by the step's last merge, which has its own: the lists form repeats them in 15 / 7 --
@@ -416,8 +434,26 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
 }
 
 
+// The argument block is eleven 64-byte lines of the kernel-argument segment, and the body reads it where it needs it: seven
+// groups of scalar loads, each behind the wait of the one before and each the first touch of another line -- a round trip
+// to the L2 per group in front of the first useful instruction of every wave (the census of R13.1: the selection wave of a
+// merge-prologue launch reaches its first instruction 0.8 us after the workgroup's first stamp).  One load per line, all in
+// flight together and waited for once, at the kernel's entry: the groups behind it hit in the scalar cache.
+template <int BYTES>
+__device__ __forceinline__ void kernarg_touch() {
+    typedef const unsigned __attribute__((address_space(4))) * KArg;
+    const KArg ka = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+    unsigned acc = ka[(BYTES - 4) / 4];
+#pragma unroll
+    for (int i = 0; i < BYTES; i += 64) acc |= ka[i / 4];
+    asm volatile("" ::"s"(acc));
+}
+
 template <int H, int D, int O, int KIND, int ROUNDS, int RW, int KREG, bool REC, int ARITH>
 __global__ __launch_bounds__(sr_threads(D, RW) + (KREG > 0 ? 64 : 0)) void sample_rollout_kernel(FastIterArgs a) {
+    // (merge-prologue launches only: iteration 0 asks for everything at entry and waits once as it is -- with the touch there
+    // too the step measured the same, R13.1)
+    if constexpr (KREG > 0) kernarg_touch<sizeof(FastIterArgs)>();
     sample_rollout_body<H, D, O, KIND, ROUNDS, RW, KREG, REC, ARITH>(a.s, a.r, a.m, a.p);
 }
 
