@@ -860,6 +860,7 @@ class MpcCemStdHip(MpcController):
     ("philox": device uniforms; "numpy_legacy": scipy's draws from the global ``np.random`` stream -- parity mode; or
     a callable ``uniforms(num) -> [num, h, d]``).
 
+    ``get_action_batch`` steps several controllers of one configuration in one library call (``icem_plan_step_cem_batch``).
     ``get_action`` is one library call (``icem_plan_step_cem``: a chain of launches, no host round trip, one
     device-to-host copy of the result) where the model is the device's built-in one, the noise is the device's, no
     subclass overrides ``compute_new_mean``, the controller is not verbose and ``IcemPlanner.cem_step_ok()``; everywhere
@@ -959,12 +960,87 @@ class MpcCemStdHip(MpcController):
         self.forward_model_state = self.forward_model.got_actual_observation_and_env_state(
             observation=obs, env_state=state, model_state=self.forward_model_state)
         executed_action = self._step_fused(obs) if self._takes_fused_step() else self._step_stagewise(obs)
+        return self._finish_action(obs, executed_action)
+
+    def _finish_action(self, obs, executed_action):
+        """The tail of ``get_action`` behind the planning step (``self.last_min_cost`` is set), shared with ``get_action_batch``."""
         self.logger.log(self.last_min_cost / self.horizon if self.cost_along_trajectory == "sum" else self.last_min_cost,
                         key="Expected_trajectory_cost")
         if self.forward_model_state is not None:
             _, self.forward_model_state, _ = self.forward_model.predict(
                 observations=obs, states=self.forward_model_state, actions=executed_action)
         return executed_action
+
+    @staticmethod
+    def _batch_refusal(ctrls):
+        """Why ``icem_plan_step_cem_batch`` cannot run these controllers' steps as one call (None: it can, as far as the
+        controllers can tell -- the library has the last word)."""
+        import dataclasses
+        for c in ctrls:
+            if c.fused_step is False:
+                return "a controller has fused_step=False (the stage-wise loop)"
+            why = c._fused_step_refusal()
+            if why is not None:
+                return why
+        c0 = ctrls[0]
+        flags = lambda c: (c.like_levine, c.shift_means, c.execute_best_elite)   # noqa: E731
+        shared = lambda c: dataclasses.replace(c.planner.cfg, seed=0)            # noqa: E731
+        if any(flags(c) != flags(c0) or shared(c) != shared(c0) for c in ctrls[1:]):
+            return "the controllers differ in configuration (everything but the seed must be equal) or in their flags"
+        if len({id(c.planner) for c in ctrls}) != len(ctrls):
+            return "a controller appears twice"
+        return None
+
+    @staticmethod
+    def get_action_batch(controllers, observations, states=None, mode="train"):
+        """``get_action`` of several controllers at once -- the reference steps its CEM baseline's episodes side by side, each
+        controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152; mpc.py:200-262) -- as ONE library call
+        (``icem_plan_step_cem_batch``: 3 launches per CEM iteration for all of them, one device-to-host copy) where every
+        controller takes the fused step by itself (``_fused_step_refusal() is None``) and the controllers share configuration
+        and flags; seeds, episodes and step counts are their own.  Each controller ends in exactly the state its own
+        ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same bookkeeping).  Where the
+        batch is not served each controller's own planning step runs, in order, with the same results; a controller with
+        ``fused_step=True`` makes that a ``RuntimeError`` naming the reason."""
+        from ._lib import ICEM_E_INVALID, ICEM_E_STATE, ICEM_E_UNSUPPORTED, IcemError
+        ctrls = list(controllers)
+        n = len(ctrls)
+        observations = list(observations)
+        states = [None] * n if states is None else list(states)
+        if len(observations) != n or len(states) != n:
+            raise ValueError("one observation (and state) per controller")
+        for c in ctrls:
+            if not c.was_reset:
+                raise AttributeError("beginning_of_rollout() needs to be called before")
+        if n == 0:
+            return []
+        for c, ob, stt in zip(ctrls, observations, states):
+            c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
+                observation=ob, env_state=stt, model_state=c.forward_model_state)
+        why = MpcCemStdHip._batch_refusal(ctrls)
+        host = None
+        if why is None:
+            try:
+                res = IcemPlanner.plan_step_cem_batch(
+                    [c.planner for c in ctrls], observations, [(c._mean, c._std, c._lower, c._upper) for c in ctrls],
+                    like_levine=ctrls[0].like_levine, shift_means=ctrls[0].shift_means, execute_best_elite=ctrls[0].execute_best_elite)
+                host = ctrls[0].planner.cem_batch_results.cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+                del res
+            except IcemError as e:   # refused before anything ran: nothing was touched, no planner has advanced
+                if e.code not in (ICEM_E_UNSUPPORTED, ICEM_E_INVALID, ICEM_E_STATE):
+                    raise
+                why = str(e)
+        if why is not None and any(c.fused_step is True for c in ctrls):
+            raise RuntimeError(f"fused_step=True, but the batched fused CEM step is not served: {why}")
+        out = []
+        for i, (c, ob) in enumerate(zip(ctrls, observations)):
+            if host is None:   # the controller's own step (fused where it is served by itself, else the loop)
+                executed_action = c._step_fused(ob) if c._takes_fused_step() else c._step_stagewise(ob)
+            else:
+                p = c.planner
+                c._elite_actions, c._elite_costs = p.cem_elites, p.cem_elite_costs
+                executed_action, c.last_min_cost = host[i, :-1].copy(), float(host[i, -1])
+            out.append(c._finish_action(ob, executed_action))
+        return out
 
     def _fused_step_refusal(self):
         """Why ``icem_plan_step_cem`` cannot run this controller's step (None: it can)."""

@@ -157,10 +157,10 @@ int refresh_act_mag(icem_handle* h, const void* low, const void* high, hipStream
     h->am_hi = high;
     return ICEM_OK;
 }
-int rollout_cost_launch(icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations, hipStream_t st) {
+int rollout_cost_launch(icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations, const LaunchCtx& cx) {
     if (observations == nullptr && n > 0 && fast_rollout_ok(h, 0))
-        return launch_fast_rollout(h, n, 0, 0, obs0, actions, costs, nullptr, nullptr, LaunchCtx{st}, nullptr);
-    return gk_rollout(h, n, obs0, actions, costs, observations, LaunchCtx{st});
+        return launch_fast_rollout(h, n, 0, 0, obs0, actions, costs, nullptr, nullptr, cx, nullptr);
+    return gk_rollout(h, n, obs0, actions, costs, observations, cx);
 }
 // what a learned-dynamics launch's HIP result means to the caller (every entry point that launches it)
 int rssm_launch_result(hipError_t e) {
@@ -698,7 +698,7 @@ int icem_rollout_cost(icem_handle* h, int32_t n, const void* obs0, const void* a
     if (n < 0 || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "null tensor / negative n");
     if (const char* e = cost_indices_error(h, h->obs_dim)) return fail(ICEM_E_INVALID, e);
     if (const char* e = wide_unsupported(h, 0, false, observations != nullptr)) return fail(ICEM_E_UNSUPPORTED, e);
-    return rollout_cost_launch(h, n, obs0, actions, costs, observations, (hipStream_t)stream);
+    return rollout_cost_launch(h, n, obs0, actions, costs, observations, LaunchCtx{(hipStream_t)stream});
 }
 
 int icem_cost_reduce(icem_handle* h, int32_t n, const void* step_costs, void* costs, void* stream) {

@@ -65,6 +65,7 @@ struct CemTailArgs {
     const T* elite_costs;     // [K]
     T* executed;              // [d]
     T* best_cost;             // [1]
+    T* result;                // [d + 1] executed | best_cost once more (a batch's row of `results`), or nullptr
 };
 
 // _update_bounds on the refitted rows (mpc.py:228); behind the last iteration executed / best_cost (mpc.py:230-233), the
@@ -77,8 +78,16 @@ __device__ __forceinline__ void cem_tail(const CemTailArgs<T>& c, T* stage) {
     const int hd = c.h * c.d;
     for (int e = tid; e < hd; e += NT) cem_bounds_element<T>(e, e % c.d, c.like_levine, c.mean, c.std, c.low, c.high, c.lower, c.upper);
     if (!c.last) return;
-    if (tid < c.d) c.executed[tid] = c.execute_best_elite ? c.elites[tid] : c.mean[tid];
-    if (tid == 0) c.best_cost[0] = c.elite_costs[0];
+    if (tid < c.d) {
+        const T x = c.execute_best_elite ? c.elites[tid] : c.mean[tid];
+        c.executed[tid] = x;
+        if (c.result) c.result[tid] = x;
+    }
+    if (tid == 0) {
+        const T bc = c.elite_costs[0];
+        c.best_cost[0] = bc;
+        if (c.result) c.result[c.d] = bc;
+    }
     for (int e = tid; e < hd; e += NT) stage[e] = c.mean[e];
     __syncthreads();
     for (int e = tid; e < hd; e += NT) {

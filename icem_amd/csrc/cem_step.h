@@ -1,4 +1,4 @@
-// cem_step.h -- what the host side of icem_plan_step_cem (cem_step.hip) asks of its kernels (k_cem.hip).
+// cem_step.h -- what the host side of icem_plan_step_cem / icem_plan_step_cem_batch (cem_step.hip) asks of its kernels (k_cem.hip).
 // Internal; not part of the public ABI.
 #pragma once
 #include "host_common.h"
@@ -26,5 +26,27 @@ int launch_cem_sample(const icem_handle* h, int n, const void* mean, const void*
 // selection + gather + refit + bounds (+ epilogue) in one workgroup: f32 on update_small_kernel's body, f64 on select_refit_kernel's
 void launch_cem_update(const UpdateSmallArgs& u, const CemTailArgs<float>& t, hipStream_t st);
 void launch_cem_update(const SelectArgs<double>& s, int* idx_out, const CemTailArgs<double>& t, hipStream_t st);
+
+// ---- icem_plan_step_cem_batch: the same three kernels' bodies for B problems per launch, argument blocks in a device array ----
+// the update kernels' blocks (the solo kernels take the members one by one)
+struct CemUpdateF32Args {
+    UpdateSmallArgs u;
+    CemTailArgs<float> t;
+};
+struct CemUpdateF64Args {
+    SelectArgs<double> s;
+    int* idx_out;
+    CemTailArgs<double> t;
+};
+// the sampler's block of the handle's dtype -> dst (zeroed by the caller; every byte defined); offset_rel: relative to the
+// problem's entry of BatchBases
+size_t cem_sample_block_bytes(const icem_handle* h);
+void cem_sample_block(const icem_handle* h, int n, const void* mean, const void* std, const void* lower, const void* upper,
+                      uint64_t offset_rel, void* out, void* dst);
+// grid (ceil(n_rows / tpw), n_problems): all problems draw n_rows rows
+void launch_cem_sample_batch(const icem_handle* h, int n_rows, const void* args_dev, const BatchBases& bases, int n_problems, hipStream_t st);
+// one workgroup per problem; hd: the dynamic LDS of cem_tail's stage
+void launch_cem_update_batch(const CemUpdateF32Args* args_dev, int n_problems, int hd, hipStream_t st);
+void launch_cem_update_batch(const CemUpdateF64Args* args_dev, int n_problems, int hd, hipStream_t st);
 
 }  // namespace icem

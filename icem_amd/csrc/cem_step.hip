@@ -7,6 +7,13 @@
 //   update   cem_update_*_kernel (k_cem.hip): icem_update_distribution's body (f32) / the one-launch selection's (f64), then
 //            icem_cem_bounds' arithmetic; the last one carries get_action's epilogue
 // The arguments go by value: no device-side argument memory, no upload, nothing allocated by the step itself.
+//
+// icem_plan_step_cem_batch is the same step for B planners of one configuration -- the reference runs its controllers side by side
+// (icem/misc/rollout_utils.py:46-58, 129-152) -- with every one of the three launches ONE launch for all of them: cem_sample_batch_kernel,
+// the batched twin of the handles' rollout launch (LAUNCH_FAMILIES, icem_fused.h; each handle's rollout_cost_launch runs under a recorder
+// and its launch is compared and issued once for all), cem_update_*_batch_kernel.  The argument blocks live in a DeviceArgArray of the
+// first handle; they carry no step-dependent value (the sampler's offset is relative to the step's base, which travels by value),
+// so a batch whose buffers stay put uploads each of its two slots once.
 #include "cem_step.h"
 
 using namespace icem;
@@ -33,9 +40,11 @@ const char* cem_unserved(const icem_handle* h) {
     return nullptr;
 }
 
+// The update's blocks, filled member by member into ZEROED memory (the solo launch's locals, a batch's blob): every byte of a
+// block is defined, so a batch's blob compares equal as bytes from step to step.  result: the problem's row of a batch's
+// `results` (nullptr: the solo entry -- the kernels then write what they always wrote)
 template <typename T>
-CemTailArgs<T> tail_args(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last) {
-    CemTailArgs<T> t;
+void fill_tail(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last, void* result, CemTailArgs<T>& t) {
     t.h = h->cfg.horizon, t.d = h->cfg.act_dim;
     t.like_levine = p.like_levine != 0, t.shift_means = p.shift_means != 0, t.execute_best_elite = p.execute_best_elite != 0;
     t.last = last ? 1 : 0;
@@ -45,36 +54,183 @@ CemTailArgs<T> tail_args(const icem_handle* h, const icem_cem_buffers& b, const 
     t.lower = (T*)b.lower, t.upper = (T*)b.upper;
     t.elites = (const T*)b.elites, t.elite_costs = (const T*)b.elite_costs;
     t.executed = (T*)b.executed, t.best_cost = (T*)b.best_cost;
-    return t;
+    t.result = (T*)result;
 }
 
-void launch_update(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last, hipStream_t st) {
+// (icem_update_distribution's block, abi.hip: no kept elites)
+void fill_update(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last, void* result, CemUpdateF32Args& g) {
     const icem_config& c = h->cfg;
-    const int N = c.num_traj, K = c.num_elites;
-    if (c.dtype == ICEM_F32) {
-        // (icem_update_distribution's block, abi.hip: no kept elites)
-        const UpdateSmallArgs u{(const float*)b.costs, (const float*)b.actions, nullptr, nullptr, N, 0, K, h->hd, (float)c.alpha,
-                                (float*)b.mean, (float*)b.std, (float*)b.elites, (float*)b.elite_costs, b.elite_idx};
-        launch_cem_update(u, tail_args<float>(h, b, p, last), st);
-        return;
-    }
-    // (gk_select_refit's block, generic_kernels.hip: every row a sampled one, no kept elites, never the step's "last" -- the
-    //  CEM epilogue is cem_tail's)
-    SelectArgs<double> s;
-    std::memset((void*)&s, 0, sizeof(s));
-    s.n_cand = s.n_loc = N;
+    UpdateSmallArgs& u = g.u;
+    u.costs = (const float*)b.costs, u.pool = (const float*)b.actions, u.keep_costs = nullptr, u.keep_actions = nullptr;
+    u.n = c.num_traj, u.n_keep = 0, u.K = c.num_elites, u.hd = h->hd;
+    u.alpha = (float)c.alpha;
+    u.mean = (float*)b.mean, u.std = (float*)b.std, u.elites_out = (float*)b.elites, u.elite_costs_out = (float*)b.elite_costs;
+    u.idx_out = b.elite_idx;
+    fill_tail<float>(h, b, p, last, result, g.t);
+}
+
+// (gk_select_refit's block, generic_kernels.hip: every row a sampled one, no kept elites, never the step's "last" -- the
+//  CEM epilogue is cem_tail's)
+void fill_update(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last, void* result, CemUpdateF64Args& g) {
+    const icem_config& c = h->cfg;
+    SelectArgs<double>& s = g.s;
+    s.n_cand = s.n_loc = c.num_traj;
     s.cap = SELECT_CAP;
     s.costs = (const double*)b.costs;
     s.actions = (const double*)b.actions;
     MergeArgs<double>& a = s.m;
-    a.K = K, a.h = c.horizon, a.d = c.act_dim, a.n_global = N;
+    a.K = c.num_elites, a.h = c.horizon, a.d = c.act_dim, a.n_global = c.num_traj;
     a.alpha = c.alpha, a.init_std = c.init_std;
     a.elites_next = (double*)b.elites, a.elites_cost_next = (double*)b.elite_costs;
     a.mean_in = (const double*)b.mean, a.std_in = (const double*)b.std;
     a.mean = (double*)b.mean, a.std = (double*)b.std;
     a.low = (const double*)b.low, a.high = (const double*)b.high;
-    a.xw = XchgWait{};
-    launch_cem_update(s, b.elite_idx, tail_args<double>(h, b, p, last), st);
+    g.idx_out = b.elite_idx;
+    fill_tail<double>(h, b, p, last, result, g.t);
+}
+
+void launch_update(const icem_handle* h, const icem_cem_buffers& b, const icem_cem_params& p, bool last, void* result, hipStream_t st) {
+    if (h->cfg.dtype == ICEM_F32) {
+        CemUpdateF32Args g;
+        std::memset((void*)&g, 0, sizeof(g));
+        fill_update(h, b, p, last, result, g);
+        launch_cem_update(g.u, g.t, st);
+        return;
+    }
+    CemUpdateF64Args g;
+    std::memset((void*)&g, 0, sizeof(g));
+    fill_update(h, b, p, last, result, g);
+    launch_cem_update(g.s, g.idx_out, g.t, st);
+}
+
+bool null_buffer(const icem_cem_buffers& b) {
+    return !b.mean || !b.std || !b.lower || !b.upper || !b.low || !b.high || !b.obs0 || !b.actions || !b.costs || !b.elites ||
+           !b.elite_costs || !b.elite_idx || !b.executed || !b.best_cost;
+}
+
+// the refusals of one handle's step, all of them before anything is launched or the handle touched (who: the entry's name)
+int cem_refusal(const icem_handle* h, const icem_cem_buffers& b, int32_t mpc_step, const std::string& who) {
+    if (mpc_step < 0) return fail(ICEM_E_INVALID, who + "negative mpc_step");
+    if (null_buffer(b)) return fail(ICEM_E_INVALID, who + "null buffer (everything but workspace is needed)");
+    if (const char* why = cem_unserved(h)) return fail(ICEM_E_UNSUPPORTED, who + why);
+    if (!h->has_model || !h->has_cost) return fail(ICEM_E_STATE, who + "icem_set_model / icem_set_cost must be called first");
+    if (const char* e = cost_indices_error(h, h->obs_dim)) return fail(ICEM_E_INVALID, e);
+    if (const char* e = wide_unsupported(h, 0, false, false)) return fail(ICEM_E_UNSUPPORTED, e);
+    return ICEM_OK;
+}
+
+// one planner's step behind its refusals: 3 launches per iteration, the arguments by value.  *launches_out: written on success
+int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, int32_t mpc_step, void* result, hipStream_t st,
+                  long long* launches_out) {
+    const icem_config& c = h->cfg;
+    const int N = c.num_traj, iters = c.opt_iters;
+    const bool own_sampler = cem_sample_ok(h);
+    long long launches = 0;
+    for (int it = 0; it < iters; ++it) {
+        const uint64_t offset = (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)iters + (uint64_t)it;
+        int rc = own_sampler ? launch_cem_sample(h, N, b->mean, b->std, b->lower, b->upper, offset, b->actions, st)
+                             : gk_sample_truncnorm(h, N, 0, b->mean, b->std, b->lower, b->upper, nullptr, offset, b->actions, st);
+        if (rc) return rc;
+        ++launches;
+        rc = rollout_cost_launch(h, N, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st});
+        if (rc) return rc;
+        ++launches;
+        launch_update(h, *b, *p, it == iters - 1, result, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    *launches_out = launches;
+    return ICEM_OK;
+}
+
+size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// B > 1 planners behind the admission of the batch.  Host state: the step keeps none per handle -- no elite double buffer, no
+// pending merge, the noise offsets follow from (episode, mpc_step) which the caller owns.  What exists is the first handle's
+// argument array (cem_batch_args + its upload counter batch_uploads; a slot that was uploaded holds exactly what its shadow says,
+// whatever happens later) and its cem_batch_launches, written behind the last launch only.  Recording a handle's rollout may
+// upload that handle's packed model (ensure_fast_model: idempotent, what its next solo step would do first).  So a HIP call that
+// fails anywhere below leaves every handle as it was.
+int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const int32_t* steps,
+                   void* results, hipStream_t st) {
+    const std::string who = "icem_plan_step_cem_batch: ";
+    icem_handle* h0 = handles[0];
+    const icem_config& c = h0->cfg;
+    const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd, d = c.act_dim;
+    const bool f64 = c.dtype == ICEM_F64;
+    if (!cem_sample_ok(h0))
+        return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its two probability tables and one row in LDS): "
+                                              "the operator's sampler has no batched form");
+    // ---- every problem's rollout launch, recorded: its batched family, its key, its argument block ----
+    BatchHint hint;
+    hint.mult = n;   // (TileHN: a batch's launches are the one-wave-per-tile kernel's; the other families keep the solo shape)
+    std::vector<LaunchRecorder> recs(n);
+    for (int i = 0; i < n; ++i) {
+        recs[i].who = "icem_plan_step_cem_batch: ";
+        const icem_cem_buffers& b = buffers[i];
+        if (int rc = rollout_cost_launch(handles[i], N, b.obs0, b.actions, b.costs, nullptr, LaunchCtx{st, hint, &recs[i]})) return rc;
+        if (recs[i].unsupported) return fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached (this handle's rollout kernel has no batched twin)");
+    }
+    const std::vector<LaunchDesc>& first = recs[0].launches;
+    const size_t L = first.size();
+    for (int i = 0; i < n; ++i) {
+        if (recs[i].launches.size() != L || L == 0) return fail(ICEM_E_STATE, who + "the problems' steps took different launches");
+        for (size_t l = 0; l < L; ++l)
+            if (!(recs[i].launches[l].key == first[l].key)) return fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
+    }
+    for (size_t l = 0; l < L; ++l)
+        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
+    // ---- argument blocks: per iteration [sample x n | rollout launch(es) x n | update x n] ----
+    const size_t sb = cem_sample_block_bytes(h0), ub = f64 ? sizeof(CemUpdateF64Args) : sizeof(CemUpdateF32Args);
+    std::vector<size_t> at(L);   // a rollout launch's array inside an iteration's part
+    size_t per_it = padded(sb * n), per_it_room = padded(sb * ICEM_MAX_BATCH);
+    for (size_t l = 0; l < L; ++l) {
+        at[l] = per_it;
+        per_it += padded(launch_family(first[l].key.family)->block_bytes * n);
+        per_it_room += padded(launch_family(first[l].key.family)->block_bytes * ICEM_MAX_BATCH);
+    }
+    const size_t at_update = per_it;
+    per_it += padded(ub * n);
+    per_it_room += padded(ub * ICEM_MAX_BATCH);
+    std::vector<unsigned char> blob(per_it * iters, 0);
+    BatchBases bases{};
+    for (int i = 0; i < n; ++i) bases.v[i] = (handles[i]->episode << 32) + (uint64_t)steps[i] * (uint64_t)iters;
+    for (int it = 0; it < iters; ++it) {
+        unsigned char* part = blob.data() + per_it * it;
+        for (int i = 0; i < n; ++i) {
+            const icem_cem_buffers& b = buffers[i];
+            cem_sample_block(handles[i], N, b.mean, b.std, b.lower, b.upper, (uint64_t)it, b.actions, part + sb * i);
+            for (size_t l = 0; l < L; ++l) {
+                const size_t one = launch_family(first[l].key.family)->block_bytes;
+                std::memcpy(part + at[l] + one * i, recs[i].launches[l].block, one);
+            }
+            void* row = results ? (unsigned char*)results + (size_t)i * (d + 1) * h0->tsize : nullptr;
+            if (f64) fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF64Args*)(part + at_update + ub * i));
+            else fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF32Args*)(part + at_update + ub * i));
+        }
+    }
+    const int slot = steps[0] & 1;
+    ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, per_it_room * iters, st, &h0->batch_uploads));
+    // ---- the launches: 3 per iteration (+ the GEMM path's row tail, which a CEM step never has: no shifted rows) ----
+    const unsigned char* dev = (const unsigned char*)h0->cem_batch_args.dev(slot);
+    long long launches = 0;
+    for (int it = 0; it < iters; ++it) {
+        const unsigned char* part = dev + per_it * it;
+        launch_cem_sample_batch(h0, N, part, bases, n, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+        for (size_t l = 0; l < L; ++l) {
+            launch_family(first[l].key.family)->launch(first[l].key, part + at[l], bases, n, st);
+            ICEM_HIP_TRY(hipGetLastError());
+            ++launches;
+        }
+        if (f64) launch_cem_update_batch((const CemUpdateF64Args*)(part + at_update), n, hd, st);
+        else launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    h0->cem_batch_launches = launches;
+    return ICEM_OK;
 }
 
 }  // namespace
@@ -86,37 +242,29 @@ int icem_plan_step_cem_ok(const icem_handle* h) { return (h && cem_unserved(h) =
 int icem_plan_step_cem(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, int32_t mpc_step, void* stream) {
     // ---- refusals: all of them before anything is launched or the handle touched ----
     if (!h || !b || !p) return fail(ICEM_E_INVALID, "icem_plan_step_cem: null handle, buffers or params");
-    if (mpc_step < 0) return fail(ICEM_E_INVALID, "icem_plan_step_cem: negative mpc_step");
-    if (!b->mean || !b->std || !b->lower || !b->upper || !b->low || !b->high || !b->obs0 || !b->actions || !b->costs || !b->elites ||
-        !b->elite_costs || !b->elite_idx || !b->executed || !b->best_cost)
-        return fail(ICEM_E_INVALID, "icem_plan_step_cem: null buffer (everything but workspace is needed)");
-    if (const char* why = cem_unserved(h)) return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_cem: ") + why);
-    if (!h->has_model || !h->has_cost) return fail(ICEM_E_STATE, "icem_plan_step_cem: icem_set_model / icem_set_cost must be called first");
-    if (const char* e = cost_indices_error(h, h->obs_dim)) return fail(ICEM_E_INVALID, e);
-    if (const char* e = wide_unsupported(h, 0, false, false)) return fail(ICEM_E_UNSUPPORTED, e);
-    const icem_config& c = h->cfg;
-    const int N = c.num_traj, iters = c.opt_iters;
-    hipStream_t st = (hipStream_t)stream;
-    const bool own_sampler = cem_sample_ok(h);
-    long long launches = 0;
+    if (int rc = cem_refusal(h, *b, mpc_step, "icem_plan_step_cem: ")) return rc;
     h->cem_launches = 0;
-    for (int it = 0; it < iters; ++it) {
-        const uint64_t offset = (h->episode << 32) + (uint64_t)mpc_step * (uint64_t)iters + (uint64_t)it;
-        int rc = own_sampler ? launch_cem_sample(h, N, b->mean, b->std, b->lower, b->upper, offset, b->actions, st)
-                             : gk_sample_truncnorm(h, N, 0, b->mean, b->std, b->lower, b->upper, nullptr, offset, b->actions, st);
-        if (rc) return rc;
-        ++launches;
-        rc = rollout_cost_launch(h, N, b->obs0, b->actions, b->costs, nullptr, st);
-        if (rc) return rc;
-        ++launches;
-        launch_update(h, *b, *p, it == iters - 1, st);
-        ICEM_HIP_TRY(hipGetLastError());
-        ++launches;
+    return cem_step_solo(h, b, p, mpc_step, nullptr, (hipStream_t)stream, &h->cem_launches);
+}
+
+int icem_plan_step_cem_batch(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
+                             const int32_t* mpc_steps_host, void* results, void* stream) {
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    if (int rc = admit_batch(handles, n, buffers && p && mpc_steps_host, true, "icem_plan_step_cem_batch: ",
+                             "icem_plan_step_cem_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = cem_refusal(handles[i], buffers[i], mpc_steps_host[i], "icem_plan_step_cem_batch: ")) return rc;
+    if (n == 1) {   // one planner: the solo launches (the same bits by construction), the results row from the last update
+        long long launches = 0;
+        const int rc = cem_step_solo(handles[0], &buffers[0], p, mpc_steps_host[0], results, (hipStream_t)stream, &launches);
+        if (rc == ICEM_OK) handles[0]->cem_batch_launches = launches;
+        return rc;
     }
-    h->cem_launches = launches;
-    return ICEM_OK;
+    return cem_step_batch(handles, n, buffers, *p, mpc_steps_host, results, (hipStream_t)stream);
 }
 
 int64_t icem_cem_step_launches(const icem_handle* h) { return h ? (int64_t)h->cem_launches : 0; }
+int64_t icem_cem_batch_launches(const icem_handle* h) { return h ? (int64_t)h->cem_batch_launches : 0; }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //   generic_kernels.hip  the generic (f32 / f64, any shape) kernels + their launchers (gk_*)
 //   plan.hip             the fused MPC step: icem_plan_* / icem_get_action and the f32 throughput-path orchestration
 //   learned_step.hip     the learned-dynamics MPC step: icem_plan_step_learned*
-//   cem_step.hip         the CEM baseline's MPC step: icem_plan_step_cem
+//   cem_step.hip         the CEM baseline's MPC step: icem_plan_step_cem, icem_plan_step_cem_batch
 //   exchange.hip         the in-library elite exchange between GPUs (icem_exchange_*)
 //   abi.hip              handle life cycle and the stateless operators of include/icem_hip.h
 // Internal; not part of the public ABI.
@@ -222,6 +222,10 @@ struct icem_handle {
     long long batch_f64_launches = 0;       // kernel launches of the last icem_plan_step_batch_f64 this handle led
     icem::LearnedCtx learned;               // icem_plan_step_learned* (learned_step.hip)
     long long cem_launches = 0;             // kernel launches of the last icem_plan_step_cem of this handle (cem_step.hip)
+    // icem_plan_step_cem_batch (cem_step.hip): the batch's argument blocks live with its FIRST handle, by that handle's step parity
+    // (the blocks carry no step-dependent value: either slot of a batch whose buffers stay put is uploaded once)
+    icem::DeviceArgArray<2> cem_batch_args;
+    long long cem_batch_launches = 0;       // kernel launches of the last icem_plan_step_cem_batch this handle led
     void* rccl_comm = nullptr;       // collective.hip: the RCCL communicator of icem_allgather_elites (world > 1)
     bool rccl_owned = false;         // ... created by icem_rccl_connect (destroyed with the handle) or adopted
 };
@@ -423,8 +427,9 @@ int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const voi
                         unsigned long long* part_k = nullptr, int n_tail = 0, int* tail_out = nullptr);
 int rssm_launch_result(hipError_t e);   // abi.hip: a learned-dynamics launch's HIP result as an ICEM_* code (+ message)
 // abi.hip: the launch icem_rollout_cost picks for this handle (the matrix-pipe rollout where it serves the handle and no
-// observations are asked for, else the generic one) -- icem_plan_step_cem (cem_step.hip) rolls out through the same dispatch
-int rollout_cost_launch(icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations, hipStream_t st);
+// observations are asked for, else the generic one) -- icem_plan_step_cem (cem_step.hip) rolls out through the same dispatch, and
+// icem_plan_step_cem_batch records it (cx.rec: nothing is launched)
+int rollout_cost_launch(icem_handle* h, int n, const void* obs0, const void* actions, void* costs, void* observations, const LaunchCtx& cx);
 int refresh_act_mag(icem_handle* h, const void* low, const void* high, hipStream_t st, bool force);   // abi.hip
 void ahead_destroy(icem_handle* h);
 void predraw_next_step(icem_handle* h, const icem_plan_buffers* b, int mpc_step, const LaunchCtx& cx);

@@ -92,7 +92,7 @@ struct FastRolloutArgs {
     unsigned* nonfinite = nullptr;        // counts the trajectories whose cost came out NaN (icem_nonfinite_costs); never NULL in a launch
 };
 bool fast_rollout_supported(int h, int d, int O, int K);
-void launch_rollout16(const FastRolloutArgs& a, int h, int d, int O, int kind, hipStream_t st);
+void launch_rollout16(const LaunchCtx& cx, const FastRolloutArgs& a, int h, int d, int O, int kind);
 // workgroups (= candidate lists) the rollout of n_rows trajectories is launched with
 int rollout_lists(int h, int d, int O, int n_rows);
 
@@ -372,9 +372,12 @@ struct BatchHint {
 //  rollout with a row of lanes / a thread per trajectory, the one-launch selection + refit; generic_kernels.hip, k_generic_batch.hip)
 // (LAUNCH_ROLLOUT_WIDE / _WIDE_SPLIT / _ROWS_WIDE: the GEMM-path rollouts -- exact f32 tiles, the 16-bit planes, the row-by-row tail
 //  behind the exact kernel; k_rollout_wide_batch.hip, k_rollout_wide_split_batch.hip.  A batch keeps each problem's SOLO launch shape)
+// (LAUNCH_ROLLOUT16: rollout16_kernel alone, the rollout of a tile shape's two-kernel iteration -- icem_plan_step_cem_batch; k_rollout.hip.
+//  Each problem's solo launch shape)
 enum LaunchFamily : int { LAUNCH_SAMPLE_ROLLOUT = 1, LAUNCH_ITER_AHEAD = 2, LAUNCH_MERGE_NOISE = 3, LAUNCH_SAMPLE = 4, LAUNCH_SAMPLE_MERGE = 5,
                           LAUNCH_ROLLOUT_HN = 6, LAUNCH_GK_SAMPLE = 7, LAUNCH_GK_SHIFT = 8, LAUNCH_GK_ROLLOUT_ROWS = 9, LAUNCH_GK_ROLLOUT_THREAD = 10,
-                          LAUNCH_GK_SELECT = 11, LAUNCH_ROLLOUT_WIDE = 12, LAUNCH_ROLLOUT_WIDE_SPLIT = 13, LAUNCH_ROLLOUT_ROWS_WIDE = 14 };
+                          LAUNCH_GK_SELECT = 11, LAUNCH_ROLLOUT_WIDE = 12, LAUNCH_ROLLOUT_WIDE_SPLIT = 13, LAUNCH_ROLLOUT_ROWS_WIDE = 14,
+                          LAUNCH_ROLLOUT16 = 15 };
 struct LaunchKey {
     int family = 0;
     int h = 0, d = 0, O = 0, kind = 0, arith = 0;   // (rollout_hn: O = the observation width o)
@@ -384,6 +387,7 @@ struct LaunchKey {
     // gk_sample: O = HMAX, waves = trajectories per workgroup, form = the generator's rounds; gk_rollout_*: O = the padded width
     // rollout_wide: O = o, arith = 1 (exact f32), waves = NT, form = EXT; rollout_wide_split: arith = 2 (fp16 planes) / 3 (bf16),
     // waves = NCT, form = EXT | FIVE << 1; rollout_rows_wide: O = o, form = EXT, wgs[0] = the tail's rows
+    // rollout16: arith = 1 the fp16 planes (Tile16H), 0 exact f32 (Tile16); waves = WAVES
     int form = 0;
     int wgs[3] = {0, 0, 0};   // workgroups per role (of ONE problem); the grid is their sum
     bool operator==(const LaunchKey& o) const { return std::memcmp(this, &o, sizeof(LaunchKey)) == 0; }
@@ -494,6 +498,15 @@ inline void batch_form(const WideRowsArgs& a, void* dst) {
     g.row0 = a.row0, g.n_tail = a.n_tail, g.o = a.o, g.d = a.d, g.h = a.h, g.cost_mode = a.cost_mode, g.wc = a.wc;
     g.cs = a.cs, g.A = a.A, g.B = a.B, g.obs0 = a.obs0, g.actions = a.actions, g.costs = a.costs;
 }
+inline void batch_form(const FastRolloutArgs& a, void* dst) {   // (member by member into the zeroed block: the padding stays zero)
+    FastRolloutArgs& g = *(FastRolloutArgs*)dst;
+    g.n_rows = a.n_rows, g.n_cand = a.n_cand, g.K = a.K, g.o = a.o, g.cost_mode = a.cost_mode;
+    g.Mp = a.Mp, g.perm = a.perm, g.obs0 = a.obs0;
+    g.ctrl_w = a.ctrl_w, g.lin_w = a.lin_w, g.flip_pen = a.flip_pen, g.flip_th = a.flip_th, g.flip_col = a.flip_col;
+    g.actions = a.actions, g.costs = a.costs, g.part_c = a.part_c, g.part_i = a.part_i, g.part_k = a.part_k;
+    g.list_wgs = a.list_wgs, g.dbg = nullptr, g.arith = a.arith, g.act_mag = a.act_mag, g.m_scale = a.m_scale, g.b_scale = a.b_scale;
+    g.nonfinite = a.nonfinite;
+}
 inline void batch_form(const HnArgs& a, void* dst) {
     HnArgs& g = *(HnArgs*)dst;
     std::memcpy(&g.r, &a.r, sizeof(a.r));
@@ -547,6 +560,8 @@ void launch_gk_select_batch(const LaunchKey& key, const SelectArgs<double>* args
 void launch_rollout_wide_batch(const LaunchKey& key, const WideRolloutArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_rollout_wide_split_batch(const LaunchKey& key, const WideRolloutArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 void launch_rollout_rows_wide_batch(const LaunchKey& key, const WideRowsArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
+// k_rollout.hip (draws nothing: bases unused; grid = key.wgs[0] x n, the problem's own)
+void launch_rollout16_batch(const LaunchKey& key, const FastRolloutArgs* args_dev, const BatchBases& bases, int n, hipStream_t st);
 // is there a batched instantiation of the thread-form rollout at this width and model kind?  (rollout_cost_kernel<double, 32, tanh>
 // spills registers -- tests/test_register_hygiene_cpu.py carries it -- and gets no twin)
 inline bool gk_rollout_thread_batched(int O, int kind) { return !(O == 32 && kind == ICEM_MODEL_TANH); }
@@ -598,6 +613,7 @@ constexpr LaunchFamilyRow LAUNCH_FAMILIES[] = {
     family_row<WideRolloutArgs, launch_rollout_wide_batch>(LAUNCH_ROLLOUT_WIDE),
     family_row<WideRolloutArgs, launch_rollout_wide_split_batch>(LAUNCH_ROLLOUT_WIDE_SPLIT),
     family_row<WideRowsArgs, launch_rollout_rows_wide_batch>(LAUNCH_ROLLOUT_ROWS_WIDE),
+    family_row<FastRolloutArgs, launch_rollout16_batch>(LAUNCH_ROLLOUT16),
 };
 inline const LaunchFamilyRow* launch_family(int family) {
     for (const LaunchFamilyRow& r : LAUNCH_FAMILIES)

@@ -1,5 +1,6 @@
-// k_cem.hip -- the kernels of icem_plan_step_cem (cem_step.hip), the CEM baseline's MPC step (MpcCemStd.get_action,
-// icem/controllers/mpc.py:200-262) as a chain of launches:
+// k_cem.hip -- the kernels of icem_plan_step_cem and icem_plan_step_cem_batch (cem_step.hip), the CEM baseline's MPC step
+// (MpcCemStd.get_action, icem/controllers/mpc.py:200-262) as a chain of launches, for one planner or for B (the *_batch_kernel
+// twins: the same bodies, blockIdx.y / blockIdx.x = the problem, the argument blocks in a device array):
 //   cem_sample_kernel      icem_sample_truncnorm's draw (mpc.py:188-198) with the two probability tables Phi(lower) and
 //                          Phi(upper) - Phi(lower) -- functions of (t, j) alone -- computed once per workgroup into LDS, and a
 //                          workgroup's rows staged in LDS and stored as one contiguous span
@@ -17,8 +18,9 @@ namespace {
 
 // One thread per (trajectory, dim) row, as sample_truncnorm_kernel: word t of the row's stream is the uniform of step t.
 // LDS: pa [h, d] | pd [h, d] | tile [tpw, h, d].
+// (the body of cem_sample_kernel and of cem_sample_batch_kernel: one device function, the same device code)
 template <typename T, int ROUNDS>
-__global__ __launch_bounds__(WG) void cem_sample_kernel(CemSampleArgs<T> a) {
+__device__ __forceinline__ void cem_sample_body(const CemSampleArgs<T>& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
     const int hd = a.h * a.d;
@@ -50,6 +52,55 @@ __global__ __launch_bounds__(WG) void cem_sample_kernel(CemSampleArgs<T> a) {
     for (int e = tid; e < total; e += WG) out[e] = tile[e];
 }
 
+template <typename T, int ROUNDS>
+__global__ __launch_bounds__(WG) void cem_sample_kernel(CemSampleArgs<T> a) {
+    cem_sample_body<T, ROUNDS>(a);
+}
+
+// ---- B problems per launch (icem_plan_step_cem_batch): the argument blocks in device memory, their pointers re-read as global
+// addresses (fused_dev.h: gptr) ----
+template <typename T>
+__device__ __forceinline__ CemSampleArgs<T> from_device(const CemSampleArgs<T>& m) {
+    CemSampleArgs<T> a = m;
+    a.mean = gptr(m.mean), a.std = gptr(m.std), a.lower = gptr(m.lower), a.upper = gptr(m.upper), a.out = gptr(m.out);
+    return a;
+}
+template <typename T>
+__device__ __forceinline__ CemTailArgs<T> from_device(const CemTailArgs<T>& m) {
+    CemTailArgs<T> t = m;
+    t.mean = gptr(m.mean), t.std = gptr(m.std), t.low = gptr(m.low), t.high = gptr(m.high), t.lower = gptr(m.lower), t.upper = gptr(m.upper);
+    t.elites = gptr(m.elites), t.elite_costs = gptr(m.elite_costs), t.executed = gptr(m.executed), t.best_cost = gptr(m.best_cost);
+    t.result = gptr(m.result);
+    return t;
+}
+__device__ __forceinline__ UpdateSmallArgs from_device(const UpdateSmallArgs& m) {
+    UpdateSmallArgs u = m;
+    u.costs = gptr(m.costs), u.pool = gptr(m.pool), u.keep_costs = gptr(m.keep_costs), u.keep_actions = gptr(m.keep_actions);
+    u.mean = gptr(m.mean), u.std = gptr(m.std), u.elites_out = gptr(m.elites_out), u.elite_costs_out = gptr(m.elite_costs_out);
+    u.idx_out = gptr(m.idx_out);
+    return u;
+}
+// (the CEM step's selection: every row a sampled one, no kept elites, nothing to wait for, never the step's "last")
+__device__ __forceinline__ SelectArgs<double> from_device(const SelectArgs<double>& m) {
+    SelectArgs<double> s = m;
+    s.costs = gptr(m.costs), s.actions = gptr(m.actions), s.dbg = nullptr;
+    MergeArgs<double>& a = s.m;
+    a.records = nullptr, a.elites_cur = gptr(m.m.elites_cur), a.elites_cost_cur = gptr(m.m.elites_cost_cur);
+    a.elites_next = gptr(m.m.elites_next), a.elites_cost_next = gptr(m.m.elites_cost_next);
+    a.mean_in = gptr(m.m.mean_in), a.std_in = gptr(m.m.std_in), a.mean = gptr(m.m.mean), a.std = gptr(m.m.std);
+    a.low = gptr(m.m.low), a.high = gptr(m.m.high), a.executed = gptr(m.m.executed), a.best_cost = gptr(m.m.best_cost);
+    a.xw = XchgWait{};
+    return s;
+}
+
+// blockIdx.y = the problem; the block's stream offset is relative to the step's base of that problem (BatchBases): it holds `it`
+template <typename T, int ROUNDS>
+__global__ __launch_bounds__(WG) void cem_sample_batch_kernel(const CemSampleArgs<T>* __restrict__ args, BatchBases bases) {
+    CemSampleArgs<T> a = from_device(args[blockIdx.y]);
+    add_base64(a.off_lo, a.off_hi, bases.v[blockIdx.y]);
+    cem_sample_body<T, ROUNDS>(a);
+}
+
 __global__ __launch_bounds__(1024) void cem_update_f32_kernel(UpdateSmallArgs u, CemTailArgs<float> t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     update_small_body<false>(u, nullptr);
@@ -59,6 +110,26 @@ __global__ __launch_bounds__(1024) void cem_update_f32_kernel(UpdateSmallArgs u,
 
 __global__ __launch_bounds__(SELECT_NT) void cem_update_f64_kernel(SelectArgs<double> s, int* idx_out, CemTailArgs<double> t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];   // (the body's new_mean: unused, s.m.last == 0)
+    select_refit_body<double>(s, idx_out);
+    __syncthreads();
+    cem_tail<double, SELECT_NT>(t, reinterpret_cast<double*>(smem_raw));
+}
+
+// one workgroup per problem (blockIdx.x)
+__global__ __launch_bounds__(1024) void cem_update_f32_batch_kernel(const CemUpdateF32Args* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const UpdateSmallArgs u = from_device(args[blockIdx.x].u);
+    const CemTailArgs<float> t = from_device(args[blockIdx.x].t);
+    update_small_body<false>(u, nullptr);
+    __syncthreads();
+    cem_tail<float, 1024>(t, reinterpret_cast<float*>(smem_raw));
+}
+
+__global__ __launch_bounds__(SELECT_NT) void cem_update_f64_batch_kernel(const CemUpdateF64Args* __restrict__ args) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const SelectArgs<double> s = from_device(args[blockIdx.x].s);
+    int* idx_out = gptr(args[blockIdx.x].idx_out);
+    const CemTailArgs<double> t = from_device(args[blockIdx.x].t);
     select_refit_body<double>(s, idx_out);
     __syncthreads();
     cem_tail<double, SELECT_NT>(t, reinterpret_cast<double*>(smem_raw));
@@ -97,6 +168,49 @@ int launch_cem_sample(const icem_handle* h, int n, const void* mean, const void*
 #undef ICEM_CS
     ICEM_HIP_TRY(hipGetLastError());
     return ICEM_OK;
+}
+
+size_t cem_sample_block_bytes(const icem_handle* h) { return h->cfg.dtype == ICEM_F64 ? sizeof(CemSampleArgs<double>) : sizeof(CemSampleArgs<float>); }
+
+template <typename T>
+static void sample_block_t(const icem_handle* h, int n, const void* mean, const void* std, const void* lower, const void* upper,
+                           uint64_t offset_rel, void* out, void* dst) {
+    const icem_config& c = h->cfg;
+    CemSampleArgs<T>& a = *(CemSampleArgs<T>*)dst;   // (no padding: four ints, four pointers, four words, a pointer)
+    a.n = n, a.h = c.horizon, a.d = c.act_dim, a.tpw = cem_sample_tpw(h);
+    a.mean = (const T*)mean, a.std = (const T*)std, a.lower = (const T*)lower, a.upper = (const T*)upper;
+    a.seed_lo = (uint32_t)c.seed, a.seed_hi = (uint32_t)(c.seed >> 32);
+    a.off_lo = (uint32_t)offset_rel, a.off_hi = (uint32_t)(offset_rel >> 32);
+    a.out = (T*)out;
+}
+
+void cem_sample_block(const icem_handle* h, int n, const void* mean, const void* std, const void* lower, const void* upper,
+                      uint64_t offset_rel, void* out, void* dst) {
+    if (h->cfg.dtype == ICEM_F64) sample_block_t<double>(h, n, mean, std, lower, upper, offset_rel, out, dst);
+    else sample_block_t<float>(h, n, mean, std, lower, upper, offset_rel, out, dst);
+}
+
+// (the launch shape of launch_cem_sample for every problem: the handles of a batch share the configuration)
+void launch_cem_sample_batch(const icem_handle* h, int n_rows, const void* args_dev, const BatchBases& bases, int n_problems, hipStream_t st) {
+    const icem_config& c = h->cfg;
+    const int tpw = cem_sample_tpw(h);
+    const dim3 grid((n_rows + tpw - 1) / tpw, n_problems);
+    const size_t lds = (size_t)(2 + tpw) * h->hd * h->tsize;
+#define ICEM_CSB(T, R) hipLaunchKernelGGL((cem_sample_batch_kernel<T, R>), grid, dim3(WG), lds, st, (const CemSampleArgs<T>*)args_dev, bases)
+    if (c.dtype == ICEM_F64) {
+        if (c.rng_rounds == 7) ICEM_CSB(double, 7); else ICEM_CSB(double, 10);
+    } else {
+        if (c.rng_rounds == 7) ICEM_CSB(float, 7); else ICEM_CSB(float, 10);
+    }
+#undef ICEM_CSB
+}
+
+void launch_cem_update_batch(const CemUpdateF32Args* args_dev, int n_problems, int hd, hipStream_t st) {
+    hipLaunchKernelGGL(cem_update_f32_batch_kernel, dim3(n_problems), dim3(1024), (size_t)hd * sizeof(float), st, args_dev);
+}
+
+void launch_cem_update_batch(const CemUpdateF64Args* args_dev, int n_problems, int hd, hipStream_t st) {
+    hipLaunchKernelGGL(cem_update_f64_batch_kernel, dim3(n_problems), dim3(SELECT_NT), (size_t)hd * sizeof(double), st, args_dev);
 }
 
 void launch_cem_update(const UpdateSmallArgs& u, const CemTailArgs<float>& t, hipStream_t st) {

@@ -1,13 +1,15 @@
 // k_rollout.hip -- K2 + K3: rollout16_kernel<H, D, O, KIND, WAVES>: one wavefront per 16 trajectories on
-// v_mfma_f32_16x16x4_f32 (Tile16, fused_dev.h), cost on the VALU, one sorted candidate list per workgroup.
+// v_mfma_f32_16x16x4_f32 (Tile16, fused_dev.h), cost on the VALU, one sorted candidate list per workgroup; and
+// rollout16_batch_kernel, the same body for B problems (blockIdx.y) with their argument blocks in device memory.
 #include "fused_dev.h"
 
 namespace icem {
 
 namespace {
 
+// (the body of rollout16_kernel and of rollout16_batch_kernel: one device function, the same device code)
 template <int H, int D, int O, int KIND, int WAVES, int ARITH>
-__global__ __launch_bounds__(64 * WAVES) void rollout16_kernel(FastRolloutArgs a) {
+__device__ __forceinline__ void rollout16_body(const FastRolloutArgs& a) {
     using Stream = Stream16<H, D, O, KIND, ARITH>;
     using Tile = typename Stream::Tile;
     __shared__ __attribute__((aligned(16))) float stage[WAVES][Stream::STG];
@@ -41,6 +43,67 @@ __global__ __launch_bounds__(64 * WAVES) void rollout16_kernel(FastRolloutArgs a
     if (a.K > 0) wg_merge_emit<WAVES>(wg_keys, run_key, a.K, lane, wave, a);
 }
 
+template <int H, int D, int O, int KIND, int WAVES, int ARITH>
+__global__ __launch_bounds__(64 * WAVES) void rollout16_kernel(FastRolloutArgs a) {
+    rollout16_body<H, D, O, KIND, WAVES, ARITH>(a);
+}
+
+// B problems in one launch (icem_plan_step_cem_batch): blockIdx.y = the problem, its argument block in device memory; grid.x =
+// the problem's own solo grid
+template <int H, int D, int O, int KIND, int WAVES, int ARITH>
+__global__ __launch_bounds__(64 * WAVES) void rollout16_batch_kernel(const FastRolloutArgs* __restrict__ args) {
+    const FastRolloutArgs a = from_device(args[blockIdx.y]);
+    rollout16_body<H, D, O, KIND, WAVES, ARITH>(a);
+}
+
+// one compiled (shape, kind, waves, arithmetic): its by-value and its device-array launch
+template <int H, int D, int O, int KIND, int WAVES, int ARITH>
+struct R16Inst {
+    static void solo(int grid, hipStream_t st, const FastRolloutArgs& a) {
+        hipLaunchKernelGGL((rollout16_kernel<H, D, O, KIND, WAVES, ARITH>), dim3(grid), dim3(64 * WAVES), 0, st, a);
+    }
+    static void batch(int grid, int n, hipStream_t st, const FastRolloutArgs* args_dev) {
+        hipLaunchKernelGGL((rollout16_batch_kernel<H, D, O, KIND, WAVES, ARITH>), dim3(grid, n), dim3(64 * WAVES), 0, st, args_dev);
+    }
+};
+
+// key (h, d, O, kind, waves, arith) -> f(R16Inst<...>{}); false: not compiled.
+// two output tiles (O > 20): at most 8 waves per workgroup and the exact arithmetic only (launch_rollout16)
+template <class F>
+bool r16_dispatch(const LaunchKey& k, F&& f) {
+#define XA(HH, DD, OO, KK, WW)                          \
+    {                                                   \
+        if constexpr (OO <= 20) {                       \
+            if (k.arith == 1) {                         \
+                f(R16Inst<HH, DD, OO, KK, WW, 1>{});    \
+                return true;                            \
+            }                                           \
+        }                                               \
+        f(R16Inst<HH, DD, OO, KK, WW, 0>{});            \
+        return true;                                    \
+    }
+#define XW(HH, DD, OO, WW)                       \
+    if constexpr (OO <= 20 || WW <= 8) {         \
+        if (k.waves == WW) {                     \
+            if (k.kind == 1) XA(HH, DD, OO, 1, WW) \
+            else XA(HH, DD, OO, 0, WW)           \
+        }                                        \
+    }
+#define XR(HH, DD, OO)                           \
+    if (k.h == HH && k.d == DD && k.O == OO) {   \
+        XW(HH, DD, OO, 1)                        \
+        XW(HH, DD, OO, 2)                        \
+        XW(HH, DD, OO, 4)                        \
+        XW(HH, DD, OO, 8)                        \
+        XW(HH, DD, OO, 16)                       \
+    }
+    ICEM_FAST_SHAPES(XR)
+#undef XR
+#undef XW
+#undef XA
+    return false;
+}
+
 }  // namespace
 
 bool fast_rollout_supported(int h, int d, int O, int K) {
@@ -58,42 +121,23 @@ int rollout_lists(int h, int d, int O, int n_rows) {
     return g;
 }
 
-void launch_rollout16(const FastRolloutArgs& a, int h, int d, int O, int kind, hipStream_t st) {
-    int grid, waves;
-    r16_shape(a.n_rows, &grid, &waves);
+void launch_rollout16(const LaunchCtx& cx, const FastRolloutArgs& a, int h, int d, int O, int kind) {
+    LaunchKey k;
+    k.family = LAUNCH_ROLLOUT16;
+    k.h = h, k.d = d, k.O = O, k.kind = kind == 1 ? 1 : 0;
+    k.arith = (O <= 20 && a.arith == 1) ? 1 : 0;
+    r16_shape(a.n_rows, &k.wgs[0], &k.waves);
     // two output tiles (O > 20): a 16-wave workgroup's 128 registers spill ~100 of the two-tile step's; at most 8 waves per
     // workgroup (256 registers, no spills), each taking its tiles one after the other (EXPERIMENTS.md R4.6)
-    if (O > 20 && waves > 8) waves = 8;
-#define XA(HH, DD, OO, KK, WW)                                                                                  \
-    {                                                                                                           \
-        if constexpr (OO <= 20) {                                                                               \
-            if (a.arith == 1) {                                                                                 \
-                hipLaunchKernelGGL((rollout16_kernel<HH, DD, OO, KK, WW, 1>), dim3(grid), dim3(64 * WW), 0, st, a); \
-                return;                                                                                         \
-            }                                                                                                   \
-        }                                                                                                       \
-        hipLaunchKernelGGL((rollout16_kernel<HH, DD, OO, KK, WW, 0>), dim3(grid), dim3(64 * WW), 0, st, a);     \
-        return;                                                                                                 \
-    }
-#define XW(HH, DD, OO, WW)                     \
-    if constexpr (OO <= 20 || WW <= 8) {       \
-        if (waves == WW) {                     \
-            if (kind == 1) XA(HH, DD, OO, 1, WW) \
-            else XA(HH, DD, OO, 0, WW)         \
-        }                                      \
-    }
-#define XR(HH, DD, OO)                   \
-    if (h == HH && d == DD && O == OO) { \
-        XW(HH, DD, OO, 1)                \
-        XW(HH, DD, OO, 2)                \
-        XW(HH, DD, OO, 4)                \
-        XW(HH, DD, OO, 8)                \
-        XW(HH, DD, OO, 16)               \
-    }
-    ICEM_FAST_SHAPES(XR)
-#undef XR
-#undef XW
-#undef XA
+    if (O > 20 && k.waves > 8) k.waves = 8;
+    hipStream_t st = cx.st;
+    submit(cx, k, true, [&](void* dst, unsigned long long) { batch_form(a, dst); },
+           [&] { r16_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0], st, a); }); });
+}
+
+// ... and the same launch for n problems (blockIdx.y), each with its solo grid
+void launch_rollout16_batch(const LaunchKey& k, const FastRolloutArgs* args_dev, const BatchBases&, int n, hipStream_t st) {
+    r16_dispatch(k, [&](auto inst) { inst.batch(k.wgs[0], n, st, args_dev); });
 }
 
 }  // namespace icem

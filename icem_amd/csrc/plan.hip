@@ -281,13 +281,14 @@ int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const voi
         if (lists_out) *lists_out = exact ? wide_rollout_lists(n_rows) : wide_split_lists(n_rows);
         return ICEM_OK;
     }
-    if (cx.rec) return no_batched_form(cx, "this configuration's rollout launch has no batched form");   // (rollout16 alone: a tile shape's two-kernel iteration)
+    // (rollout16 alone: a tile shape's two-kernel iteration.  Recorded as LAUNCH_ROLLOUT16 -- icem_plan_step_cem_batch; the steps of
+    //  icem_plan_step_batch take the single-launch and noise-ahead families at these shapes and do not come here)
     FastRolloutArgs a = fast_rollout_args(h, n_rows, n_cand, K, obs0, actions, costs, part_c, part_i);
     a.part_k = part_k;
     const int grid = rollout_lists(h->cfg.horizon, h->cfg.act_dim, h->Of, n_rows);
     {
         ProfScope prof(h, ICEM_K_ROLLOUT, (long long)n_rows * h->cfg.horizon, st);
-        launch_rollout16(a, h->cfg.horizon, h->cfg.act_dim, h->Of, h->model_kind, st);
+        launch_rollout16(cx, a, h->cfg.horizon, h->cfg.act_dim, h->Of, h->model_kind);
     }
     ICEM_HIP_TRY(hipGetLastError());
     if (lists_out) *lists_out = grid;

@@ -612,6 +612,15 @@ class IcemPlanner:
         / ``cem_elite_idx`` / ``cem_actions`` / ``cem_costs`` hold the last iteration's elite set and pool, ``cem_result``
         is ``[executed | best_cost]``.  Returns ``executed`` (device tensor, no host sync) and advances ``mpc_step``.
         Raises ``IcemError`` (``ICEM_E_UNSUPPORTED``) before anything runs where :meth:`cem_step_ok` is false."""
+        cb = self._cem_cb(obs, mean, std, lower, upper)
+        prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        L.check(self.lib.icem_plan_step_cem(self._h, C.byref(cb), C.byref(prm), self.mpc_step, self._stream()))
+        self.mpc_step += 1
+        return self._cem_buffers()["result"][:self.d]
+
+    def _cem_cb(self, obs, mean, std, lower, upper) -> "L.IcemCemBuffersC":
+        """The observation into the planner's own buffer and the step's ``icem_cem_buffers`` (kept while the caller's tensors
+        stay where they are)."""
         b = self._cem_buffers()
         for t in (mean, std, lower, upper):
             if t.dtype != self.dt or t.device != self.device or tuple(t.shape) != (self.h, self.d) or not t.is_contiguous():
@@ -629,10 +638,46 @@ class IcemPlanner:
                 elites=b["elites"].data_ptr(), elite_costs=b["elite_costs"].data_ptr(), elite_idx=b["elite_idx"].data_ptr(),
                 executed=r.data_ptr(), best_cost=r[self.d:].data_ptr(), workspace=None)
             b["key"] = key
+        return b["cb"]
+
+    @staticmethod
+    def plan_step_cem_batch(planners: Sequence["IcemPlanner"], observations, dists, *, like_levine: bool, shift_means: bool,
+                            execute_best_elite: bool) -> torch.Tensor:
+        """:meth:`plan_step_cem` of every planner of ``planners`` (one configuration; models, costs, seeds, episodes, step
+        counts and observations of their own) as ``icem_plan_step_cem_batch``: the reference's side-by-side CEM episodes
+        (icem/misc/rollout_utils.py:46-58, 129-152), every iteration 3 launches for all of them.  ``dists[i]``: planner i's
+        ``(mean, std, lower, upper)``, updated in place.  Each planner's ``cem_*`` views afterwards are bit for bit those of
+        its own :meth:`plan_step_cem`, and each ``mpc_step`` has advanced by one.  Returns the executed actions ``[B, d]`` -- a
+        view of the batch's results ``[B, d + 1]`` (executed | best cost; ``planners[0].cem_batch_results``), the one tensor a
+        caller copies to the host.  Raises ``IcemError`` before anything runs, and before any planner has advanced, where
+        the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_cem_batch(None, 0, None, None, None, None, None))
+        p0 = pls[0]
+        observations, dists = list(observations), list(dists)
+        if len(observations) != n or len(dists) != n:
+            raise ValueError("one observation and one (mean, std, lower, upper) per planner")
+        cbs = [pl._cem_cb(ob, *dist) for pl, ob, dist in zip(pls, observations, dists)]
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemCemBuffersC * n)(*cbs)
+        steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
+        res = getattr(p0, "_cem_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
+        if res is None or res.shape[0] != n:
+            res = p0._cem_batch_results = torch.zeros((n, p0.d + 1), dtype=p0.dt, device=p0.device)
         prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
-        L.check(self.lib.icem_plan_step_cem(self._h, C.byref(b["cb"]), C.byref(prm), self.mpc_step, self._stream()))
-        self.mpc_step += 1
-        return b["result"][:self.d]
+        L.check(p0.lib.icem_plan_step_cem_batch(hs, n, bs, C.byref(prm), steps, _ptr(res), p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        return res[:, :p0.d]
+
+    cem_batch_results = property(lambda self: getattr(self, "_cem_batch_results", None))
+
+    @property
+    def cem_batch_launches(self) -> int:
+        """Kernel launches of the last batched CEM step this planner led (``icem_cem_batch_launches``): 3 per iteration."""
+        return int(self.lib.icem_cem_batch_launches(self._h))
 
     cem_actions = property(lambda self: self._cem_buffers()["actions"])
     cem_costs = property(lambda self: self._cem_buffers()["costs"])

@@ -247,6 +247,32 @@ typedef struct icem_cem_buffers {   /* all device, handle dtype */
 int     icem_plan_step_cem_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
 int     icem_plan_step_cem(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, int32_t mpc_step, void* stream);
 int64_t icem_cem_step_launches(const icem_handle* h);  /* kernel launches of the last such step of this handle; measurement */
+/* The same step for n planners of ONE configuration at once: the reference compares the CEM baseline with iCEM over many
+ * episodes and seeds and runs those controllers side by side (icem/misc/rollout_utils.py:46-58, 129-152), each its own
+ * MpcCemStd.get_action (mpc.py:200-262).  One problem leaves the chip mostly empty and its step is a chain of 3 * opt_iters
+ * launch latencies; n problems share those launches: the sampler, the rollout and the update of an iteration are each ONE
+ * launch for all of them (blockIdx.y = the problem, its argument block read from device memory) -- 3 launches per iteration
+ * whatever n, no host round trip, no allocation after the first call of a batch size.
+ *   handles[n], n in [1, 32]: no NULL, no handle twice, one configuration -- everything but the seed equal (as for
+ * icem_plan_step_learned_batch); models, costs, observations, seeds, episodes differ.  p: one set of flags for the batch.
+ * mpc_steps_host[n]: the MPC step of every problem (a controller that was reset later than its neighbours steps with them).
+ * buffers[i]: problem i's, as for icem_plan_step_cem (workspace may be NULL).  results: NULL, or a device buffer [n, d + 1]
+ * of the handle dtype -- row i is executed | best_cost of problem i, written by the last update in addition to the
+ * problem's own executed / best_cost (one device-to-host copy fetches the batch).
+ *   Every output of problem i -- mean, std, lower, upper, elites, elite_costs, elite_idx, executed, best_cost, the last
+ * pool and its costs -- is bit for bit what icem_plan_step_cem gives for that handle alone at the same seed, episode and
+ * step: the batched kernels run the solo kernels' bodies.
+ *   Served: handles icem_plan_step_cem serves whose rollout launch has a batched twin -- the tile shapes (HalfCheetah ...), the
+ * TileHN shapes, the GEMM-kernel shapes, the float64 generic rollouts -- and whose rollout launches are equal in shape (tile /
+ * wide / f64 arithmetic, cost-term program).  ICEM_E_INVALID: n outside [1, 32], a NULL argument, handle or buffer, a handle
+ * twice, unequal configurations, a negative step; ICEM_E_UNSUPPORTED: a handle icem_plan_step_cem refuses, a rollout without a
+ * batched form (the f32 thread-per-trajectory kernel, the float64 matrix-core rollout, the float64 thread form at padded width 32
+ * with a tanh model), and for n > 1 a shape whose row does not fit the step's sampler; ICEM_E_STATE: no model or cost set, or the
+ * problems' rollout launches differ.  Whatever is refused is refused before anything is launched.  n == 1 is
+ * icem_plan_step_cem (+ the results row).  Development option cem_step = 0 switches this entry off too. */
+int     icem_plan_step_cem_batch(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
+                                 const int32_t* mpc_steps_host, void* results, void* stream);
+int64_t icem_cem_batch_launches(const icem_handle* h); /* kernel launches of the last such batch this handle led as handles[0]; measurement */
 
 /* MpcRandom.sample_action_sequences (icem/controllers/mpc.py:96-109, random shooting): actions[i, t, :] = low +
  * (high - low) * U(block), uniform draws held for consecutive calls of MpcRandom.sample() (mpc.py:96-102) -- one call

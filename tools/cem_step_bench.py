@@ -13,6 +13,12 @@ with min and max over BLOCKS blocks.
                                                (sample_truncnorm_kernel) -- in a run of its own:
                                                    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- \\
                                                        python tools/cem_step_bench.py --trace
+  python tools/cem_step_bench.py --batch B [--dtype f32|f64] [--sizes 512,4096]
+                                               B planners: blocks of batched steps (``icem_plan_step_cem_batch``, each ending in
+                                               the one device-to-host copy of its results) alternating with blocks of B solo
+                                               ``icem_plan_step_cem`` steps issued back to back (each block step ending in one
+                                               synchronisation) -- what these callers had before the batched entry; B may be a
+                                               list (2,4,8,16).  With --trace: TRACE_STEPS steps of each and nothing else.
 """
 import ctypes as C
 import os
@@ -61,6 +67,88 @@ def report(what, n, ms, extra=""):
           f"{len(ms)} blocks of {BLOCK}){extra}", flush=True)
 
 
+def _arg(flag, default):
+    return sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else default
+
+
+BATCH_BLOCK, BATCH_BLOCKS, BATCH_WARMUP = 30, 7, 10
+
+
+def batch_planners(n, B, dtype):
+    """B planners at the HalfCheetah shape (seeds of their own) with their distributions, as ``MpcCemStdHip`` holds them."""
+    from icem_amd import DeviceSyntheticModel, IcemConfig, IcemPlanner, halfcheetah_env
+    env = halfcheetah_env(O_)
+    out = []
+    for i in range(B):
+        cfg = IcemConfig(horizon=H, act_dim=D, num_traj=n, elites_size=10, opt_iters=ITERS, cost_mode="sum", use_mean_actions=False,
+                         keep_previous_elites=False, shift_elites=False, factor_decrease=1.0, alpha=0.1, init_std=0.5, dtype=dtype,
+                         seed=1 + i)
+        pl = IcemPlanner(cfg, env.action_space.low, env.action_space.high)
+        m = DeviceSyntheticModel.make(O_, D, kind=0)
+        pl.set_model(m.kind, m.A, m.B)
+        pl.set_cost_spec(env.cost_spec)
+        pl.new_episode()
+        mean = torch.empty((H, D), dtype=pl.dt, device=pl.device)
+        std = torch.empty_like(mean)
+        pl.reset_distribution(mean, std)
+        lower, upper = pl.cem_bounds(mean, std, False)
+        pl.mpc_step = 0
+        out.append((pl, (mean, std, lower, upper)))
+    return out
+
+
+def main_batch():
+    from icem_amd import IcemPlanner
+    trace = "--trace" in sys.argv
+    Bs = [int(x) for x in _arg("--batch", "8").split(",")]
+    dtype = _arg("--dtype", "f32")
+    sizes = [int(x) for x in _arg("--sizes", ",".join(str(n) for n in SIZES)).split(",")]
+    lib = L.load_library()
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  h = {H}, d = {D}, o = {O_}, "
+          f"{ITERS} iterations, {dtype}; warm-up {BATCH_WARMUP} steps; {BATCH_BLOCKS} blocks of {BATCH_BLOCK} steps per variant, alternating",
+          flush=True)
+    flags = dict(like_levine=False, shift_means=True, execute_best_elite=True)
+    for n in sizes:
+        for B in Bs:
+            both = {"batched": batch_planners(n, B, dtype), "solo": batch_planners(n, B, dtype)}
+            obs = [torch.as_tensor(0.1 * np.random.RandomState(i).randn(O_), dtype=both["solo"][0][0].dt, device="cuda") for i in range(B)]
+
+            def step(kind):
+                ps = both[kind]
+                if kind == "batched":
+                    IcemPlanner.plan_step_cem_batch([p for p, _ in ps], obs, [dist for _, dist in ps], **flags)
+                    return ps[0][0].cem_batch_results.cpu()   # the batch's one device-to-host copy
+                for (p, dist), ob in zip(ps, obs):
+                    p.plan_step_cem(ob, *dist, **flags)
+                torch.cuda.synchronize()
+                return None
+
+            def block(kind, reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    step(kind)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / reps * 1e3
+
+            for kind in both:
+                block(kind, BATCH_WARMUP)
+            if trace:
+                for kind in both:
+                    block(kind, TRACE_STEPS)
+                continue
+            same = all(torch.equal(a[0].cem_result, b[0].cem_result) and torch.equal(a[1][0], b[1][0]) for a, b in zip(both["batched"], both["solo"]))
+            t = {k: [] for k in both}
+            for _ in range(BATCH_BLOCKS):
+                for kind in both:
+                    t[kind].append(block(kind, BATCH_BLOCK))
+            b, s = sorted(t["batched"]), sorted(t["solo"])
+            print(f"  {dtype} N = {n:5d} B = {B:2d}: batched median {b[len(b) // 2]:7.4f} ms per step of the batch (min {b[0]:.4f}, max {b[-1]:.4f}) | "
+                  f"{B} solo steps median {s[len(s) // 2]:7.4f} (min {s[0]:.4f}, max {s[-1]:.4f}) | solo median / batched median "
+                  f"{s[len(s) // 2] / b[len(b) // 2]:.2f}x | batched median < solo min: {b[len(b) // 2] < s[0]} | equal bits: {same}; "
+                  f"launches per batched step {both['batched'][0][0].cem_batch_launches}, uploads {both['batched'][0][0].batch_uploads}", flush=True)
+
+
 def main():
     stagewise_only, trace = "--stagewise" in sys.argv, "--trace" in sys.argv
     if stagewise_only:
@@ -100,4 +188,7 @@ def main():
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures and has nothing to say without one")
-    main()
+    if "--batch" in sys.argv:
+        main_batch()
+    else:
+        main()
