@@ -34,7 +34,9 @@ under the linear model (x 5.9, 101 rows on door-fast), len - 1 / a + 1 there (x 
 What the table CANNOT see: that term's weight x 1.01 under tanh (every velocity below 1: 3e-6 of a step's cost); a low fp16
 plane dropped, or a model entry wrong, in a column that no term of ANY case reads and that feeds none (the unit readouts read
 every column, so there is none at o = 39 / 28 -- the narrow tile kernels, Tile16H / Tile16 / Tile4 at o = 17 .. 24, which no case
-of THIS table reaches, have the same readouts and an entry-by-entry model table in tile_cases.py, test_gpu_tile_probes.py);
+of THIS table reaches, have the same readouts and an entry-by-entry model table in tile_cases.py, test_gpu_tile_probes.py; the
+wide GEMM kernels are reached here at o = 39 only -- one column tile per wave, NT = 4, uniform ksc / csc --, which is NOT their
+entry coverage: NCT > 1, NT > 4, the FIVE instantiation and the per-entry scales are wide_cases.py, test_gpu_wide_probes.py);
 'final' over steps 1 .. h-1 (the same step); a zero threshold x 1.1.
 
 The table (all cases <= 1100 rows, one launch each; h = 30 where TileHN serves the shape, h = 12 for the other kernels):
