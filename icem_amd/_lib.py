@@ -138,6 +138,10 @@ SYMBOLS = [
     ("icem_cem_step_launches", C.c_int64, [_H]),
     ("icem_plan_step_cem_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), C.POINTER(_I32), _VP, _VP]),
     ("icem_cem_batch_launches", C.c_int64, [_H]),
+    ("icem_plan_step_cem_learned_ok", C.c_int, [_H]),
+    ("icem_plan_step_cem_learned", C.c_int, [_H, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _VP, _I32, _VP]),
+    ("icem_plan_step_cem_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _VP,
+                                                   C.POINTER(_I32), _VP, _VP]),
     ("icem_rccl_load", C.c_int, [C.c_char_p]),
     ("icem_rccl_library", C.c_char_p, []),
     ("icem_rccl_unique_id", C.c_int, [_VP]),

@@ -320,6 +320,18 @@ class MpcController(ModelBasedController, StatefulController, ABC):
         if self.torch_spec_cost:
             self.planner.set_cost_spec(self.env.cost_spec)
 
+    def _model_is_the_library_rssm(self) -> bool:
+        """The library's steps (``icem_plan_step_learned*``, ``icem_plan_step_cem_learned*``) roll out through the declared
+        RSSM itself.  ``rssm_path`` is duck-typed (``rollout_cost`` + ``params``): a model whose ``rollout_cost`` /
+        ``rollout_cost_batch`` is not ``DeviceRSSMModel``'s own -- a subclass's, or one replaced on the instance to time or
+        count the rollouts -- is called stage by stage, as it asks to be."""
+        from .models import DeviceRSSMModel
+        m = self.forward_model
+        return (isinstance(m, DeviceRSSMModel) and type(m).rollout_cost is DeviceRSSMModel.rollout_cost
+                and type(m).rollout_cost_batch is DeviceRSSMModel.rollout_cost_batch
+                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
+                and m.params.device == self.planner.device)
+
     def _costs_of(self, obs, actions: torch.Tensor) -> torch.Tensor:
         """Per-trajectory costs (device tensor) of a batch of device action sequences, through whichever
         model this controller was given."""
@@ -761,17 +773,6 @@ class MpcICemHip(MpcController):
         return bool(self.rssm_path and not self.device_path and noise is None and self.planner.cfg.world == 1
                     and not self.verbose and self._model_is_the_library_rssm() and self.planner.learned_step_ok())
 
-    def _model_is_the_library_rssm(self) -> bool:
-        """The library's step rolls out through the declared RSSM itself.  ``rssm_path`` is duck-typed (``rollout_cost`` +
-        ``params``): a model whose ``rollout_cost`` / ``rollout_cost_batch`` is not ``DeviceRSSMModel``'s own -- a subclass's,
-        or one replaced on the instance to time or count the rollouts -- is called stage by stage, as it asks to be."""
-        from .models import DeviceRSSMModel
-        m = self.forward_model
-        return (isinstance(m, DeviceRSSMModel) and type(m).rollout_cost is DeviceRSSMModel.rollout_cost
-                and type(m).rollout_cost_batch is DeviceRSSMModel.rollout_cost_batch
-                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
-                and m.params.device == self.planner.device)
-
     def _elites_into_planner(self):
         """A fused step reads the kept / shifted elites from the planner's current elite half: behind a stage-wise step
         they are the controller's own tensors and go there first (behind a fused step they already are that half)."""
@@ -864,8 +865,10 @@ class MpcCemStdHip(MpcController):
     ``get_action`` is one library call (``icem_plan_step_cem``: a chain of launches, no host round trip, one
     device-to-host copy of the result) where the model is the device's built-in one, the noise is the device's, no
     subclass overrides ``compute_new_mean``, the controller is not verbose and ``IcemPlanner.cem_step_ok()``; everywhere
-    else it is the stage-wise loop over the operators -- the same bits.  ``fused_step``: None (the rule above), False
-    (always the loop) or True (raise where the fused step is not served)."""
+    else it is the stage-wise loop over the operators -- the same bits.  With a ``DeviceRSSMModel`` whose ``rollout_cost``
+    is its own (learned dynamics: the planner PlaNet uses) the same holds through ``icem_plan_step_cem_learned`` /
+    ``icem_plan_step_cem_learned_batch`` where ``IcemPlanner.cem_learned_step_ok()``; a batch then shares one model.
+    ``fused_step``: None (the rule above), False (always the loop) or True (raise where the fused step is not served)."""
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
                  noise_source: Union[str, Callable] = "philox", deterministic_replay=False, fused_step=None, **kwargs):
@@ -989,6 +992,12 @@ class MpcCemStdHip(MpcController):
             return "the controllers differ in configuration (everything but the seed must be equal) or in their flags"
         if len({id(c.planner) for c in ctrls}) != len(ctrls):
             return "a controller appears twice"
+        learned = [c._steps_through_the_rssm() for c in ctrls]
+        if any(learned):   # one launch rolls every problem's rows out through ONE parameter buffer
+            if not all(learned):
+                return "learned-dynamics controllers cannot be mixed with controllers of the built-in model"
+            if any(c.forward_model is not c0.forward_model for c in ctrls[1:]):
+                return "learned-dynamics controllers must share one DeviceRSSMModel"
         return None
 
     @staticmethod
@@ -1019,10 +1028,14 @@ class MpcCemStdHip(MpcController):
         why = MpcCemStdHip._batch_refusal(ctrls)
         host = None
         if why is None:
+            c0 = ctrls[0]
+            pls, dists = [c.planner for c in ctrls], [(c._mean, c._std, c._lower, c._upper) for c in ctrls]
+            flags = dict(like_levine=c0.like_levine, shift_means=c0.shift_means, execute_best_elite=c0.execute_best_elite)
             try:
-                res = IcemPlanner.plan_step_cem_batch(
-                    [c.planner for c in ctrls], observations, [(c._mean, c._std, c._lower, c._upper) for c in ctrls],
-                    like_levine=ctrls[0].like_levine, shift_means=ctrls[0].shift_means, execute_best_elite=ctrls[0].execute_best_elite)
+                if c0._steps_through_the_rssm():
+                    res = IcemPlanner.plan_step_cem_learned_batch(pls, c0.forward_model, observations, dists, **flags)
+                else:
+                    res = IcemPlanner.plan_step_cem_batch(pls, observations, dists, **flags)
                 host = ctrls[0].planner.cem_batch_results.cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
                 del res
             except IcemError as e:   # refused before anything ran: nothing was touched, no planner has advanced
@@ -1043,8 +1056,12 @@ class MpcCemStdHip(MpcController):
         return out
 
     def _fused_step_refusal(self):
-        """Why ``icem_plan_step_cem`` cannot run this controller's step (None: it can)."""
-        if not self.device_path:
+        """Why ``icem_plan_step_cem`` -- ``icem_plan_step_cem_learned`` where the model is the library's own RSSM -- cannot
+        run this controller's step (None: it can)."""
+        learned = self._steps_through_the_rssm()
+        if not self.device_path and not learned:
+            if self.rssm_path:
+                return "the learned-dynamics model is not the library's own RSSM (its rollout_cost is called stage by stage)"
             return "the model is not the device's built-in one"
         if self.noise_source != "philox":
             return "the noise source is not the device's (external uniforms keep the operator loop)"
@@ -1052,9 +1069,15 @@ class MpcCemStdHip(MpcController):
             return "compute_new_mean is overridden"
         if self.verbose:
             return "the controller is verbose"
-        if not self.planner.cem_step_ok():
+        if learned and not self.planner.cem_learned_step_ok():
+            return "the library does not serve this handle through the learned dynamics (IcemPlanner.cem_learned_step_ok)"
+        if not learned and not self.planner.cem_step_ok():
             return "the library does not serve this handle (IcemPlanner.cem_step_ok)"
         return None
+
+    def _steps_through_the_rssm(self) -> bool:
+        """The fused step of this controller is the learned-dynamics one: its model is the library's own RSSM."""
+        return bool(self.rssm_path and not self.device_path and self._model_is_the_library_rssm())
 
     def _takes_fused_step(self) -> bool:
         if self.fused_step is False:
@@ -1065,10 +1088,14 @@ class MpcCemStdHip(MpcController):
         return why is None
 
     def _step_fused(self, obs):
-        """The whole step in the library (``icem_plan_step_cem``); one device-to-host copy of ``[executed | best_cost]``."""
+        """The whole step in the library (``icem_plan_step_cem``, or ``icem_plan_step_cem_learned`` through the library's
+        RSSM); one device-to-host copy of ``[executed | best_cost]``."""
         p = self.planner
-        p.plan_step_cem(obs, self._mean, self._std, self._lower, self._upper, like_levine=self.like_levine,
-                        shift_means=self.shift_means, execute_best_elite=self.execute_best_elite)
+        flags = dict(like_levine=self.like_levine, shift_means=self.shift_means, execute_best_elite=self.execute_best_elite)
+        if self._steps_through_the_rssm():
+            p.plan_step_cem_learned(self.forward_model, obs, self._mean, self._std, self._lower, self._upper, **flags)
+        else:
+            p.plan_step_cem(obs, self._mean, self._std, self._lower, self._upper, **flags)
         host = p.cem_result.cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
         self._elite_actions, self._elite_costs = p.cem_elites, p.cem_elite_costs
         self.last_min_cost = float(host[-1])

@@ -1,4 +1,5 @@
-// cem_step.h -- what the host side of icem_plan_step_cem / icem_plan_step_cem_batch (cem_step.hip) asks of its kernels (k_cem.hip).
+// cem_step.h -- what the host side of icem_plan_step_cem / icem_plan_step_cem_batch and of icem_plan_step_cem_learned /
+// icem_plan_step_cem_learned_batch (cem_step.hip) asks of its kernels (k_cem.hip).
 // Internal; not part of the public ABI.
 #pragma once
 #include "host_common.h"
@@ -45,6 +46,11 @@ void cem_sample_block(const icem_handle* h, int n, const void* mean, const void*
                       uint64_t offset_rel, void* out, void* dst);
 // grid (ceil(n_rows / tpw), n_problems): all problems draw n_rows rows
 void launch_cem_sample_batch(const icem_handle* h, int n_rows, const void* args_dev, const BatchBases& bases, int n_problems, hipStream_t st);
+// the same launch (f32 handles) whose workgroups of blockIdx.x == 0 also copy their problem's observation og.src[p] [og.width]
+// to og.dst + p * og.width: the first iteration's launch of icem_plan_step_cem_learned_batch builds the batched RSSM rollout's
+// contiguous observation table on the way (ObsGather: icem_fused.h)
+void launch_cem_sample_gather_batch(const icem_handle* h, int n_rows, const void* args_dev, const BatchBases& bases, const ObsGather& og,
+                                    int n_problems, hipStream_t st);
 // one workgroup per problem; hd: the dynamic LDS of cem_tail's stage
 void launch_cem_update_batch(const CemUpdateF32Args* args_dev, int n_problems, int hd, hipStream_t st);
 void launch_cem_update_batch(const CemUpdateF64Args* args_dev, int n_problems, int hd, hipStream_t st);

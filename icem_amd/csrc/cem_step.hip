@@ -14,7 +14,13 @@
 // and its launch is compared and issued once for all), cem_update_*_batch_kernel.  The argument blocks live in a DeviceArgArray of the
 // first handle; they carry no step-dependent value (the sampler's offset is relative to the step's base, which travels by value),
 // so a batch whose buffers stay put uploads each of its two slots once.
+//
+// icem_plan_step_cem_learned / icem_plan_step_cem_learned_batch are the same step through the learned dynamics (the declared RSSM,
+// BASELINE configs[4]) -- the planner PlaNet uses: the sampler and the update above around launch_rssm_rollout (one problem) /
+// launch_rssm_split_batch (several, their rows back to back in the learned step's pool of the first handle, icem_plan_step_learned_batch's
+// arrangement).  The refusals, the block filling and the update launch are the ones above.
 #include "cem_step.h"
+#include "icem_rssm.h"
 
 using namespace icem;
 
@@ -108,20 +114,37 @@ bool null_buffer(const icem_cem_buffers& b) {
            !b.elite_costs || !b.elite_idx || !b.executed || !b.best_cost;
 }
 
-// the refusals of one handle's step, all of them before anything is launched or the handle touched (who: the entry's name)
-int cem_refusal(const icem_handle* h, const icem_cem_buffers& b, int32_t mpc_step, const std::string& who) {
+static_assert(rssm::DET + rssm::STOCH == ICEM_RSSM_OBS_DIM, "the RSSM's observation width");
+
+// "who is served" through the learned dynamics: the step above, f32 at the RSSM's action width, drawn by the step's own sampler
+// (the batch has no other), rolled out by the RSSM's split launch
+const char* cem_learned_unserved(const icem_handle* h) {
+    const icem_config& c = h->cfg;
+    if (c.dtype != ICEM_F32) return "the learned-dynamics rollout is f32 only";
+    if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
+    if (const char* why = cem_unserved(h)) return why;
+    if (!cem_sample_ok(h)) return "a row of this shape does not fit the step's sampler (its two probability tables and one row in LDS)";
+    if (!rssm_split_ok(c.num_traj, c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
+    return nullptr;
+}
+
+// the refusals of one handle's step, all of them before anything is launched or the handle touched (who: the entry's name;
+// learned: through the RSSM -- no built-in model or cost is asked for)
+int cem_refusal(const icem_handle* h, const icem_cem_buffers& b, int32_t mpc_step, const std::string& who, bool learned = false) {
     if (mpc_step < 0) return fail(ICEM_E_INVALID, who + "negative mpc_step");
     if (null_buffer(b)) return fail(ICEM_E_INVALID, who + "null buffer (everything but workspace is needed)");
-    if (const char* why = cem_unserved(h)) return fail(ICEM_E_UNSUPPORTED, who + why);
+    if (const char* why = learned ? cem_learned_unserved(h) : cem_unserved(h)) return fail(ICEM_E_UNSUPPORTED, who + why);
+    if (learned) return ICEM_OK;
     if (!h->has_model || !h->has_cost) return fail(ICEM_E_STATE, who + "icem_set_model / icem_set_cost must be called first");
     if (const char* e = cost_indices_error(h, h->obs_dim)) return fail(ICEM_E_INVALID, e);
     if (const char* e = wide_unsupported(h, 0, false, false)) return fail(ICEM_E_UNSUPPORTED, e);
     return ICEM_OK;
 }
 
-// one planner's step behind its refusals: 3 launches per iteration, the arguments by value.  *launches_out: written on success
+// one planner's step behind its refusals: 3 launches per iteration, the arguments by value.  *launches_out: written on success.
+// rssm_params: nullptr (the handle's built-in model), or the packed RSSM the rows are rolled out through
 int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, int32_t mpc_step, void* result, hipStream_t st,
-                  long long* launches_out) {
+                  long long* launches_out, const void* rssm_params = nullptr) {
     const icem_config& c = h->cfg;
     const int N = c.num_traj, iters = c.opt_iters;
     const bool own_sampler = cem_sample_ok(h);
@@ -132,7 +155,9 @@ int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_para
                              : gk_sample_truncnorm(h, N, 0, b->mean, b->std, b->lower, b->upper, nullptr, offset, b->actions, st);
         if (rc) return rc;
         ++launches;
-        rc = rollout_cost_launch(h, N, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st});
+        rc = rssm_params ? rssm_launch_result(launch_rssm_rollout(N, c.horizon, c.cost_mode, (const unsigned short*)rssm_params,
+                                                                  (const float*)b->obs0, (const float*)b->actions, (float*)b->costs, st))
+                         : rollout_cost_launch(h, N, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st});
         if (rc) return rc;
         ++launches;
         launch_update(h, *b, *p, it == iters - 1, result, st);
@@ -233,6 +258,64 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
     return ICEM_OK;
 }
 
+// B > 1 planners through the RSSM, behind the admission of the batch, the tile check and rssm_split_prepare.  Per iteration
+// [sample x n | update x n] blocks in the first handle's cem_batch_args (no step-dependent value in them, as above); problem i's
+// rows are drawn into the slice [i * N, (i + 1) * N) of the first handle's learned-step pool, ONE split launch scores the pool, every
+// update reads its slice.  The first iteration's sampler launch also gathers the observations into the pool's [n, 230] table.
+int cem_learned_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const void* params,
+                      const int32_t* steps, void* results, hipStream_t st) {
+    icem_handle* h0 = handles[0];
+    const icem_config& c = h0->cfg;
+    const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd, d = c.act_dim;
+    LearnedCtx& ctx = h0->learned;
+    ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
+    float* pool_a = ctx.pool;
+    float* pool_c = pool_a + ctx.pool_rows * (size_t)hd;
+    float* pool_o = pool_c + ctx.pool_rows;
+    const size_t sb = cem_sample_block_bytes(h0), ub = sizeof(CemUpdateF32Args);
+    const size_t at_update = padded(sb * n), per_it = at_update + padded(ub * n);
+    const size_t per_it_room = padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH);
+    std::vector<unsigned char> blob(per_it * iters, 0);
+    BatchBases bases{};
+    ObsGather og{};
+    og.dst = pool_o, og.width = ICEM_RSSM_OBS_DIM;
+    for (int i = 0; i < n; ++i) {
+        bases.v[i] = (handles[i]->episode << 32) + (uint64_t)steps[i] * (uint64_t)iters;
+        og.src[i] = (const float*)buffers[i].obs0;
+    }
+    for (int it = 0; it < iters; ++it) {
+        unsigned char* part = blob.data() + per_it * it;
+        for (int i = 0; i < n; ++i) {
+            icem_cem_buffers b = buffers[i];   // (the problem's own, but its pool: the slice)
+            b.actions = pool_a + (size_t)i * N * hd, b.costs = pool_c + (size_t)i * N;
+            cem_sample_block(handles[i], N, b.mean, b.std, b.lower, b.upper, (uint64_t)it, b.actions, part + sb * i);
+            void* row = results ? (unsigned char*)results + (size_t)i * (d + 1) * h0->tsize : nullptr;
+            fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF32Args*)(part + at_update + ub * i));
+        }
+    }
+    const int slot = steps[0] & 1;
+    ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, per_it_room * iters, st, &h0->batch_uploads));
+    const unsigned char* dev = (const unsigned char*)h0->cem_batch_args.dev(slot);
+    const std::vector<int> rows(n, N);
+    long long launches = 0;
+    for (int it = 0; it < iters; ++it) {
+        const unsigned char* part = dev + per_it * it;
+        if (it == 0) launch_cem_sample_gather_batch(h0, N, part, bases, og, n, st);
+        else launch_cem_sample_batch(h0, N, part, bases, n, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+        if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.cost_mode, (const unsigned short*)params, pool_o,
+                                                                pool_a, pool_c, st)))
+            return rc;
+        ++launches;
+        launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    h0->cem_batch_launches = launches;
+    return ICEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -262,6 +345,44 @@ int icem_plan_step_cem_batch(icem_handle* const* handles, int32_t n, const icem_
         return rc;
     }
     return cem_step_batch(handles, n, buffers, *p, mpc_steps_host, results, (hipStream_t)stream);
+}
+
+int icem_plan_step_cem_learned_ok(const icem_handle* h) { return (h && cem_learned_unserved(h) == nullptr) ? 1 : 0; }
+
+int icem_plan_step_cem_learned(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, const void* params, int32_t mpc_step,
+                               void* stream) {
+    // ---- refusals: all of them before anything is launched or the handle touched ----
+    if (!h || !b || !p || !params) return fail(ICEM_E_INVALID, "icem_plan_step_cem_learned: null handle, buffers, flags or params");
+    if (int rc = cem_refusal(h, *b, mpc_step, "icem_plan_step_cem_learned: ", true)) return rc;
+    // the rollout's staging area and its host-visible status word, BEFORE the first launch (as learned_step.hip)
+    if (int rc = rssm_launch_result(rssm_split_prepare((h->cfg.num_traj + 15) / 16, h->cfg.horizon, (hipStream_t)stream))) return rc;
+    h->cem_launches = 0;
+    return cem_step_solo(h, b, p, mpc_step, nullptr, (hipStream_t)stream, &h->cem_launches, params);
+}
+
+int icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
+                                     const void* params, const int32_t* mpc_steps_host, void* results, void* stream) {
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    const std::string who = "icem_plan_step_cem_learned_batch: ";
+    if (int rc = admit_batch(handles, n, buffers && p && params && mpc_steps_host, true, who.c_str(),
+                             "icem_plan_step_cem_learned_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = cem_refusal(handles[i], buffers[i], mpc_steps_host[i], who, true)) return rc;
+    const icem_config& c = handles[0]->cfg;
+    const std::vector<int> rows(n, c.num_traj);
+    const int tiles = rssm_batch_tiles(n, rows.data());
+    if (tiles < 0 || !rssm_split_batch_ok(tiles, c.horizon))
+        return fail(ICEM_E_UNSUPPORTED, who + "the batch's tiles (the sum over the problems of ceil(rows / 16)) exceed the split launch's "
+                                              "limit; nothing was launched");
+    if (int rc = rssm_launch_result(rssm_split_prepare(tiles, c.horizon, (hipStream_t)stream))) return rc;
+    if (n == 1) {   // one planner: the solo launches (the same bits by construction), the results row from the last update
+        long long launches = 0;
+        const int rc = cem_step_solo(handles[0], &buffers[0], p, mpc_steps_host[0], results, (hipStream_t)stream, &launches, params);
+        if (rc == ICEM_OK) handles[0]->cem_batch_launches = launches;
+        return rc;
+    }
+    return cem_learned_batch(handles, n, buffers, *p, params, mpc_steps_host, results, (hipStream_t)stream);
 }
 
 int64_t icem_cem_step_launches(const icem_handle* h) { return h ? (int64_t)h->cem_launches : 0; }

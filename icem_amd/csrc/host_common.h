@@ -59,6 +59,23 @@ struct LearnedCtx {
     int pool_n = 0;
     int* idx = nullptr;                      // [ICEM_MAX_BATCH, ICEM_MAX_ELITES]: the updates' index output (not kept)
     long long launches = 0;                  // kernel launches of the last learned step this handle led
+    // the pool of a batch of n problems with cap_rows rows in all (icem_plan_step_learned_batch, icem_plan_step_cem_learned_batch:
+    // both lay it out as above); it only grows, behind a synchronisation of `st` (an earlier step's launches may still use the old one)
+    hipError_t reserve(size_t cap_rows, int n, int hd, hipStream_t st) {
+        if (pool_rows >= cap_rows && pool_n >= n) return hipSuccess;
+        const size_t rws = std::max(cap_rows, pool_rows);
+        const int pn = std::max(n, pool_n);
+        if (pool) {
+            if (hipError_t e = hipStreamSynchronize(st)) return e;
+            (void)hipFree(pool);
+            pool = nullptr;
+            pool_rows = 0;
+        }
+        if (hipError_t e = hipMalloc((void**)&pool, (rws * (size_t)(hd + 1) + (size_t)pn * ICEM_RSSM_OBS_DIM) * sizeof(float))) return e;
+        pool_rows = rws;
+        pool_n = pn;
+        return hipSuccess;
+    }
     ~LearnedCtx() {
         if (pool) (void)hipFree(pool);
         if (idx) (void)hipFree(idx);
@@ -221,8 +238,8 @@ struct icem_handle {
     unsigned long long batch_uploads = 0;   // how often a batched step of either kind (re)wrote its array (steady state: never)
     long long batch_f64_launches = 0;       // kernel launches of the last icem_plan_step_batch_f64 this handle led
     icem::LearnedCtx learned;               // icem_plan_step_learned* (learned_step.hip)
-    long long cem_launches = 0;             // kernel launches of the last icem_plan_step_cem of this handle (cem_step.hip)
-    // icem_plan_step_cem_batch (cem_step.hip): the batch's argument blocks live with its FIRST handle, by that handle's step parity
+    long long cem_launches = 0;             // kernel launches of the last icem_plan_step_cem / _cem_learned of this handle (cem_step.hip)
+    // icem_plan_step_cem_batch / _cem_learned_batch (cem_step.hip): the batch's argument blocks live with its FIRST handle, by that handle's step parity
     // (the blocks carry no step-dependent value: either slot of a batch whose buffers stay put is uploaded once)
     icem::DeviceArgArray<2> cem_batch_args;
     long long cem_batch_launches = 0;       // kernel launches of the last icem_plan_step_cem_batch this handle led

@@ -8,6 +8,8 @@
 //                          update_small_kernel's in f32, select_refit_kernel's in f64 --, then _update_bounds (mpc.py:290-301)
 //                          and, behind the last iteration, get_action's epilogue (mpc.py:230-245): cem_dev.h::cem_tail
 // The arithmetic of every value is a device function shared with the operator that computes it: the step's bits are theirs.
+// icem_plan_step_cem_learned* (the same step through the declared RSSM) launches these kernels around the RSSM's rollout;
+// its batch's first sampler launch is cem_sample_gather_batch_kernel, which also builds the batch's observation table.
 #include "update_small_body.h"
 #include "generic_dev.h"
 #include "cem_step.h"
@@ -96,6 +98,21 @@ __device__ __forceinline__ SelectArgs<double> from_device(const SelectArgs<doubl
 // blockIdx.y = the problem; the block's stream offset is relative to the step's base of that problem (BatchBases): it holds `it`
 template <typename T, int ROUNDS>
 __global__ __launch_bounds__(WG) void cem_sample_batch_kernel(const CemSampleArgs<T>* __restrict__ args, BatchBases bases) {
+    CemSampleArgs<T> a = from_device(args[blockIdx.y]);
+    add_base64(a.off_lo, a.off_hi, bases.v[blockIdx.y]);
+    cem_sample_body<T, ROUNDS>(a);
+}
+
+// cem_sample_batch_kernel for the first iteration of icem_plan_step_cem_learned_batch: workgroup 0 of a problem also copies its
+// observation into the batch's contiguous [n, og.width] table, which the batched RSSM rollout reads (as sample_folded_batch_kernel
+// does for icem_plan_step_learned_batch, k_sample.hip) -- the callers' observation buffers need not be adjacent, and no launch
+// is spent on it
+template <typename T, int ROUNDS>
+__global__ __launch_bounds__(WG) void cem_sample_gather_batch_kernel(const CemSampleArgs<T>* __restrict__ args, BatchBases bases, ObsGather og) {
+    if (blockIdx.x == 0) {
+        const float* src = og.src[blockIdx.y];
+        for (int e = threadIdx.x; e < og.width; e += WG) og.dst[(size_t)blockIdx.y * og.width + e] = src[e];
+    }
     CemSampleArgs<T> a = from_device(args[blockIdx.y]);
     add_base64(a.off_lo, a.off_hi, bases.v[blockIdx.y]);
     cem_sample_body<T, ROUNDS>(a);
@@ -203,6 +220,18 @@ void launch_cem_sample_batch(const icem_handle* h, int n_rows, const void* args_
         if (c.rng_rounds == 7) ICEM_CSB(float, 7); else ICEM_CSB(float, 10);
     }
 #undef ICEM_CSB
+}
+
+// (f32 handles: the learned-dynamics step serves no other)
+void launch_cem_sample_gather_batch(const icem_handle* h, int n_rows, const void* args_dev, const BatchBases& bases, const ObsGather& og,
+                                    int n_problems, hipStream_t st) {
+    const int tpw = cem_sample_tpw(h);
+    const dim3 grid((n_rows + tpw - 1) / tpw, n_problems);
+    const size_t lds = (size_t)(2 + tpw) * h->hd * h->tsize;
+    if (h->cfg.rng_rounds == 7)
+        hipLaunchKernelGGL((cem_sample_gather_batch_kernel<float, 7>), grid, dim3(WG), lds, st, (const CemSampleArgs<float>*)args_dev, bases, og);
+    else
+        hipLaunchKernelGGL((cem_sample_gather_batch_kernel<float, 10>), grid, dim3(WG), lds, st, (const CemSampleArgs<float>*)args_dev, bases, og);
 }
 
 void launch_cem_update_batch(const CemUpdateF32Args* args_dev, int n_problems, int hd, hipStream_t st) {

@@ -90,19 +90,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     LearnedCtx* ctx = &h0->learned;
     if (!ctx->idx) ICEM_HIP_TRY(hipMalloc((void**)&ctx->idx, (size_t)ICEM_MAX_BATCH * ICEM_MAX_ELITES * sizeof(int)));
     const size_t cap_rows = (size_t)n * (size_t)max_rows(h0);   // (what any mix of steps of this batch size needs)
-    if (n > 1 && (ctx->pool_rows < cap_rows || ctx->pool_n < n)) {
-        if (ctx->pool) {
-            ICEM_HIP_TRY(hipStreamSynchronize(st));   // (an earlier step's launches may still use the old pool)
-            (void)hipFree(ctx->pool);
-            ctx->pool = nullptr;
-            ctx->pool_rows = 0;
-        }
-        const size_t rws = std::max(cap_rows, ctx->pool_rows);
-        const int pn = std::max(n, ctx->pool_n);
-        ICEM_HIP_TRY(hipMalloc((void**)&ctx->pool, (rws * (size_t)(hd + 1) + (size_t)pn * (rssm::DET + rssm::STOCH)) * sizeof(float)));
-        ctx->pool_rows = rws;
-        ctx->pool_n = pn;
-    }
+    if (n > 1) ICEM_HIP_TRY(ctx->reserve(cap_rows, n, hd, st));
     float* pool_a = ctx->pool;
     float* pool_c = ctx->pool ? ctx->pool + ctx->pool_rows * (size_t)hd : nullptr;
     float* pool_o = ctx->pool ? pool_c + ctx->pool_rows : nullptr;

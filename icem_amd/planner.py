@@ -590,17 +590,22 @@ class IcemPlanner:
         """Kernel launches of the last CEM step of this planner (``icem_cem_step_launches``): 3 per iteration."""
         return int(self.lib.icem_cem_step_launches(self._h))
 
-    def _cem_buffers(self):
+    def _cem_buffers(self, obs: Optional[str] = None):
         """The step's buffers, owned by the planner: the last pool and its costs, the elite set, its costs and indices,
-        the observation, and ``[executed | best_cost]`` as one tensor (one device-to-host copy fetches both)."""
+        and ``[executed | best_cost]`` as one tensor (one device-to-host copy fetches both).  ``obs``: also the observation
+        buffer of one of the two steps -- ``"obs0"`` ``[obs_dim]`` of the planner dtype for the built-in model (which must
+        be set), ``"obs_rssm"`` ``[230]`` f32 for the learned-dynamics step, which needs no built-in model."""
         b = getattr(self, "_cem", None)
+        new = lambda *shape, dt=self.dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
         if b is None:
-            if self.obs_dim == 0:
-                raise RuntimeError("set_model()/set_cost() must be called before planning")
-            n, new = self.cfg.num_traj, lambda *shape, dt=self.dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+            n = self.cfg.num_traj
             b = self._cem = dict(actions=new(n, self.h, self.d), costs=new(n), elites=new(self.K, self.h, self.d),
-                                 elite_costs=new(self.K), elite_idx=new(self.K, dt=torch.int32), obs0=new(self.obs_dim),
+                                 elite_costs=new(self.K), elite_idx=new(self.K, dt=torch.int32), obs0=None, obs_rssm=None,
                                  result=new(self.d + 1), cb=None, key=None)
+        if obs is not None and b[obs] is None:
+            if obs == "obs0" and self.obs_dim == 0:
+                raise RuntimeError("set_model()/set_cost() must be called before planning")
+            b[obs] = new(self.obs_dim) if obs == "obs0" else new(L.RSSM_OBS_DIM, dt=torch.float32)
         return b
 
     def plan_step_cem(self, obs, mean: torch.Tensor, std: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, *,
@@ -618,23 +623,30 @@ class IcemPlanner:
         self.mpc_step += 1
         return self._cem_buffers()["result"][:self.d]
 
-    def _cem_cb(self, obs, mean, std, lower, upper) -> "L.IcemCemBuffersC":
+    def _cem_cb(self, obs, mean, std, lower, upper, which: str = "obs0", obs_ptr: Optional[int] = None) -> "L.IcemCemBuffersC":
         """The observation into the planner's own buffer and the step's ``icem_cem_buffers`` (kept while the caller's tensors
-        stay where they are)."""
-        b = self._cem_buffers()
+        stay where they are).  ``which``: the built-in model's observation buffer or the learned-dynamics step's
+        (:meth:`_cem_buffers`); ``obs_ptr``: the observation already lies on the device there (a row of a batch's table) --
+        nothing is copied."""
+        b = self._cem_buffers(None if obs_ptr is not None else which)
         for t in (mean, std, lower, upper):
             if t.dtype != self.dt or t.device != self.device or tuple(t.shape) != (self.h, self.d) or not t.is_contiguous():
                 raise ValueError("mean / std / lower / upper must be contiguous [h, d] device tensors of the planner dtype")
-        if isinstance(obs, torch.Tensor) and obs.device == self.device:
-            b["obs0"].copy_(obs.reshape(-1))
-        else:
-            b["obs0"].copy_(torch.as_tensor(np.asarray(obs, dtype=np.float64).reshape(self.obs_dim), dtype=self.dt))
-        key = (mean.data_ptr(), std.data_ptr(), lower.data_ptr(), upper.data_ptr())
+        if obs_ptr is None:
+            dst = b[which]
+            if isinstance(obs, torch.Tensor) and obs.device == self.device:
+                if obs.numel() != dst.numel():
+                    raise ValueError(f"expected an observation of {dst.numel()} values")
+                dst.copy_(obs.reshape(-1))
+            else:
+                dst.copy_(torch.as_tensor(np.asarray(obs, dtype=np.float64).reshape(dst.numel()), dtype=dst.dtype))
+            obs_ptr = dst.data_ptr()
+        key = (mean.data_ptr(), std.data_ptr(), lower.data_ptr(), upper.data_ptr(), obs_ptr)
         if b["key"] != key:
             r = b["result"]
             b["cb"] = L.IcemCemBuffersC(
                 mean=key[0], std=key[1], lower=key[2], upper=key[3], low=self.low.data_ptr(), high=self.high.data_ptr(),
-                obs0=b["obs0"].data_ptr(), actions=b["actions"].data_ptr(), costs=b["costs"].data_ptr(),
+                obs0=obs_ptr, actions=b["actions"].data_ptr(), costs=b["costs"].data_ptr(),
                 elites=b["elites"].data_ptr(), elite_costs=b["elite_costs"].data_ptr(), elite_idx=b["elite_idx"].data_ptr(),
                 executed=r.data_ptr(), best_cost=r[self.d:].data_ptr(), workspace=None)
             b["key"] = key
@@ -678,6 +690,75 @@ class IcemPlanner:
     def cem_batch_launches(self) -> int:
         """Kernel launches of the last batched CEM step this planner led (``icem_cem_batch_launches``): 3 per iteration."""
         return int(self.lib.icem_cem_batch_launches(self._h))
+
+    # ------------------------------------------------------------------ ... through the learned dynamics (declared RSSM)
+    def cem_learned_step_ok(self) -> bool:
+        """Does ``icem_plan_step_cem_learned`` serve THIS handle?  (:meth:`cem_step_ok`'s conditions, f32, six action
+        dimensions, a population the RSSM's split launch takes: asked of the handle.)"""
+        return bool(self.lib.icem_plan_step_cem_learned_ok(self._h))
+
+    def plan_step_cem_learned(self, model, obs, mean: torch.Tensor, std: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, *,
+                              like_levine: bool, shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
+        """:meth:`plan_step_cem` through ``model`` (a ``DeviceRSSMModel``: its packed ``params``) as
+        ``icem_plan_step_cem_learned`` -- the planner PlaNet uses.  ``obs``: the observation ``[230]`` (array-like, or a
+        device tensor); no built-in model or cost need be set.  The same arguments, views, return value and launch count
+        (:attr:`cem_step_launches`) as :meth:`plan_step_cem`, and the same bits as the operator loop
+        (``sample_truncnorm``, ``model.rollout_cost``, ``update_distribution``, ``cem_bounds``).  Raises ``IcemError``
+        (``ICEM_E_UNSUPPORTED``) before anything runs where :meth:`cem_learned_step_ok` is false."""
+        cb = self._cem_cb(obs, mean, std, lower, upper, "obs_rssm")
+        prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        L.check(self.lib.icem_plan_step_cem_learned(self._h, C.byref(cb), C.byref(prm), C.c_void_p(model.params.data_ptr()),
+                                                    self.mpc_step, self._stream()))
+        self.mpc_step += 1
+        return self._cem_buffers()["result"][:self.d]
+
+    @staticmethod
+    def plan_step_cem_learned_batch(planners: Sequence["IcemPlanner"], model, observations, dists, *, like_levine: bool,
+                                    shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
+        """:meth:`plan_step_cem_learned` of every planner of ``planners`` (one configuration; seeds, episodes, step counts
+        and observations of their own) through the one ``model`` as ``icem_plan_step_cem_learned_batch``: every iteration 3
+        launches for all of them.  ``observations``: ``[B, 230]`` array-like -- one host-to-device copy for the batch -- or
+        an f32 device tensor, used where it lies.  ``dists[i]``: planner i's ``(mean, std, lower, upper)``, updated in
+        place.  Each planner's ``cem_elites`` / ``cem_elite_costs`` / ``cem_elite_idx`` / ``cem_result`` afterwards are bit
+        for bit those of its own :meth:`plan_step_cem_learned`; its ``cem_actions`` / ``cem_costs`` are scratch for B > 1
+        (the batch scores its rows in a pool of the first planner's handle).  Returns the executed actions ``[B, d]``, a
+        view of ``planners[0].cem_batch_results`` ``[B, d + 1]`` (kept per batch size).  Raises ``IcemError`` before anything
+        runs, and before any planner has advanced, where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_cem_learned_batch(None, 0, None, None, None, None, None, None))
+        p0 = pls[0]
+        dists = list(dists)
+        if len(dists) != n:
+            raise ValueError("one (mean, std, lower, upper) per planner")
+        obs_dev = getattr(p0, "_cem_learned_obs", None)   # (kept per batch size, as the results)
+        if obs_dev is None or obs_dev.shape[0] != n:
+            obs_dev = p0._cem_learned_obs = torch.zeros((n, L.RSSM_OBS_DIM), dtype=torch.float32, device=p0.device)
+        if isinstance(observations, torch.Tensor) and observations.device == p0.device:
+            src = observations.reshape(n, -1)
+            if src.dtype == torch.float32 and src.is_contiguous() and src.shape[1] == L.RSSM_OBS_DIM:
+                obs_dev = src
+            else:
+                obs_dev.copy_(src)
+        else:
+            host = np.ascontiguousarray(np.asarray(observations, dtype=np.float32).reshape(n, -1))
+            if host.shape[1] != L.RSSM_OBS_DIM:
+                raise ValueError(f"expected observations of shape ({n}, {L.RSSM_OBS_DIM})")
+            obs_dev.copy_(torch.as_tensor(host))   # one host-to-device copy for the whole batch
+        cbs = [pl._cem_cb(None, *dist, obs_ptr=obs_dev[i].data_ptr()) for i, (pl, dist) in enumerate(zip(pls, dists))]
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemCemBuffersC * n)(*cbs)
+        steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
+        res = getattr(p0, "_cem_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
+        if res is None or res.shape[0] != n:
+            res = p0._cem_batch_results = torch.zeros((n, p0.d + 1), dtype=p0.dt, device=p0.device)
+        prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        L.check(p0.lib.icem_plan_step_cem_learned_batch(hs, n, bs, C.byref(prm), C.c_void_p(model.params.data_ptr()), steps, _ptr(res),
+                                                        p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        return res[:, :p0.d]
 
     cem_actions = property(lambda self: self._cem_buffers()["actions"])
     cem_costs = property(lambda self: self._cem_buffers()["costs"])

@@ -273,6 +273,44 @@ int64_t icem_cem_step_launches(const icem_handle* h);  /* kernel launches of the
 int     icem_plan_step_cem_batch(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
                                  const int32_t* mpc_steps_host, void* results, void* stream);
 int64_t icem_cem_batch_launches(const icem_handle* h); /* kernel launches of the last such batch this handle led as handles[0]; measurement */
+/* The same step through the LEARNED dynamics -- the declared RSSM of icem_rssm_rollout_cost, BASELINE configs[4]; the planner
+ * PlaNet itself uses and the baseline of the reference's "iCEM with PlaNet" column -- for one planner and for n planners at once.
+ * The step is icem_plan_step_cem's in every respect but the rollout: per iteration cfg.num_traj rows drawn with
+ * icem_sample_truncnorm's arithmetic at stream offset (episode << 32) + s * opt_iters + i, rolled out through the RSSM (params:
+ * the packed parameter buffer of icem_rssm_rollout_cost, shared by the problems of a batch) under the handle's cost_mode, the K
+ * best rows in (cost, index) order gathered and refitted with alpha, the bounds as icem_cem_bounds writes them, the epilogue
+ * behind the last iteration.  icem_cem_buffers and icem_cem_params are icem_plan_step_cem's: b->obs0 is [ICEM_RSSM_OBS_DIM] f32,
+ * workspace is unused.  No built-in model or cost need be set on the handle.  The stream offsets are the operator loop's and
+ * icem_plan_step_cem's: a caller may alternate freely between the loop, the solo entry and the batched entry.
+ *   3 launches per iteration whatever n (3 * opt_iters in all; reported by icem_cem_step_launches for the solo entry and by
+ * icem_cem_batch_launches of handles[0] for the batched one), no host synchronisation, no allocation after the first call of a
+ * batch size on a stream.  Every output of the solo entry -- mean, std, lower, upper, elites, elite_costs, elite_idx, executed,
+ * best_cost, the last pool in actions / costs -- is bit for bit what the operator loop gives (icem_sample_truncnorm,
+ * icem_rssm_rollout_cost, icem_update_distribution, icem_cem_bounds).  Every problem of a batch is bit for bit its own solo step
+ * on the first nine of those and on its row of results ([n, act_dim + 1] f32: executed | best cost; may be NULL).  A batch scores
+ * its rows back to back in a pool owned by handles[0] (the batched RSSM launch wants them contiguous): for n > 1 A PROBLEM'S OWN
+ * actions / costs ARE SCRATCH -- they must be valid, their contents afterwards are unspecified.  The problems' obs0 buffers need
+ * not be adjacent: the first iteration's sampler launch gathers them into the pool's [n, 230] table.  The batch's argument blocks
+ * live in a device array of handles[0] and are uploaded only when a byte changed (icem_batch_uploads: the steady state uploads
+ * nothing).  n == 1 is the solo step plus the results row.
+ *   Served: f32 handles, world == 1, act_dim == 6, rng_rounds 7 or 10, profiling off, factor_decrease == 1, keep_previous_elites and
+ * shift_elites off, icem_update_distribution_ok(num_traj, K), a row that fits the step's sampler, a population the RSSM's split
+ * launch takes (for a batch: all problems' tiles together), any horizon the handle and that launch accept.  Development option
+ * cem_step = 0 switches these entries off too.  ICEM_E_INVALID: a NULL handle / buffers / flags / params, a negative step, a NULL
+ * buffer other than workspace, n outside [1, 32], a handle twice, unequal configurations; ICEM_E_UNSUPPORTED: anything not served;
+ * ICEM_E_STATE: the learned-dynamics rollout's own rules (its staging area's first call of a size must not be under capture; its
+ * host-visible status word, looked at before the step's first launch).  Whatever is refused is refused before anything is
+ * launched or any handle touched.
+ *   Measured (EXPERIMENTS R15.1; N = 1024, h = 12, K = 10, 5 iterations, MpcCemStdHip.get_action): 0.50 ms against 0.57 ms for the
+ * operator loop in the same process (1.14 x: the rollout's 74 us of every iteration are the same in both; sampler 12 us, update +
+ * bounds 23 us); batched, per step of the batch against B solo steps: B = 2 0.52 / 0.96 ms, B = 4 0.68 / 1.89, B = 8 1.01 / 3.76,
+ * B = 16 1.71 / 7.47 ms (1.9 x to 4.4 x). */
+int     icem_plan_step_cem_learned_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
+int     icem_plan_step_cem_learned(icem_handle* h, const icem_cem_buffers* b, const icem_cem_params* p, const void* params,
+                                   int32_t mpc_step, void* stream);
+int     icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers,
+                                         const icem_cem_params* p, const void* params, const int32_t* mpc_steps_host, void* results,
+                                         void* stream);
 
 /* MpcRandom.sample_action_sequences (icem/controllers/mpc.py:96-109, random shooting): actions[i, t, :] = low +
  * (high - low) * U(block), uniform draws held for consecutive calls of MpcRandom.sample() (mpc.py:96-102) -- one call

@@ -19,6 +19,14 @@ with min and max over BLOCKS blocks.
                                                ``icem_plan_step_cem`` steps issued back to back (each block step ending in one
                                                synchronisation) -- what these callers had before the batched entry; B may be a
                                                list (2,4,8,16).  With --trace: TRACE_STEPS steps of each and nothing else.
+  python tools/cem_step_bench.py --learned [--batch B]
+                                               the same legs through the learned dynamics: ``MpcCemStdHip`` with ``DeviceRSSMModel``
+                                               at N = 1024, h = 12, d = 6, K = 10, 5 iterations -- the learned configuration's
+                                               population on the CEM baseline -- ``icem_plan_step_cem_learned`` against the loop
+                                               (``fused_step=False``), and with --batch ``icem_plan_step_cem_learned_batch`` against B
+                                               solo fused steps.  The solo leg also prints the device time per launch of the three
+                                               stages (sampler, rollout, update + bounds: each operator launched back to back between
+                                               two events).  --stagewise runs on the parent commit's library as above.
 """
 import ctypes as C
 import os
@@ -32,6 +40,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from icem_amd import _lib as L  # noqa: E402
 
 H, D, O_, ITERS, SIZES = 30, 6, 17, 5, (512, 4096)
+LEARNED = "--learned" in sys.argv
+if LEARNED:   # BASELINE configs[4]'s population on the CEM baseline; the RSSM's observation is [h (200) | z (30)]
+    H, O_, SIZES = 12, 230, (1024,)
 WARMUP, BLOCK, BLOCKS, TRACE_STEPS = 20, 200, 9, 50
 
 
@@ -41,9 +52,20 @@ def bind_what_the_library_has():
     L.SYMBOLS[:] = [s for s in L.SYMBOLS if hasattr(have, s[0])]
 
 
+_rssm = []
+
+
+def rssm():
+    from icem_amd import DeviceRSSMModel
+    if not _rssm:
+        _rssm.append(DeviceRSSMModel(seed=3))
+    return _rssm[0]
+
+
 def controller(n, fused):
     from icem_amd import DeviceSyntheticModel, MpcCemStdHip, halfcheetah_env
-    c = MpcCemStdHip(env=halfcheetah_env(O_), forward_model=DeviceSyntheticModel.make(O_, D, kind=0), horizon=H,
+    model = rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0)
+    c = MpcCemStdHip(env=halfcheetah_env(17 if LEARNED else O_), forward_model=model, horizon=H,
                      num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=1,
                      **({"fused_step": fused} if fused is not None else {}),
                      action_sampler_params=dict(alpha=0.1, elites_size=10, opt_iterations=ITERS, init_std=0.5, shift_means=True,
@@ -77,16 +99,17 @@ BATCH_BLOCK, BATCH_BLOCKS, BATCH_WARMUP = 30, 7, 10
 def batch_planners(n, B, dtype):
     """B planners at the HalfCheetah shape (seeds of their own) with their distributions, as ``MpcCemStdHip`` holds them."""
     from icem_amd import DeviceSyntheticModel, IcemConfig, IcemPlanner, halfcheetah_env
-    env = halfcheetah_env(O_)
+    env = halfcheetah_env(17 if LEARNED else O_)
     out = []
     for i in range(B):
         cfg = IcemConfig(horizon=H, act_dim=D, num_traj=n, elites_size=10, opt_iters=ITERS, cost_mode="sum", use_mean_actions=False,
                          keep_previous_elites=False, shift_elites=False, factor_decrease=1.0, alpha=0.1, init_std=0.5, dtype=dtype,
                          seed=1 + i)
         pl = IcemPlanner(cfg, env.action_space.low, env.action_space.high)
-        m = DeviceSyntheticModel.make(O_, D, kind=0)
-        pl.set_model(m.kind, m.A, m.B)
-        pl.set_cost_spec(env.cost_spec)
+        if not LEARNED:   # (the learned-dynamics step needs no built-in model)
+            m = DeviceSyntheticModel.make(O_, D, kind=0)
+            pl.set_model(m.kind, m.A, m.B)
+            pl.set_cost_spec(env.cost_spec)
         pl.new_episode()
         mean = torch.empty((H, D), dtype=pl.dt, device=pl.device)
         std = torch.empty_like(mean)
@@ -112,14 +135,21 @@ def main_batch():
         for B in Bs:
             both = {"batched": batch_planners(n, B, dtype), "solo": batch_planners(n, B, dtype)}
             obs = [torch.as_tensor(0.1 * np.random.RandomState(i).randn(O_), dtype=both["solo"][0][0].dt, device="cuda") for i in range(B)]
+            obs_all = torch.stack(obs)   # (the learned batch takes the table where it lies)
 
             def step(kind):
                 ps = both[kind]
                 if kind == "batched":
-                    IcemPlanner.plan_step_cem_batch([p for p, _ in ps], obs, [dist for _, dist in ps], **flags)
+                    if LEARNED:
+                        IcemPlanner.plan_step_cem_learned_batch([p for p, _ in ps], rssm(), obs_all, [dist for _, dist in ps], **flags)
+                    else:
+                        IcemPlanner.plan_step_cem_batch([p for p, _ in ps], obs, [dist for _, dist in ps], **flags)
                     return ps[0][0].cem_batch_results.cpu()   # the batch's one device-to-host copy
                 for (p, dist), ob in zip(ps, obs):
-                    p.plan_step_cem(ob, *dist, **flags)
+                    if LEARNED:
+                        p.plan_step_cem_learned(rssm(), ob, *dist, **flags)
+                    else:
+                        p.plan_step_cem(ob, *dist, **flags)
                 torch.cuda.synchronize()
                 return None
 
@@ -149,13 +179,39 @@ def main_batch():
                   f"launches per batched step {both['batched'][0][0].cem_batch_launches}, uploads {both['batched'][0][0].batch_uploads}", flush=True)
 
 
+def stage_times(n, reps=200):
+    """Device time per launch of the three stages of one CEM iteration through the RSSM: each operator launched `reps` times back to
+    back between two events (the step's kernels run the operators' bodies)."""
+    (pl, (mean, std, lower, upper)), = batch_planners(n, 1, "f32")
+    m, obs = rssm(), (0.1 * np.random.RandomState(0).randn(O_)).astype(np.float32)
+    actions = pl.sample_truncnorm(n, mean, std, lower, upper, None, offset=0)
+    costs = m.rollout_cost(obs, actions, 0)
+
+    def update():
+        pl.update_distribution(costs, actions, pl.K, mean, std)
+        pl.cem_bounds(mean, std, False)
+    stages = {"sampler": lambda: pl.sample_truncnorm(n, mean, std, lower, upper, None, offset=1, out=actions),
+              "rollout": lambda: m.rollout_cost(obs, actions, 0), "update + bounds (2 launches)": update}
+    for name, launch in stages.items():
+        for _ in range(20):
+            launch()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(reps):
+            launch()
+        b.record()
+        torch.cuda.synchronize()
+        print(f"  N = {n}: {name:<30s} {a.elapsed_time(b) / reps * 1e3:7.1f} us per call, back to back", flush=True)
+
+
 def main():
     stagewise_only, trace = "--stagewise" in sys.argv, "--trace" in sys.argv
     if stagewise_only:
         bind_what_the_library_has()
     lib = L.load_library()
     print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  h = {H}, d = {D}, o = {O_}, "
-          f"{ITERS} iterations, f32; warm-up {WARMUP} calls", flush=True)
+          f"{ITERS} iterations, f32{', learned dynamics (DeviceRSSMModel)' if LEARNED else ''}; warm-up {WARMUP} calls", flush=True)
     obs = 0.1 * np.random.RandomState(0).randn(O_)
     for n in SIZES:
         # (a library without the keyword's entry: the constructor of its own tree would not know `fused_step` either, but the
@@ -183,6 +239,8 @@ def main():
         if not stagewise_only:
             f, s = (sorted(t[k])[BLOCKS // 2] for k in ("fused step", "stage-wise loop"))
             print(f"  stage-wise / fused at N = {n}: {s / f:.2f}x", flush=True)
+        if LEARNED:
+            stage_times(n)
 
 
 if __name__ == "__main__":
