@@ -82,6 +82,11 @@ class IcemCemBuffersC(C.Structure):
         "executed", "best_cost", "workspace")]
 
 
+class IcemRandomBuffersC(C.Structure):
+    """include/icem_hip.h: struct icem_random_buffers."""
+    _fields_ = [(n, C.c_void_p) for n in ("low", "high", "obs0", "actions", "costs", "best_actions", "result")]
+
+
 # every symbol include/icem_hip.h declares: (name, restype, argtypes)
 _VP, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 _H = C.c_void_p
@@ -142,6 +147,11 @@ SYMBOLS = [
     ("icem_plan_step_cem_learned", C.c_int, [_H, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _VP, _I32, _VP]),
     ("icem_plan_step_cem_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _VP,
                                                    C.POINTER(_I32), _VP, _VP]),
+    ("icem_plan_step_random_ok", C.c_int, [_H]),
+    ("icem_plan_step_random", C.c_int, [_H, C.POINTER(IcemRandomBuffersC), _I32, _I64, _I64, _VP, _VP]),
+    ("icem_random_step_launches", C.c_int64, [_H]),
+    ("icem_plan_step_random_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemRandomBuffersC), _I32, C.POINTER(_I64), _VP, _VP]),
+    ("icem_random_batch_launches", C.c_int64, [_H]),
     ("icem_rccl_load", C.c_int, [C.c_char_p]),
     ("icem_rccl_library", C.c_char_p, []),
     ("icem_rccl_unique_id", C.c_int, [_VP]),

@@ -1147,11 +1147,21 @@ class MpcRandomHip(MpcController):
     Extra optional keywords: ``dtype``, ``seed``, ``rng_rounds``, ``device``, ``noise_source`` ("philox": device
     uniforms keyed by the block index; "action_space": ``env.action_space``-style draws ``np.random.random_sample(d)``
     in the reference's call order, two of them at construction -- parity mode; or a callable
-    ``uniforms(first_block, n_blocks) -> [n_blocks, d]``)."""
+    ``uniforms(first_block, n_blocks) -> [n_blocks, d]``).
+
+    ``get_action`` is one library call (``icem_plan_step_random``: sampler, rollout and one selection launch with no host
+    round trip, one device-to-host copy of ``[executed | best cost | best index]``) where the model is the device's
+    built-in one, the noise is the device's, the controller is not verbose and ``IcemPlanner.random_step_ok()``;
+    everywhere else it is the chain of operators -- the same bits.  ``get_action_batch`` steps several controllers of one
+    configuration in one library call (``icem_plan_step_random_batch``).  ``fused_step``: None (the rule above), False
+    (always the operator chain) or True (raise where the fused step is not served)."""
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
-                 noise_source: Union[str, Callable] = "philox", **kwargs):
+                 noise_source: Union[str, Callable] = "philox", fused_step=None, **kwargs):
         super().__init__(**kwargs)
+        if fused_step not in (None, True, False):
+            raise ValueError("fused_step must be None (where served), True (or raise) or False (the operator chain)")
+        self.fused_step = fused_step
         asp = action_sampler_params
         self.action_change_frequency = int(asp["action_change_frequency"] if isinstance(asp, Mapping)
                                            else asp.action_change_frequency)
@@ -1204,6 +1214,52 @@ class MpcRandomHip(MpcController):
     def get_action(self, obs, state, mode="train"):  # mpc.py:114-138
         self.forward_model_state = self.forward_model.got_actual_observation_and_env_state(
             observation=obs, env_state=state, model_state=self.forward_model_state)
+        executed_action = self._step_fused(obs) if self._takes_fused_step() else self._step_stagewise(obs)
+        return self._finish_action(obs, executed_action)
+
+    def _finish_action(self, obs, executed_action):
+        """The tail of ``get_action`` behind the planning step, shared with ``get_action_batch``."""
+        if self.forward_model_state is not None:
+            _, self.forward_model_state, _ = self.forward_model.predict(
+                observations=obs, states=self.forward_model_state, actions=executed_action)
+        return executed_action
+
+    def _fused_step_refusal(self):
+        """Why ``icem_plan_step_random`` cannot run this controller's step (None: it can)."""
+        if not self.device_path:
+            return "the model is not the device's built-in one"
+        if self.noise_source != "philox":
+            return "the noise source is not the device's (external uniforms keep the operator chain)"
+        if self.verbose:
+            return "the controller is verbose"
+        if not self.planner.random_step_ok():
+            return "the library does not serve this handle (IcemPlanner.random_step_ok)"
+        return None
+
+    def _takes_fused_step(self) -> bool:
+        if self.fused_step is False:
+            return False
+        why = self._fused_step_refusal()
+        if why is not None and self.fused_step is True:
+            raise RuntimeError(f"fused_step=True, but the fused random-shooting step is not served: {why}")
+        return why is None
+
+    def _took_step(self, host):
+        """The bookkeeping of a fused step from its ``result`` row on the host: ``[executed | best cost | best index]``."""
+        p = self.planner
+        self.calls += self.num_sim_traj * p.h
+        self.best_traj_idx = int(host[-1])
+        self.last_min_cost = float(host[-2])
+        self._last_actions, self._last_costs = p.random_actions, p.random_costs
+        return host[:-2].copy()
+
+    def _step_fused(self, obs):
+        """The whole step in the library (``icem_plan_step_random``); one device-to-host copy of ``result``."""
+        p = self.planner
+        p.plan_step_random(obs, self.calls, self.action_change_frequency)
+        return self._took_step(p.random_result.cpu().numpy().astype(np.float64))   # one device-to-host copy, one synchronisation
+
+    def _step_stagewise(self, obs):
         p = self.planner
         actions = self.sample_action_sequences(obs, self.num_sim_traj)
         costs = self._costs_of(obs, actions)
@@ -1211,11 +1267,69 @@ class MpcRandomHip(MpcController):
         self.best_traj_idx = int(idx[0])
         self.last_min_cost = float(best_cost[0])
         self._last_actions, self._last_costs = actions, costs
-        executed_action = actions[self.best_traj_idx, 0].cpu().numpy().astype(np.float64)
-        if self.forward_model_state is not None:
-            _, self.forward_model_state, _ = self.forward_model.predict(
-                observations=obs, states=self.forward_model_state, actions=executed_action)
-        return executed_action
+        return actions[self.best_traj_idx, 0].cpu().numpy().astype(np.float64)
+
+    @staticmethod
+    def _batch_refusal(ctrls):
+        """Why ``icem_plan_step_random_batch`` cannot run these controllers' steps as one call (None: it can, as far as the
+        controllers can tell -- the library has the last word)."""
+        import dataclasses
+        for c in ctrls:
+            if c.fused_step is False:
+                return "a controller has fused_step=False (the operator chain)"
+            why = c._fused_step_refusal()
+            if why is not None:
+                return why
+        c0 = ctrls[0]
+        shared = lambda c: (c.action_change_frequency, dataclasses.replace(c.planner.cfg, seed=0))   # noqa: E731
+        if any(shared(c) != shared(c0) for c in ctrls[1:]):
+            return "the controllers differ in configuration (everything but the seed must be equal) or in action_change_frequency"
+        if len({id(c.planner) for c in ctrls}) != len(ctrls):
+            return "a controller appears twice"
+        return None
+
+    @staticmethod
+    def get_action_batch(controllers, observations, states=None, mode="train"):
+        """``get_action`` of several controllers at once -- the reference steps its baseline's episodes side by side, each
+        controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152; mpc.py:114-138) -- as ONE library call
+        (``icem_plan_step_random_batch``: the step's launches once for all of them, one device-to-host copy) where every
+        controller takes the fused step by itself and the controllers share configuration and ``action_change_frequency``;
+        seeds, models and call counters are their own.  Each controller ends in exactly the state its own
+        ``get_action(observations[i], states[i])`` leaves.  Where the batch is not served each controller's own step runs, in
+        order, with the same results; a controller with ``fused_step=True`` makes that a ``RuntimeError`` naming the reason."""
+        from ._lib import ICEM_E_INVALID, ICEM_E_STATE, ICEM_E_UNSUPPORTED, IcemError
+        ctrls = list(controllers)
+        n = len(ctrls)
+        observations = list(observations)
+        states = [None] * n if states is None else list(states)
+        if len(observations) != n or len(states) != n:
+            raise ValueError("one observation (and state) per controller")
+        if n == 0:
+            return []
+        for c, ob, stt in zip(ctrls, observations, states):
+            c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
+                observation=ob, env_state=stt, model_state=c.forward_model_state)
+        why = MpcRandomHip._batch_refusal(ctrls)
+        host = None
+        if why is None:
+            try:
+                IcemPlanner.plan_step_random_batch([c.planner for c in ctrls], observations, [c.calls for c in ctrls],
+                                                   ctrls[0].action_change_frequency)
+                host = ctrls[0].planner.random_batch_results.cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+            except IcemError as e:   # refused before anything ran: nothing was touched
+                if e.code not in (ICEM_E_UNSUPPORTED, ICEM_E_INVALID, ICEM_E_STATE):
+                    raise
+                why = str(e)
+        if why is not None and any(c.fused_step is True for c in ctrls):
+            raise RuntimeError(f"fused_step=True, but the batched fused random-shooting step is not served: {why}")
+        out = []
+        for i, (c, ob) in enumerate(zip(ctrls, observations)):
+            if host is None:   # the controller's own step (fused where it is served by itself, else the operator chain)
+                executed_action = c._step_fused(ob) if c._takes_fused_step() else c._step_stagewise(ob)
+            else:
+                executed_action = c._took_step(host[i])
+            out.append(c._finish_action(ob, executed_action))
+        return out
 
 
 # ---------------------------------------------------------------------------------------------

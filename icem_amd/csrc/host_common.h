@@ -5,7 +5,8 @@
 //   plan.hip             the fused MPC step: icem_plan_* / icem_get_action and the f32 throughput-path orchestration
 //   learned_step.hip     the learned-dynamics MPC step: icem_plan_step_learned*
 //   cem_step.hip         the CEM baseline's MPC step: icem_plan_step_cem, icem_plan_step_cem_batch
-//   exchange.hip         the in-library elite exchange between GPUs (icem_exchange_*)
+//   random_step.hip      the random-shooting baseline's MPC step: icem_plan_step_random, icem_plan_step_random_batch
+//   exchange.hip        the in-library elite exchange between GPUs (icem_exchange_*)
 //   abi.hip              handle life cycle and the stateless operators of include/icem_hip.h
 // Internal; not part of the public ABI.
 #pragma once
@@ -79,6 +80,18 @@ struct LearnedCtx {
     ~LearnedCtx() {
         if (pool) (void)hipFree(pool);
         if (idx) (void)hipFree(idx);
+    }
+};
+
+// icem_plan_step_random* (random_step.hip): device words of the selection launch, zeroed once (the launch leaves them zero)
+struct RandomWs {
+    void* dev = nullptr;
+    size_t bytes = 0;
+    RandomWs() = default;
+    RandomWs(const RandomWs&) = delete;
+    RandomWs& operator=(const RandomWs&) = delete;
+    ~RandomWs() {
+        if (dev) (void)hipFree(dev);
     }
 };
 
@@ -243,6 +256,12 @@ struct icem_handle {
     // (the blocks carry no step-dependent value: either slot of a batch whose buffers stay put is uploaded once)
     icem::DeviceArgArray<2> cem_batch_args;
     long long cem_batch_launches = 0;       // kernel launches of the last icem_plan_step_cem_batch this handle led
+    // icem_plan_step_random / _random_batch (random_step.hip): the selection's per-workgroup partials + ticket of THIS handle's
+    // problem (pools of more than one slice), the batch's argument blocks with its FIRST handle (no step-dependent value in them)
+    icem::RandomWs random_ws;
+    icem::DeviceArgArray<1> random_batch_args;
+    long long random_launches = 0;          // kernel launches of the last icem_plan_step_random of this handle
+    long long random_batch_launches = 0;    // kernel launches of the last icem_plan_step_random_batch this handle led
     void* rccl_comm = nullptr;       // collective.hip: the RCCL communicator of icem_allgather_elites (world > 1)
     bool rccl_owned = false;         // ... created by icem_rccl_connect (destroyed with the handle) or adopted
 };

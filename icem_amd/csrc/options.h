@@ -38,7 +38,8 @@ namespace icem {
     X(BATCH_MAX_RW, "batch_max_rw", 0.0)             /* icem_plan_step_batch: cap of the tiles per workgroup (0: as one population of all rows) */ \
     X(LEARNED_STEP, "learned_step", 1.0)             /* 0: icem_plan_step_learned* refuse (the controllers then run the stage-wise loop) */ \
     X(CEM_STEP, "cem_step", 1.0)                     /* 0: icem_plan_step_cem*, the learned-dynamics entries included, refuse (MpcCemStdHip then runs the stage-wise loop) */ \
-    X(XCHG_LOOPBACK, "xchg_loopback", 0.0)           /* 1: time one rank without its peers (tools/sharded_rank_bench.py) */ \
+    X(RANDOM_STEP, "random_step", 1.0)               /* 0: icem_plan_step_random* refuse (MpcRandomHip then runs the operator chain) */ \
+    X(XCHG_LOOPBACK,"xchg_loopback", 0.0)           /* 1: time one rank without its peers (tools/sharded_rank_bench.py) */ \
     X(XCHG_MAX_POLLS, "xchg_max_polls", 0.0)         /* bound of the exchange's device-side waits (0: the default) */
 enum Opt {
 #define X(id, name, def) OPT_##id,

@@ -1,0 +1,203 @@
+// random_step.hip -- the MPC step of the random-shooting baseline (MpcRandom.get_action, icem/controllers/mpc.py:114-138) as one
+// C call: icem_plan_step_random.  The step is the operator chain of MpcRandomHip.get_action (icem_amd/controllers.py) as three
+// stages with nothing between them:
+//   sample   random_sample_kernel (k_random.hip): icem_sample_piecewise's pool at the caller's call offset
+//   rollout  rollout_cost_launch (abi.hip): the launch icem_rollout_cost picks for the handle
+//   select   random_select_kernel (k_random.hip): icem_topk_sorted(costs, 1), the best row's gather, result
+// The arguments go by value.  The entry keeps no step state: the call offset (MpcRandom's counter of sample() calls) is the caller's.
+//
+// icem_plan_step_random_batch is the same step for B planners of one configuration, every stage ONE launch for all of them:
+// random_sample_batch_kernel, the batched twin of the handles' rollout launch (LAUNCH_FAMILIES, icem_fused.h; recorded per handle,
+// compared, issued once -- cem_step.hip's arrangement), random_select_batch_kernel.  The argument blocks live in a DeviceArgArray of
+// the first handle and carry no step-dependent value (the call offsets travel by value): a batch whose buffers stay put uploads them once.
+#include "random_step.h"
+
+using namespace icem;
+
+namespace {
+
+// "who is served" (nullptr: this handle is)
+const char* random_unserved(const icem_handle* h) {
+    const icem_config& c = h->cfg;
+    if (opt_i(OPT_RANDOM_STEP) == 0) return "option random_step is 0";
+    if (c.world != 1) return "world must be 1";
+    if (h->profiling) return "per-kernel profiling is per launch of one operator: switch it off";
+    if (h->dbg) return "debug stamps are per launch of one operator: switch them off";
+    if (c.rng_rounds != 7 && c.rng_rounds != 10) return "rng_rounds must be 7 or 10";
+    if (c.dtype == ICEM_F32 && c.num_traj > (1 << 24)) return "f32: result holds the best index as a float, exact up to num_traj = 2^24";
+    return nullptr;
+}
+
+bool null_buffer(const icem_random_buffers& b) {
+    return !b.low || !b.high || !b.obs0 || !b.actions || !b.costs || !b.best_actions || !b.result;
+}
+
+// the refusals that read no handle (the entries make them first), then those of one handle's step: all of them before anything
+// is launched or the handle touched
+int random_arg_refusal(const icem_random_buffers& b, int32_t change_freq, int64_t call_offset, const std::string& who) {
+    if (change_freq < 0) return fail(ICEM_E_INVALID, who + "negative change_freq");
+    if (call_offset < 0) return fail(ICEM_E_INVALID, who + "negative call_offset");
+    if (null_buffer(b)) return fail(ICEM_E_INVALID, who + "null buffer");
+    return ICEM_OK;
+}
+int random_refusal(const icem_handle* h, int32_t change_freq, const std::string& who) {
+    if (change_freq >= h->cfg.horizon) return fail(ICEM_E_INVALID, who + "change_freq must be below the horizon (mpc.py:92)");
+    if (const char* why = random_unserved(h)) return fail(ICEM_E_UNSUPPORTED, who + why);
+    if (!h->has_model || !h->has_cost) return fail(ICEM_E_STATE, who + "icem_set_model / icem_set_cost must be called first");
+    if (const char* e = cost_indices_error(h, h->obs_dim)) return fail(ICEM_E_INVALID, e);
+    if (const char* e = wide_unsupported(h, 0, false, false)) return fail(ICEM_E_UNSUPPORTED, e);
+    return ICEM_OK;
+}
+
+// the selection's partials + ticket of a pool of more than one slice: allocated and zeroed once per handle (ordered on `st`
+// before the step's launches); every selection launch leaves the ticket at zero
+int reserve_ws(icem_handle* h, hipStream_t st) {
+    if (random_select_blocks(h->cfg.num_traj) <= 1 || h->random_ws.dev) return ICEM_OK;
+    const size_t bytes = random_ws_bytes(h->cfg.num_traj);
+    void* p = nullptr;
+    ICEM_HIP_TRY(hipMalloc(&p, bytes));
+    if (hipError_t e = hipMemsetAsync(p, 0, bytes, st)) {
+        (void)hipFree(p);
+        ICEM_HIP_TRY(e);
+    }
+    h->random_ws.dev = p, h->random_ws.bytes = bytes;
+    return ICEM_OK;
+}
+
+// the argument blocks' room on the host stack (no padding in either; k_random.hip)
+struct alignas(8) Block {
+    unsigned char bytes[RANDOM_BLOCK_MAX];
+};
+
+// one planner's step behind its refusals.  *launches_out: written on success
+int random_step_solo(icem_handle* h, const icem_random_buffers* b, int32_t change_freq, int64_t call_offset, int64_t first_block, const void* u,
+                     void* result_row, hipStream_t st, long long* launches_out) {
+    if (int rc = reserve_ws(h, st)) return rc;
+    Block blk;
+    std::memset(&blk, 0, sizeof(blk));
+    random_sample_block(h, *b, change_freq, call_offset, first_block, u, &blk);
+    launch_random_sample(h, &blk, st);
+    ICEM_HIP_TRY(hipGetLastError());
+    if (int rc = rollout_cost_launch(h, h->cfg.num_traj, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st})) return rc;
+    std::memset(&blk, 0, sizeof(blk));
+    random_select_block(h, *b, result_row, &blk);
+    launch_random_select(h, &blk, st);
+    ICEM_HIP_TRY(hipGetLastError());
+    *launches_out = 3;
+    return ICEM_OK;
+}
+
+size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// B > 1 planners behind the admission of the batch.  Host state: the first handle's argument array (+ its upload counter) and its
+// random_batch_launches, written behind the last launch; each handle's RandomWs (allocated once, whatever happens later).
+// Recording a handle's rollout may upload that handle's packed model (idempotent, what its next solo step would do first).
+int random_step_batch(icem_handle* const* handles, int n, const icem_random_buffers* buffers, int32_t change_freq, const int64_t* offsets,
+                      void* results, hipStream_t st) {
+    const std::string who = "icem_plan_step_random_batch: ";
+    icem_handle* h0 = handles[0];
+    const icem_config& c = h0->cfg;
+    const int N = c.num_traj, d = c.act_dim;
+    // ---- every problem's rollout launch, recorded: its batched family, its key, its argument block ----
+    BatchHint hint;
+    hint.mult = n;
+    std::vector<LaunchRecorder> recs(n);
+    for (int i = 0; i < n; ++i) {
+        recs[i].who = "icem_plan_step_random_batch: ";
+        const icem_random_buffers& b = buffers[i];
+        if (int rc = rollout_cost_launch(handles[i], N, b.obs0, b.actions, b.costs, nullptr, LaunchCtx{st, hint, &recs[i]})) return rc;
+        if (recs[i].unsupported) return fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached (this handle's rollout kernel has no batched twin)");
+    }
+    const std::vector<LaunchDesc>& first = recs[0].launches;
+    const size_t L = first.size();
+    for (int i = 0; i < n; ++i) {
+        if (recs[i].launches.size() != L || L == 0) return fail(ICEM_E_STATE, who + "the problems' steps took different launches");
+        for (size_t l = 0; l < L; ++l)
+            if (!(recs[i].launches[l].key == first[l].key)) return fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
+    }
+    for (size_t l = 0; l < L; ++l)
+        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
+    for (int i = 0; i < n; ++i)
+        if (int rc = reserve_ws(handles[i], st)) return rc;
+    // ---- argument blocks: [sample x n | rollout launch(es) x n | select x n] ----
+    const size_t sb = random_sample_block_bytes(h0), ub = random_select_block_bytes(h0);
+    std::vector<size_t> at(L);
+    size_t total = padded(sb * n), room = padded(sb * ICEM_MAX_BATCH);
+    for (size_t l = 0; l < L; ++l) {
+        at[l] = total;
+        total += padded(launch_family(first[l].key.family)->block_bytes * n);
+        room += padded(launch_family(first[l].key.family)->block_bytes * ICEM_MAX_BATCH);
+    }
+    const size_t at_select = total;
+    total += padded(ub * n);
+    room += padded(ub * ICEM_MAX_BATCH);
+    std::vector<unsigned char> blob(total, 0);
+    BatchBases bases{};
+    for (int i = 0; i < n; ++i) {
+        const icem_random_buffers& b = buffers[i];
+        bases.v[i] = (unsigned long long)offsets[i];
+        random_sample_block(handles[i], b, change_freq, 0, 0, nullptr, blob.data() + sb * i);
+        for (size_t l = 0; l < L; ++l) {
+            const size_t one = launch_family(first[l].key.family)->block_bytes;
+            std::memcpy(blob.data() + at[l] + one * i, recs[i].launches[l].block, one);
+        }
+        void* row = results ? (unsigned char*)results + (size_t)i * (d + 2) * h0->tsize : nullptr;
+        random_select_block(handles[i], b, row, blob.data() + at_select + ub * i);
+    }
+    ICEM_HIP_TRY(h0->random_batch_args.put(0, blob, room, st, &h0->batch_uploads));
+    // ---- the launches ----
+    const unsigned char* dev = (const unsigned char*)h0->random_batch_args.dev(0);
+    long long launches = 0;
+    launch_random_sample_batch(h0, dev, bases, n, st);
+    ICEM_HIP_TRY(hipGetLastError());
+    ++launches;
+    const BatchBases none{};   // (a rollout draws nothing)
+    for (size_t l = 0; l < L; ++l) {
+        launch_family(first[l].key.family)->launch(first[l].key, dev + at[l], none, n, st);
+        ICEM_HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    launch_random_select_batch(h0, dev + at_select, n, st);
+    ICEM_HIP_TRY(hipGetLastError());
+    ++launches;
+    h0->random_batch_launches = launches;
+    return ICEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icem_plan_step_random_ok(const icem_handle* h) { return (h && random_unserved(h) == nullptr) ? 1 : 0; }
+
+int icem_plan_step_random(icem_handle* h, const icem_random_buffers* b, int32_t change_freq, int64_t call_offset, int64_t first_block,
+                          const void* u, void* stream) {
+    // ---- refusals: all of them before anything is launched or the handle touched ----
+    const std::string who = "icem_plan_step_random: ";
+    if (!h || !b) return fail(ICEM_E_INVALID, who + "null handle or buffers");
+    if (int rc = random_arg_refusal(*b, change_freq, call_offset, who)) return rc;
+    if (int rc = random_refusal(h, change_freq, who)) return rc;
+    return random_step_solo(h, b, change_freq, call_offset, first_block, u, nullptr, (hipStream_t)stream, &h->random_launches);
+}
+
+int icem_plan_step_random_batch(icem_handle* const* handles, int32_t n, const icem_random_buffers* buffers, int32_t change_freq,
+                                const int64_t* call_offsets_host, void* results, void* stream) {
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    const std::string who = "icem_plan_step_random_batch: ";
+    if (int rc = admit_batch(handles, n, buffers && call_offsets_host, true, who.c_str(),
+                             "icem_plan_step_random_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = random_arg_refusal(buffers[i], change_freq, call_offsets_host[i], who)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = random_refusal(handles[i], change_freq, who)) return rc;
+    if (n == 1)   // one planner: the solo launches (the same bits by construction) + the results row
+        return random_step_solo(handles[0], &buffers[0], change_freq, call_offsets_host[0], 0, nullptr, results, (hipStream_t)stream,
+                                &handles[0]->random_batch_launches);
+    return random_step_batch(handles, n, buffers, change_freq, call_offsets_host, results, (hipStream_t)stream);
+}
+
+int64_t icem_random_step_launches(const icem_handle* h) { return h ? (int64_t)h->random_launches : 0; }
+int64_t icem_random_batch_launches(const icem_handle* h) { return h ? (int64_t)h->random_batch_launches : 0; }
+
+}  // extern "C"

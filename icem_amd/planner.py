@@ -132,6 +132,7 @@ class IcemPlanner:
         self.obs_dim = o
         self._bufs = None
         self._cem = None
+        self._random = None
 
     def set_cost(self, ctrl_weight=0.1, lin_idx=8, lin_weight=-1.0, flip_idx=1, flip_penalty=10.0,
                  flip_thresh=float(np.pi / 2)):
@@ -690,6 +691,98 @@ class IcemPlanner:
     def cem_batch_launches(self) -> int:
         """Kernel launches of the last batched CEM step this planner led (``icem_cem_batch_launches``): 3 per iteration."""
         return int(self.lib.icem_cem_batch_launches(self._h))
+
+    # ------------------------------------------------------------------ the random-shooting baseline's step (MpcRandom)
+    def random_step_ok(self) -> bool:
+        """Does ``icem_plan_step_random`` serve THIS handle?  (One GPU, profiling and stamps off, option ``random_step`` on:
+        asked of the handle.)"""
+        return bool(self.lib.icem_plan_step_random_ok(self._h))
+
+    @property
+    def random_step_launches(self) -> int:
+        """Kernel launches of the last random-shooting step of this planner (``icem_random_step_launches``)."""
+        return int(self.lib.icem_random_step_launches(self._h))
+
+    @property
+    def random_batch_launches(self) -> int:
+        """Kernel launches of the last batched random-shooting step this planner led (``icem_random_batch_launches``)."""
+        return int(self.lib.icem_random_batch_launches(self._h))
+
+    def _random_buffers(self):
+        """The step's buffers, owned by the planner (a captured step replays into the same tensors): the pool and its
+        costs, the cheapest row, ``result`` = ``[executed | best cost | best index]`` (one device-to-host copy fetches all
+        three), the observation and the step's ``icem_random_buffers``."""
+        b = getattr(self, "_random", None)
+        if b is None:
+            if self.obs_dim == 0:
+                raise RuntimeError("set_model()/set_cost() must be called before planning")
+            new = lambda *shape: torch.zeros(shape, dtype=self.dt, device=self.device)  # noqa: E731
+            n = self.cfg.num_traj
+            b = self._random = dict(actions=new(n, self.h, self.d), costs=new(n), best_actions=new(self.h, self.d),
+                                    result=new(self.d + 2), obs0=new(self.obs_dim))
+            b["cb"] = L.IcemRandomBuffersC(
+                low=self.low.data_ptr(), high=self.high.data_ptr(), obs0=b["obs0"].data_ptr(), actions=b["actions"].data_ptr(),
+                costs=b["costs"].data_ptr(), best_actions=b["best_actions"].data_ptr(), result=b["result"].data_ptr())
+        return b
+
+    def _random_cb(self, obs) -> "L.IcemRandomBuffersC":
+        """The observation into the planner's own buffer; the step's ``icem_random_buffers``."""
+        b = self._random_buffers()
+        dst = b["obs0"]
+        if isinstance(obs, torch.Tensor) and obs.device == self.device:
+            if obs.numel() != dst.numel():
+                raise ValueError(f"expected an observation of {dst.numel()} values")
+            dst.copy_(obs.reshape(-1))
+        else:
+            dst.copy_(torch.as_tensor(np.asarray(obs, dtype=np.float64).reshape(dst.numel()), dtype=dst.dtype))
+        return b["cb"]
+
+    random_actions = property(lambda self: self._random_buffers()["actions"])
+    random_costs = property(lambda self: self._random_buffers()["costs"])
+    random_best_actions = property(lambda self: self._random_buffers()["best_actions"])
+    random_result = property(lambda self: self._random_buffers()["result"])
+
+    def plan_step_random(self, obs, call_offset: int, change_freq: int, u=None, first_block: int = 0) -> torch.Tensor:
+        """One MPC step of random shooting (``MpcRandom.get_action``, icem/controllers/mpc.py:114-138) as
+        ``icem_plan_step_random``: :meth:`sample_piecewise` at ``call_offset`` (``MpcRandom``'s counter of ``sample()`` calls:
+        the caller's -- the planner keeps none), :meth:`rollout_cost`, ``topk_sorted(costs, 1)`` and the gathers, no host
+        synchronisation.  ``u``: the draws ``[*, d]`` of blocks ``first_block..`` (parity), or None for the device's Philox
+        streams.  Afterwards ``random_actions`` / ``random_costs`` hold the pool, ``random_best_actions`` its cheapest row,
+        ``random_result`` is ``[executed | best cost | best index]``.  Returns ``executed`` (device tensor, no host sync).
+        Raises ``IcemError`` before anything runs where the step is refused."""
+        cb = self._random_cb(obs)
+        u_t = None if u is None else self._t(u)
+        L.check(self.lib.icem_plan_step_random(self._h, C.byref(cb), int(change_freq), int(call_offset), int(first_block),
+                                               _ptr(u_t), self._stream()))
+        return self._random_buffers()["result"][:self.d]
+
+    @staticmethod
+    def plan_step_random_batch(planners: Sequence["IcemPlanner"], observations, call_offsets, change_freq: int) -> torch.Tensor:
+        """:meth:`plan_step_random` of every planner of ``planners`` (one configuration; models, costs, seeds, observations
+        and call offsets of their own) as ``icem_plan_step_random_batch``: the same three stages, each ONE launch for all of
+        them.  Each planner's ``random_*`` views afterwards are bit for bit those of its own :meth:`plan_step_random`.
+        Returns the executed actions ``[B, d]`` -- a view of the batch's results ``[B, d + 2]``
+        (``planners[0].random_batch_results``), the one tensor a caller copies to the host.  Raises ``IcemError`` before
+        anything runs where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_random_batch(None, 0, None, 0, None, None, None))
+        p0 = pls[0]
+        observations, call_offsets = list(observations), list(call_offsets)
+        if len(observations) != n or len(call_offsets) != n:
+            raise ValueError("one observation and one call offset per planner")
+        cbs = [pl._random_cb(ob) for pl, ob in zip(pls, observations)]
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemRandomBuffersC * n)(*cbs)
+        offs = (C.c_int64 * n)(*[int(o) for o in call_offsets])
+        res = getattr(p0, "_random_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
+        if res is None or res.shape[0] != n:
+            res = p0._random_batch_results = torch.zeros((n, p0.d + 2), dtype=p0.dt, device=p0.device)
+        L.check(p0.lib.icem_plan_step_random_batch(hs, n, bs, int(change_freq), offs, _ptr(res), p0._stream()))
+        return res[:, :p0.d]
+
+    random_batch_results = property(lambda self: getattr(self, "_random_batch_results", None))
 
     # ------------------------------------------------------------------ ... through the learned dynamics (declared RSSM)
     def cem_learned_step_ok(self) -> bool:

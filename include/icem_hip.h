@@ -321,6 +321,56 @@ int     icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n,
 int icem_sample_piecewise(icem_handle* h, int32_t n, int64_t call_offset, int32_t change_freq, int64_t first_block,
                           const void* low, const void* high, const void* u, void* actions, void* stream);
 
+/* MpcRandom.get_action (mpc.py:114-138) as ONE call: the chain a caller would otherwise drive operator by operator
+ * (icem_sample_piecewise, icem_rollout_cost, icem_topk_sorted(costs, 1) and the gathers behind it), with no host round trip:
+ *   - actions [N, h, d] <- icem_sample_piecewise(N = cfg.num_traj, call_offset, change_freq, first_block, low, high, u), drawn by
+ *     the step's own sampler: a workgroup draws every held (block, dimension) value its elements need ONCE into LDS and stores
+ *     its span of the pool from there -- the generator work of a launch falls by about change_freq + 1; the same bits;
+ *   - costs [N] <- the launch icem_rollout_cost picks for this handle (every model width, tile / wide / f64 arithmetic and
+ *     cost-term list the operator serves);
+ *   - ONE selection launch: best = the row of the smallest (cost, index) pair, NaN counted as +inf (np.argmin, mpc.py:122, as
+ *     icem_topk_sorted(costs, 1) gives it); best_actions = actions[best]; result = actions[best, 0, :] | the cost
+ *     icem_topk_sorted reports for that row | best -- the index stored as a value of the handle dtype (exact: f32 handles with
+ *     num_traj > 2^24 are refused).  One device-to-host copy of result fetches all a controller needs.
+ * 3 launches on the one-launch rollouts, no host synchronisation, no allocation after the first call.  call_offset is
+ * MpcRandom's counter of sample() calls (mpc.py:95-102) and is the caller's: the entry keeps no per-handle step state, so
+ * the operator chain and the entry may alternate.  u != NULL is icem_sample_piecewise's parity mode (the caller's uniforms
+ * for blocks first_block ..).
+ *   Served: world == 1, profiling and debug stamps off, rng_rounds 7 and 10, f32 and f64, whatever icem_rollout_cost serves
+ * for the handle; development option random_step = 0 switches both entries off.  ICEM_E_INVALID: a NULL argument or buffer,
+ * change_freq < 0 or >= horizon, a negative call_offset; ICEM_E_STATE: no model or cost set; ICEM_E_UNSUPPORTED: anything
+ * else.  Whatever is refused is refused before anything is launched or the handle touched. */
+typedef struct icem_random_buffers {      /* all device, handle dtype */
+    void *low, *high;                     /* [d]                                             */
+    void *obs0;                           /* [obs_dim]                                       */
+    void *actions, *costs;                /* [N,h,d], [N]: the step's pool (mpc.py:120-123)  */
+    void *best_actions;                   /* [h,d]: the cheapest row (mpc.py:129-131)        */
+    void *result;                         /* [d+2]: executed | best_cost | best index        */
+} icem_random_buffers;
+int     icem_plan_step_random_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
+int     icem_plan_step_random(icem_handle* h, const icem_random_buffers* b, int32_t change_freq, int64_t call_offset,
+                              int64_t first_block, const void* u, void* stream);
+int64_t icem_random_step_launches(const icem_handle* h);  /* kernel launches of the last such step of this handle; measurement */
+/* The same step for n planners of ONE configuration at once (the reference runs its baseline episodes side by side,
+ * icem/misc/rollout_utils.py:46-58, 129-152): the sampler, the rollout and the selection are each ONE launch for all of them
+ * (blockIdx.y = the problem, its argument block read from a device array of handles[0]).  Admission is
+ * icem_plan_step_cem_batch's: n in [1, 32], no NULL, no handle twice, everything but the seed equal, rollout launches equal in
+ * shape and each with a batched twin; models, costs, seeds, observations and call offsets (call_offsets_host[n]) are per problem;
+ * external uniforms are not offered.  The call offsets travel by value, not in the blocks: a batch whose buffers stay put
+ * uploads its blocks once (icem_batch_uploads of handles[0]).  results: NULL, or [n, d + 2] of the handle dtype -- row i is
+ * problem i's result.  Every output of problem i is bit for bit that of its solo step at the same seed and offset.  n == 1 is
+ * the solo step (+ the results row).  ICEM_E_STATE also where the problems' rollout launches differ.
+ *   Measured (EXPERIMENTS R16.1; HalfCheetah shape, change_freq 4, f32, MpcRandomHip.get_action): 0.05 ms at N = 512 and at
+ * N = 4096 against 0.10 ms for the operator chain in the same process and on the parent commit's library (2.0 x: the chain's three
+ * device-to-host reads and its allocations are gone; the kernels are about 5 + 9 + 5 us of it).  The step's sampler is NOT faster
+ * than the operator's at these sizes -- both sit at the floor of a launch: 3.6-5.0 against 3.1 us at N = 512, 5.4-5.8 against
+ * 5.5-5.6 us at N = 4096 over two traces -- and is at N = 65 536 (29.7 against 40.2 us; the step 0.09 against 0.14 ms).
+ * Batched, per step of the batch against B solo steps: B = 8 0.08 / 0.18 ms at N = 512, 0.10 / 0.19 ms at N = 4096 (1.9 x to 2.3 x),
+ * B = 16 2.2 x to 2.8 x. */
+int     icem_plan_step_random_batch(icem_handle* const* handles, int32_t n, const icem_random_buffers* buffers,
+                                    int32_t change_freq, const int64_t* call_offsets_host, void* results, void* stream);
+int64_t icem_random_batch_launches(const icem_handle* h); /* kernel launches of the last such batch this handle led as handles[0]; measurement */
+
 /* Raw white noise of the Philox path (for RNG known-answer tests): z_r, z_i [n, d, F]. */
 int icem_philox_normals(icem_handle* h, int32_t n, int64_t first_index, uint64_t offset,
                         void* z_r, void* z_i, void* stream);

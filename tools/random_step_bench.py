@@ -1,0 +1,177 @@
+"""ms per ``MpcRandomHip.get_action`` at the HalfCheetah shape (h = 30, d = 6, o = 17, ``action_change_frequency`` 4, f32),
+N in {512, 4096}: the fused step (``icem_plan_step_random``) against the operator chain (``fused_step=False``), same process, warm,
+in alternating blocks -- a host clock around BLOCK calls, each of which ends in its device-to-host copy; min / median / max over
+BLOCKS blocks.
+
+  python tools/random_step_bench.py [--sizes 512,4096]
+                                                 fused and chain, both sizes (+ the launch count and an equality check)
+  python tools/random_step_bench.py --stagewise  the operator chain alone.  It binds only what the library exports, so it also
+                                                 runs on a library from before the entry -- the parent commit's chain, same box:
+                                                     ICEM_HIP_LIB=<parent's libicem_hip.so> python tools/random_step_bench.py --stagewise
+  python tools/random_step_bench.py --trace      TRACE_STEPS steps of each variant and nothing else, for the kernels' own times --
+                                                 the step's sampler (random_sample_kernel) against the operator's
+                                                 (sample_piecewise_kernel), the selection launch against the operator's top-k -- in
+                                                 a run of its own:
+                                                     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o t -- \\
+                                                         python tools/random_step_bench.py --trace
+  python tools/random_step_bench.py --batch B [--dtype f32|f64] [--sizes 512,4096]
+                                                 B planners: blocks of batched steps (``icem_plan_step_random_batch``, each ending in
+                                                 the one device-to-host copy of its results) alternating with blocks of B solo
+                                                 ``icem_plan_step_random`` steps issued back to back (each block step ending in one
+                                                 synchronisation); B may be a list (2,4,8,16).
+"""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from icem_amd import _lib as L  # noqa: E402
+
+H, D, O_, FREQ, SIZES = 30, 6, 17, 4, (512, 4096)
+WARMUP, BLOCK, BLOCKS, TRACE_STEPS = 20, 200, 9, 50
+BATCH_BLOCK, BATCH_BLOCKS, BATCH_WARMUP = 30, 7, 10
+
+
+def bind_what_the_library_has():
+    """An older library lacks the newest entries: the operator chain needs none of them."""
+    have = C.CDLL(L.lib_path())
+    L.SYMBOLS[:] = [s for s in L.SYMBOLS if hasattr(have, s[0])]
+
+
+def controller(n, fused):
+    from icem_amd import DeviceSyntheticModel, MpcRandomHip, halfcheetah_env
+    c = MpcRandomHip(env=halfcheetah_env(O_), forward_model=DeviceSyntheticModel.make(O_, D, kind=0), horizon=H,
+                     num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=1, fused_step=fused,
+                     action_sampler_params=dict(action_change_frequency=FREQ))
+    c.beginning_of_rollout(observation=np.zeros(O_), state=None, mode="train")
+    return c
+
+
+def block_ms(c, obs, reps=BLOCK):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        c.get_action(obs, None)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def report(what, n, ms):
+    ms = sorted(ms)
+    print(f"  {what:<18s} N = {n:5d}: median {ms[len(ms) // 2]:7.4f} ms per get_action (min {ms[0]:.4f}, max {ms[-1]:.4f}; "
+          f"{len(ms)} blocks of {BLOCK})", flush=True)
+
+
+def _arg(flag, default):
+    return sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else default
+
+
+def batch_planners(n, B, dtype):
+    from icem_amd import DeviceSyntheticModel, IcemConfig, IcemPlanner, halfcheetah_env
+    env = halfcheetah_env(O_)
+    out = []
+    for i in range(B):
+        pl = IcemPlanner(IcemConfig(horizon=H, act_dim=D, num_traj=n, elites_size=2, opt_iters=1, cost_mode="sum", dtype=dtype, seed=1 + i),
+                         env.action_space.low, env.action_space.high)
+        m = DeviceSyntheticModel.make(O_, D, kind=0)
+        pl.set_model(m.kind, m.A, m.B)
+        pl.set_cost_spec(env.cost_spec)
+        out.append(pl)
+    return out
+
+
+def main_batch():
+    from icem_amd import IcemPlanner
+    Bs = [int(x) for x in _arg("--batch", "8").split(",")]
+    dtype = _arg("--dtype", "f32")
+    sizes = [int(x) for x in _arg("--sizes", ",".join(str(n) for n in SIZES)).split(",")]
+    lib = L.load_library()
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  h = {H}, d = {D}, o = {O_}, hold {FREQ}, {dtype}; "
+          f"warm-up {BATCH_WARMUP} steps; {BATCH_BLOCKS} blocks of {BATCH_BLOCK} steps per variant, alternating", flush=True)
+    for n in sizes:
+        for B in Bs:
+            both = {"batched": batch_planners(n, B, dtype), "solo": batch_planners(n, B, dtype)}
+            calls = {"batched": 0, "solo": 0}
+            obs = [torch.as_tensor(0.1 * np.random.RandomState(i).randn(O_), dtype=both["solo"][0].dt, device="cuda") for i in range(B)]
+
+            def step(kind):
+                ps, off = both[kind], calls[kind]
+                calls[kind] += n * H
+                if kind == "batched":
+                    IcemPlanner.plan_step_random_batch(ps, obs, [off] * B, FREQ)
+                    return ps[0].random_batch_results.cpu()   # the batch's one device-to-host copy
+                for p, ob in zip(ps, obs):
+                    p.plan_step_random(ob, off, FREQ)
+                torch.cuda.synchronize()
+                return None
+
+            def block(kind, reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    step(kind)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / reps * 1e3
+
+            for kind in both:
+                block(kind, BATCH_WARMUP)
+            same = all(torch.equal(a.random_result, b.random_result) and torch.equal(a.random_costs, b.random_costs)
+                       for a, b in zip(both["batched"], both["solo"]))
+            t = {k: [] for k in both}
+            for _ in range(BATCH_BLOCKS):
+                for kind in both:
+                    t[kind].append(block(kind, BATCH_BLOCK))
+            b, s = sorted(t["batched"]), sorted(t["solo"])
+            print(f"  {dtype} N = {n:5d} B = {B:2d}: batched median {b[len(b) // 2]:7.4f} ms per step of the batch (min {b[0]:.4f}, max {b[-1]:.4f}) | "
+                  f"{B} solo steps median {s[len(s) // 2]:7.4f} (min {s[0]:.4f}, max {s[-1]:.4f}) | solo median / batched median "
+                  f"{s[len(s) // 2] / b[len(b) // 2]:.2f}x | equal bits: {same}; launches per batched step "
+                  f"{both['batched'][0].random_batch_launches}, uploads {both['batched'][0].batch_uploads}", flush=True)
+
+
+def main():
+    stagewise_only, trace = "--stagewise" in sys.argv, "--trace" in sys.argv
+    if stagewise_only:
+        bind_what_the_library_has()
+    lib = L.load_library()
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  h = {H}, d = {D}, o = {O_}, hold {FREQ}, f32; "
+          f"warm-up {WARMUP} calls", flush=True)
+    obs = 0.1 * np.random.RandomState(0).randn(O_)
+    for n in [int(x) for x in _arg("--sizes", ",".join(str(n) for n in SIZES)).split(",")]:
+        # (a library without the entry: False never asks the library for it)
+        ctrls = {"operator chain": controller(n, False)}
+        if not stagewise_only:
+            ctrls = {"fused step": controller(n, True), **ctrls}
+        for c in ctrls.values():
+            for _ in range(WARMUP):
+                c.get_action(obs, None)
+        if trace:
+            for c in ctrls.values():
+                block_ms(c, obs, TRACE_STEPS)
+            continue
+        if not stagewise_only:   # the same seed, the same steps so far: the two controllers agree bit for bit
+            a, b = ctrls["fused step"], ctrls["operator chain"]
+            same = (np.array_equal(a.get_action(obs, None), b.get_action(obs, None)) and a.best_traj_idx == b.best_traj_idx
+                    and torch.equal(a._last_costs, b._last_costs))
+            print(f"  N = {n}: fused == chain: {same}; launches per fused step: {a.planner.random_step_launches}", flush=True)
+        t = {k: [] for k in ctrls}
+        for _ in range(BLOCKS):
+            for k, c in ctrls.items():
+                t[k].append(block_ms(c, obs))
+        for k in ctrls:
+            report(k, n, t[k])
+        if not stagewise_only:
+            f, s = (sorted(t[k])[BLOCKS // 2] for k in ("fused step", "operator chain"))
+            print(f"  chain / fused at N = {n}: {s / f:.2f}x", flush=True)
+
+
+if __name__ == "__main__":
+    if not torch.cuda.is_available():
+        sys.exit("no GPU: this tool measures and has nothing to say without one")
+    if "--batch" in sys.argv:
+        main_batch()
+    else:
+        main()
