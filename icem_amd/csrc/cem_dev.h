@@ -19,15 +19,21 @@ __device__ __forceinline__ T word_uniform(uint32_t x) {
     return ((T)x + (T)0.5) * (T)2.3283064365386963e-10;
 }
 
-// ppf(uu; lo_z, hi_z) of the truncated standard normal (scipy.stats.truncnorm.rvs, mpc.py:188-198) from pa = Phi(lo_z) and
-// pd = Phi(hi_z) - Phi(lo_z).  The quantile lies in [lo_z, hi_z] by definition; in f32 a uniform that rounds to 1 or an
-// interval deep in one tail (pd == 0) would otherwise come back as +-inf
+// ppf(uu; lo_z, hi_z) of the truncated standard normal (scipy.stats.truncnorm.rvs, mpc.py:188-198) from pa = Phi(lo_z),
+// qb = Phi(-hi_z) = 1 - Phi(hi_z) and pd = Phi(hi_z) - Phi(lo_z), two-sided: the probability below the quantile is
+// p = pa + uu pd and the one above it q = qb + (1 - uu) pd; the smaller of the two, which the number format resolves to
+// RELATIVE precision, is the one inverted (p + q = 1: p <= q is the lower half).  Through p alone the upper tail is resolved
+// to 2^-24 of 1 only -- in f32 a uniform within 2^-24 of 1 at lo_z = 0 came back as hi_z, 5 sigma and more off.
+// The quantile lies in [lo_z, hi_z] by definition, and ppf(1) = hi_z; an interval deep in one tail (pd == 0) or hi_z beyond
+// the format's Phi(-hi_z) would otherwise come back as +-inf.  (mean inside the action box: lo_z <= 0 <= hi_z.)
 template <typename T>
-__device__ __forceinline__ T truncnorm_quantile(T uu, T pa, T pd, T lo_z, T hi_z) {
-    T z = std_normal_icdf(fmad(uu, pd, pa));
+__device__ __forceinline__ T truncnorm_quantile(T uu, T pa, T qb, T pd, T lo_z, T hi_z) {
+    const T p = fmad(uu, pd, pa), q = fmad((T)1 - uu, pd, qb);
+    T z = std_normal_icdf(p <= q ? p : q);   // one inverse for both halves
+    z = p <= q ? z : -z;
     z = z < lo_z ? lo_z : z;
     z = z > hi_z ? hi_z : z;
-    return z;
+    return uu < (T)1 ? z : hi_z;
 }
 
 // MpcCemStd._update_bounds (mpc.py:290-301) of element e = (t, j): in place on std (like_levine) and into lower / upper

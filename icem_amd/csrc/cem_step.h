@@ -19,7 +19,7 @@ struct CemSampleArgs {
     T* out;
 };
 
-// the step's sampler serves this handle's shape (its LDS holds the two probability tables and at least one row); where it does
+// the step's sampler serves this handle's shape (its LDS holds the three probability tables and at least one row); where it does
 // not, the step launches the operator's kernel
 bool cem_sample_ok(const icem_handle* h);
 int launch_cem_sample(const icem_handle* h, int n, const void* mean, const void* std, const void* lower, const void* upper,

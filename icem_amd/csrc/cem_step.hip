@@ -123,7 +123,7 @@ const char* cem_learned_unserved(const icem_handle* h) {
     if (c.dtype != ICEM_F32) return "the learned-dynamics rollout is f32 only";
     if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
     if (const char* why = cem_unserved(h)) return why;
-    if (!cem_sample_ok(h)) return "a row of this shape does not fit the step's sampler (its two probability tables and one row in LDS)";
+    if (!cem_sample_ok(h)) return "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS)";
     if (!rssm_split_ok(c.num_traj, c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
     return nullptr;
 }
@@ -184,7 +184,7 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
     const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd, d = c.act_dim;
     const bool f64 = c.dtype == ICEM_F64;
     if (!cem_sample_ok(h0))
-        return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its two probability tables and one row in LDS): "
+        return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS): "
                                               "the operator's sampler has no batched form");
     // ---- every problem's rollout launch, recorded: its batched family, its key, its argument block ----
     BatchHint hint;

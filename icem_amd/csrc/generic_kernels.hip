@@ -149,7 +149,8 @@ __global__ __launch_bounds__(WG) void shift_sample_batch_kernel(const ShiftSampl
 // ---------------------------------------------------------------------------------------------
 // (the quantile and _update_bounds of one element: cem_dev.h, shared with the kernels of icem_plan_step_cem)
 // actions[i, t, j] = mean[t, j] + std[t, j] * ppf(u; lower[t, j], upper[t, j]) with the truncated standard normal's
-// inverse CDF ppf(u; a, b) = Phi^-1(Phi(a) + u (Phi(b) - Phi(a)))  (scipy.stats.truncnorm.rvs, mpc.py:188-198).
+// inverse CDF ppf(u; a, b) = Phi^-1(Phi(a) + u (Phi(b) - Phi(a)))  (scipy.stats.truncnorm.rvs, mpc.py:188-198), its upper
+// half taken through the complement (cem_dev.h::truncnorm_quantile).
 // u: the caller's uniforms [n, h, d] (parity: scipy draws exactly that array), or, if null, word t of row (i, j)'s
 // Philox / xoshiro stream mapped to (x + 0.5) * 2^-32.  One thread per (trajectory, dim) row.
 template <typename T, int ROUNDS>
@@ -165,8 +166,8 @@ __global__ __launch_bounds__(WG) void sample_truncnorm_kernel(int n, int h, int 
         const size_t e = ((size_t)i * h + t) * d + j;
         const uint32_t x = rng.next();
         const T uu = u ? u[e] : word_uniform<T>(x);
-        const T pa = std_normal_cdf(lower[t * d + j]), pb = std_normal_cdf(upper[t * d + j]);
-        const T z = truncnorm_quantile<T>(uu, pa, pb - pa, lower[t * d + j], upper[t * d + j]);
+        const T pa = std_normal_cdf(lower[t * d + j]), pb = std_normal_cdf(upper[t * d + j]), qb = std_normal_cdf(-upper[t * d + j]);
+        const T z = truncnorm_quantile<T>(uu, pa, qb, pb - pa, lower[t * d + j], upper[t * d + j]);
         out[e] = fmad(z, std[t * d + j], mean[t * d + j]);
     }
 }

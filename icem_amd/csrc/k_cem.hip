@@ -1,9 +1,9 @@
 // k_cem.hip -- the kernels of icem_plan_step_cem and icem_plan_step_cem_batch (cem_step.hip), the CEM baseline's MPC step
 // (MpcCemStd.get_action, icem/controllers/mpc.py:200-262) as a chain of launches, for one planner or for B (the *_batch_kernel
 // twins: the same bodies, blockIdx.y / blockIdx.x = the problem, the argument blocks in a device array):
-//   cem_sample_kernel      icem_sample_truncnorm's draw (mpc.py:188-198) with the two probability tables Phi(lower) and
-//                          Phi(upper) - Phi(lower) -- functions of (t, j) alone -- computed once per workgroup into LDS, and a
-//                          workgroup's rows staged in LDS and stored as one contiguous span
+//   cem_sample_kernel      icem_sample_truncnorm's draw (mpc.py:188-198) with the three probability tables Phi(lower),
+//                          Phi(-upper) and Phi(upper) - Phi(lower) -- functions of (t, j) alone -- computed once per workgroup
+//                          into LDS, and a workgroup's rows staged in LDS and stored as one contiguous span
 //   cem_update_*_kernel    one workgroup: selection + gather + refit (mpc.py:270-281) by the body of the operator's kernel --
 //                          update_small_kernel's in f32, select_refit_kernel's in f64 --, then _update_bounds (mpc.py:290-301)
 //                          and, behind the last iteration, get_action's epilogue (mpc.py:230-245): cem_dev.h::cem_tail
@@ -19,7 +19,7 @@ namespace icem {
 namespace {
 
 // One thread per (trajectory, dim) row, as sample_truncnorm_kernel: word t of the row's stream is the uniform of step t.
-// LDS: pa [h, d] | pd [h, d] | tile [tpw, h, d].
+// LDS: pa [h, d] | qb [h, d] | pd [h, d] | tile [tpw, h, d].
 // (the body of cem_sample_kernel and of cem_sample_batch_kernel: one device function, the same device code)
 template <typename T, int ROUNDS>
 __device__ __forceinline__ void cem_sample_body(const CemSampleArgs<T>& a) {
@@ -27,11 +27,13 @@ __device__ __forceinline__ void cem_sample_body(const CemSampleArgs<T>& a) {
     const int tid = threadIdx.x;
     const int hd = a.h * a.d;
     T* pa = reinterpret_cast<T*>(smem_raw);
-    T* pd = pa + hd;
+    T* qb = pa + hd;
+    T* pd = qb + hd;
     T* tile = pd + hd;
     for (int e = tid; e < hd; e += WG) {
         const T p = std_normal_cdf(a.lower[e]), q = std_normal_cdf(a.upper[e]);
         pa[e] = p;
+        qb[e] = std_normal_cdf(-a.upper[e]);
         pd[e] = q - p;
     }
     __syncthreads();
@@ -44,7 +46,7 @@ __device__ __forceinline__ void cem_sample_body(const CemSampleArgs<T>& a) {
         for (int t = 0; t < a.h; ++t) {
             const int c = t * a.d + j;
             const uint32_t x = rng.next();
-            const T z = truncnorm_quantile<T>(word_uniform<T>(x), pa[c], pd[c], a.lower[c], a.upper[c]);
+            const T z = truncnorm_quantile<T>(word_uniform<T>(x), pa[c], qb[c], pd[c], a.lower[c], a.upper[c]);
             row[c] = fmad(z, a.std[c], a.mean[c]);
         }
     }
@@ -154,11 +156,11 @@ __global__ __launch_bounds__(SELECT_NT) void cem_update_f64_batch_kernel(const C
 
 constexpr size_t CEM_SAMPLE_LDS_MAX = 64 * 1024;
 
-// rows per workgroup: one thread per (row, dim), and the tile beside the two tables within the LDS bound (0: no room)
+// rows per workgroup: one thread per (row, dim), and the tile beside the three tables within the LDS bound (0: no room)
 int cem_sample_tpw(const icem_handle* h) {
     const size_t row = (size_t)h->hd * h->tsize;
-    if (row == 0 || 3 * row > CEM_SAMPLE_LDS_MAX) return 0;
-    return (int)std::min<size_t>((size_t)(WG / h->cfg.act_dim), CEM_SAMPLE_LDS_MAX / row - 2);
+    if (row == 0 || 4 * row > CEM_SAMPLE_LDS_MAX) return 0;
+    return (int)std::min<size_t>((size_t)(WG / h->cfg.act_dim), CEM_SAMPLE_LDS_MAX / row - 3);
 }
 
 }  // namespace
@@ -170,7 +172,7 @@ int launch_cem_sample(const icem_handle* h, int n, const void* mean, const void*
     const icem_config& c = h->cfg;
     const int tpw = cem_sample_tpw(h);
     const int grid = (n + tpw - 1) / tpw;
-    const size_t lds = (size_t)(2 + tpw) * h->hd * h->tsize;
+    const size_t lds = (size_t)(3 + tpw) * h->hd * h->tsize;
 #define ICEM_CS(T, R)                                                                                                       \
     do {                                                                                                                    \
         CemSampleArgs<T> a{n, c.horizon, c.act_dim, tpw, (const T*)mean, (const T*)std, (const T*)lower, (const T*)upper,    \
@@ -212,7 +214,7 @@ void launch_cem_sample_batch(const icem_handle* h, int n_rows, const void* args_
     const icem_config& c = h->cfg;
     const int tpw = cem_sample_tpw(h);
     const dim3 grid((n_rows + tpw - 1) / tpw, n_problems);
-    const size_t lds = (size_t)(2 + tpw) * h->hd * h->tsize;
+    const size_t lds = (size_t)(3 + tpw) * h->hd * h->tsize;
 #define ICEM_CSB(T, R) hipLaunchKernelGGL((cem_sample_batch_kernel<T, R>), grid, dim3(WG), lds, st, (const CemSampleArgs<T>*)args_dev, bases)
     if (c.dtype == ICEM_F64) {
         if (c.rng_rounds == 7) ICEM_CSB(double, 7); else ICEM_CSB(double, 10);
@@ -227,7 +229,7 @@ void launch_cem_sample_gather_batch(const icem_handle* h, int n_rows, const void
                                     int n_problems, hipStream_t st) {
     const int tpw = cem_sample_tpw(h);
     const dim3 grid((n_rows + tpw - 1) / tpw, n_problems);
-    const size_t lds = (size_t)(2 + tpw) * h->hd * h->tsize;
+    const size_t lds = (size_t)(3 + tpw) * h->hd * h->tsize;
     if (h->cfg.rng_rounds == 7)
         hipLaunchKernelGGL((cem_sample_gather_batch_kernel<float, 7>), grid, dim3(WG), lds, st, (const CemSampleArgs<float>*)args_dev, bases, og);
     else

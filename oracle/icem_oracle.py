@@ -1043,6 +1043,26 @@ def truncnorm_from_uniform(u: np.ndarray, lower, upper, mean: np.ndarray, std: n
     return truncnorm.ppf(u, lower, upper) * std[None] + mean[None]
 
 
+def truncnorm_quantile_f64(u, lower, upper) -> np.ndarray:
+    """The quantile ``z`` of the standard normal truncated to ``[lower, upper]`` at probability ``u``, two-sided in float64
+    (broadcasting): with ``pa = Phi(lower)``, ``qb = Phi(-upper)`` and the interval's mass ``pd``, the probability below
+    ``z`` is ``p = pa + u pd`` and the one above it ``q = qb + (1 - u) pd``; the lower half (``p <= q``) is
+    ``Phi^-1(p)``, the upper half ``-Phi^-1(q)`` -- each through the probability that float64 holds to relative precision.
+    Clamped to ``[lower, upper]``; ``u == 0`` is ``lower`` and ``u == 1`` is ``upper``.  The yardstick of the device's
+    sampler (tests/truncnorm_cases.py): :func:`truncnorm_from_uniform`'s ``scipy.stats.truncnorm.ppf`` is one-sided where
+    ``lower < 0 < upper`` and stays what it is, the reference project's own call."""
+    from scipy.special import ndtr, ndtri
+    u, lower, upper = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (u, lower, upper)))
+    pa, qb = ndtr(lower), ndtr(-upper)
+    # the mass as a difference of the two tails on the side where both are small
+    pd = np.where(lower > 0, ndtr(-lower) - qb, ndtr(upper) - pa)
+    p, q = pa + u * pd, qb + (1.0 - u) * pd
+    with np.errstate(divide="ignore"):   # (p or q == 0: -inf, clamped below)
+        z = np.where(p <= q, ndtri(np.minimum(p, 0.5)), -ndtri(np.minimum(q, 0.5)))
+    z = np.minimum(np.maximum(z, lower), upper)
+    return np.where(u >= 1.0, upper, np.where(u <= 0.0, lower, z))
+
+
 def cem_bounds(mean: np.ndarray, std: np.ndarray, low: np.ndarray, high: np.ndarray, like_levine: bool):
     """``MpcCemStd._update_bounds`` (mpc.py:290-301) -> (std, lower, upper); lower / upper broadcast to ``[h, d]``."""
     if like_levine:

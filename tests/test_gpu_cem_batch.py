@@ -264,7 +264,7 @@ REFUSALS = {
     "a NULL buffer": (lambda i, **kw: _tile(**kw), lambda g: dict(edit=_null_costs), "ICEM_E_INVALID"),
     "a negative step": (lambda i, **kw: _tile(**kw), lambda g: dict(steps=[0, -1]), "ICEM_E_INVALID"),
     "profiling on": (lambda i, **kw: _tile(**kw), lambda g: {}, "ICEM_E_UNSUPPORTED"),
-    # h * d = 3072 doubles: the sampler's two tables and one row would need 72 KB of LDS (cem_sample_ok false; the solo step draws
+    # h * d = 3072 doubles: the sampler's three tables and one row would need 96 KB of LDS (cem_sample_ok false; the solo step draws
     # with the operator's kernel, which has no batched twin)
     "a row that does not fit the sampler": (lambda i, **kw: planner("f64", 64, 64, 48, 8, 1, **kw), lambda g: {}, "ICEM_E_UNSUPPORTED"),
     # a rollout without a batched form: the float64 matrix-core rollout
