@@ -344,6 +344,16 @@ static void update_paths(icem_handle* h) {
     bool finite = true;
     h->tile_m_scale = lift(h->A_host, &finite);
     h->tile_b_scale = lift(h->B_host, &finite);
+    // the kernels multiply by the reciprocals instead of dividing by the scales (tile_scales.h): the same bits exactly where
+    // the reciprocal is exact -- a normal power of two with a normal reciprocal, which lift() returns for every model whose
+    // entries are below 1e30 (2^-93 .. 2^106).  Anything else (a model that is not finite, served by no fp16-plane kernel)
+    // carries the neutral scale.
+    if (!tile_scale_is_pow2(h->tile_m_scale) || !tile_scale_is_pow2(h->tile_b_scale)) {
+        finite = false;
+        h->tile_m_scale = h->tile_b_scale = 1.f;
+    }
+    h->tile_inv_m_scale = tile_scale_reciprocal(h->tile_m_scale);
+    h->tile_inv_b_scale = tile_scale_reciprocal(h->tile_b_scale);
     // ... and the planes are served only where the model cannot take a state out of fp16's range, whatever the actions: the
     // operands are x S with S max(|obs0|, action bound) in [16, 32), so a state may grow to 2^11 times that magnitude before
     // f16(x S) is infinite -- and an infinite operand is a NaN cost where the reference ranks a finite one (icem.py:147-159,

@@ -457,6 +457,7 @@ template <> struct VecOf<2> { using type = float2; };
 template <int H, int D, int O, int KIND>
 struct Tile16 {
     static constexpr bool LONE_STEP = false;   // (Tile16H's hand-ordered step for a lone wave: none here)
+    static constexpr bool SPLIT_SETUP = false;   // (... nor its set-up in separately placed pieces: load_obs() is all there is)
     // O <= 20: ONE 16-column output tile on the matrix pipe + up to 4 extra columns as permlane-reduced dot products;
     // 20 < O <= 28: TWO output tiles (columns 0..15 and 16..31, zero padded), no extra columns.
     static constexpr int NT = O > 20 ? 2 : 1;
@@ -717,15 +718,18 @@ struct Tile16H {
     f32x4 obs_init;
     float rem_init[REM > 0 ? REM : 1];
     int perm_base[4], perm_rem[REM > 0 ? REM : 1];
-    float pen, lin_w, ksum, flip_th, T, invT, invM, sM, sB, act_mag;
+    float pen, lin_w, ksum, flip_th, T, invT, invM, sM, sB, iM, iB, act_mag;   // (iM / iB: 1 / sM, 1 / sB, exact)
     bool ang_is_col1, use_min;
     int g;
+    static constexpr bool SPLIT_SETUP = true;   // read_obs / load_scales / scale_obs: a caller may place the set-up's pieces
 
     __device__ __forceinline__ void load(const FastRolloutArgs& a, int lane) {
         const int j = lane & 15;
         g = lane >> 4;
         sM = a.m_scale;
         sB = a.b_scale;
+        iM = a.inv_m_scale;
+        iB = a.inv_b_scale;
         float m[8];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -745,7 +749,7 @@ struct Tile16H {
                 for (int r = 0; r < REM; ++r) wR[r][4 + q] = a.Mp[k * CT4 + 16 + r];
                 is_act[q] = valid && e >= REM;
                 cw[q] = is_act[q] ? a.ctrl_w : 0.f;
-                sc[q] = valid ? (is_act[q] ? 0.f : 1.f / sM) : 0.f;   // (actions: set in load_obs)
+                sc[q] = valid ? (is_act[q] ? 0.f : iM) : 0.f;   // (actions: set in load_scales)
                 xoff[q] = valid ? 4 * q : REM - g;
             }
         }
@@ -764,48 +768,68 @@ struct Tile16H {
         act_mag = a.act_mag;
     }
 
-    // obs: 32 floats in LDS (natural order, zeros behind).  Also fixes the launch's power-of-two scale S.
-    __device__ __forceinline__ void load_obs(const float* obs) {
-        const int lane = (int)(threadIdx.x & 63);
-        float mx = __builtin_fabsf(obs[lane & 31]);
-        mx = mx != mx ? 0.f : mx;   // (a NaN observation poisons every cost anyway: keep S finite)
-        // max over the wave: non-negative floats order like their bit patterns
-        const unsigned mb = ~wave_min_u32(~__float_as_uint(mx));
-        float mm = __uint_as_float(mb);
-        mm = mm > act_mag ? mm : act_mag;
-        if (KIND == 1) mm = mm > 1.f ? mm : 1.f;
-        int ex = (int)((__float_as_uint(mm) >> 23) & 0xFF) - 127;   // 2^ex <= mm < 2^(ex+1); mm == 0 or subnormal: -127
-        ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
-        // (wave-uniform values: pinned to scalar registers -- this tile lives on the 128 registers a wave has at four per SIMD)
-        auto uni = [](float x) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
-        const float S = __uint_as_float((unsigned)(127 + 4 - ex) << 23);   // the B operand's scale: S x in [16, 32) at most
-        T = uni(S * sM);                                                    // the accumulators' (and the kept state's): S sM x
-        invT = uni(__uint_as_float((unsigned)(127 - 4 + ex) << 23) / sM);
-        invM = uni(1.f / sM);
-        flip_th = uni(flip_th);
-        ksum = uni(ksum);
+    // The set-up from the start observation (obs: 32 floats in LDS, natural order, zeros behind), in the three pieces a caller
+    // may place separately -- none of them needs anything but obs and what load() left:
+    //   read_obs     requests this lane's entries of obs through perm (LDS reads; nothing waits for them here);
+    //   load_scales  fixes the launch's power-of-two scale S: a wave-wide maximum, then the scalars of tile_scales.h and what
+    //                they scale (products only: the reciprocals of sM / sB come with the arguments);
+    //   scale_obs    the requested entries x T: the first step's state.
+    // load_obs() is the three in that order, the reads in flight across the scalar chain.
+    struct ObsRaw {
+        float v[4], r[REM > 0 ? REM : 1];
+    };
+    __device__ __forceinline__ void read_obs(const float* obs, ObsRaw& raw) const {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             int pb = perm_base[v];
             asm volatile("" : "+v"(pb));
-            obs_init[v] = obs[pb] * T;
+            raw.v[v] = obs[pb];
         }
 #pragma unroll
         for (int r = 0; r < REM; ++r) {
             int pb = perm_rem[r];
             asm volatile("" : "+v"(pb));
-            rem_init[r] = obs[pb] * T;
+            raw.r[r] = obs[pb];
         }
+    }
+    __device__ __forceinline__ void load_scales(const float* obs) {
+        const int lane = (int)(threadIdx.x & 63);
+        const float mx = tile_obs_magnitude(obs[lane & 31]);   // (a NaN observation poisons every cost anyway: keep S finite)
+        // max over the wave: non-negative floats order like their bit patterns
+        const unsigned mb = ~wave_min_u32(~__float_as_uint(mx));
+        const int ex = tile_scale_exponent(__uint_as_float(mb), act_mag, KIND == 1);
+        // (wave-uniform values: pinned to scalar registers -- this tile lives on the 128 registers a wave has at four per SIMD)
+        auto uni = [](float x) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
+        const TileScales s = tile_scales(ex, sM, iM, iB);
+        T = uni(s.T);
+        invT = uni(s.invT);
+        invM = uni(s.invM);
+        const float sact = uni(s.sact);
+        flip_th = uni(flip_th);
+        ksum = uni(ksum);
         flip_th *= T;
         lin_w *= invT;
 #pragma unroll
         for (int q = 0; q < NKX; ++q) {
             if (is_act[q]) {
-                sc[q] = T / sB;   // (B sB) x (a T / sB) = T B a: the action's contribution at the accumulators' scale
+                sc[q] = sact;   // (B sB) x (a T / sB) = T B a: the action's contribution at the accumulators' scale
 #pragma unroll
                 for (int r = 0; r < REM; ++r) wR[r][4 + q] *= T;
             }
         }
+    }
+    __device__ __forceinline__ void scale_obs(const ObsRaw& raw) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) obs_init[v] = raw.v[v] * T;
+#pragma unroll
+        for (int r = 0; r < REM; ++r) rem_init[r] = raw.r[r] * T;
+    }
+    __device__ __forceinline__ void load_obs(const float* obs) {
+        ObsRaw raw;
+        read_obs(obs, raw);
+        __builtin_amdgcn_sched_barrier(0);   // (the reads are requested in front of the scalar chain, not behind it)
+        load_scales(obs);
+        scale_obs(raw);
     }
 
     __device__ __forceinline__ const float* read_ptr(const float* buf, int lane, int stride) const {
@@ -1026,6 +1050,7 @@ __device__ __forceinline__ float reduce_quads(float x) {
 template <int H, int D, int O, int KIND>
 struct Tile4 {
     using T16 = Tile16<H, D, O, KIND>;
+    static constexpr bool SPLIT_SETUP = false;
     static_assert(T16::NT == 1, "one 16-column tile (O <= 20)");
     static constexpr int REM = T16::REM, NKX = T16::NKX, NX = T16::NX, CT4 = T16::CT4, OP = T16::OP, ZROW = T16::ZROW;
     static constexpr int NE = 4 * NKX;     // extra contraction entries incl. padding (columns >= 16, then the actions)

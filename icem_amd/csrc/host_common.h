@@ -168,6 +168,7 @@ struct icem_handle {
     void* hn_cs_dev = nullptr;
     bool hn_tile = false;        // the f32 rollout is k_rollout_hn.hip's TileHN kernel (Door / Relocate / FetchPickAndPlace shapes; fp16 planes)
     float tile_m_scale = 1.f, tile_b_scale = 1.f;   // FastRolloutArgs::m_scale / b_scale (update_paths)
+    float tile_inv_m_scale = 1.f, tile_inv_b_scale = 1.f;   // ... and inv_m_scale / inv_b_scale: their exact reciprocals
     float act_mag = 1.f;         // max(|low|, |high|) of the action bounds last seen (FastRolloutArgs::act_mag), from ...
     const void* am_lo = nullptr; // ... this (low, high) buffer pair (refreshed by icem_reset_distribution and the plan calls)
     const void* am_hi = nullptr;

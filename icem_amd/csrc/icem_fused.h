@@ -10,6 +10,7 @@
 #include <vector>
 #include "cost_args.h"
 #include "options.h"
+#include "tile_scales.h"
 
 namespace icem {
 
@@ -89,6 +90,7 @@ struct FastRolloutArgs {
     int arith = 0;
     float act_mag = 1.f;   // arith 1: magnitude of the action bounds, max(|low|, |high|) -- with |obs0| it fixes the launch's scale
     float m_scale = 1.f, b_scale = 1.f;   // arith 1: powers of two that put the largest |entry| of A / of B into [64, 128)
+    float inv_m_scale = 1.f, inv_b_scale = 1.f;   // ... and their reciprocals, exact (update_paths; tile_scales.h): the kernels multiply
     unsigned* nonfinite = nullptr;        // counts the trajectories whose cost came out NaN (icem_nonfinite_costs); never NULL in a launch
 };
 bool fast_rollout_supported(int h, int d, int O, int K);
@@ -505,6 +507,7 @@ inline void batch_form(const FastRolloutArgs& a, void* dst) {   // (member by me
     g.ctrl_w = a.ctrl_w, g.lin_w = a.lin_w, g.flip_pen = a.flip_pen, g.flip_th = a.flip_th, g.flip_col = a.flip_col;
     g.actions = a.actions, g.costs = a.costs, g.part_c = a.part_c, g.part_i = a.part_i, g.part_k = a.part_k;
     g.list_wgs = a.list_wgs, g.dbg = nullptr, g.arith = a.arith, g.act_mag = a.act_mag, g.m_scale = a.m_scale, g.b_scale = a.b_scale;
+    g.inv_m_scale = a.inv_m_scale, g.inv_b_scale = a.inv_b_scale;
     g.nonfinite = a.nonfinite;
 }
 inline void batch_form(const HnArgs& a, void* dst) {

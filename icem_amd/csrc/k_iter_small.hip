@@ -47,6 +47,17 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
     using T16 = typename TileSel<H, D, O, KIND, ARITH>::type;
     using Tile = typename std::conditional<T4, Tile4<H, D, (O <= 20 ? O : 17), KIND>, T16>::type;
     constexpr int RWV = T4 ? 4 * RW : RW;            // rollout wavefronts
+    // HOIST (merge-prologue launches with ONE rollout wave on the fp16-plane tile: the metric's shape): the rollout wave's set-up
+    // from the start observation -- the wave-wide maximum, the launch scalars, the state's first entries (Tile16H::load_obs) --
+    // needs neither the refit nor the map, which is what the chain waits for behind the prologue's barriers.  Wave 0 is one of
+    // the older sampling waves: it is through its draws 0.5-0.75 us before the selection wave releases the first barrier
+    // (EXPERIMENTS R13.1), and the 32 lanes that stage the observation are its own.  So the observation is requested at the
+    // kernel's entry, staged by wave 0 behind its draws, and wave 0 runs the set-up right there, in that slack; behind the
+    // barrier that publishes the mapped tile it starts the first model step.  Same operations on the same operands: the same
+    // bits.  (The other placement -- between issuing the elite gather's loads and waiting for them, any RW -- was built and
+    // measured too: it lengthens gather + refit by 0.2 us and gains 0.5 us less per step, EXPERIMENTS R18.1.  With RW > 1 the
+    // other rollout waves would need a barrier between the staging and the set-up: they keep it in place.)
+    constexpr bool HOIST = PM && !T4 && RW == 1 && Tile::SPLIT_SETUP;
     constexpr int HD = H * D;
     constexpr int TPB = 16 * RW;                     // trajectories per workgroup
     constexpr int ROWS = TPB * D;                    // (trajectory, dim) rows: one thread (QS: one quad) each
@@ -114,7 +125,7 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
     // waves of the first and of the last workgroup of a merge-prologue launch run, and how the selection wave's time into the
     // first barrier splits.  Per workgroup 24 words behind the 16 stamps: [0..6] HW_ID of wave w (SIMD_ID = bits 5:4),
     // [8] the workgroup's first stamp, [9] selection wave's first instruction, [10] its keys loaded, [11] selected,
-    // [12 + w] wave w at the first barrier, [19] wave 0 behind it.
+    // [12 + w] wave w at the first barrier, [19] wave 0 behind it, [20] wave 0 in front of its first model step.
     const int cen_wg = wg == 0 ? 0 : (base + TPB >= n_rows ? 1 : -1);
     long long* const cen = (PM && !REC && ra.dbg && cen_wg >= 0) ? ra.dbg + 16 + 24 * cen_wg : nullptr;
     if (cen && lane == 0) cen[wave] = (long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID, all 32 bits
@@ -155,6 +166,7 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
         lo_reg = sa.low[jd];
         hi_reg = sa.high[jd];
     }
+    if constexpr (HOIST) obs_reg = ra.obs0[(tid < 32 && tid < ra.o) ? tid : 0];   // (one register parked across the draws)
     // drawn-ahead iteration 0: the slab's raw rows (sampled rows, then the shifted elites' rows of stream off2) are one
     // contiguous block, NVR vectors of it per thread (more than 4: the first 4 ride the entry's wait, the rest follow in rounds)
     constexpr int NVR = !PM ? (TPB * (HD / VW) + NTT - 1) / NTT : 1;
@@ -286,8 +298,21 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
         if (!REC && cen && lane == 0) cen[12 + wave] = wall_clock64();
     }
     if (PM) {  // now the rest of the inputs: in flight across the barriers below
-        obs_reg = ra.obs0[(tid < 32 && tid < ra.o) ? tid : 0];
+        // (HOIST: requested at the entry, long here)
+        if constexpr (HOIST) {
+            if (tid < 32) obs_stage[tid] = tid < ra.o ? obs_reg : 0.f;
+        } else {
+            obs_reg = ra.obs0[(tid < 32 && tid < ra.o) ? tid : 0];
+        }
         if (wave < RWV) tile.load(ra, lane);
+        if constexpr (HOIST) {
+            if (wave == 0) {   // the wave that staged the observation is the one that reads it: its LDS operations execute in order
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                tile.load_obs(obs_stage);
+            }
+        }
     }
     const float* rd0 = nullptr;
     if constexpr (!T4) rd0 = tile.read_ptr(tilebuf + (wave < RW ? wave : 0) * 16 * HD, lane, HD);
@@ -335,10 +360,12 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             }
         }
     }
-    if (tid < 32) {  // start observation -> LDS (consumed after the barrier)
-        float ov = obs_reg;
-        asm volatile("" : "+v"(ov));  // wait for the load here, not where it was issued
-        obs_stage[tid] = tid < ra.o ? ov : 0.f;
+    if constexpr (!HOIST) {
+        if (tid < 32) {  // start observation -> LDS (consumed after the barrier)
+            float ov = obs_reg;
+            asm volatile("" : "+v"(ov));  // wait for the load here, not where it was issued
+            obs_stage[tid] = tid < ra.o ? ov : 0.f;
+        }
     }
     if (ra.dbg && tid == 0 && wg == 0) ra.dbg[10] = wall_clock64();
     __syncthreads();
@@ -423,7 +450,8 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
         }
     } else {
         if (wave < RW) {
-            tile.load_obs(obs_stage);
+            if constexpr (!HOIST) tile.load_obs(obs_stage);
+            if (cen && tid == 0) cen[20] = wall_clock64();   // (census builds: set-up done, the first model step follows)
             run_key = rollout_slab<Tile, H, D, true>(tile, ra, rd0, base + wave * 16 + (lane & 15), n_rows, run_key, true, lane);
             if (ra.dbg && tid == 0 && wg == 0) ra.dbg[12] = wall_clock64();
         }

@@ -66,7 +66,7 @@ struct TileHN {
     float pen_g, lin_g, ksum;                // icem_cost_spec's flip penalty / linear weight in lane group 0, 0 elsewhere; 1 (sum) / 0 (final)
     int flip_i;
     int g, cost_mode;
-    float sM, sB, act_mag;
+    float sM, sB, iM, iB, act_mag;   // (iM / iB: 1 / sM, 1 / sB, exact)
 
     // A [o, lda] row-major (x' = x A + a B), B [d, ldb]
     // with_model = false: a wave that only evaluates costs (rollout_hn_pair_kernel) leaves the model's planes alone
@@ -76,6 +76,8 @@ struct TileHN {
         g = lane >> 4;
         sM = a.m_scale;
         sB = a.b_scale;
+        iM = a.inv_m_scale;
+        iB = a.inv_b_scale;
 #pragma unroll
         for (int c = 0; c < NT; ++c) {
             if (!with_model) break;
@@ -115,19 +117,14 @@ struct TileHN {
     // obs: OP floats in LDS (natural order, zeros behind entry o - 1); rows: this wave's [16][RS] observation rows
     __device__ __forceinline__ void load_obs(const float* obs, float* rows) {
         const int lane = (int)(threadIdx.x & 63);
-        float mx = lane < OP ? __builtin_fabsf(obs[lane < OP ? lane : 0]) : 0.f;
-        mx = mx != mx ? 0.f : mx;
-        float mm = __uint_as_float(~wave_min_u32(~__float_as_uint(mx)));
-        mm = mm > act_mag ? mm : act_mag;
-        if (KIND == 1) mm = mm > 1.f ? mm : 1.f;
-        int ex = (int)((__float_as_uint(mm) >> 23) & 0xFF) - 127;
-        ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
+        const float mx = lane < OP ? tile_obs_magnitude(obs[lane < OP ? lane : 0]) : 0.f;
+        const int ex = tile_scale_exponent(__uint_as_float(~wave_min_u32(~__float_as_uint(mx))), act_mag, KIND == 1);
         auto uni = [](float x) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
-        const float S = __uint_as_float((unsigned)(127 + 4 - ex) << 23);
-        T = uni(S * sM);
-        invT = uni(__uint_as_float((unsigned)(127 - 4 + ex) << 23) / sM);
-        invM = uni(1.f / sM);
-        sact = uni(T / sB);
+        const TileScales ts = tile_scales(ex, sM, iM, iB);   // (products: the scales' exact reciprocals come with the arguments)
+        T = uni(ts.T);
+        invT = uni(ts.invT);
+        invM = uni(ts.invM);
+        sact = uni(ts.sact);
 #pragma unroll
         for (int c = 0; c < NT; ++c)
 #pragma unroll
@@ -504,7 +501,7 @@ struct TileHNc {
     f32x4 obs_init;
     float T, invT, invM, sact, part_w;
     int part_off, c, g;
-    float sM, sB, act_mag;
+    float sM, sB, iM, iB, act_mag;   // (iM / iB: 1 / sM, 1 / sB, exact)
     float* row;
 
     __device__ __forceinline__ void load(const FastRolloutArgs& a, const float* A, int lda, const float* B, int ldb, int o, int lane, int tile_c) {
@@ -513,6 +510,8 @@ struct TileHNc {
         c = tile_c;
         sM = a.m_scale;
         sB = a.b_scale;
+        iM = a.inv_m_scale;
+        iB = a.inv_b_scale;
         const int i = 16 * c + j;   // output column
 #pragma unroll
         for (int kb = 0; kb < NT; ++kb) {
@@ -536,19 +535,14 @@ struct TileHNc {
     }
     __device__ __forceinline__ void load_obs(const float* obs, float* rows) {
         const int lane = (int)(threadIdx.x & 63);
-        float mx = lane < OP ? __builtin_fabsf(obs[lane < OP ? lane : 0]) : 0.f;
-        mx = mx != mx ? 0.f : mx;
-        float mm = __uint_as_float(~wave_min_u32(~__float_as_uint(mx)));
-        mm = mm > act_mag ? mm : act_mag;
-        if (KIND == 1) mm = mm > 1.f ? mm : 1.f;
-        int ex = (int)((__float_as_uint(mm) >> 23) & 0xFF) - 127;
-        ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
+        const float mx = lane < OP ? tile_obs_magnitude(obs[lane < OP ? lane : 0]) : 0.f;
+        const int ex = tile_scale_exponent(__uint_as_float(~wave_min_u32(~__float_as_uint(mx))), act_mag, KIND == 1);
         auto uni = [](float x) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
-        const float S = __uint_as_float((unsigned)(127 + 4 - ex) << 23);
-        T = uni(S * sM);
-        invT = uni(__uint_as_float((unsigned)(127 - 4 + ex) << 23) / sM);
-        invM = uni(1.f / sM);
-        sact = uni(T / sB);
+        const TileScales ts = tile_scales(ex, sM, iM, iB);   // (products: the scales' exact reciprocals come with the arguments)
+        T = uni(ts.T);
+        invT = uni(ts.invT);
+        invM = uni(ts.invM);
+        sact = uni(ts.sact);
 #pragma unroll
         for (int s = 0; s < 4; ++s) obs_init[s] = obs[16 * c + 4 * g + s] * T;
         row = rows + (lane & 15) * RS;

@@ -178,6 +178,8 @@ FastRolloutArgs fast_rollout_args(const icem_handle* h, int n_rows, int n_cand, 
     a.act_mag = h->act_mag;
     a.m_scale = h->tile_m_scale;
     a.b_scale = h->tile_b_scale;
+    a.inv_m_scale = h->tile_inv_m_scale;
+    a.inv_b_scale = h->tile_inv_b_scale;
     a.nonfinite = h->nonfinite_dev;
     return a;
 }

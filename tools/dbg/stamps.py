@@ -2,7 +2,9 @@
 
 ``--census`` (a library built with ``-DICEM_WAVE_CENSUS``: ``ICEM_WAVE_CENSUS=1 python -m icem_amd.build``; a product library
 leaves the words zero): where the waves of the first and the last workgroup of the last merge-prologue launch ran (HW_ID:
-SIMD, CU, SE) and how the selection wave's time into the prologue's first barrier splits -- words [16..63] of the buffer."""
+SIMD, CU, SE), how the selection wave's time into the prologue's first barrier splits, and where between "mapped" (stamp 10)
+and "rolled out" (stamp 12) wave 0 starts its first model step (the set-up from the start observation lies in front of it:
+hoisted ahead of the barriers for the fp16-plane tile, tile_scales.h) -- words [16..63] of the buffer."""
 import sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from icem_amd import IcemConfig, IcemPlanner, DeviceSyntheticModel, halfcheetah_env
@@ -31,6 +33,7 @@ pro = np.zeros(2)
 gap = 0.0
 R = 20
 cen_t = np.zeros((2, 11))     # per census workgroup: first instruction, keys loaded, selected, waves 0..6 at the barrier, met
+first_step = np.zeros(4)      # workgroup 0 of the last merge-prologue launch: mapped, behind the barrier, first model step, rolled out
 placements = [dict(), dict()]  # (SIMD of wave 0..6) -> number of steps it was seen in
 where = [None, None]
 for _ in range(R):
@@ -47,6 +50,8 @@ for _ in range(R):
             placements[g][simd] = placements[g].get(simd, 0) + 1
             where[g] = sorted({((v >> 13) & 7, (v >> 8) & 15) for v in ids})   # (SE, CU)
             cen_t[g] += (np.concatenate([c[9:12], c[12:19], c[19:20]]) - c[8]) / 100.0 / R
+            if g == 0 and c[20] != 0:   # (word 20: wave 0 of workgroup 0 in front of its first model step)
+                first_step += np.array([d[10] - d[8], d[11] - d[8], c[20] - d[8], d[12] - d[8]]) / 100.0 / R
     acc[:7] += (d[:7] - d[0]) / 100.0
     acc[8:15] += (d[8:15] - d[8]) / 100.0
     gap += (d[0] - d[14]) / 100.0 / R   # (slot 15 itself is a stamp of the prologue: pro, below)
@@ -64,6 +69,10 @@ if ITERS > 1:   # the prologue's own stamps 5 / 6, which the last merge overwrit
 print("(with ITERS > 1 the stamps are those of the LAST iteration: the single-launch kernel then carries the previous merge in its prologue"
       " and 'sampled' includes selection + gather + refit + affine map)")
 if CENSUS:
+    if first_step[2] > 0:
+        print("wave 0 of workgroup 0 [us from kernel start]: mapped %.2f | behind the last barrier %.2f | first model step %.2f | rolled out %.2f"
+              "  (barrier to first step %.2f, the steps %.2f)"
+              % (*first_step, first_step[2] - first_step[1], first_step[3] - first_step[2]))
     for g, name in enumerate(("first", "last")):
         if not placements[g]:
             print("census, %s workgroup: nothing recorded (a library without -DICEM_WAVE_CENSUS, or no merge-prologue launch)" % name)
