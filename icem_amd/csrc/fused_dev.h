@@ -840,6 +840,13 @@ struct Tile16H {
         f32x4 cur[1];                    // T x the lane's four tile columns (T = S sM, the accumulators' scale)
         float xr[REM > 0 ? REM : 1];     // T x column 16 + r
         float acc_s, acc_b;
+        // step_lone_pairs only: `zero`, the lo plane's empty fourth pair (written once, not every step); what the previous step
+        // made of this step's extra entries -- `xsq`, their squares, and `xh`, the hi plane of their scaled pair; and `xn`, the
+        // next step's pair as read, not yet selected.  Every other user of the tile (step(), step_lone(): StreamT, the noise-ahead
+        // launch on its 128 registers) never reads them: they must stay dead there, so nothing but init()'s asm -- not volatile:
+        // it goes with them -- may write them outside step_lone_pairs (tests/test_register_hygiene_cpu.py holds the spill counts).
+        unsigned zero, xh;
+        f32x2_t xsq, xn;
     };
     __device__ __forceinline__ void init(State& st) const {
         st.cur[0] = obs_init;
@@ -847,6 +854,8 @@ struct Tile16H {
         for (int r = 0; r < REM; ++r) st.xr[r] = rem_init[r];
         st.acc_s = 0.f;
         st.acc_b = INFINITY;
+        // a zero the compiler takes for a value: a constant would be written into the plane's quad again in every step
+        asm("v_mov_b32 %0, 0" : "=v"(st.zero));
     }
     // PLANES_FIRST: the operand planes and the MFMAs in front of the step's cost block (which needs the OLD state only and then
     // sits in the MFMAs' shadow) -- same operations, same bits, another issue order.  For the kernels with a lone tile wave per
@@ -925,8 +934,13 @@ struct Tile16H {
     // the spine, a plane and a cost instruction beside each link -- and fenced (sched_barrier) so that the order survives.
     // Same operations on the same operands in the same per-value order as step(): the same bits.  `raw`: the step's two extra
     // entries as read from the tile, replaced by the next step's (requested at the top: nothing crosses a fence).
+    //   PAIRS: the same step in 40.5 issue slots instead of 47.5 (step_lone_pairs() below) for a caller whose tile can promise
+    // what its paired read needs -- the single-launch kernel; the noise-ahead launch's staging buffer (a chunk of the row, its
+    // padding never written) cannot, and keeps this form.  `raw` then carries the entries already selected: lone_begin().
+    template <bool PAIRS = false>
     __device__ __forceinline__ void step_lone(State& st, float (&raw)[NKX], const float* rd_next) const {
         static_assert(REM == 1 && NKX == 2, "written for one extra column and two extra entries per lane");
+        if constexpr (PAIRS) return step_lone_pairs(st, raw, rd_next);
 #define ICEM_FENCE() __builtin_amdgcn_sched_barrier(0)
         const float c0 = st.cur[0][0], c1 = st.cur[0][1], c2 = st.cur[0][2], c3 = st.cur[0][3];
         const float xv0 = (g == 0) ? st.xr[0] : raw[0], xv1 = raw[1];
@@ -1004,6 +1018,126 @@ struct Tile16H {
         }
         raw[0] = n0;
         raw[1] = n1;
+#undef ICEM_FENCE
+    }
+    // step_lone() with the instructions a lone wave pays a slot for and the result does not need taken out (EXPERIMENTS R19.1):
+    // the same operations on the same operands in the same per-value order, so the same bits.
+    //  * The two extra entries come as ONE ds_read2_b32 at the lane-uniform offsets 0 and 4 of the read pointer.  A padding
+    //    entry (weight 0, scale 0, cost weight 0) then reads up to six floats behind the step's last action instead of the
+    //    step's first action: the next step's actions, the next row's, or -- the last step of row 15 -- the tile's TAIL.  The
+    //    caller guarantees that all of these are written with finite values before the first step: the single-launch kernel
+    //    fills every row of the tile (rows past the end with zeros) and zeroes TAIL in front of its barrier.
+    //  * The pair the read returns is adjacent: the products with the scales and the squares are two v_pk_mul_f32 (each half
+    //    rounds as v_mul_f32 does).
+    //  * The lo plane's empty fourth pair is State::zero, written once.
+    //  * No hazard filler.  The wait states in front of the second MFMA (behind its B plane's last conversion) are the
+    //    reduction's first exchange; those in front of the second lane swap are the third MFMA and the next step's read; and
+    //    those between the third MFMA and the first instruction that reads its result are what the NEXT step does with its
+    //    extra entries alone -- the select, the two packed products, the hi plane's conversion -- done here, at the step's end,
+    //    and handed over in `raw` (the entries, selected) and State::xsq / xh.  lone_begin() does the same for the first step.
+    //    The step's read is the entries of the step after the next (State::xn holds the next step's until they are selected).
+    __device__ __forceinline__ void lone_extras(State& st, float (&raw)[NKX], float n0, float n1) const {
+        const f32x2_t xv = f32x2_t{(g == 0) ? st.xr[0] : n0, n1};
+        const f32x2_t m45 = xv * f32x2_t{sc[0], sc[1]};
+        st.xsq = xv * xv;
+        st.xh = __builtin_bit_cast(unsigned, __builtin_convertvector(m45, f16x2_t));
+        raw[0] = xv[0];
+        raw[1] = xv[1];
+    }
+    // (rd, rd1: the read pointers of the first and of the second step)
+    __device__ __forceinline__ void lone_begin(State& st, float (&raw)[NKX], const float* rd, const float* rd1) const {
+        lone_extras(st, raw, rd[0], rd[4]);
+        st.xn = f32x2_t{rd1[0], rd1[4]};
+    }
+    // `rd_next`: the read pointer of the step AFTER the next -- what is read here is selected at the end of the next step, a
+    // whole step later (read and selected within one step, the wave would wait out the LDS latency in every step: measured)
+    __device__ __forceinline__ void step_lone_pairs(State& st, float (&raw)[NKX], const float* rd_next) const {
+#define ICEM_FENCE() __builtin_amdgcn_sched_barrier(0)
+        const float c0 = st.cur[0][0], c1 = st.cur[0][1], c2 = st.cur[0][2], c3 = st.cur[0][3];
+        const float xv0 = raw[0], xv1 = raw[1];
+        auto cvt = [](f32x2_t v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t)); };
+        auto res = [](float x, float s_, unsigned h, bool upper) {
+            float r;
+            if (upper) asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(s_), "v"(h));
+            else asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(s_), "v"(h));
+            return r;
+        };
+        // link 1
+        const f32x2_t m01 = f32x2_t{c0 * invM, c1 * invM}, m23 = f32x2_t{c2 * invM, c3 * invM};
+        float p = __builtin_fmaf(c0, wR[0][0], 0.f);
+        const float ang = ang_is_col1 ? c1 : c0;
+        ICEM_FENCE();
+        // link 2
+        unsigned bH[4], bL[4];
+        bH[0] = cvt(m01);
+        bH[1] = cvt(m23);
+        bH[2] = st.xh;
+        bH[3] = 0u;
+        p = __builtin_fmaf(c1, wR[0][1], p);
+        const bool flipped = __builtin_fabsf(ang) > flip_th;
+        ICEM_FENCE();
+        // link 3, link 4 (the select on `flipped` two links behind the compare: its wait states)
+        p = __builtin_fmaf(c2, wR[0][2], p);
+        ICEM_FENCE();
+        p = __builtin_fmaf(c3, wR[0][3], p);
+        ICEM_FENCE();
+        const f32x4 nxt1 = mfma_f16_32(aL, bH, f32x4{0.f, 0.f, 0.f, 0.f});
+        // link 5
+        const float r0 = res(c0, invM, bH[0], false), r1 = res(c1, invM, bH[0], true);
+        p = __builtin_fmaf(xv0, wR[0][4], p);
+        float c = flipped ? pen : 0.f;
+        c = __builtin_fmaf(st.xsq[0], cw[0], c);
+        ICEM_FENCE();
+        // link 6
+        const float r2 = res(c2, invM, bH[1], false), r3 = res(c3, invM, bH[1], true);
+        p = __builtin_fmaf(xv1, wR[0][5], p);
+        c = __builtin_fmaf(st.xsq[1], cw[1], c);
+        ICEM_FENCE();
+        c = __builtin_fmaf(lin_w, c0, c);
+        const float r4 = res(xv0, sc[0], bH[2], false), r5 = res(xv1, sc[1], bH[2], true);
+        bL[0] = cvt(f32x2_t{r0, r1});
+        bL[1] = cvt(f32x2_t{r2, r3});
+        bL[2] = cvt(f32x2_t{r4, r5});
+        bL[3] = st.zero;
+        ICEM_FENCE();
+        // reduce_groups_pair(p, c), first half: the two wait states between the plane's last conversion and its MFMA
+        auto x32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(p), __float_as_uint(c), false, false);
+        const float half = __uint_as_float(x32[0]) + __uint_as_float(x32[1]);
+        unsigned xa = x32[0];
+        asm volatile("" : "+v"(xa));   // (the second copy of `half`, below, is not folded into the first)
+        ICEM_FENCE();
+        f32x4 nxt = mfma_f16_32(aH, bL, nxt1);
+        ICEM_FENCE();
+        // (an MFMA that accumulates onto the one in front of it holds the wave's issue until that one is through: the second
+        // copy of `half` the second exchange swaps with and the next step's read go between the two.  The copy is the same sum
+        // with its operands exchanged -- addition commutes: the same bits for every pair of operands but two NaNs of different
+        // payloads, where the step's cost, NaN either way and ranked and counted as such, may carry the other's payload -- and,
+        // unlike a v_mov in an asm statement, an instruction the compiler knows: it keeps the swap's wait states)
+        const float half2 = __uint_as_float(x32[1]) + __uint_as_float(xa);
+        ICEM_FENCE();
+        // lane-uniform offsets: every word this can reach is written and finite (the caller's tile: see above)
+        const float n0 = rd_next[0], n1 = rd_next[4];
+        ICEM_FENCE();
+        nxt = mfma_f16_32(aH, bH, nxt);
+        ICEM_FENCE();
+        // (the first MFMA's result, which the second has read as its accumulator operand, counts as live up to here: its
+        // registers, free behind the second MFMA, would otherwise be the allocator's choice for the copy or for the read, and
+        // writing them right behind the MFMA that reads them costs three wait states of its own)
+        asm volatile("" ::"v"(nxt1));
+        auto x16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(half), __float_as_uint(half2), false, false);
+        p = c = __uint_as_float(x16[0]) + __uint_as_float(x16[1]);
+        st.acc_s = __builtin_fmaf(st.acc_s, ksum, c);
+        st.acc_b = __builtin_fminf(c, st.acc_b);
+        st.xr[0] = KIND == 1 ? fast_tanh(p * invT) * T : p;
+        lone_extras(st, raw, st.xn[0], st.xn[1]);
+        st.xn = f32x2_t{n0, n1};
+        ICEM_FENCE();
+        if (KIND == 1) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) st.cur[0][v] = fast_tanh(nxt[v] * invT) * T;
+        } else {
+            st.cur[0] = nxt;
+        }
 #undef ICEM_FENCE
     }
     __device__ __forceinline__ float cost(const State& st) const {
@@ -1956,9 +2090,13 @@ __device__ __forceinline__ unsigned long long rollout_slab(Tile& tile, const Fas
     typename Tile::State st;
     tile.init(st);
     if constexpr (PLANES_FIRST && Tile::LONE_STEP) {
-        float raw[2] = {rd0[tile.xoff[0]], rd0[tile.xoff[1]]};
+        // (the paired read of step_lone<true>: the caller's tile has every row and its TAIL written before this is reached)
+        float raw[2];
+        tile.lone_begin(st, raw, rd0, rd0 + (H > 1 ? 1 : 0) * D);
 #pragma unroll
-        for (int t = 0; t < H; ++t) tile.step_lone(st, raw, rd0 + (t + 1 < H ? t + 1 : t) * D);
+        // (the last two steps read what nobody selects -- behind the row: the next row or TAIL, written like everything the paired
+        // read reaches -- so that every step has the read its second swap's wait states count on)
+        for (int t = 0; t < H; ++t) tile.template step_lone<true>(st, raw, rd0 + (t + 2 < H ? t + 2 : H) * D);
     } else {
 #pragma unroll
         for (int t = 0; t < H; ++t) tile.template step<PLANES_FIRST>(st, rd0 + t * D);

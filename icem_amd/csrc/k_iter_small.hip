@@ -367,6 +367,12 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
             obs_stage[tid] = tid < ra.o ? ov : 0.f;
         }
     }
+    if constexpr (!T4 && T16::LONE_STEP) {
+        // step_lone<true>'s paired read: a padding entry of the tile's last row reads into TAIL (times weight 0, so any FINITE
+        // value serves; LDS is as the last kernel left it).  Every row in front of it is written above, past the end with zeros.
+        constexpr int Z0 = NT >= 128 ? 64 : 0;   // (wave 1 where it is a sampling wave: neither rolling out nor selecting)
+        if (tid >= Z0 && tid < Z0 + T16::TAIL) tile_rows[TPB * HD + (tid - Z0)] = 0.f;
+    }
     if (ra.dbg && tid == 0 && wg == 0) ra.dbg[10] = wall_clock64();
     __syncthreads();
     if (sa.row0_mean && sa.first_index + base == 0) {  // icem.py:87-88
