@@ -1968,9 +1968,12 @@ __device__ __forceinline__ void merge_select_split_rank(const MergeSingleArgs& a
 }
 
 // pointers to the K selected rows (icem.py:201): pool rows, or kept elites behind index n_global
-template <int KREG, bool REC>
+// KX > 0 ("exact K"): the caller knows a.K == KX -- rows[0..KX) only, no clamp of the row number to K per register slot
+// (three scalar instructions each, in front of the gather's cold round trip) and no load of a row past KX - 1 behind it
+template <int KREG, bool REC, int KX = 0>
 __device__ __forceinline__ void merge_rows(const MergeSingleArgs& a, const unsigned long long* sel, const int* slot,
                                            const float* (&rows)[KREG]) {
+    static_assert(KX >= 0 && KX <= KREG, "exact K within the register slots");
     const int hd = a.h * a.d;
     // ONE LDS read per lane (lane r: selected key / slot r), then a v_readlane per row: read one by one through the same
     // uniform address, the K entries were K dependent LDS round trips in front of the gather's loads (0.3 us of the merge
@@ -1978,7 +1981,8 @@ __device__ __forceinline__ void merge_rows(const MergeSingleArgs& a, const unsig
     // ... and lane r also works out row r's address (one set of vector instructions for all K rows instead of K sets of a
     // dozen scalar ones in front of the first load); the 64-bit addresses come back through v_readlane.
     const int lane = (int)(threadIdx.x & 63);
-    const int v = REC ? slot[lane < a.K ? lane : 0] : key_idx(sel[lane < a.K ? lane : 0]);
+    const int nk = KX > 0 ? KX : a.K;
+    const int v = REC ? slot[lane < nk ? lane : 0] : key_idx(sel[lane < nk ? lane : 0]);
     const float* mine;
     if (REC) mine = v < a.n_rec ? a.records + (size_t)v * (hd + 2) + 2 : a.elites_cur + (size_t)(v - a.n_rec) * hd;   // sharded run: candidates are records
     else mine = v < a.n_pool ? a.actions + (size_t)v * hd : a.elites_cur + (size_t)(v - a.n_global) * hd;
@@ -1987,8 +1991,8 @@ __device__ __forceinline__ void merge_rows(const MergeSingleArgs& a, const unsig
     typedef const float __attribute__((address_space(1))) * GRow;
     const unsigned long long bits = (unsigned long long)(size_t)mine;
 #pragma unroll
-    for (int r = 0; r < KREG; ++r) {
-        const int rr = r < a.K ? r : 0;
+    for (int r = 0; r < (KX > 0 ? KX : KREG); ++r) {
+        const int rr = (KX > 0 || r < a.K) ? r : 0;
         const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, rr);
         const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), rr);
         rows[r] = (const float*)reinterpret_cast<GRow>((size_t)(((unsigned long long)hi << 32) | lo));

@@ -35,7 +35,9 @@ constexpr int sr_threads(int d, int rw) { return (((sr_quad(d, rw) ? 4 : 1) * 16
 // that arithmetic, so the slab is rolled out by RW waves of Tile16H whatever the sampling shape.
 // (the body is a device function: sample_rollout_kernel reads its argument block from the kernel-argument segment,
 //  sample_rollout_batch_kernel -- B problems in one launch, icem_plan_step_batch -- from an array in device memory)
-template <int H, int D, int O, int KIND, int ROUNDS, int RW, int KREG, bool REC, int ARITH>
+// KX > 0 ("exact K", merge-prologue launches): the launcher has checked am.K == KX -- the gather and the refit run over exactly
+// KX rows (merge_rows, refit_element_regs: no per-slot select on K, no load past row KX - 1, unconditional elite stores)
+template <int H, int D, int O, int KIND, int ROUNDS, int RW, int KREG, bool REC, int ARITH, int KX = 0>
 __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, const FastRolloutArgs& ra, const MergeSingleArgs& am,
                                                     const PackPrev& ap) {
     constexpr bool PM = KREG > 0;
@@ -331,24 +333,25 @@ __device__ __forceinline__ void sample_rollout_body(const FastSampleArgs& sa, co
         if (!REC && ra.dbg && tid == 0 && wg == 0) ra.dbg[15] = wall_clock64();
         // all threads: gather the elite rows + refit (icem.py:201-211) -> this workgroup's mean / std
         const float* rows[KREG > 0 ? KREG : 1];
-        merge_rows<KREG, REC>(m, sel, slot, rows);
+        constexpr int NR = KX > 0 ? KX : KREG;   // rows gathered
+        merge_rows<KREG, REC, KX>(m, sel, slot, rows);
         for (int e = tid; e < HD; e += NTT) {
             float xs[KREG > 0 ? KREG : 1];
 #pragma unroll
-            for (int r = 0; r < KREG; ++r) xs[r] = rows[r][e];
+            for (int r = 0; r < NR; ++r) xs[r] = rows[r][e];
             float nm, ns;
-            refit_element_regs<float, KREG>(m.K, m.alpha, m.mean[e], m.std[e], xs, nm, ns);
+            refit_element_regs<float, KREG, KX>(m.K, m.alpha, m.mean[e], m.std[e], xs, nm, ns);
             ms[e] = nm;
             ms[HD + e] = ns;
             if (wg == 0) {
                 m.mean_out[e] = nm;
                 m.std_out[e] = ns;
 #pragma unroll
-                for (int r = 0; r < KREG; ++r)
-                    if (r < m.K) m.elites_next[(size_t)r * HD + e] = xs[r];
+                for (int r = 0; r < NR; ++r)
+                    if (KX > 0 || r < m.K) m.elites_next[(size_t)r * HD + e] = xs[r];
             }
         }
-        if (wg == 0 && tid < m.K) m.elites_cost_next[tid] = key_cost(sel[tid]);
+        if (wg == 0 && tid < (KX > 0 ? KX : m.K)) m.elites_cost_next[tid] = key_cost(sel[tid]);
         __syncthreads();
         if (ra.dbg && tid == 0 && wg == 0) ra.dbg[6] = wall_clock64();
         if (!REC && ra.dbg && tid == 0 && wg == 0) ra.dbg[7] = wall_clock64();
@@ -491,6 +494,15 @@ __global__ __launch_bounds__(sr_threads(D, RW) + (KREG > 0 ? 64 : 0)) void sampl
     sample_rollout_body<H, D, O, KIND, ROUNDS, RW, KREG, REC, ARITH>(a.s, a.r, a.m, a.p);
 }
 
+// The merge-prologue launch for K == KX known at compile time (launch_sample_rollout picks it where am.K == KX; the
+// development option merge_exact_k = 0 keeps every K on the kernel above): the same body, a name of its own
+template <int H, int D, int O, int KIND, int ROUNDS, int RW, int KREG, int ARITH, int KX>
+__global__ __launch_bounds__(sr_threads(D, RW) + 64) void sample_rollout_exactk_kernel(FastIterArgs a) {
+    static_assert(KREG > 0 && KX > 0, "a merge-prologue form");
+    kernarg_touch<sizeof(FastIterArgs)>();
+    sample_rollout_body<H, D, O, KIND, ROUNDS, RW, KREG, false, ARITH, KX>(a.s, a.r, a.m, a.p);
+}
+
 // B problems in one launch: blockIdx.y = the problem, its argument block in device memory (scalar loads: the index is
 // uniform), the sampling calls' stream offsets stored relative to the step's base of that problem (BatchBases)
 template <int H, int D, int O, int KIND, int ROUNDS, int RW, int KREG, int ARITH>
@@ -595,7 +607,15 @@ template <int H, int D, int O, int KIND, int RW, int KREG, bool REC, int ARITH>
 struct SrInst {
     static constexpr int THREADS = sr_threads(D, RW) + (KREG > 0 ? 64 : 0);
     static constexpr bool BATCHED = !REC;   // (the records merge is a sharded run's: not batched)
-    static void solo(int grid, hipStream_t st, const FastIterArgs& a) {
+    // exact_k: the lists merge prologue with a.m.K == MERGE_EXACT_K, where that form is compiled (one rollout wave per workgroup)
+    static constexpr bool HAS_EXACT_K = KREG > 0 && !REC && RW == 1;
+    static void solo(int grid, hipStream_t st, const FastIterArgs& a, bool exact_k) {
+        if constexpr (HAS_EXACT_K) {
+            if (exact_k) {
+                hipLaunchKernelGGL((sample_rollout_exactk_kernel<H, D, O, KIND, 10, RW, KREG, ARITH, MERGE_EXACT_K>), dim3(grid), dim3(THREADS), 0, st, a);
+                return;
+            }
+        }
         hipLaunchKernelGGL((sample_rollout_kernel<H, D, O, KIND, 10, RW, KREG, REC, ARITH>), dim3(grid), dim3(THREADS), 0, st, a);
     }
     static void batch(int grid, int n, hipStream_t st, const FastIterArgs* args_dev, const BatchBases& bases) {
@@ -644,7 +664,10 @@ void launch_sample_rollout(const LaunchCtx& cx, const FastIterArgs& a, int h, in
     k.form = !merge_prologue ? 0 : a.m.records ? 2 : 1;
     k.wgs[1] = (k.form == 2 && a.p.part_k) ? 1 : 0;   // workgroup 0: the riding pack
     submit(cx, k, k.form != 2, [&](void* dst, unsigned long long base) { batch_form(a, base, dst); },
-           [&] { sample_rollout_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0] + k.wgs[1], cx.st, a); }); });
+           [&] {
+               const bool exact_k = k.form == 1 && a.m.K == MERGE_EXACT_K && opt_i(OPT_MERGE_EXACT_K) != 0;
+               sample_rollout_dispatch(k, [&](auto inst) { inst.solo(k.wgs[0] + k.wgs[1], cx.st, a, exact_k); });
+           });
 }
 
 // ... and the same launch for n problems (blockIdx.y)

@@ -9,7 +9,8 @@ namespace icem {
 
 namespace {
 
-template <int KREG, bool REC>
+// KX > 0 ("exact K"): the launcher has checked a.K == KX (merge_rows, refit_element_regs)
+template <int KREG, bool REC, int KX = 0>
 __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsigned char* smem_raw) {
     __shared__ unsigned long long sel[64];
     __shared__ unsigned long long cand[64];
@@ -56,7 +57,8 @@ __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsi
     }
     // ---- all 4 waves: gather + refit (icem.py:201-211); row pointers first, then all K loads in flight ----
     const float* rows[KREG];
-    merge_rows<KREG, REC>(a, sel, slot, rows);
+    constexpr int NR = KX > 0 ? KX : KREG;   // rows gathered
+    merge_rows<KREG, REC, KX>(a, sel, slot, rows);
     // (stores count on the same counter as loads here: a store between two of the gather's loads makes every later wait a
     // wait for that store's acknowledgement.  So: all K loads, ONE wait for them (the refit needs them all anyway), and only
     // then the K stores, back to back with nothing left to wait for.)
@@ -64,14 +66,14 @@ __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsi
     auto finish_one = [&](int e, float old_mean, float old_std) {
         float xs[KREG];
 #pragma unroll
-        for (int r = 0; r < KREG; ++r) xs[r] = rows[r][e];
+        for (int r = 0; r < NR; ++r) xs[r] = rows[r][e];
 #pragma unroll
-        for (int r = 0; r < KREG; ++r) asm volatile("" : "+v"(xs[r]));   // every row's value has arrived HERE
+        for (int r = 0; r < NR; ++r) asm volatile("" : "+v"(xs[r]));   // every row's value has arrived HERE
         float nm, ns;
-        refit_element_regs<float, KREG>(a.K, a.alpha, old_mean, old_std, xs, nm, ns);
+        refit_element_regs<float, KREG, KX>(a.K, a.alpha, old_mean, old_std, xs, nm, ns);
 #pragma unroll
-        for (int r = 0; r < KREG; ++r)
-            if (r < a.K) a.elites_next[(size_t)r * hd + e] = xs[r];
+        for (int r = 0; r < NR; ++r)
+            if (KX > 0 || r < a.K) a.elites_next[(size_t)r * hd + e] = xs[r];
         if (!a.last) {
             a.mean_out[e] = nm;
             a.std_out[e] = ns;
@@ -90,7 +92,7 @@ __device__ __forceinline__ void merge_single_body(const MergeSingleArgs& a, unsi
         for (int e = tid; e < hd; e += MERGE_WG) finish_one(e, a.mean[e], a.std[e]);
     }
     if (a.dbg && threadIdx.x == 0) a.dbg[5] = wall_clock64();
-    if (tid < a.K) a.elites_cost_next[tid] = key_cost(sel[tid]);
+    if (tid < (KX > 0 ? KX : a.K)) a.elites_cost_next[tid] = key_cost(sel[tid]);
     if (a.last) {
         __syncthreads();
         if (pre) {   // (the bounds are in registers: request_bounds; the loop below is the same epilogue for hd > EPL * MERGE_WG)
@@ -121,14 +123,22 @@ __global__ __launch_bounds__(MERGE_WG) void merge_single_kernel(MergeSingleArgs 
     merge_single_body<KREG, REC>(a, smem_raw);
 }
 
+// ... for K == KX known at compile time (launch_merge_single picks it where a.K == KX): the same body, a name of its own
+template <int KREG, int KX>
+__global__ __launch_bounds__(MERGE_WG) void merge_single_exactk_kernel(MergeSingleArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    merge_single_body<KREG, false, KX>(a, smem_raw);
+}
+
 // The last merge of an MPC step with company (noise-ahead pipeline, plan.hip): workgroup 0 is merge_single_kernel, the
 // other workgroups draw raw colored noise (noise_rows_kernel's work: sample_row into an LDS tile, coalesced copy-out) for
 // iteration 0 of the NEXT MPC step -- the one launch of a step during which 255 of the 256 CUs had nothing to do.
-template <int H, int KREG>
-__global__ __launch_bounds__(MERGE_WG) void merge_noise_kernel(MergeSingleArgs a, FastSampleArgs z1, FastSampleArgs z2, int wgs1) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+// (KX > 0: workgroup 0 is the exact-K merge -- merge_noise_exactk_kernel below, the same body under a name of its own)
+template <int H, int KREG, int KX>
+__device__ __forceinline__ void merge_noise_body(const MergeSingleArgs& a, const FastSampleArgs& z1, const FastSampleArgs& z2, int wgs1,
+                                                 unsigned char* smem_raw) {
     if (blockIdx.x == 0) {
-        merge_single_body<KREG, false>(a, smem_raw);
+        merge_single_body<KREG, false, KX>(a, smem_raw);
         return;
     }
     // workgroups 1 .. wgs1: the sampling call z1; behind them: z2 (a few rows of another stream)
@@ -155,6 +165,16 @@ __global__ __launch_bounds__(MERGE_WG) void merge_noise_kernel(MergeSingleArgs a
     } else {
         for (int e = tid; e < total; e += MERGE_WG) gdst[e] = tile[e];
     }
+}
+template <int H, int KREG>
+__global__ __launch_bounds__(MERGE_WG) void merge_noise_kernel(MergeSingleArgs a, FastSampleArgs z1, FastSampleArgs z2, int wgs1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    merge_noise_body<H, KREG, 0>(a, z1, z2, wgs1, smem_raw);
+}
+template <int H, int KREG, int KX>
+__global__ __launch_bounds__(MERGE_WG) void merge_noise_exactk_kernel(MergeSingleArgs a, FastSampleArgs z1, FastSampleArgs z2, int wgs1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    merge_noise_body<H, KREG, KX>(a, z1, z2, wgs1, smem_raw);
 }
 
 // The same launch for B problems at once (icem_plan_step_batch): blockIdx.y = the problem, its arguments in device memory,
@@ -340,7 +360,10 @@ void launch_merge_noise(const LaunchCtx& cx, const MergeSingleArgs& a, const Fas
     const LaunchKey k = merge_key(a, &z, &z2);
     submit(cx, k, true, [&](void* dst, unsigned long long base) { batch_form(a, &z, &z2, base, dst); }, [&] {
         merge_noise_dispatch(k, [&](auto H, int grid, size_t lds) {
-            hipLaunchKernelGGL((merge_noise_kernel<decltype(H)::value, 12>), dim3(grid), dim3(MERGE_WG), lds, cx.st, a, z, z2, k.wgs[1]);
+            if (a.K == MERGE_EXACT_K && opt_i(OPT_MERGE_EXACT_K) != 0)
+                hipLaunchKernelGGL((merge_noise_exactk_kernel<decltype(H)::value, 12, MERGE_EXACT_K>), dim3(grid), dim3(MERGE_WG), lds, cx.st, a, z, z2, k.wgs[1]);
+            else
+                hipLaunchKernelGGL((merge_noise_kernel<decltype(H)::value, 12>), dim3(grid), dim3(MERGE_WG), lds, cx.st, a, z, z2, k.wgs[1]);
         });
     });
 }
@@ -362,6 +385,8 @@ void launch_merge_single(const LaunchCtx& cx, const MergeSingleArgs& a) {
                 hipLaunchKernelGGL((merge_single_kernel<12, true>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
             else
                 hipLaunchKernelGGL((merge_single_kernel<34, true>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
+        } else if (a.K == MERGE_EXACT_K && opt_i(OPT_MERGE_EXACT_K) != 0) {
+            hipLaunchKernelGGL((merge_single_exactk_kernel<12, MERGE_EXACT_K>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
         } else if (a.K + 1 <= 12) {
             hipLaunchKernelGGL((merge_single_kernel<12, false>), dim3(1), dim3(MERGE_WG), lds, cx.st, a);
         } else {

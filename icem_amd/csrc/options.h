@@ -24,6 +24,7 @@ namespace icem {
     X(AHEAD_TAIL_FRAC, "ahead_tail_frac", 0.4)                                                                             \
     X(AHEAD_NEXT1_FRAC, "ahead_next1_frac", 0.3)                                                                           \
     X(AHEAD_NOISE_LDS_KB, "ahead_noise_lds_kb", -1.0)                                                                      \
+    X(MERGE_EXACT_K, "merge_exact_k", 1.0)           /* 0: K = 10 on the runtime-K merge kernels too (solo steps; the exact-K forms compute the same bits) */ \
     X(PREDRAW, "predraw", 1.0)                       /* 0: iteration 0 of small populations samples its own noise */       \
     X(GK_SAMPLE, "gk_sample", 1.0)                   /* strict-parity path: 0 = one thread per row in the sampler */       \
     X(GK_ROLLOUT_THREAD, "gk_rollout_thread", 0.0)   /* ... 1 = one thread per trajectory in the rollout */                \
@@ -47,6 +48,7 @@ enum Opt {
 #undef X
     OPT_COUNT
 };
+constexpr int MERGE_EXACT_K = 10;   // the K the exact-K merge kernels are compiled for: the reference's shipped elite count, every default here
 double opt(Opt k);                 // the option's current value (abi.hip)
 inline int opt_i(Opt k) { return (int)opt(k); }
 

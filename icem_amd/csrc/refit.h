@@ -32,24 +32,29 @@ __device__ __forceinline__ void refit_element(int K, T alpha, T old_mean, T old_
 
 // Same arithmetic, same order, for K values already in registers (x[r], r < K <= KMAX): every loop is
 // static so nothing is indexed dynamically.
-template <typename T, int KMAX>
+// KX > 0 ("exact K"): the caller knows K == KX at compile time -- the loops run to KX and the `r < K` selects on the two
+// dependent sum chains are gone; the operations and their order are the same, so the bits are the same.
+template <typename T, int KMAX, int KX = 0>
 __device__ __forceinline__ void refit_element_regs(int K, T alpha, T old_mean, T old_std, const T (&x)[KMAX], T& new_mean,
                                                    T& new_std) {
 #pragma clang fp contract(off)
+    static_assert(KX >= 0 && KX <= KMAX, "exact K within the register slots");
+    constexpr int NR = KX > 0 ? KX : KMAX;
+    const T Kt = KX > 0 ? (T)KX : (T)K;
     T s = (T)0;
 #pragma unroll
-    for (int r = 0; r < KMAX; ++r)
-        if (r < K) s = s + x[r];
-    const T m = s / (T)K;
+    for (int r = 0; r < NR; ++r)
+        if (KX > 0 || r < K) s = s + x[r];
+    const T m = s / Kt;
     T v = (T)0;
 #pragma unroll
-    for (int r = 0; r < KMAX; ++r) {
-        if (r < K) {
+    for (int r = 0; r < NR; ++r) {
+        if (KX > 0 || r < K) {
             const T dx = x[r] - m;
             v = fma_t(dx, dx, v);
         }
     }
-    const T sd = sqrt_t(v / (T)K);
+    const T sd = sqrt_t(v / Kt);
     const T one_m = (T)1 - alpha;
     new_mean = fma_t(one_m, m, alpha * old_mean);
     new_std = fma_t(one_m, sd, alpha * old_std);
