@@ -1,6 +1,7 @@
-// arg_array.h -- the device arrays a batched step's argument blocks live in (icem_plan_step_batch, icem_plan_step_learned*): SLOTS
-// of them, each with a host shadow of what it holds and written only when a byte changed -- a steady-state step uploads nothing.
-// Which slot a step uses and how much room a slot gets when it has to grow are the caller's.  Internal; not part of the public ABI.
+// arg_array.h -- the device arrays a batched step's argument blocks live in (every icem_plan_step_*_batch): SLOTS of them, each
+// with a host shadow of what it holds and written only when a byte changed -- a steady-state step uploads nothing.  Which slot a
+// step uses and how much room a slot gets when it has to grow are the caller's; what a blob holds where is block_layout.h's, and
+// the blocks of recorded launches get there through recorded_batch.h.  Internal; not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -10,10 +10,9 @@
 //
 // icem_plan_step_cem_batch is the same step for B planners of one configuration -- the reference runs its controllers side by side
 // (icem/misc/rollout_utils.py:46-58, 129-152) -- with every one of the three launches ONE launch for all of them: cem_sample_batch_kernel,
-// the batched twin of the handles' rollout launch (LAUNCH_FAMILIES, icem_fused.h; each handle's rollout_cost_launch runs under a recorder
-// and its launch is compared and issued once for all), cem_update_*_batch_kernel.  The argument blocks live in a DeviceArgArray of the
-// first handle; they carry no step-dependent value (the sampler's offset is relative to the step's base, which travels by value),
-// so a batch whose buffers stay put uploads each of its two slots once.
+// the batched twin of the handles' rollout launch (the recorded-launch plan, recorded_batch.h), cem_update_*_batch_kernel.  The argument
+// blocks live in a DeviceArgArray of the first handle, laid out by block_layout.h; they carry no step-dependent value (the sampler's
+// offset is relative to the step's base, which travels by value), so a batch whose buffers stay put uploads each of its two slots once.
 //
 // icem_plan_step_cem_learned / icem_plan_step_cem_learned_batch are the same step through the learned dynamics (the declared RSSM,
 // BASELINE configs[4]) -- the planner PlaNet uses: the sampler and the update above around launch_rssm_rollout (one problem) /
@@ -21,6 +20,7 @@
 // arrangement).  The refusals, the block filling and the update launch are the ones above.
 #include "cem_step.h"
 #include "icem_rssm.h"
+#include "recorded_batch.h"
 
 using namespace icem;
 
@@ -168,147 +168,80 @@ int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_para
     return ICEM_OK;
 }
 
-size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-// B > 1 planners behind the admission of the batch.  Host state: the step keeps none per handle -- no elite double buffer, no
-// pending merge, the noise offsets follow from (episode, mpc_step) which the caller owns.  What exists is the first handle's
-// argument array (cem_batch_args + its upload counter batch_uploads; a slot that was uploaded holds exactly what its shadow says,
-// whatever happens later) and its cem_batch_launches, written behind the last launch only.  Recording a handle's rollout may
-// upload that handle's packed model (ensure_fast_model: idempotent, what its next solo step would do first).  So a HIP call that
-// fails anywhere below leaves every handle as it was.
-int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const int32_t* steps,
-                   void* results, hipStream_t st) {
+// B > 1 planners behind the admission of the batch (through the RSSM, params != nullptr: and behind the tile check and
+// rssm_split_prepare).  Host state: the step keeps none per handle -- no elite double buffer, no pending merge, the noise offsets
+// follow from (episode, mpc_step) which the caller owns.  What exists is the first handle's argument array (cem_batch_args + its
+// upload counter batch_uploads; a slot that was uploaded holds exactly what its shadow says, whatever happens later), its
+// cem_batch_launches, written behind the last launch only, and through the RSSM its learned-step pool.  Recording a handle's rollout
+// may upload that handle's packed model (ensure_fast_model: idempotent, what its next solo step would do first).  So a HIP call
+// that fails anywhere below leaves every handle as it was.
+int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const void* params,
+                   const int32_t* steps, void* results, hipStream_t st) {
     const std::string who = "icem_plan_step_cem_batch: ";
     icem_handle* h0 = handles[0];
     const icem_config& c = h0->cfg;
-    const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd, d = c.act_dim;
+    const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd;
     const bool f64 = c.dtype == ICEM_F64;
-    if (!cem_sample_ok(h0))
-        return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS): "
-                                              "the operator's sampler has no batched form");
-    // ---- every problem's rollout launch, recorded: its batched family, its key, its argument block ----
-    BatchHint hint;
-    hint.mult = n;   // (TileHN: a batch's launches are the one-wave-per-tile kernel's; the other families keep the solo shape)
-    std::vector<LaunchRecorder> recs(n);
-    for (int i = 0; i < n; ++i) {
-        recs[i].who = "icem_plan_step_cem_batch: ";
-        const icem_cem_buffers& b = buffers[i];
-        if (int rc = rollout_cost_launch(handles[i], N, b.obs0, b.actions, b.costs, nullptr, LaunchCtx{st, hint, &recs[i]})) return rc;
-        if (recs[i].unsupported) return fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached (this handle's rollout kernel has no batched twin)");
+    // ---- the rollout.  Through the RSSM: problem i's rows are drawn into the slice [i * N, (i + 1) * N) of the first handle's
+    // learned-step pool, ONE split launch scores the pool, every update reads its slice; the first sampler launch also gathers the
+    // observations into the pool's [n, 230] table.  Else: every problem's rollout launch, recorded and compared (recorded_batch.h) ----
+    RecordedBatch rb(params ? 0 : n);
+    float *pool_a = nullptr, *pool_c = nullptr;
+    ObsGather og{};
+    if (params) {
+        LearnedCtx& ctx = h0->learned;
+        ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
+        pool_a = ctx.pool_actions(), pool_c = ctx.pool_costs(hd);
+        og.dst = ctx.pool_obs(hd), og.width = ICEM_RSSM_OBS_DIM;
+        for (int i = 0; i < n; ++i) og.src[i] = (const float*)buffers[i].obs0;
+    } else {
+        if (!cem_sample_ok(h0))
+            return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS): "
+                                                  "the operator's sampler has no batched form");
+        for (int i = 0; i < n; ++i)
+            if (int rc = record_rollout(rb, i, handles[i], buffers[i].obs0, buffers[i].actions, buffers[i].costs, st, who)) return rc;
+        if (int rc = rb.check(who)) return rc;
     }
-    const std::vector<LaunchDesc>& first = recs[0].launches;
-    const size_t L = first.size();
-    for (int i = 0; i < n; ++i) {
-        if (recs[i].launches.size() != L || L == 0) return fail(ICEM_E_STATE, who + "the problems' steps took different launches");
-        for (size_t l = 0; l < L; ++l)
-            if (!(recs[i].launches[l].key == first[l].key)) return fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
-    }
-    for (size_t l = 0; l < L; ++l)
-        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
-    // ---- argument blocks: per iteration [sample x n | rollout launch(es) x n | update x n] ----
+    // ---- argument blocks: per iteration [sample x n | rollout launch(es) x n | update x n]; no step-dependent value in them ----
     const size_t sb = cem_sample_block_bytes(h0), ub = f64 ? sizeof(CemUpdateF64Args) : sizeof(CemUpdateF32Args);
-    std::vector<size_t> at(L);   // a rollout launch's array inside an iteration's part
-    size_t per_it = padded(sb * n), per_it_room = padded(sb * ICEM_MAX_BATCH);
-    for (size_t l = 0; l < L; ++l) {
-        at[l] = per_it;
-        per_it += padded(launch_family(first[l].key.family)->block_bytes * n);
-        per_it_room += padded(launch_family(first[l].key.family)->block_bytes * ICEM_MAX_BATCH);
-    }
-    const size_t at_update = per_it;
-    per_it += padded(ub * n);
-    per_it_room += padded(ub * ICEM_MAX_BATCH);
+    BlockLayout layout(n, ICEM_MAX_BATCH);
+    layout.add(sb);   // (at 0)
+    rb.place(layout);
+    const size_t at_update = layout.add(ub), per_it = layout.bytes();
     std::vector<unsigned char> blob(per_it * iters, 0);
     BatchBases bases{};
     for (int i = 0; i < n; ++i) bases.v[i] = (handles[i]->episode << 32) + (uint64_t)steps[i] * (uint64_t)iters;
     for (int it = 0; it < iters; ++it) {
         unsigned char* part = blob.data() + per_it * it;
         for (int i = 0; i < n; ++i) {
-            const icem_cem_buffers& b = buffers[i];
+            icem_cem_buffers b = buffers[i];
+            if (params) b.actions = pool_a + (size_t)i * N * hd, b.costs = pool_c + (size_t)i * N;   // (the problem's own, but its pool: the slice)
             cem_sample_block(handles[i], N, b.mean, b.std, b.lower, b.upper, (uint64_t)it, b.actions, part + sb * i);
-            for (size_t l = 0; l < L; ++l) {
-                const size_t one = launch_family(first[l].key.family)->block_bytes;
-                std::memcpy(part + at[l] + one * i, recs[i].launches[l].block, one);
-            }
-            void* row = results ? (unsigned char*)results + (size_t)i * (d + 1) * h0->tsize : nullptr;
+            rb.copy(i, part);
+            void* row = results_row(results, i, (size_t)(c.act_dim + 1) * h0->tsize);
             if (f64) fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF64Args*)(part + at_update + ub * i));
             else fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF32Args*)(part + at_update + ub * i));
         }
     }
     const int slot = steps[0] & 1;
-    ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, per_it_room * iters, st, &h0->batch_uploads));
+    ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, layout.room() * iters, st, &h0->batch_uploads));
     // ---- the launches: 3 per iteration (+ the GEMM path's row tail, which a CEM step never has: no shifted rows) ----
     const unsigned char* dev = (const unsigned char*)h0->cem_batch_args.dev(slot);
+    const std::vector<int> rows(params ? n : 0, N);
     long long launches = 0;
     for (int it = 0; it < iters; ++it) {
         const unsigned char* part = dev + per_it * it;
-        launch_cem_sample_batch(h0, N, part, bases, n, st);
-        ICEM_HIP_TRY(hipGetLastError());
-        ++launches;
-        for (size_t l = 0; l < L; ++l) {
-            launch_family(first[l].key.family)->launch(first[l].key, part + at[l], bases, n, st);
-            ICEM_HIP_TRY(hipGetLastError());
-            ++launches;
-        }
-        if (f64) launch_cem_update_batch((const CemUpdateF64Args*)(part + at_update), n, hd, st);
-        else launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
-        ICEM_HIP_TRY(hipGetLastError());
-        ++launches;
-    }
-    h0->cem_batch_launches = launches;
-    return ICEM_OK;
-}
-
-// B > 1 planners through the RSSM, behind the admission of the batch, the tile check and rssm_split_prepare.  Per iteration
-// [sample x n | update x n] blocks in the first handle's cem_batch_args (no step-dependent value in them, as above); problem i's
-// rows are drawn into the slice [i * N, (i + 1) * N) of the first handle's learned-step pool, ONE split launch scores the pool, every
-// update reads its slice.  The first iteration's sampler launch also gathers the observations into the pool's [n, 230] table.
-int cem_learned_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const void* params,
-                      const int32_t* steps, void* results, hipStream_t st) {
-    icem_handle* h0 = handles[0];
-    const icem_config& c = h0->cfg;
-    const int N = c.num_traj, iters = c.opt_iters, hd = h0->hd, d = c.act_dim;
-    LearnedCtx& ctx = h0->learned;
-    ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
-    float* pool_a = ctx.pool;
-    float* pool_c = pool_a + ctx.pool_rows * (size_t)hd;
-    float* pool_o = pool_c + ctx.pool_rows;
-    const size_t sb = cem_sample_block_bytes(h0), ub = sizeof(CemUpdateF32Args);
-    const size_t at_update = padded(sb * n), per_it = at_update + padded(ub * n);
-    const size_t per_it_room = padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH);
-    std::vector<unsigned char> blob(per_it * iters, 0);
-    BatchBases bases{};
-    ObsGather og{};
-    og.dst = pool_o, og.width = ICEM_RSSM_OBS_DIM;
-    for (int i = 0; i < n; ++i) {
-        bases.v[i] = (handles[i]->episode << 32) + (uint64_t)steps[i] * (uint64_t)iters;
-        og.src[i] = (const float*)buffers[i].obs0;
-    }
-    for (int it = 0; it < iters; ++it) {
-        unsigned char* part = blob.data() + per_it * it;
-        for (int i = 0; i < n; ++i) {
-            icem_cem_buffers b = buffers[i];   // (the problem's own, but its pool: the slice)
-            b.actions = pool_a + (size_t)i * N * hd, b.costs = pool_c + (size_t)i * N;
-            cem_sample_block(handles[i], N, b.mean, b.std, b.lower, b.upper, (uint64_t)it, b.actions, part + sb * i);
-            void* row = results ? (unsigned char*)results + (size_t)i * (d + 1) * h0->tsize : nullptr;
-            fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF32Args*)(part + at_update + ub * i));
-        }
-    }
-    const int slot = steps[0] & 1;
-    ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, per_it_room * iters, st, &h0->batch_uploads));
-    const unsigned char* dev = (const unsigned char*)h0->cem_batch_args.dev(slot);
-    const std::vector<int> rows(n, N);
-    long long launches = 0;
-    for (int it = 0; it < iters; ++it) {
-        const unsigned char* part = dev + per_it * it;
-        if (it == 0) launch_cem_sample_gather_batch(h0, N, part, bases, og, n, st);
+        if (params && it == 0) launch_cem_sample_gather_batch(h0, N, part, bases, og, n, st);
         else launch_cem_sample_batch(h0, N, part, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
-        if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.cost_mode, (const unsigned short*)params, pool_o,
-                                                                pool_a, pool_c, st)))
+        if (int rc = params ? rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.cost_mode, (const unsigned short*)params,
+                                                                         og.dst, pool_a, pool_c, st))
+                            : rb.launch(part, bases, st, &launches))
             return rc;
-        ++launches;
-        launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
+        if (params) ++launches;
+        if (f64) launch_cem_update_batch((const CemUpdateF64Args*)(part + at_update), n, hd, st);
+        else launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
     }
@@ -344,7 +277,7 @@ int icem_plan_step_cem_batch(icem_handle* const* handles, int32_t n, const icem_
         if (rc == ICEM_OK) handles[0]->cem_batch_launches = launches;
         return rc;
     }
-    return cem_step_batch(handles, n, buffers, *p, mpc_steps_host, results, (hipStream_t)stream);
+    return cem_step_batch(handles, n, buffers, *p, nullptr, mpc_steps_host, results, (hipStream_t)stream);
 }
 
 int icem_plan_step_cem_learned_ok(const icem_handle* h) { return (h && cem_learned_unserved(h) == nullptr) ? 1 : 0; }
@@ -382,7 +315,7 @@ int icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n, con
         if (rc == ICEM_OK) handles[0]->cem_batch_launches = launches;
         return rc;
     }
-    return cem_learned_batch(handles, n, buffers, *p, params, mpc_steps_host, results, (hipStream_t)stream);
+    return cem_step_batch(handles, n, buffers, *p, params, mpc_steps_host, results, (hipStream_t)stream);
 }
 
 int64_t icem_cem_step_launches(const icem_handle* h) { return h ? (int64_t)h->cem_launches : 0; }

@@ -1,6 +1,7 @@
 // host_common.h -- what the host-side translation units of libicem_hip.so share: the handle, error plumbing,
-// per-kernel timing scopes, the launcher interfaces between them, and what the batched steps of plan.hip and learned_step.hip
-// share (arg_array.h, admit_batch, call_base / shift_rows / elite_parity).
+// per-kernel timing scopes, the launcher interfaces between them, and what the batched steps share (arg_array.h, admit_batch,
+// results_row, call_base / shift_rows / elite_parity; their blobs' sections are block_layout.h's, the recorded-launch plan of
+// plan.hip, cem_step.hip and random_step.hip is recorded_batch.h's).
 //   generic_kernels.hip  the generic (f32 / f64, any shape) kernels + their launchers (gk_*)
 //   plan.hip             the fused MPC step: icem_plan_* / icem_get_action and the f32 throughput-path orchestration
 //   learned_step.hip     the learned-dynamics MPC step: icem_plan_step_learned*
@@ -77,6 +78,10 @@ struct LearnedCtx {
         pool_n = pn;
         return hipSuccess;
     }
+    // the pool's parts as reserve() laid them out (nullptr: no pool yet -- one problem alone needs none)
+    float* pool_actions() const { return pool; }
+    float* pool_costs(int hd) const { return pool ? pool + pool_rows * (size_t)hd : nullptr; }
+    float* pool_obs(int hd) const { return pool ? pool + pool_rows * (size_t)(hd + 1) : nullptr; }
     ~LearnedCtx() {
         if (pool) (void)hipFree(pool);
         if (idx) (void)hipFree(idx);
@@ -346,6 +351,10 @@ inline int admit_batch(icem_handle* const* handles, int n, bool other_args, bool
     for (int i = 1; i < n; ++i)
         if (!same_batch_config(handles[i]->cfg, handles[0]->cfg, exact)) return fail(ICEM_E_INVALID, config_msg);
     return ICEM_OK;
+}
+// problem i's row of a batch's `results` (rows of row_bytes), or nullptr where the caller asked for none
+inline void* results_row(void* results, int i, size_t row_bytes) {
+    return results ? (unsigned char*)results + (size_t)i * row_bytes : nullptr;
 }
 inline int topk_blocks(int n) { return (n + TOPK_CHUNK - 1) / TOPK_CHUNK; }
 

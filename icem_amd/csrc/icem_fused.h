@@ -586,7 +586,7 @@ inline void launch_sample_batch_recorded(const LaunchKey& key, const FastSampleA
 }
 
 // The launch families, each written once: the size of the family's argument block and its batched launch.  A recorded launch
-// whose family has no row here is refused by icem_plan_step_batch (launch_family -> nullptr).
+// whose family has no row here is refused by every batched entry (launch_family -> nullptr; RecordedBatch::check, recorded_batch.h).
 struct LaunchFamilyRow {
     int family;
     size_t block_bytes;

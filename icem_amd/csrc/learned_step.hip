@@ -11,11 +11,13 @@
 //   update   update_small_batch_kernel (k_merge.hip): icem_update_distribution's body, one workgroup per problem; the last
 //            one carries the epilogue (icem_shift's arithmetic, executed, best_cost, the results row)
 // i.e. 3 launches per iteration, + 1 in the steps that shift elites.  The step shares icem_plan_step_batch's plumbing rather
-// than restating it: the argument blocks live in a DeviceArgArray (arg_array.h) with the step's first handle, stream offsets
-// relative to each problem's base (BatchBases, call_base), uploaded only when a byte changed -- the steady state uploads
-// nothing; a batch is admitted by admit_batch; noise offsets, shifted rows and elite halves are host_common.h's call_base,
-// shift_rows and elite_parity, so a controller may alternate between the two steps.  A batch's rows sit back to back in a
-// pool of the first handle's (the batched rollout wants them contiguous); one problem alone uses its own actions / costs buffers.
+// than restating it: the argument blocks live in a DeviceArgArray (arg_array.h) with the step's first handle, their sections laid
+// out by block_layout.h, stream offsets relative to each problem's base (BatchBases, call_base), uploaded only when a byte
+// changed -- the steady state uploads nothing; a batch is admitted by admit_batch; noise offsets, shifted rows and elite halves
+// are host_common.h's call_base, shift_rows and elite_parity, so a controller may alternate between the two steps.  A batch's
+// rows sit back to back in a pool of the first handle's (LearnedCtx: the batched rollout wants them contiguous); one problem
+// alone uses its own actions / costs buffers.
+#include "block_layout.h"
 #include "host_common.h"
 #include "icem_rssm.h"
 
@@ -46,8 +48,6 @@ const char* learned_unserved(const icem_handle* h) {
     if (!rssm_split_ok(max_rows(h), c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
     return nullptr;
 }
-
-size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
                  void* results, hipStream_t st) {
@@ -91,14 +91,16 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     if (!ctx->idx) ICEM_HIP_TRY(hipMalloc((void**)&ctx->idx, (size_t)ICEM_MAX_BATCH * ICEM_MAX_ELITES * sizeof(int)));
     const size_t cap_rows = (size_t)n * (size_t)max_rows(h0);   // (what any mix of steps of this batch size needs)
     if (n > 1) ICEM_HIP_TRY(ctx->reserve(cap_rows, n, hd, st));
-    float* pool_a = ctx->pool;
-    float* pool_c = ctx->pool ? ctx->pool + ctx->pool_rows * (size_t)hd : nullptr;
-    float* pool_o = ctx->pool ? pool_c + ctx->pool_rows : nullptr;
-    // ---- argument blocks: per iteration [sample x n | update x n], then [shift x n] ----
+    float* pool_a = ctx->pool_actions();
+    float* pool_c = ctx->pool_costs(hd);
+    float* pool_o = ctx->pool_obs(hd);
+    // ---- argument blocks (block_layout.h): per iteration [sample x n | update x n], then [shift x n] ----
     const size_t sb = sizeof(FastSampleArgs), ub = sizeof(UpdateFinishArgs), hb = gk_shift_sample_block_bytes();
-    const size_t per_it = padded(sb * n) + padded(ub * n);
-    const size_t bytes = per_it * iters + padded(hb * n);
-    std::vector<unsigned char> blob(bytes, 0);
+    BlockLayout part(n, ICEM_MAX_BATCH), tail(n, ICEM_MAX_BATCH);
+    part.add(sb);   // (at 0)
+    const size_t at_update = part.add(ub), per_it = part.bytes(), at_shift = per_it * iters;
+    tail.add(hb);
+    std::vector<unsigned char> blob(at_shift + tail.bytes(), 0);
     BatchBases bases{};
     for (int p = 0; p < n; ++p) bases.v[p] = call_base(handles[p], steps[p]);
     for (int it = 0; it < iters; ++it) {
@@ -127,8 +129,8 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             s.white = c.noise_beta <= 0 ? 1 : 0;
             if (it == 0)
                 gk_shift_sample_block(h, n_shift, b.mean, b.std, b.low, b.high, (uint64_t)iters, el_r, acts + (size_t)n_it * hd,
-                                      blob.data() + per_it * iters + hb * p);
-            UpdateFinishArgs& u = *(UpdateFinishArgs*)(blob.data() + per_it * it + padded(sb * n) + ub * p);
+                                      blob.data() + at_shift + hb * p);
+            UpdateFinishArgs& u = *(UpdateFinishArgs*)(blob.data() + per_it * it + at_update + ub * p);
             const bool keep = it > 0 && c.keep_previous_elites && n_reuse > 0;
             u.u.costs = csts, u.u.pool = acts;
             u.u.keep_costs = keep ? ec_r : nullptr, u.u.keep_actions = keep ? el_r : nullptr;
@@ -142,13 +144,12 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
                 u.init_std = (float)c.init_std;
                 u.low = (const float*)b.low, u.high = (const float*)b.high;
                 u.executed = (float*)b.executed, u.best_cost = (float*)b.best_cost;
-                u.result = results ? (float*)results + (size_t)p * (d + 1) : nullptr;
+                u.result = (float*)results_row(results, p, (size_t)(d + 1) * sizeof(float));
             }
         }
     }
     const int slot = steps[0] & 1;
-    const size_t room = (padded(sb * ICEM_MAX_BATCH) + padded(ub * ICEM_MAX_BATCH)) * iters + padded(hb * ICEM_MAX_BATCH);
-    ICEM_HIP_TRY(ctx->args.put(slot, blob, room, st, &h0->batch_uploads));
+    ICEM_HIP_TRY(ctx->args.put(slot, blob, part.room() * iters + tail.room(), st, &h0->batch_uploads));
     // ---- the launches ----
     const unsigned char* dev = (const unsigned char*)ctx->args.dev(slot);
     long long launches = 0;
@@ -167,7 +168,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
         if (it == 0 && shift_max > 0) {
-            if (int rc = gk_shift_sample_batch(h0, n, shift_max, dev + per_it * iters, bases, st)) return rc;
+            if (int rc = gk_shift_sample_batch(h0, n, shift_max, dev + at_shift, bases, st)) return rc;
             ++launches;
         }
         hipError_t e;
@@ -178,7 +179,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             e = launch_rssm_split_batch(n, &rows[(size_t)it * n], H, c.cost_mode, (const unsigned short*)params, pool_o, pool_a, pool_c, st);
         if (int rc = rssm_launch_result(e)) return rc;
         ++launches;
-        launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + padded(sb * n)), n, it == iters - 1, st);
+        launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + at_update), n, it == iters - 1, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
     }

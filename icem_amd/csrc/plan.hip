@@ -4,6 +4,7 @@
 // where a sharded rank's record pack rides (own launch or workgroup 0 of the next local launch), which trailing
 // shifted-elite rows go around the candidate lists, and which of the ping-pong buffers each launch reads and writes.  No device code here except the result publisher.
 #include "host_common.h"
+#include "recorded_batch.h"
 #include "cost_terms_dev.h"
 
 using namespace icem;
@@ -1526,10 +1527,10 @@ static const char* batch_ineligible(icem_handle* h, const icem_plan_buffers* b, 
     return nullptr;
 }
 
-// What the batched entries share behind their admission: the host side of every problem's step under a recorder, the
-// comparison of the problems' launch keys, the argument blob in handles[0]'s six-slot array (uploaded only when a byte changed),
-// one launch per recorded launch.  who: the entry's name for messages; spare: room a new array gets beyond the first blob (a later
-// step's blob may be larger: shifted elites); *launches_out: the kernel launches issued.
+// What the batched entries share behind their admission: the host side of every problem's step under a recorder, then the
+// recorded-launch plan (recorded_batch.h: comparison, placement, copy, launch) with the blob in handles[0]'s six-slot array.
+// who: the entry's name for messages; spare: room a new array gets beyond the first blob (a later step's blob may be larger:
+// shifted elites -- so the room is this rule, not the layout's); *launches_out: the kernel launches issued.
 static int run_recorded_batch(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, int32_t mpc_step, hipStream_t st,
                               const BatchHint& hint, const std::string& who, size_t spare, long long* launches_out) {
     // ---- the host side of every problem's step, recorded ----
@@ -1544,48 +1545,34 @@ static int run_recorded_batch(icem_handle* const* handles, int n, const icem_pla
         }
     } disarm_all{handles, n};
     BatchBases bases{};   // each problem's noise stream base of this step: the recorded blocks' offsets are relative to it
-    std::vector<LaunchRecorder> recs(n);
-    int rc = ICEM_OK;
+    RecordedBatch rb(n);
     bool unsupported = false;
-    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        recs[i].base = bases.v[i] = call_base(handles[i], mpc_step);
-        recs[i].who = who.c_str();
-        recs[i].launches.reserve(3 * handles[i]->cfg.opt_iters + 2);   // (the float64 step's count; the f32 plans record 2 * iters + 1)
-        rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &recs[i]});
-        unsupported = unsupported || recs[i].unsupported;
+    for (int i = 0; i < n; ++i) {
+        LaunchRecorder& rec = rb.recs[i];
+        rec.base = bases.v[i] = call_base(handles[i], mpc_step);
+        rec.who = who.c_str();
+        rec.launches.reserve(3 * handles[i]->cfg.opt_iters + 2);   // (the float64 step's count; the f32 plans record 2 * iters + 1)
+        if (int rc = plan_step_body(handles[i], &buffers[i], mpc_step, LaunchCtx{st, hint, &rec})) return rc;
+        unsupported = unsupported || rec.unsupported;
     }
-    if (rc == ICEM_OK && unsupported) rc = fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached");
-    const std::vector<LaunchDesc>& first = recs[0].launches;
-    const size_t L = first.size();
-    for (int i = 0; i < n && rc == ICEM_OK; ++i) {
-        if (recs[i].launches.size() != L || L == 0) rc = fail(ICEM_E_STATE, who + "the problems' steps took different launches");
-        for (size_t l = 0; l < L && rc == ICEM_OK; ++l)
-            if (!(recs[i].launches[l].key == first[l].key)) rc = fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
-    }
-    if (rc != ICEM_OK) return rc;   // nothing was launched: the handles' half-armed state goes
+    if (unsupported) return fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached");
+    if (int rc = rb.check(who)) return rc;   // nothing was launched: the handles' half-armed state goes
     // ---- argument blocks: one array per launch ----
-    std::vector<size_t> at(L);
-    size_t bytes = 0;
-    for (size_t l = 0; l < L; ++l) {
-        at[l] = bytes;
-        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
-        bytes += ((launch_family(first[l].key.family)->block_bytes * (size_t)n + 255) / 256) * 256;
-    }
+    BlockLayout layout(n, ICEM_MAX_BATCH);
+    rb.place(layout);
+    const size_t bytes = layout.bytes();
     std::vector<unsigned char> blob(bytes, 0);
-    for (size_t l = 0; l < L; ++l) {
-        const size_t one = launch_family(first[l].key.family)->block_bytes;
-        for (int i = 0; i < n; ++i) std::memcpy(blob.data() + at[l] + (size_t)i * one, recs[i].launches[l].block, one);
-    }
+    for (int i = 0; i < n; ++i) rb.copy(i, blob.data());
     icem_handle* owner = handles[0];
     const int slot = mpc_step % 6;
     if (opt_i(OPT_AHEAD_STAMPS) && owner->batch_args.holds(slot).size() == bytes) {   // development: which bytes moved
         const std::vector<unsigned char>& held = owner->batch_args.holds(slot);
         int shown = 0;
-        for (size_t l = 0; l < L && shown < 12; ++l) {
-            const size_t one = launch_family(first[l].key.family)->block_bytes;
+        for (size_t l = 0; l < rb.launches() && shown < 12; ++l) {
+            const size_t one = rb.block_bytes(l);
             for (size_t o = 0; o < one * (size_t)n && shown < 12; ++o)
-                if (blob[at[l] + o] != held[at[l] + o]) {
-                    std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, first[l].key.family, o / one, o % one);
+                if (blob[rb.at[l] + o] != held[rb.at[l] + o]) {
+                    std::fprintf(stderr, "batch args changed: step %d launch %zu kind %d problem %zu byte %zu\n", mpc_step, l, rb.key(l).family, o / one, o % one);
                     ++shown;
                     o = (o / 8 + 1) * 8 - 1;
                 }
@@ -1593,12 +1580,10 @@ static int run_recorded_batch(icem_handle* const* handles, int n, const icem_pla
     }
     ICEM_HIP_TRY(owner->batch_args.put(slot, blob, bytes + spare, st, &owner->batch_uploads));
     // ---- the launches ----
-    for (size_t l = 0; l < L; ++l) {
-        launch_family(first[l].key.family)->launch(first[l].key, (const unsigned char*)owner->batch_args.dev(slot) + at[l], bases, n, st);
-        ICEM_HIP_TRY(hipGetLastError());
-    }
+    long long launches = 0;
+    if (int rc = rb.launch((const unsigned char*)owner->batch_args.dev(slot), bases, st, &launches)) return rc;
     disarm_all.armed = false;
-    if (launches_out) *launches_out = (long long)L;
+    if (launches_out) *launches_out = launches;
     return ICEM_OK;
 }
 

@@ -7,10 +7,11 @@
 // The arguments go by value.  The entry keeps no step state: the call offset (MpcRandom's counter of sample() calls) is the caller's.
 //
 // icem_plan_step_random_batch is the same step for B planners of one configuration, every stage ONE launch for all of them:
-// random_sample_batch_kernel, the batched twin of the handles' rollout launch (LAUNCH_FAMILIES, icem_fused.h; recorded per handle,
-// compared, issued once -- cem_step.hip's arrangement), random_select_batch_kernel.  The argument blocks live in a DeviceArgArray of
-// the first handle and carry no step-dependent value (the call offsets travel by value): a batch whose buffers stay put uploads them once.
+// random_sample_batch_kernel, the batched twin of the handles' rollout launch (the recorded-launch plan, recorded_batch.h),
+// random_select_batch_kernel.  The argument blocks live in a DeviceArgArray of the first handle, laid out by block_layout.h, and carry
+// no step-dependent value (the call offsets travel by value): a batch whose buffers stay put uploads them once.
 #include "random_step.h"
+#include "recorded_batch.h"
 
 using namespace icem;
 
@@ -87,8 +88,6 @@ int random_step_solo(icem_handle* h, const icem_random_buffers* b, int32_t chang
     return ICEM_OK;
 }
 
-size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
 // B > 1 planners behind the admission of the batch.  Host state: the first handle's argument array (+ its upload counter) and its
 // random_batch_launches, written behind the last launch; each handle's RandomWs (allocated once, whatever happens later).
 // Recording a handle's rollout may upload that handle's packed model (idempotent, what its next solo step would do first).
@@ -96,67 +95,36 @@ int random_step_batch(icem_handle* const* handles, int n, const icem_random_buff
                       void* results, hipStream_t st) {
     const std::string who = "icem_plan_step_random_batch: ";
     icem_handle* h0 = handles[0];
-    const icem_config& c = h0->cfg;
-    const int N = c.num_traj, d = c.act_dim;
-    // ---- every problem's rollout launch, recorded: its batched family, its key, its argument block ----
-    BatchHint hint;
-    hint.mult = n;
-    std::vector<LaunchRecorder> recs(n);
-    for (int i = 0; i < n; ++i) {
-        recs[i].who = "icem_plan_step_random_batch: ";
-        const icem_random_buffers& b = buffers[i];
-        if (int rc = rollout_cost_launch(handles[i], N, b.obs0, b.actions, b.costs, nullptr, LaunchCtx{st, hint, &recs[i]})) return rc;
-        if (recs[i].unsupported) return fail(ICEM_E_UNSUPPORTED, who + "a launch without a batched form was reached (this handle's rollout kernel has no batched twin)");
-    }
-    const std::vector<LaunchDesc>& first = recs[0].launches;
-    const size_t L = first.size();
-    for (int i = 0; i < n; ++i) {
-        if (recs[i].launches.size() != L || L == 0) return fail(ICEM_E_STATE, who + "the problems' steps took different launches");
-        for (size_t l = 0; l < L; ++l)
-            if (!(recs[i].launches[l].key == first[l].key)) return fail(ICEM_E_STATE, who + "the problems' launches differ in shape");
-    }
-    for (size_t l = 0; l < L; ++l)
-        if (!launch_family(first[l].key.family)) return fail(ICEM_E_STATE, who + "a recorded launch's family has no batched launch");
+    // ---- every problem's rollout launch, recorded and compared (recorded_batch.h) ----
+    RecordedBatch rb(n);
+    for (int i = 0; i < n; ++i)
+        if (int rc = record_rollout(rb, i, handles[i], buffers[i].obs0, buffers[i].actions, buffers[i].costs, st, who)) return rc;
+    if (int rc = rb.check(who)) return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = reserve_ws(handles[i], st)) return rc;
     // ---- argument blocks: [sample x n | rollout launch(es) x n | select x n] ----
     const size_t sb = random_sample_block_bytes(h0), ub = random_select_block_bytes(h0);
-    std::vector<size_t> at(L);
-    size_t total = padded(sb * n), room = padded(sb * ICEM_MAX_BATCH);
-    for (size_t l = 0; l < L; ++l) {
-        at[l] = total;
-        total += padded(launch_family(first[l].key.family)->block_bytes * n);
-        room += padded(launch_family(first[l].key.family)->block_bytes * ICEM_MAX_BATCH);
-    }
-    const size_t at_select = total;
-    total += padded(ub * n);
-    room += padded(ub * ICEM_MAX_BATCH);
-    std::vector<unsigned char> blob(total, 0);
+    BlockLayout layout(n, ICEM_MAX_BATCH);
+    layout.add(sb);   // (at 0)
+    rb.place(layout);
+    const size_t at_select = layout.add(ub);
+    std::vector<unsigned char> blob(layout.bytes(), 0);
     BatchBases bases{};
     for (int i = 0; i < n; ++i) {
         const icem_random_buffers& b = buffers[i];
         bases.v[i] = (unsigned long long)offsets[i];
         random_sample_block(handles[i], b, change_freq, 0, 0, nullptr, blob.data() + sb * i);
-        for (size_t l = 0; l < L; ++l) {
-            const size_t one = launch_family(first[l].key.family)->block_bytes;
-            std::memcpy(blob.data() + at[l] + one * i, recs[i].launches[l].block, one);
-        }
-        void* row = results ? (unsigned char*)results + (size_t)i * (d + 2) * h0->tsize : nullptr;
-        random_select_block(handles[i], b, row, blob.data() + at_select + ub * i);
+        rb.copy(i, blob.data());
+        random_select_block(handles[i], b, results_row(results, i, (size_t)(h0->cfg.act_dim + 2) * h0->tsize), blob.data() + at_select + ub * i);
     }
-    ICEM_HIP_TRY(h0->random_batch_args.put(0, blob, room, st, &h0->batch_uploads));
+    ICEM_HIP_TRY(h0->random_batch_args.put(0, blob, layout.room(), st, &h0->batch_uploads));
     // ---- the launches ----
     const unsigned char* dev = (const unsigned char*)h0->random_batch_args.dev(0);
     long long launches = 0;
     launch_random_sample_batch(h0, dev, bases, n, st);
     ICEM_HIP_TRY(hipGetLastError());
     ++launches;
-    const BatchBases none{};   // (a rollout draws nothing)
-    for (size_t l = 0; l < L; ++l) {
-        launch_family(first[l].key.family)->launch(first[l].key, dev + at[l], none, n, st);
-        ICEM_HIP_TRY(hipGetLastError());
-        ++launches;
-    }
+    if (int rc = rb.launch(dev, BatchBases{}, st, &launches)) return rc;   // (a rollout draws nothing: no bases)
     launch_random_select_batch(h0, dev + at_select, n, st);
     ICEM_HIP_TRY(hipGetLastError());
     ++launches;
