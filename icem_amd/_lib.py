@@ -152,6 +152,10 @@ SYMBOLS = [
     ("icem_random_step_launches", C.c_int64, [_H]),
     ("icem_plan_step_random_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemRandomBuffersC), _I32, C.POINTER(_I64), _VP, _VP]),
     ("icem_random_batch_launches", C.c_int64, [_H]),
+    ("icem_plan_step_random_learned_ok", C.c_int, [_H]),
+    ("icem_plan_step_random_learned", C.c_int, [_H, C.POINTER(IcemRandomBuffersC), _VP, _I32, _I64, _VP]),
+    ("icem_plan_step_random_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemRandomBuffersC), _VP, _I32, C.POINTER(_I64),
+                                                      _VP, _VP]),
     ("icem_rccl_load", C.c_int, [C.c_char_p]),
     ("icem_rccl_library", C.c_char_p, []),
     ("icem_rccl_unique_id", C.c_int, [_VP]),

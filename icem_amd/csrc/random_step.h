@@ -58,4 +58,18 @@ void launch_random_select(const icem_handle* h, const void* block, hipStream_t s
 void launch_random_sample_batch(const icem_handle* h, const void* args_dev, const BatchBases& bases, int n_problems, hipStream_t st);
 void launch_random_select_batch(const icem_handle* h, const void* args_dev, int n_problems, hipStream_t st);
 
+// ---- icem_plan_step_random_learned_batch (k_random_learned.hip): the same blocks, the rows scored in a pool ----
+// the pool of a batch's first handle (LearnedCtx), by value: problem p's slice is actions + p * N * hd, costs + p * N
+template <typename T>
+struct RandomPool {
+    T* actions;
+    T* costs;
+};
+// the batched sampler on the pool's slices, every store mirrored into the problem's own actions; the workgroups of
+// blockIdx.x == 0 also copy their problem's observation og.src[p] [og.width] to og.dst + p * og.width (ObsGather: icem_fused.h)
+void launch_random_sample_gather_batch(const icem_handle* h, const void* args_dev, const BatchBases& bases, const ObsGather& og,
+                                       const RandomPool<float>& pool, int n_problems, hipStream_t st);
+// the batched selection on the pool's slices, every cost it reads stored into the problem's own costs
+void launch_random_select_pool_batch(const icem_handle* h, const void* args_dev, const RandomPool<float>& pool, int n_problems, hipStream_t st);
+
 }  // namespace icem

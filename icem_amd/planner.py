@@ -708,34 +708,39 @@ class IcemPlanner:
         """Kernel launches of the last batched random-shooting step this planner led (``icem_random_batch_launches``)."""
         return int(self.lib.icem_random_batch_launches(self._h))
 
-    def _random_buffers(self):
+    def _random_buffers(self, obs: Optional[str] = None):
         """The step's buffers, owned by the planner (a captured step replays into the same tensors): the pool and its
         costs, the cheapest row, ``result`` = ``[executed | best cost | best index]`` (one device-to-host copy fetches all
-        three), the observation and the step's ``icem_random_buffers``."""
+        three).  ``obs``: also the observation buffer of that name -- ``"obs0"`` ``[obs_dim]`` for the built-in model,
+        ``"obs_rssm"`` ``[230]`` f32 for the learned-dynamics step (no model need be set for it) -- and under ``"cb_" + obs``
+        the step's ``icem_random_buffers`` with it."""
         b = getattr(self, "_random", None)
+        new = lambda *shape, dt=self.dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
         if b is None:
-            if self.obs_dim == 0:
-                raise RuntimeError("set_model()/set_cost() must be called before planning")
-            new = lambda *shape: torch.zeros(shape, dtype=self.dt, device=self.device)  # noqa: E731
             n = self.cfg.num_traj
             b = self._random = dict(actions=new(n, self.h, self.d), costs=new(n), best_actions=new(self.h, self.d),
-                                    result=new(self.d + 2), obs0=new(self.obs_dim))
-            b["cb"] = L.IcemRandomBuffersC(
-                low=self.low.data_ptr(), high=self.high.data_ptr(), obs0=b["obs0"].data_ptr(), actions=b["actions"].data_ptr(),
+                                    result=new(self.d + 2), obs0=None, obs_rssm=None)
+        if obs is not None and b[obs] is None:
+            if obs == "obs0" and self.obs_dim == 0:
+                raise RuntimeError("set_model()/set_cost() must be called before planning")
+            b[obs] = new(self.obs_dim) if obs == "obs0" else new(L.RSSM_OBS_DIM, dt=torch.float32)
+            b["cb_" + obs] = L.IcemRandomBuffersC(
+                low=self.low.data_ptr(), high=self.high.data_ptr(), obs0=b[obs].data_ptr(), actions=b["actions"].data_ptr(),
                 costs=b["costs"].data_ptr(), best_actions=b["best_actions"].data_ptr(), result=b["result"].data_ptr())
         return b
 
-    def _random_cb(self, obs) -> "L.IcemRandomBuffersC":
-        """The observation into the planner's own buffer; the step's ``icem_random_buffers``."""
-        b = self._random_buffers()
-        dst = b["obs0"]
+    def _random_cb(self, obs, which: str = "obs0") -> "L.IcemRandomBuffersC":
+        """The observation into the planner's own buffer (``which``: the built-in model's or the learned-dynamics step's,
+        :meth:`_random_buffers`); the step's ``icem_random_buffers``."""
+        b = self._random_buffers(which)
+        dst = b[which]
         if isinstance(obs, torch.Tensor) and obs.device == self.device:
             if obs.numel() != dst.numel():
                 raise ValueError(f"expected an observation of {dst.numel()} values")
             dst.copy_(obs.reshape(-1))
         else:
             dst.copy_(torch.as_tensor(np.asarray(obs, dtype=np.float64).reshape(dst.numel()), dtype=dst.dtype))
-        return b["cb"]
+        return b["cb_" + which]
 
     random_actions = property(lambda self: self._random_buffers()["actions"])
     random_costs = property(lambda self: self._random_buffers()["costs"])
@@ -783,6 +788,50 @@ class IcemPlanner:
         return res[:, :p0.d]
 
     random_batch_results = property(lambda self: getattr(self, "_random_batch_results", None))
+
+    def random_learned_step_ok(self) -> bool:
+        """Does ``icem_plan_step_random_learned`` serve THIS handle?  (:meth:`random_step_ok`'s conditions, f32, six action
+        dimensions, a population the RSSM's split launch takes: asked of the handle.)"""
+        return bool(self.lib.icem_plan_step_random_learned_ok(self._h))
+
+    def plan_step_random_learned(self, model, obs, call_offset: int, change_freq: int) -> torch.Tensor:
+        """:meth:`plan_step_random` through ``model`` (a ``DeviceRSSMModel``: its packed ``params``) as
+        ``icem_plan_step_random_learned``.  ``obs``: the observation ``[230]`` (array-like, or a device tensor); no built-in
+        model or cost need be set; the uniforms are the device's.  The same views, return value and launch count
+        (:attr:`random_step_launches`) as :meth:`plan_step_random`, and the same bits as the operator chain
+        (``sample_piecewise``, ``model.rollout_cost``, ``topk_sorted(costs, 1)`` and the gathers).  Raises ``IcemError``
+        before anything runs where the step is refused."""
+        cb = self._random_cb(obs, "obs_rssm")
+        L.check(self.lib.icem_plan_step_random_learned(self._h, C.byref(cb), C.c_void_p(model.params.data_ptr()), int(change_freq),
+                                                       int(call_offset), self._stream()))
+        return self._random_buffers()["result"][:self.d]
+
+    @staticmethod
+    def plan_step_random_learned_batch(planners: Sequence["IcemPlanner"], model, observations, call_offsets, change_freq: int) -> torch.Tensor:
+        """:meth:`plan_step_random_learned` of every planner of ``planners`` (one configuration; seeds, observations and call
+        offsets of their own) through the one ``model`` as ``icem_plan_step_random_learned_batch``: 3 launches for all of
+        them.  Each planner's ``random_*`` views afterwards -- its pool and costs included -- are bit for bit those of its own
+        :meth:`plan_step_random_learned`.  Returns the executed actions ``[B, d]``, a view of
+        ``planners[0].random_batch_results`` ``[B, d + 2]`` (kept per batch size).  Raises ``IcemError`` before anything runs
+        where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_random_learned_batch(None, 0, None, None, 0, None, None, None))
+        p0 = pls[0]
+        observations, call_offsets = list(observations), list(call_offsets)
+        if len(observations) != n or len(call_offsets) != n:
+            raise ValueError("one observation and one call offset per planner")
+        cbs = [pl._random_cb(ob, "obs_rssm") for pl, ob in zip(pls, observations)]
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemRandomBuffersC * n)(*cbs)
+        offs = (C.c_int64 * n)(*[int(o) for o in call_offsets])
+        res = getattr(p0, "_random_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
+        if res is None or res.shape[0] != n:
+            res = p0._random_batch_results = torch.zeros((n, p0.d + 2), dtype=p0.dt, device=p0.device)
+        L.check(p0.lib.icem_plan_step_random_learned_batch(hs, n, bs, C.c_void_p(model.params.data_ptr()), int(change_freq), offs,
+                                                           _ptr(res), p0._stream()))
+        return res[:, :p0.d]
 
     # ------------------------------------------------------------------ ... through the learned dynamics (declared RSSM)
     def cem_learned_step_ok(self) -> bool:

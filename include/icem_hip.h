@@ -371,6 +371,40 @@ int     icem_plan_step_random_batch(icem_handle* const* handles, int32_t n, cons
                                     int32_t change_freq, const int64_t* call_offsets_host, void* results, void* stream);
 int64_t icem_random_batch_launches(const icem_handle* h); /* kernel launches of the last such batch this handle led as handles[0]; measurement */
 
+/* The same MPC step through the LEARNED dynamics (the declared RSSM): the chain icem_sample_piecewise (the device's own uniforms),
+ * icem_rssm_rollout_cost(params: its packed parameter buffer, shared by the problems of a batch) under the handle's cost_mode,
+ * icem_topk_sorted(costs, 1) and the gathers behind it, as ONE call for one planner or for n planners of one configuration.
+ * icem_random_buffers is icem_plan_step_random's: b->obs0 is [ICEM_RSSM_OBS_DIM] f32.  External uniforms are not offered.  No
+ * built-in model or cost need be set on the handle.  call_offset(s) are the caller's, as above: the chain, the solo entry and the
+ * batched entry may alternate freely, and so may these entries and icem_plan_step_random* on one handle.
+ *   3 launches whatever n (icem_random_step_launches for the solo entry, icem_random_batch_launches of handles[0] for the batched
+ * one), no host synchronisation, no allocation after the first call of a batch size on a stream.  Every output of the solo entry
+ * -- actions, costs, best_actions, result -- is bit for bit what the chain leaves.  A batch scores its rows back to back in a pool
+ * owned by handles[0] (the batched RSSM launch wants them contiguous); its sampler writes every row into the pool AND into the
+ * problem's own actions, its selection leaves every cost in the problem's own costs: EVERY buffer of EVERY problem -- actions,
+ * costs, best_actions, result, its row of results ([n, d + 2] f32; may be NULL) -- is bit for bit its solo step's at the same seed
+ * and offset (a controller keeps its pool; icem_plan_step_cem_learned_batch, whose pools are scratch, promises less).  The
+ * problems' obs0 buffers need not be adjacent: the sampler launch gathers them into the pool's [n, 230] table.  The argument blocks
+ * are those of icem_plan_step_random_batch, in the same device array of handles[0], uploaded only when a byte changed.  n == 1 is
+ * the solo step plus the results row.
+ *   Served: whatever icem_plan_step_random_ok asks of the handle, f32, act_dim == 6, a population the RSSM's split launch takes (for
+ * a batch: all problems' tiles together; development option rssm_split = 0 switches the entries off, as random_step = 0 does), any
+ * horizon that launch accepts.  ICEM_E_INVALID: a NULL handle / buffers / params, a NULL buffer, change_freq < 0 or >= horizon, a
+ * negative call offset, n outside [1, 32], a handle twice, unequal configurations; ICEM_E_UNSUPPORTED: anything not served;
+ * ICEM_E_STATE: the learned-dynamics rollout's own rules (icem_plan_step_cem_learned).  Whatever is refused is refused before
+ * anything is launched or any handle touched.
+ *   Measured (EXPERIMENTS R22.1; N = 1024, h = 12, change_freq 4, MpcRandomHip.get_action): 0.123 ms against 0.148 ms for the
+ * operator chain in the same process and 0.145 ms on the parent commit's library (1.2 x: the chain's three device-to-host reads and its
+ * allocations are gone; the rollout's 74 us are the same in both, the three launches together 82 us).  Batched, per step of the
+ * batch against B solo steps: B = 2 0.12 / 0.19 ms, B = 4 0.19 / 0.36, B = 8 0.29 / 0.69, B = 16 0.43 / 1.34 ms (1.5 x to 3.2 x); on
+ * the device B = 16 is 376 us, 23.5 us per problem, 332 us of them the batched rollout (20.8 us per problem). */
+int     icem_plan_step_random_learned_ok(const icem_handle* h);   /* 1 if THIS handle is served, else 0 */
+int     icem_plan_step_random_learned(icem_handle* h, const icem_random_buffers* b, const void* params, int32_t change_freq,
+                                      int64_t call_offset, void* stream);
+int     icem_plan_step_random_learned_batch(icem_handle* const* handles, int32_t n, const icem_random_buffers* buffers,
+                                            const void* params, int32_t change_freq, const int64_t* call_offsets_host,
+                                            void* results, void* stream);
+
 /* Raw white noise of the Philox path (for RNG known-answer tests): z_r, z_i [n, d, F]. */
 int icem_philox_normals(icem_handle* h, int32_t n, int64_t first_index, uint64_t offset,
                         void* z_r, void* z_i, void* stream);

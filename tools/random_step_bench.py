@@ -19,6 +19,15 @@ BLOCKS blocks.
                                                  the one device-to-host copy of its results) alternating with blocks of B solo
                                                  ``icem_plan_step_random`` steps issued back to back (each block step ending in one
                                                  synchronisation); B may be a list (2,4,8,16).
+  ... --learned                                  every mode above through the learned dynamics (``DeviceRSSMModel``; N = 1024, h = 12,
+                                                 hold 4): ``icem_plan_step_random_learned`` against the chain, ``--stagewise`` for the
+                                                 chain alone (also on the parent commit's library), ``--batch B`` for
+                                                 ``icem_plan_step_random_learned_batch`` against B solo fused steps
+  python tools/random_step_bench.py --learned --events [--batch 2,4,8,16]
+                                                 device times from HIP events around EVENT_REPS back-to-back launches, per launch:
+                                                 the chain's sampler, rollout and selection one by one, the solo fused step as a
+                                                 whole, and per B the batched step as a whole and its batched rollout alone (the
+                                                 difference is the batch's sampler + selection)
 """
 import ctypes as C
 import os
@@ -34,6 +43,18 @@ from icem_amd import _lib as L  # noqa: E402
 H, D, O_, FREQ, SIZES = 30, 6, 17, 4, (512, 4096)
 WARMUP, BLOCK, BLOCKS, TRACE_STEPS = 20, 200, 9, 50
 BATCH_BLOCK, BATCH_BLOCKS, BATCH_WARMUP = 30, 7, 10
+LEARNED = "--learned" in sys.argv
+if LEARNED:   # the declared RSSM's shape (BASELINE configs[4])
+    H, O_, SIZES = 12, 230, (1024,)
+EVENT_REPS, EVENT_BLOCKS = 50, 5
+_model = {}
+
+
+def rssm():
+    from icem_amd import DeviceRSSMModel
+    if "m" not in _model:
+        _model["m"] = DeviceRSSMModel(seed=3)
+    return _model["m"]
 
 
 def bind_what_the_library_has():
@@ -44,7 +65,7 @@ def bind_what_the_library_has():
 
 def controller(n, fused):
     from icem_amd import DeviceSyntheticModel, MpcRandomHip, halfcheetah_env
-    c = MpcRandomHip(env=halfcheetah_env(O_), forward_model=DeviceSyntheticModel.make(O_, D, kind=0), horizon=H,
+    c = MpcRandomHip(env=halfcheetah_env(17 if LEARNED else O_), forward_model=rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0), horizon=H,
                      num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=1, fused_step=fused,
                      action_sampler_params=dict(action_change_frequency=FREQ))
     c.beginning_of_rollout(observation=np.zeros(O_), state=None, mode="train")
@@ -72,14 +93,15 @@ def _arg(flag, default):
 
 def batch_planners(n, B, dtype):
     from icem_amd import DeviceSyntheticModel, IcemConfig, IcemPlanner, halfcheetah_env
-    env = halfcheetah_env(O_)
+    env = halfcheetah_env(17 if LEARNED else O_)
     out = []
     for i in range(B):
         pl = IcemPlanner(IcemConfig(horizon=H, act_dim=D, num_traj=n, elites_size=2, opt_iters=1, cost_mode="sum", dtype=dtype, seed=1 + i),
                          env.action_space.low, env.action_space.high)
-        m = DeviceSyntheticModel.make(O_, D, kind=0)
-        pl.set_model(m.kind, m.A, m.B)
-        pl.set_cost_spec(env.cost_spec)
+        if not LEARNED:
+            m = DeviceSyntheticModel.make(O_, D, kind=0)
+            pl.set_model(m.kind, m.A, m.B)
+            pl.set_cost_spec(env.cost_spec)
         out.append(pl)
     return out
 
@@ -102,10 +124,16 @@ def main_batch():
                 ps, off = both[kind], calls[kind]
                 calls[kind] += n * H
                 if kind == "batched":
-                    IcemPlanner.plan_step_random_batch(ps, obs, [off] * B, FREQ)
+                    if LEARNED:
+                        IcemPlanner.plan_step_random_learned_batch(ps, rssm(), obs, [off] * B, FREQ)
+                    else:
+                        IcemPlanner.plan_step_random_batch(ps, obs, [off] * B, FREQ)
                     return ps[0].random_batch_results.cpu()   # the batch's one device-to-host copy
                 for p, ob in zip(ps, obs):
-                    p.plan_step_random(ob, off, FREQ)
+                    if LEARNED:
+                        p.plan_step_random_learned(rssm(), ob, off, FREQ)
+                    else:
+                        p.plan_step_random(ob, off, FREQ)
                 torch.cuda.synchronize()
                 return None
 
@@ -132,6 +160,54 @@ def main_batch():
                   f"{both['batched'][0].random_batch_launches}, uploads {both['batched'][0].batch_uploads}", flush=True)
 
 
+def event_us(fn, reps=EVENT_REPS, blocks=EVENT_BLOCKS):
+    """us per call of fn from HIP events around `reps` back-to-back calls: (min, median, max) over `blocks` blocks."""
+    for _ in range(5):
+        fn()
+    out = []
+    for _ in range(blocks):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) / reps * 1e3)
+    out.sort()
+    return out[0], out[len(out) // 2], out[-1]
+
+
+def main_events():
+    """Device times per launch (HIP events; the host enqueues ahead, so these are the launches' own times plus the gaps between
+    launches of one stream)."""
+    from icem_amd import IcemPlanner
+    n = SIZES[0]
+    lib = L.load_library()
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  N = {n}, h = {H}, d = {D}, hold {FREQ}, f32; "
+          f"HIP events around {EVENT_REPS} back-to-back calls, {EVENT_BLOCKS} blocks: min / median / max us per call", flush=True)
+    pl = batch_planners(n, 1, "f32")[0]
+    m = rssm()
+    obs = (0.3 * np.random.RandomState(0).randn(O_)).astype(np.float32)
+    actions = pl.sample_piecewise(n, 0, FREQ, None, 0)
+    costs = m.rollout_cost(obs, actions, 0)
+    show = lambda what, t: print(f"  {what:<58s} {t[0]:8.2f} / {t[1]:8.2f} / {t[2]:8.2f}", flush=True)   # noqa: E731
+    show("chain: sample_piecewise", event_us(lambda: pl.sample_piecewise(n, 0, FREQ, None, 0)))
+    show("chain: rollout_cost (icem_rssm_rollout_cost)", event_us(lambda: m.rollout_cost(obs, actions, 0)))
+    show("chain: topk_sorted(costs, 1)", event_us(lambda: pl.topk_sorted(costs, 1)))
+    obs_t = torch.as_tensor(obs, device="cuda")
+    show("fused solo step (3 launches)", event_us(lambda: pl.plan_step_random_learned(m, obs_t, 0, FREQ)))
+    for B in [int(x) for x in _arg("--batch", "2,4,8,16").split(",")]:
+        ps = batch_planners(n, B, "f32")
+        ob = [obs_t] * B
+        t = event_us(lambda: IcemPlanner.plan_step_random_learned_batch(ps, m, ob, [0] * B, FREQ))
+        pool = torch.cat([p.random_actions for p in ps])
+        table = obs_t.repeat(B, 1).contiguous()
+        r = event_us(lambda: m.rollout_cost_batch(table, pool, [n] * B, 0))
+        show(f"batched step B = {B:2d} (3 launches)", t)
+        show(f"  its batched rollout alone; per problem of the step {t[1] / B:.2f} us", r)
+
+
 def main():
     stagewise_only, trace = "--stagewise" in sys.argv, "--trace" in sys.argv
     if stagewise_only:
@@ -139,7 +215,7 @@ def main():
     lib = L.load_library()
     print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  h = {H}, d = {D}, o = {O_}, hold {FREQ}, f32; "
           f"warm-up {WARMUP} calls", flush=True)
-    obs = 0.1 * np.random.RandomState(0).randn(O_)
+    obs = (0.3 if LEARNED else 0.1) * np.random.RandomState(0).randn(O_)
     for n in [int(x) for x in _arg("--sizes", ",".join(str(n) for n in SIZES)).split(",")]:
         # (a library without the entry: False never asks the library for it)
         ctrls = {"operator chain": controller(n, False)}
@@ -171,7 +247,9 @@ def main():
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures and has nothing to say without one")
-    if "--batch" in sys.argv:
+    if LEARNED and "--events" in sys.argv:
+        main_events()
+    elif "--batch" in sys.argv:
         main_batch()
     else:
         main()
