@@ -104,6 +104,10 @@ SYMBOLS = [
     ("icem_rssm_param_elems", _SZ, []),
     ("icem_rssm_rollout_cost", C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     ("icem_rssm_rollout_cost_batch", C.c_int, [_I32, C.POINTER(_I32), _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_rssm_rollout_cost_w", C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_rssm_rollout_cost_batch_w", C.c_int, [_I32, C.POINTER(_I32), _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_set_rssm_act_dim", C.c_int, [_VP, _I32]),
+    ("icem_rssm_act_dim", _I32, [_VP]),
     ("icem_get_action", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), _VP]),
     ("icem_set_cost_terms", C.c_int, [_H, C.POINTER(IcemCostTermsC)]),

@@ -771,7 +771,7 @@ class MpcICemHip(MpcController):
     # -- the learned-dynamics step as one library call (icem_plan_step_learned / _batch): same bits as the stage-wise loop
     def _learned_step_ok(self, noise) -> bool:
         return bool(self.rssm_path and not self.device_path and noise is None and self.planner.cfg.world == 1
-                    and not self.verbose and self._model_is_the_library_rssm() and self.planner.learned_step_ok())
+                    and not self.verbose and self._model_is_the_library_rssm() and self.planner.learned_step_ok(self.forward_model))
 
     def _elites_into_planner(self):
         """A fused step reads the kept / shifted elites from the planner's current elite half: behind a stage-wise step
@@ -1069,7 +1069,7 @@ class MpcCemStdHip(MpcController):
             return "compute_new_mean is overridden"
         if self.verbose:
             return "the controller is verbose"
-        if learned and not self.planner.cem_learned_step_ok():
+        if learned and not self.planner.cem_learned_step_ok(self.forward_model):
             return "the library does not serve this handle through the learned dynamics (IcemPlanner.cem_learned_step_ok)"
         if not learned and not self.planner.cem_step_ok():
             return "the library does not serve this handle (IcemPlanner.cem_step_ok)"
@@ -1242,7 +1242,7 @@ class MpcRandomHip(MpcController):
             return "the noise source is not the device's (external uniforms keep the operator chain)"
         if self.verbose:
             return "the controller is verbose"
-        if learned and not self.planner.random_learned_step_ok():
+        if learned and not self.planner.random_learned_step_ok(self.forward_model):
             return "the library does not serve this handle through the learned dynamics (IcemPlanner.random_learned_step_ok)"
         if not learned and not self.planner.random_step_ok():
             return "the library does not serve this handle (IcemPlanner.random_step_ok)"

@@ -916,28 +916,53 @@ int icem_rssm_trim(void) {
     return ICEM_OK;
 }
 
-int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
-                           const void* actions, void* costs, void* stream) {
+static_assert(rssm::ACT_MAX == ICEM_RSSM_MAX_ACT_DIM, "the widest action the RSSM's one action K block holds");
+
+int icem_rssm_rollout_cost_w(int32_t n, int32_t horizon, int32_t act_dim, int32_t cost_mode, const void* params, const void* obs0,
+                             const void* actions, void* costs, void* stream) {
     if (n < 0 || horizon < 1 || cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL || !params || !obs0 || !actions || !costs)
         return fail(ICEM_E_INVALID, "null tensor / bad n, horizon or cost_mode");
-    return rssm_launch_result(launch_rssm_rollout(n, horizon, cost_mode, (const unsigned short*)params, (const float*)obs0,
+    if (act_dim < 1 || act_dim > rssm::ACT_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_rssm_rollout_cost_w: act_dim must be in [1, 32]");
+    return rssm_launch_result(launch_rssm_rollout(n, horizon, act_dim, cost_mode, (const unsigned short*)params, (const float*)obs0,
                                                   (const float*)actions, (float*)costs, (hipStream_t)stream));
+}
+
+int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
+                           const void* actions, void* costs, void* stream) {
+    return icem_rssm_rollout_cost_w(n, horizon, rssm::ACT, cost_mode, params, obs0, actions, costs, stream);
 }
 
 int icem_rssm_rollout_cost_batch(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t cost_mode,
                                  const void* params, const void* obs0, const void* actions, void* costs, void* stream) {
+    return icem_rssm_rollout_cost_batch_w(n_problems, rows_host, horizon, rssm::ACT, cost_mode, params, obs0, actions, costs, stream);
+}
+
+int icem_set_rssm_act_dim(icem_handle* h, int32_t act_dim) {
+    if (!h) return fail(ICEM_E_INVALID, "icem_set_rssm_act_dim: null handle");
+    if (act_dim != h->cfg.act_dim) return fail(ICEM_E_INVALID, "icem_set_rssm_act_dim: act_dim must be the handle's own (cfg.act_dim)");
+    if (act_dim < 1 || act_dim > rssm::ACT_MAX)
+        return fail(ICEM_E_UNSUPPORTED, "icem_set_rssm_act_dim: the RSSM takes 1 to 32 action dimensions (one 32-wide K block of its input layer)");
+    h->rssm_act = act_dim;
+    return ICEM_OK;
+}
+
+int32_t icem_rssm_act_dim(const icem_handle* h) { return h ? rssm_width(h) : 0; }
+
+int icem_rssm_rollout_cost_batch_w(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t act_dim, int32_t cost_mode,
+                                   const void* params, const void* obs0, const void* actions, void* costs, void* stream) {
     if (!rows_host || !params || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: null pointer");
     if (n_problems < 1 || n_problems > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: n_problems must be in [1, 32]");
     for (int p = 0; p < n_problems; ++p)
         if (rows_host[p] < 1) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: every problem needs at least one row");
     if (horizon < 1) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: horizon must be >= 1");
     if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_batch: bad cost_mode");
+    if (act_dim < 1 || act_dim > rssm::ACT_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_rssm_rollout_cost_batch_w: act_dim must be in [1, 32]");
     // (no fused twin: a batch is served by the split launch or not at all)
     const int tiles = rssm_batch_tiles(n_problems, rows_host);
     if (tiles < 0 || !rssm_split_batch_ok(tiles, horizon))
         return fail(ICEM_E_UNSUPPORTED, "icem_rssm_rollout_cost_batch: the batch's tiles (the sum over the problems of ceil(rows / 16)) "
                                         "exceed the split launch's limit, or the split launch is switched off; nothing was launched");
-    return rssm_launch_result(launch_rssm_split_batch(n_problems, rows_host, horizon, cost_mode, (const unsigned short*)params,
+    return rssm_launch_result(launch_rssm_split_batch(n_problems, rows_host, horizon, act_dim, cost_mode, (const unsigned short*)params,
                                                       (const float*)obs0, (const float*)actions, (float*)costs, (hipStream_t)stream));
 }
 

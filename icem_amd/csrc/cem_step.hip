@@ -121,7 +121,8 @@ static_assert(rssm::DET + rssm::STOCH == ICEM_RSSM_OBS_DIM, "the RSSM's observat
 const char* cem_learned_unserved(const icem_handle* h) {
     const icem_config& c = h->cfg;
     if (c.dtype != ICEM_F32) return "the learned-dynamics rollout is f32 only";
-    if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
+    // (a handle bound to an RSSM of its own width -- icem_set_rssm_act_dim, which takes no other -- passes; one never bound is served at 6)
+    if (c.act_dim != rssm_width(h)) return "the declared RSSM takes 6 action dimensions";
     if (const char* why = cem_unserved(h)) return why;
     if (!cem_sample_ok(h)) return "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS)";
     if (!rssm_split_ok(c.num_traj, c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
@@ -155,7 +156,7 @@ int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_para
                              : gk_sample_truncnorm(h, N, 0, b->mean, b->std, b->lower, b->upper, nullptr, offset, b->actions, st);
         if (rc) return rc;
         ++launches;
-        rc = rssm_params ? rssm_launch_result(launch_rssm_rollout(N, c.horizon, c.cost_mode, (const unsigned short*)rssm_params,
+        rc = rssm_params ? rssm_launch_result(launch_rssm_rollout(N, c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)rssm_params,
                                                                   (const float*)b->obs0, (const float*)b->actions, (float*)b->costs, st))
                          : rollout_cost_launch(h, N, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st});
         if (rc) return rc;
@@ -235,7 +236,7 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
         else launch_cem_sample_batch(h0, N, part, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
-        if (int rc = params ? rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.cost_mode, (const unsigned short*)params,
+        if (int rc = params ? rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params,
                                                                          og.dst, pool_a, pool_c, st))
                             : rb.launch(part, bases, st, &launches))
             return rc;
@@ -299,6 +300,8 @@ int icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n, con
     const std::string who = "icem_plan_step_cem_learned_batch: ";
     if (int rc = admit_batch(handles, n, buffers && p && params && mpc_steps_host, true, who.c_str(),
                              "icem_plan_step_cem_learned_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    if (int rc = admit_rssm_binding(handles, n, "icem_plan_step_cem_learned_batch: the handles must share one configuration (everything but the seed)"))
         return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = cem_refusal(handles[i], buffers[i], mpc_steps_host[i], who, true)) return rc;

@@ -120,6 +120,7 @@ struct icem_handle {
     std::vector<int> pop;
     int n_reuse = 0;
     int n_local_max = 0;
+    int rssm_act = 0;   // icem_set_rssm_act_dim: the action width of the RSSM the learned-dynamics steps roll out through (0: never bound)
     // optional per-kernel timing with HIP events on the caller's stream (bench.py roofline leg)
     bool profiling = false;
     struct Span {
@@ -350,6 +351,16 @@ inline int admit_batch(icem_handle* const* handles, int n, bool other_args, bool
             if (handles[i] == handles[j]) return fail(ICEM_E_INVALID, std::string(who) + "the same handle twice in one batch");
     for (int i = 1; i < n; ++i)
         if (!same_batch_config(handles[i]->cfg, handles[0]->cfg, exact)) return fail(ICEM_E_INVALID, config_msg);
+    return ICEM_OK;
+}
+// The action width of the RSSM a handle's learned-dynamics steps serve: the bound one (icem_set_rssm_act_dim, which only takes the
+// handle's own cfg.act_dim), else the declared 6 -- the library cannot see the width a `params` buffer was packed at, so a handle
+// of another act_dim is served only once its caller has said that the model is that wide.
+inline int rssm_width(const icem_handle* h) { return h->rssm_act ? h->rssm_act : 6; }
+// ... and a batch shares one model, so one binding: differing ones are an unequal configuration (config_msg: admit_batch's)
+inline int admit_rssm_binding(icem_handle* const* handles, int n, const char* config_msg) {
+    for (int i = 1; i < n; ++i)
+        if (rssm_width(handles[i]) != rssm_width(handles[0])) return fail(ICEM_E_INVALID, config_msg);
     return ICEM_OK;
 }
 // problem i's row of a batch's `results` (rows of row_bytes), or nullptr where the caller asked for none

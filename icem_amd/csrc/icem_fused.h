@@ -243,8 +243,10 @@ struct UpdateSmallArgs {
 void launch_update_small(const UpdateSmallArgs& a, hipStream_t st);
 // ... for B problems in one launch (one workgroup each, args[n] in DEVICE memory), and -- finish -- with the MPC step's
 // epilogue behind the refit: shift of the new mean, reset of std (icem_shift's arithmetic), executed = elites[0, 0, :],
-// best_cost = elite_costs[0], both also as `result` [d + 1] (nullptr: not wanted).  hd <= UPDATE_FINISH_MAX_HD.
-constexpr int UPDATE_FINISH_MAX_HD = 256;
+// best_cost = elite_costs[0], both also as `result` [d + 1] (nullptr: not wanted).  hd <= UPDATE_FINISH_MAX_HD: the new mean
+// passes through that many floats of LDS (2 KB; the learned-dynamics step at h = 12 / 13 and the RSSM's widest action, 32,
+// needs 384 / 416 of them).
+constexpr int UPDATE_FINISH_MAX_HD = 512;
 struct UpdateFinishArgs {
     UpdateSmallArgs u;
     int d;

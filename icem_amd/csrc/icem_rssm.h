@@ -13,7 +13,8 @@
 
 namespace icem {
 namespace rssm {
-constexpr int DET = 200, STOCH = 30, HID = 200, ACT = 6;
+constexpr int DET = 200, STOCH = 30, HID = 200, ACT = 6;   // ACT: the declared action width (kernels with it compiled in)
+constexpr int ACT_MAX = 32;                              // any width 1 .. 32 fits the one action K block (columns 32 .. 63 of [z | a])
 constexpr int DETB = 13, STB = 2, HIDB = 13;             // 16-wide OUTPUT blocks (200 -> 208, 30 -> 32)
 constexpr int DETK = 7, STK = 1, ACTK = 1, HIDK = 7;     // 32-wide K blocks (200 -> 224, 30 -> 32, 6 -> 32)
 constexpr int K1K = STK + ACTK;                          // [z | a]
@@ -35,14 +36,17 @@ constexpr int SPLIT_MAX_TILES = 4096;  // populations up to 65 536: recurrence a
 constexpr int BATCH_MAX = 32;          // problems of one batched split launch (their table travels in the kernel arguments)
 }  // namespace rssm
 
-// costs[i] = reduce_t -reward(state_t) along the rollout of actions[i] from obs0 (cost_mode: 0 sum, 1 best, 2 final)
-hipError_t launch_rssm_rollout(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
+// costs[i] = reduce_t -reward(state_t) along the rollout of actions[i] from obs0 (cost_mode: 0 sum, 1 best, 2 final).
+// act_dim: the model's action width, 1 .. ACT_MAX (hipErrorInvalidValue outside); actions is [n, horizon, act_dim] and `params`
+// a buffer packed from a model of that width (W1's action columns at 32 .. 32 + act_dim, zeros behind them).  act_dim == ACT
+// runs the kernels that have the width compiled in, every other width their runtime-width twins.
+hipError_t launch_rssm_rollout(int n, int horizon, int act_dim, int cost_mode, const unsigned short* params, const float* obs0,
                                const float* actions, float* costs, hipStream_t st);
 // n <= 16 * SPLIT_MAX_TILES: one launch of recurrence workgroups + reward-head workgroups (ICEM_RSSM_SPLIT=0 turns it off)
 bool rssm_split_ok(int n, int horizon);
 void rssm_split_trim();                     // frees the split launch's per-(device, stream) staging areas
 void rssm_set_stamps(long long* dev_ptr);   // development aid: 16 int64 of wall_clock64 phase stamps of tile 0 (NULL = off)
-hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
+hipError_t launch_rssm_split(int n, int horizon, int act_dim, int cost_mode, const unsigned short* params, const float* obs0,
                              const float* actions, float* costs, hipStream_t st);
 // B <= BATCH_MAX problems that share `params` in ONE split launch: problem p has rows[p] >= 1 trajectories from its own
 // obs0 + 230 p, its rows back to back in actions / costs; every problem is cut into tiles of its own, so each cost is the
@@ -50,6 +54,6 @@ hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned s
 int rssm_batch_tiles(int n_problems, const int* rows);   // (-1: more than the staging bookkeeping could ever hold)
 bool rssm_split_batch_ok(int tiles, int horizon);
 hipError_t rssm_split_prepare(int tiles, int horizon, hipStream_t st);   // staging + status check of such a launch, no kernel
-hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int cost_mode, const unsigned short* params,
+hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int act_dim, int cost_mode, const unsigned short* params,
                                    const float* obs0, const float* actions, float* costs, hipStream_t st);
 }  // namespace icem

@@ -13,11 +13,16 @@ using namespace rssm_dev;
 
 
 // TT tiles of 16 trajectories per workgroup: every weight block a wave requests feeds TT MFMAs (large populations are
-// bound by re-streaming the weights from L2 per tile; small ones want as many workgroups as possible: TT = 1)
-template <int TT>
-__global__ __launch_bounds__(NTHR) void rssm_rollout_kernel(int n, int horizon, int cost_mode, const unsigned short* __restrict__ Pg,
-                                                           const float* __restrict__ obs0, const float* __restrict__ actions,
-                                                           float* __restrict__ costs) {
+// bound by re-streaming the weights from L2 per tile; small ones want as many workgroups as possible: TT = 1).
+// AW: the action width as a compile-time constant (the declared 6: `d` is not read), or 0: the width is `d`, 1 <= d <= 32 --
+// a row of `actions` is horizon * d floats of which only the d entries of a step are ever loaded, and every column of the
+// action K block behind them is written as zero.
+template <int TT, int AW>
+__device__ __forceinline__ void rssm_rollout_body(int n, int horizon, int d, int cost_mode, const unsigned short* __restrict__ Pg,
+                                                  const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                  float* __restrict__ costs) {
+    static_assert(AW == 0 || AW == ACT, "the compiled-in staging of phase 4 is written for the declared width");
+    const int aw = AW ? AW : d;
     constexpr int NR = 16 * TT;   // trajectories (LDS rows) of the workgroup
     __shared__ __attribute__((aligned(16))) unsigned short zA[NR * ZS];       // [z_t | a_t]
     __shared__ __attribute__((aligned(16))) unsigned short hb[2][NR * RS];    // h_t in bf16 (operand), ping-pong
@@ -50,7 +55,7 @@ __global__ __launch_bounds__(NTHR) void rssm_rollout_kernel(int n, int horizon, 
         const int k = e % ZS, jj = e / ZS;
         float v = 0.f;
         if (k < STOCH) v = obs0[DET + k];
-        else if (k >= 32 && k < 32 + ACT) v = actions[(size_t)(base + jj < n ? base + jj : n - 1) * horizon * ACT + (k - 32)];
+        else if (k >= 32 && k < 32 + aw) v = actions[(size_t)(base + jj < n ? base + jj : n - 1) * horizon * aw + (k - 32)];
         zA[e] = to_bf16(v);   // padding trajectories repeat the last one, never stored
     }
     __syncthreads();
@@ -191,12 +196,25 @@ __global__ __launch_bounds__(NTHR) void rssm_rollout_kernel(int n, int horizon, 
                 const v4f a = mma<HIDK>(A5, xb + tt * 16 * RS + xr, b5);
                 *reinterpret_cast<v4s*>(zA + tt * 16 * ZS + zo + w * 16) = pack4(a[0], a[1], a[2], a[3]);
             }
+        } else if (AW == 0) {
+            if (w < STB + 2) {   // two waves, 16 entries each: lane (j, g) of wave STB + q takes entries 16 q + 4 g .. + 3 below d, zero from d on
+                const int e0 = (w - STB) * 16 + 4 * g;
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) {
+                    const int rr = base + tt * 16 + j;
+                    const float* an = actions + ((size_t)(rr < n ? rr : n - 1) * horizon + (t + 1)) * d;
+                    float a[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) a[r] = e0 + r < d ? an[e0 + r] : 0.f;
+                    *reinterpret_cast<v4s*>(zA + (tt * 16 + j) * ZS + 32 + e0) = pack4(a[0], a[1], a[2], a[3]);
+                }
+            }
         } else if (w == STB) {
             if (g < 2) {   // lanes (j, 0): a[0..3]; lanes (j, 1): a[4], a[5], 0, 0
 #pragma unroll
                 for (int tt = 0; tt < TT; ++tt) {
                     const int rr = base + tt * 16 + j;
-                    const float* an = actions + ((size_t)(rr < n ? rr : n - 1) * horizon + (t + 1)) * ACT;
+                    const float* an = actions + ((size_t)(rr < n ? rr : n - 1) * horizon + (t + 1)) * AW;
                     const float a0 = an[4 * g], a1 = an[4 * g + 1];
                     const float a2 = g == 0 ? an[2] : 0.f, a3 = g == 0 ? an[3] : 0.f;
                     *reinterpret_cast<v4s*>(zA + (tt * 16 + j) * ZS + 32 + 4 * g) = pack4(a0, a1, a2, a3);
@@ -241,18 +259,39 @@ __global__ __launch_bounds__(NTHR) void rssm_rollout_kernel(int n, int horizon, 
             if (base + tt * 16 + j < n) costs[base + tt * 16 + j] = acc_cost[tt];
     }
 }
+
+// the declared width (6, compiled in) and any width d in [1, 32]
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_rollout_kernel(int n, int horizon, int cost_mode, const unsigned short* __restrict__ Pg,
+                                                           const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                           float* __restrict__ costs) {
+    rssm_rollout_body<TT, ACT>(n, horizon, ACT, cost_mode, Pg, obs0, actions, costs);
+}
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_rollout_w_kernel(int n, int horizon, int d, int cost_mode, const unsigned short* __restrict__ Pg,
+                                                             const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                             float* __restrict__ costs) {
+    rssm_rollout_body<TT, 0>(n, horizon, d, cost_mode, Pg, obs0, actions, costs);
+}
 }  // namespace
 
-hipError_t launch_rssm_rollout(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
+hipError_t launch_rssm_rollout(int n, int horizon, int act_dim, int cost_mode, const unsigned short* params, const float* obs0,
                                const float* actions, float* costs, hipStream_t st) {
+    if (act_dim < 1 || act_dim > ACT_MAX) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
-    if (rssm_split_ok(n, horizon)) return launch_rssm_split(n, horizon, cost_mode, params, obs0, actions, costs, st);
-    if (n >= 8192)   // more tiles than CUs several times over: two tiles per workgroup share every weight load
-        hipLaunchKernelGGL(rssm_rollout_kernel<2>, dim3((n + 31) / 32), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0,
-                           actions, costs);
-    else
-        hipLaunchKernelGGL(rssm_rollout_kernel<1>, dim3((n + 15) / 16), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0,
-                           actions, costs);
+    if (rssm_split_ok(n, horizon)) return launch_rssm_split(n, horizon, act_dim, cost_mode, params, obs0, actions, costs, st);
+    // more tiles than CUs several times over: two tiles per workgroup share every weight load.  (The declared width only: the
+    // two-tile body spills 40 registers as it is and 48 with a runtime width, and nothing but a switched-off split launch or a
+    // population above 65 536 rows comes here at all -- the other widths stay on one tile per workgroup.)
+    const bool two = n >= 8192 && act_dim == ACT;
+    const dim3 grid(two ? (n + 31) / 32 : (n + 15) / 16);
+    if (act_dim != ACT) {
+        hipLaunchKernelGGL(rssm_rollout_w_kernel<1>, grid, dim3(NTHR), 0, st, n, horizon, act_dim, cost_mode, params, obs0, actions, costs);
+    } else if (two) {
+        hipLaunchKernelGGL(rssm_rollout_kernel<2>, grid, dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions, costs);
+    } else {
+        hipLaunchKernelGGL(rssm_rollout_kernel<1>, grid, dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions, costs);
+    }
     return hipGetLastError();
 }
 }  // namespace icem

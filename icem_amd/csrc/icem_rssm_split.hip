@@ -162,8 +162,9 @@ __device__ __forceinline__ void publish(const ProducerLds<TT>& s, int cur, unsig
 // straight-line, so the compiler's in-order vmcnt bookkeeping is exact (a wave only ever waits for the chunk it is
 // about to use), and nobody issues a load it does not need (a "dummy" broadcast load costs the L1 more than a real
 // one: measured).  TT tiles per workgroup share every chunk (one request, TT accumulation chains).
-template <bool CLASS_A, int TT>
-__device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int lane, int base, int row_end, int horizon,
+// AW: the action width compiled in (the declared 6), or 0: the width is the runtime d in [1, ACT_MAX] (icem_rssm.hip).
+template <bool CLASS_A, int TT, int AW>
+__device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int lane, int base, int row_end, int horizon, int d,
                                                  const unsigned short* __restrict__ Pg, const float* __restrict__ actions,
                                                  unsigned short* items, size_t tile_stride, unsigned* flag, int ntl,
                                                  long long* stamps, bool stamp) {
@@ -274,8 +275,8 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
         derive();
         const unsigned short* X = s.xb + xr;
         const unsigned short* H = s.hb[cur] + xr;
-        // the next action of the trajectories (every wave asks, wave 2 stores: a load inside a branch would cost the
-        // waves behind the branch their exact vmcnt).  One tile: asked for in phase 3, a phase ahead of its use (four
+        // the next action of the trajectories (every wave asks, wave 2 stores -- at a runtime width waves 2 and 3: a load
+        // inside a branch would cost the waves behind the branch their exact vmcnt).  One tile: asked for in phase 3, a phase ahead of its use (four
         // registers less across phase 2, where the wave's pressure peaks -- and a spilled register is a scratch reload,
         // a vmcnt(0) wait among the weight requests); two tiles: at the step's top (measured: 3 % faster there)
         float an[TT][4];
@@ -283,9 +284,16 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
 #pragma unroll
             for (int tt = 0; tt < TT; ++tt) {
                 const int rr = base + tt * 16 + j;
-                const float* ap = actions + ((size_t)(rr < row_end ? rr : row_end - 1) * horizon + (t + 1)) * ACT;
-                const int o = g & 1 ? 4 : 0;
-                an[tt][0] = ap[o]; an[tt][1] = ap[o + 1]; an[tt][2] = ap[g & 1 ? 5 : 2]; an[tt][3] = ap[g & 1 ? 5 : 3];
+                const float* ap = actions + ((size_t)(rr < row_end ? rr : row_end - 1) * horizon + (t + 1)) * (AW ? AW : d);
+                if constexpr (AW == 0) {   // runtime width: waves 2 and 3 store, sixteen entries each -- lane (j, g) of an even wave
+                    // asks for entries 4 g .. 4 g + 3, of an odd wave for 16 + 4 g ..; only entries below d are loaded
+                    const int e0 = (w & 1) * 16 + 4 * g;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) an[tt][r] = e0 + r < d ? ap[e0 + r] : 0.f;
+                } else {
+                    const int o = g & 1 ? 4 : 0;
+                    an[tt][0] = ap[o]; an[tt][1] = ap[o + 1]; an[tt][2] = ap[g & 1 ? 5 : 2]; an[tt][3] = ap[g & 1 ? 5 : 3];
+                }
             }
         };
         if (!EARLY) ask_actions();
@@ -365,6 +373,13 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
                     const v4f a = mma<HIDK>(A5, s.xb + tt * 16 * RS + xr, bias4(s.bs, B5, w * 16 + 4 * g));
                     *reinterpret_cast<v4s*>(s.zA + tt * 16 * ZS + zo + w * 16) = pack4(a[0], a[1], a[2], a[3]);
                 }
+            } else if (AW == 0) {   // waves 2 and 3: all 32 columns of the action K block, zeros from column 32 + d on
+                if (w < STB + 2) {
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt)
+                        *reinterpret_cast<v4s*>(s.zA + (tt * 16 + j) * ZS + 32 + (w - STB) * 16 + 4 * g) =
+                            pack4(an[tt][0], an[tt][1], an[tt][2], an[tt][3]);
+                }
             } else if (w == STB && g < 2) {   // lanes (j, 0): a[0..3]; lanes (j, 1): a[4], a[5], 0, 0
 #pragma unroll
                 for (int tt = 0; tt < TT; ++tt)
@@ -385,8 +400,8 @@ __device__ __forceinline__ void recurrence_steps(ProducerLds<TT>& s, int w, int 
 // The workgroup's ntl <= TT tiles are launch-global tiles tile0 .. (items and flags); their rows are base + 16 tt + j of
 // actions, all of ONE problem, which starts from obs0 and ends in front of row_end (rows past it repeat row_end - 1).
 // A launch of one problem has base = 16 tile0; in a batched launch a problem starts at any row.
-template <int TT>
-__device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, int tile0, int ntl, int base, int row_end, int horizon,
+template <int TT, int AW>
+__device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, int tile0, int ntl, int base, int row_end, int horizon, int d,
                                            const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
                                            const float* __restrict__ actions, unsigned short* stage, unsigned* flags, long long* stamps) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -417,10 +432,19 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, in
 #pragma unroll
         for (int q = 0; q < (N5 + NTHR - 1) / NTHR; ++q)
             if (tid + NTHR * q < N5) c5[q] = reinterpret_cast<const v4i*>(Pg + W5)[tid + NTHR * q];
-        float av = 0.f;
-        if (tid < TT * 16 * ACT) {
+        static_assert(AW == 0 || AW == ACT, "the compiled-in staging is written for the declared width");
+        static_assert(TT * 16 * ACT <= NTHR && 16 * ACT_MAX == NTHR, "one thread per staged action entry (runtime width: per pass of 16 rows)");
+        float av[TT];   // (compiled-in width: av[0] alone)
+        av[0] = 0.f;
+        if constexpr (AW == 0) {   // thread tid, pass q: entry tid % 32 of row tid / 32 + 16 q, loaded only if it is below d
+#pragma unroll
+            for (int q = 0; q < TT; ++q) {
+                const int jj = (tid >> 5) + 16 * q, k = tid & 31;
+                av[q] = k < d ? actions[(size_t)(base + jj < row_end ? base + jj : row_end - 1) * horizon * d + k] : 0.f;
+            }
+        } else if (tid < TT * 16 * ACT) {
             const int jj = tid / ACT;
-            av = actions[(size_t)(base + jj < row_end ? base + jj : row_end - 1) * horizon * ACT + tid % ACT];
+            av[0] = actions[(size_t)(base + jj < row_end ? base + jj : row_end - 1) * horizon * ACT + tid % ACT];
         }
         s.ob[tid < 232 ? tid : 231] = tid < 232 ? ob : 0.f;
 #pragma unroll
@@ -434,7 +458,12 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, in
 #pragma unroll
         for (int q = 0; q < (N5 + NTHR - 1) / NTHR; ++q)
             if (tid + NTHR * q < N5) reinterpret_cast<v4i*>(s.w5)[tid + NTHR * q] = c5[q];
-        if (tid < TT * 16 * ACT) s.zA[(tid / ACT) * ZS + 32 + tid % ACT] = to_bf16(av);
+        if constexpr (AW == 0) {
+#pragma unroll
+            for (int q = 0; q < TT; ++q) s.zA[((tid >> 5) + 16 * q) * ZS + 32 + (tid & 31)] = to_bf16(av[q]);
+        } else if (tid < TT * 16 * ACT) {
+            s.zA[(tid / ACT) * ZS + 32 + tid % ACT] = to_bf16(av[0]);
+        }
         if constexpr (TT == 1) {   // the class-A waves' two LDS chunks (ChunkPlan)
             constexpr int PC = DETK * BLK / 8, NP = LDS_CHUNKS * PC;   // 16-byte pieces per chunk, in all
             v4i cl[(NP + NTHR - 1) / NTHR];
@@ -463,10 +492,10 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, in
     for (int e = tid; e < TT * 16 * ZS; e += NTHR) {
         const int k = e % ZS;
         if (k < 32) s.zA[e] = to_bf16(k < STOCH ? s.ob[DET + k] : 0.f);
-        else if (k >= 32 + ACT) s.zA[e] = 0;
+        else if (k >= 32 + (AW ? AW : ACT_MAX)) s.zA[e] = 0;   // (runtime width: the staging above wrote all 32 action columns)
     }
-    if (w < 5) recurrence_steps<true, TT>(s, w, lane, base, row_end, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
-    else recurrence_steps<false, TT>(s, w, lane, base, row_end, horizon, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
+    if (w < 5) recurrence_steps<true, TT, AW>(s, w, lane, base, row_end, horizon, d, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
+    else recurrence_steps<false, TT, AW>(s, w, lane, base, row_end, horizon, d, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
 }
 
 // tiles first, first + stride, ...: one tile per workgroup while both workgroup kinds fit the chip together, several for
@@ -604,8 +633,26 @@ __global__ __launch_bounds__(NTHR) void rssm_split_kernel(int n, int horizon, in
     const int b = blockIdx.x;
     if (b < prods) {
         const int tile0 = b * TT;
-        recurrence<TT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tile0, tiles - tile0 < TT ? tiles - tile0 : TT, tile0 * 16, n, horizon, Pg,
-                       obs0, actions, stage, flags, stamps);
+        recurrence<TT, ACT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tile0, tiles - tile0 < TT ? tiles - tile0 : TT, tile0 * 16, n, horizon,
+                            ACT, Pg, obs0, actions, stage, flags, stamps);
+    } else {
+        reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
+                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+    }
+}
+// ... at any action width d in [1, ACT_MAX]: the recurrence stages d entries per row and step (row stride horizon * d); the
+// reward head never sees an action
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_split_w_kernel(int n, int horizon, int d, int cost_mode, const unsigned short* __restrict__ Pg,
+                                                           const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                           float* __restrict__ costs, unsigned short* stage, unsigned* flags,
+                                                           unsigned* status, int tiles, int prods, long long* stamps) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
+    const int b = blockIdx.x;
+    if (b < prods) {
+        const int tile0 = b * TT;
+        recurrence<TT, 0>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tile0, tiles - tile0 < TT ? tiles - tile0 : TT, tile0 * 16, n, horizon,
+                          d, Pg, obs0, actions, stage, flags, stamps);
     } else {
         reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
                     [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
@@ -638,10 +685,37 @@ __global__ __launch_bounds__(NTHR) void rssm_split_batch_kernel(const BatchTable
         for (int q = 1; q < n_problems; ++q) p = b >= tab.wg0[q] ? q : p;
         const int lt0 = (b - tab.wg0[p]) * TT;                 // the workgroup's first tile within its problem
         const int left = (tab.rows[p] + 15) / 16 - lt0;        // (a problem with an odd tile count ends in a one-tile workgroup)
-        recurrence<TT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tab.tile0[p] + lt0, left < TT ? left : TT, tab.row0[p] + lt0 * 16,
-                       tab.row0[p] + tab.rows[p], horizon, Pg, obs0 + (size_t)p * (DET + STOCH), actions, stage, flags, stamps);
+        recurrence<TT, ACT>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tab.tile0[p] + lt0, left < TT ? left : TT, tab.row0[p] + lt0 * 16,
+                            tab.row0[p] + tab.rows[p], horizon, ACT, Pg, obs0 + (size_t)p * (DET + STOCH), actions, stage, flags, stamps);
     } else {
         int p = 0;   // (a walking workgroup's tiles ascend: the scan goes on from the problem of the tile before)
+        reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
+                    [&tab, &p, n_problems](int tile, int& base, int& end) {
+                        while (p + 1 < n_problems && tile >= tab.tile0[p + 1]) ++p;
+                        base = tab.row0[p] + (tile - tab.tile0[p]) * 16;
+                        end = tab.row0[p] + tab.rows[p];
+                    },
+                    horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+    }
+}
+// ... at any action width d in [1, ACT_MAX] (rssm_split_w_kernel)
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_split_batch_w_kernel(const BatchTable tab, int n_problems, int horizon, int d, int cost_mode,
+                                                                 const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
+                                                                 const float* __restrict__ actions, float* __restrict__ costs,
+                                                                 unsigned short* stage, unsigned* flags, unsigned* status, int tiles,
+                                                                 int prods, long long* stamps) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
+    const int b = blockIdx.x;
+    if (b < prods) {
+        int p = 0;
+        for (int q = 1; q < n_problems; ++q) p = b >= tab.wg0[q] ? q : p;
+        const int lt0 = (b - tab.wg0[p]) * TT;
+        const int left = (tab.rows[p] + 15) / 16 - lt0;
+        recurrence<TT, 0>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tab.tile0[p] + lt0, left < TT ? left : TT, tab.row0[p] + lt0 * 16,
+                          tab.row0[p] + tab.rows[p], horizon, d, Pg, obs0 + (size_t)p * (DET + STOCH), actions, stage, flags, stamps);
+    } else {
+        int p = 0;
         reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
                     [&tab, &p, n_problems](int tile, int& base, int& end) {
                         while (p + 1 < n_problems && tile >= tab.tile0[p + 1]) ++p;
@@ -777,16 +851,24 @@ hipError_t rssm_split_prepare(int tiles, int horizon, hipStream_t st) {
     return staging_for(tiles, horizon, st, lk, sg);
 }
 
-hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned short* params, const float* obs0,
+hipError_t launch_rssm_split(int n, int horizon, int act_dim, int cost_mode, const unsigned short* params, const float* obs0,
                              const float* actions, float* costs, hipStream_t st) {
+    if (act_dim < 1 || act_dim > ACT_MAX) return hipErrorInvalidValue;
     const int tiles = (n + 15) / 16;
     std::unique_lock<std::mutex> lk;
     const Staging* sg = nullptr;
     const hipError_t e = staging_for(tiles, horizon, st, lk, sg);
     if (e != hipSuccess) return e;
     const Arrangement a = arrangement(tiles);
-    if (a.tt == 2) {
-        const int prods = (tiles + 1) / 2;
+    const int prods = (tiles + a.tt - 1) / a.tt;
+    if (act_dim != ACT) {   // the runtime-width twins
+        if (a.tt == 2)
+            hipLaunchKernelGGL(rssm_split_w_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, n, horizon, act_dim, cost_mode, params, obs0,
+                               actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+        else
+            hipLaunchKernelGGL(rssm_split_w_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, n, horizon, act_dim, cost_mode, params, obs0,
+                               actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    } else if (a.tt == 2) {
         hipLaunchKernelGGL(rssm_split_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, n, horizon, cost_mode, params, obs0, actions,
                            costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
     } else {
@@ -796,10 +878,10 @@ hipError_t launch_rssm_split(int n, int horizon, int cost_mode, const unsigned s
     return hipGetLastError();
 }
 
-hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int cost_mode, const unsigned short* params,
+hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int act_dim, int cost_mode, const unsigned short* params,
                                    const float* obs0, const float* actions, float* costs, hipStream_t st) {
     const int tiles = rssm_batch_tiles(n_problems, rows);
-    if (n_problems < 1 || n_problems > rssm::BATCH_MAX || tiles < 1) return hipErrorInvalidValue;
+    if (n_problems < 1 || n_problems > rssm::BATCH_MAX || tiles < 1 || act_dim < 1 || act_dim > ACT_MAX) return hipErrorInvalidValue;
     const Arrangement a = arrangement(tiles);
     BatchTable tab{};
     int prods = 0;
@@ -812,7 +894,14 @@ hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon,
     const Staging* sg = nullptr;
     const hipError_t e = staging_for(tiles, horizon, st, lk, sg);
     if (e != hipSuccess) return e;
-    if (a.tt == 2)
+    if (act_dim != ACT) {   // the runtime-width twins
+        if (a.tt == 2)
+            hipLaunchKernelGGL(rssm_split_batch_w_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, act_dim, cost_mode,
+                               params, obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+        else
+            hipLaunchKernelGGL(rssm_split_batch_w_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, act_dim, cost_mode,
+                               params, obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    } else if (a.tt == 2)
         hipLaunchKernelGGL(rssm_split_batch_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, params,
                            obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
     else

@@ -37,11 +37,13 @@ const char* learned_unserved(const icem_handle* h) {
     if (opt_i(OPT_LEARNED_STEP) == 0) return "option learned_step is 0";
     if (c.dtype != ICEM_F32) return "dtype f32 only";
     if (c.world != 1) return "world must be 1";
-    if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
+    // (a handle bound to an RSSM of its own width -- icem_set_rssm_act_dim, which takes no other -- passes; one never bound is served at 6)
+    if (c.act_dim != rssm_width(h)) return "the declared RSSM takes 6 action dimensions";
     if (!h->use_fast) return "the handle's fast path is off";
     if (h->profiling) return "per-kernel profiling is per launch of one handle: switch it off";
-    if (!fast_sample_supported(c.horizon, c.act_dim) || c.horizon > 32 || h->hd > UPDATE_FINISH_MAX_HD)
+    if (!fast_sample_supported(c.horizon, c.act_dim) || c.horizon > 32)
         return "the horizon is outside the folded sampler's list (30, 12, 13, 10)";
+    if (h->hd > UPDATE_FINISH_MAX_HD) return "horizon * act_dim exceeds what the last update's epilogue holds (512)";
     if (c.rng_rounds != 10) return "the batched sampler is compiled for the default generator (rng_rounds 10)";
     if ((int)h->pop.size() != c.opt_iters || c.opt_iters < 1) return "opt_iters";
     if (!topk_small_ok(max_rows(h) + std::max(0, h->n_reuse), c.num_elites)) return "the one-launch update does not take this pool / num_elites (<= 16384 candidates, <= 32 elites)";
@@ -173,10 +175,10 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         }
         hipError_t e;
         if (n == 1)
-            e = launch_rssm_rollout(rows[it], H, c.cost_mode, (const unsigned short*)params, (const float*)buffers[0].obs0,
+            e = launch_rssm_rollout(rows[it], H, d, c.cost_mode, (const unsigned short*)params, (const float*)buffers[0].obs0,
                                     (const float*)buffers[0].actions, (float*)buffers[0].costs, st);
         else
-            e = launch_rssm_split_batch(n, &rows[(size_t)it * n], H, c.cost_mode, (const unsigned short*)params, pool_o, pool_a, pool_c, st);
+            e = launch_rssm_split_batch(n, &rows[(size_t)it * n], H, d, c.cost_mode, (const unsigned short*)params, pool_o, pool_a, pool_c, st);
         if (int rc = rssm_launch_result(e)) return rc;
         ++launches;
         launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + at_update), n, it == iters - 1, st);
@@ -197,6 +199,8 @@ int icem_plan_step_learned_batch(icem_handle* const* handles, int32_t n, const i
                                  const int32_t* mpc_steps_host, void* results, void* stream) {
     if (int rc = admit_batch(handles, n, buffers && params && mpc_steps_host, true, "icem_plan_step_learned_batch: ",
                              "icem_plan_step_learned_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    if (int rc = admit_rssm_binding(handles, n, "icem_plan_step_learned_batch: the handles must share one configuration (everything but the seed)"))
         return rc;
     return learned_step(handles, n, buffers, params, mpc_steps_host, results, (hipStream_t)stream);
 }

@@ -43,7 +43,8 @@ static_assert(rssm::DET + rssm::STOCH == ICEM_RSSM_OBS_DIM, "the RSSM's observat
 const char* random_learned_unserved(const icem_handle* h) {
     const icem_config& c = h->cfg;
     if (c.dtype != ICEM_F32) return "the learned-dynamics rollout is f32 only";
-    if (c.act_dim != rssm::ACT) return "the declared RSSM takes 6 action dimensions";
+    // (a handle bound to an RSSM of its own width -- icem_set_rssm_act_dim, which takes no other -- passes; one never bound is served at 6)
+    if (c.act_dim != rssm_width(h)) return "the declared RSSM takes 6 action dimensions";
     if (const char* why = random_unserved(h)) return why;
     if (!rssm_split_ok(c.num_traj, c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
     return nullptr;
@@ -103,7 +104,7 @@ int random_step_solo(icem_handle* h, const icem_random_buffers* b, int32_t chang
     launch_random_sample(h, &blk, st);
     ICEM_HIP_TRY(hipGetLastError());
     const icem_config& c = h->cfg;
-    if (int rc = rssm_params ? rssm_launch_result(launch_rssm_rollout(c.num_traj, c.horizon, c.cost_mode, (const unsigned short*)rssm_params,
+    if (int rc = rssm_params ? rssm_launch_result(launch_rssm_rollout(c.num_traj, c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)rssm_params,
                                                                       (const float*)b->obs0, (const float*)b->actions, (float*)b->costs, st))
                              : rollout_cost_launch(h, c.num_traj, b->obs0, b->actions, b->costs, nullptr, LaunchCtx{st}))
         return rc;
@@ -194,7 +195,7 @@ int random_learned_step_batch(icem_handle* const* handles, int n, const icem_ran
     launch_random_sample_gather_batch(h0, dev, bases, og, pool, n, st);
     ICEM_HIP_TRY(hipGetLastError());
     const std::vector<int> rows(n, N);
-    if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.cost_mode, (const unsigned short*)params, og.dst,
+    if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params, og.dst,
                                                             pool.actions, pool.costs, st)))
         return rc;
     launch_random_select_pool_batch(h0, dev + at_select, pool, n, st);
@@ -256,6 +257,8 @@ int icem_plan_step_random_learned_batch(icem_handle* const* handles, int32_t n, 
     const std::string who = "icem_plan_step_random_learned_batch: ";
     if (int rc = admit_batch(handles, n, buffers && params && call_offsets_host, true, who.c_str(),
                              "icem_plan_step_random_learned_batch: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    if (int rc = admit_rssm_binding(handles, n, "icem_plan_step_random_learned_batch: the handles must share one configuration (everything but the seed)"))
         return rc;
     for (int i = 0; i < n; ++i)
         if (int rc = random_arg_refusal(buffers[i], change_freq, call_offsets_host[i], who)) return rc;

@@ -260,14 +260,18 @@ def declared_rssm(act_dim: int = 6, det: int = 200, stoch: int = 30, hidden: int
 
 
 def pack_rssm(module):
-    """The packed bf16 parameter buffer ``icem_rssm_rollout_cost`` reads (layout: icem_amd/csrc/icem_rssm.h) from a
-    ``declared_rssm`` module: every weight padded (outputs to multiples of 16, contraction to multiples of 32), cut
-    into 16 x 32 blocks stored as ``v_mfma_f32_16x16x32_bf16`` A operands ``[out block][k block][lane = 16*g + i][v]``
-    = ``W[16*ob + i][32*kb + 8*g + v]``, each layer followed by its f32 bias."""
+    """The packed bf16 parameter buffer ``icem_rssm_rollout_cost_w`` reads (layout: icem_amd/csrc/icem_rssm.h) from a
+    ``declared_rssm`` module of any action width 1 .. 32: every weight padded (outputs to multiples of 16, contraction to
+    multiples of 32), cut into 16 x 32 blocks stored as ``v_mfma_f32_16x16x32_bf16`` A operands
+    ``[out block][k block][lane = 16*g + i][v]`` = ``W[16*ob + i][32*kb + 8*g + v]``, each layer followed by its f32 bias.
+    The action columns of the input layer fill the front of its second K block (columns 32 .. 32 + act of ``[z | a]``) with
+    zeros behind them, so the buffer has the same size at every width."""
     import torch
     sd = {k: v.detach().float().cpu() for k, v in module.state_dict().items()}
     det, st = module.det, module.stoch
-    assert (det, st) == (200, 30) and sd["inp.weight"].shape == (200, 36), "icem_rssm_rollout_cost is compiled for the declared sizes"
+    act = sd["inp.weight"].shape[1] - st
+    assert (det, st) == (200, 30) and sd["inp.weight"].shape[0] == 200 and 1 <= act <= 32, \
+        "icem_rssm_rollout_cost is compiled for the declared sizes (200 / 30 / 200) and 1 to 32 action dimensions"
 
     def pad(w, rows, cols, col_map=None):
         out = torch.zeros(rows, cols)
@@ -285,7 +289,7 @@ def pack_rssm(module):
         return torch.cat([pad(b[i * det:(i + 1) * det][None], 1, 208)[0] for i in range(3)])
 
     layers = [
-        (pad(sd["inp.weight"], 208, 64, [(0, st, 0), (st, st + 6, 32)]), pad(sd["inp.bias"][None], 1, 208)[0]),
+        (pad(sd["inp.weight"], 208, 64, [(0, st, 0), (st, st + act, 32)]), pad(sd["inp.bias"][None], 1, 208)[0]),
         (gates(sd["gru.weight_ih"], 224), gate_bias(sd["gru.bias_ih"])),
         (gates(sd["gru.weight_hh"], 224), gate_bias(sd["gru.bias_hh"])),
         (pad(sd["prior1.weight"], 208, 224), pad(sd["prior1.bias"][None], 1, 208)[0]),
@@ -305,23 +309,29 @@ def pack_rssm(module):
 
 class DeviceRSSMModel(ForwardModel):
     """The declared RSSM with its whole h-step rollout + cost fused into one HIP launch on the bf16 matrix cores
-    (``icem_rssm_rollout_cost``); ``MpcICemHip`` scores a population with it in a single kernel.  ``reference`` is the
+    (``icem_rssm_rollout_cost_w``); ``MpcICemHip`` scores a population with it in a single kernel.  ``reference`` is the
     f32 torch module the weights come from (``predict`` serves the reference-style NumPy interface through it):
-    ``declared_rssm(seed)``'s, or a copy of the caller's ``module`` -- any module of the declared sizes with the declared
-    parameter names, e.g. a ``declared_rssm(...).module`` whose weights were trained or edited."""
+    ``declared_rssm(act_dim, seed=seed)``'s, or a copy of the caller's ``module`` -- any module of the declared sizes with the
+    declared parameter names, e.g. a ``declared_rssm(...).module`` whose weights were trained or edited.  ``act_dim``
+    (1 .. 32) is the action width: the argument's, or with a ``module`` that of its input layer."""
 
-    def __init__(self, seed: int = 0, device="cuda:0", env=None, module=None):
+    act_dim = 6   # the declared width (an instance carries its own; the shape checks of the wrappers read it first)
+
+    def __init__(self, seed: int = 0, device="cuda:0", env=None, module=None, act_dim: int = 6):
         super().__init__(env=env)
         import torch
         from . import _lib as L
         if module is None:
-            self._tm = declared_rssm(seed=seed, device=device)
+            if not 1 <= int(act_dim) <= 32:
+                raise ValueError(f"the device RSSM takes 1 to 32 action dimensions, not {act_dim}")
+            self._tm = declared_rssm(act_dim=int(act_dim), seed=seed, device=device)
         else:
             import copy
             net = copy.deepcopy(module).float()
-            self._tm = TorchForwardModel(net, lambda o, a: -net.reward(o), net.det + net.stoch, 6, device=device, env=env)
+            act_dim = net.inp.in_features - net.stoch
+            self._tm = TorchForwardModel(net, lambda o, a: -net.reward(o), net.det + net.stoch, act_dim, device=device, env=env)
         self.reference = self._tm.module
-        self.obs_dim, self.act_dim = 230, 6
+        self.obs_dim, self.act_dim = 230, int(act_dim)
         self.device = torch.device(device)
         self.params = pack_rssm(self.reference).to(self.device)
         self.lib = L.load_library()
@@ -331,10 +341,12 @@ class DeviceRSSMModel(ForwardModel):
             raise RuntimeError("packed RSSM parameters do not match the library's layout")
 
     def rollout_cost(self, obs, actions, cost_mode: int = 0):
-        """costs ``[n]`` (f32 device tensor) of f32 device action sequences ``[n, h, 6]`` from observation ``obs [230]``."""
+        """costs ``[n]`` (f32 device tensor) of f32 device action sequences ``[n, h, act_dim]`` from observation ``obs [230]``."""
         import ctypes as C
         import torch
         from . import _lib as L
+        if actions.ndim != 3 or actions.shape[2] != self.act_dim:
+            raise ValueError(f"actions must be [n, h, {self.act_dim}], got {tuple(actions.shape)}")
         actions = actions.to(torch.float32).contiguous()
         n, h, _ = actions.shape
         ob = np.asarray(obs, dtype=np.float32)
@@ -343,21 +355,21 @@ class DeviceRSSMModel(ForwardModel):
         o = self._obs_dev
         costs = torch.empty((n,), dtype=torch.float32, device=self.device)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib.icem_rssm_rollout_cost(n, h, cost_mode, C.c_void_p(self.params.data_ptr()), C.c_void_p(o.data_ptr()),
-                                                C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
+        L.check(self.lib.icem_rssm_rollout_cost_w(n, h, self.act_dim, cost_mode, C.c_void_p(self.params.data_ptr()), C.c_void_p(o.data_ptr()),
+                                                  C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
         return costs
 
     def rollout_cost_batch(self, observations, actions, rows, cost_mode: int = 0):
-        """``rollout_cost`` of B problems in ONE launch (``icem_rssm_rollout_cost_batch``): problem p scores its ``rows[p]``
-        action sequences -- back to back in ``actions [sum rows, h, 6]`` (f32 device tensor) -- from ``observations[p]``
+        """``rollout_cost`` of B problems in ONE launch (``icem_rssm_rollout_cost_batch_w``): problem p scores its ``rows[p]``
+        action sequences -- back to back in ``actions [sum rows, h, act_dim]`` (f32 device tensor) -- from ``observations[p]``
         (``[B, 230]`` array-like, or an f32 device tensor that is used as is).  -> costs ``[sum rows]``, every problem's
         slice bit for bit what ``rollout_cost`` gives for it alone; B = 1 is ``rollout_cost``."""
         import ctypes as C
         import torch
         from . import _lib as L
         rows = [int(r) for r in rows]
-        if actions.ndim != 3 or actions.shape[2] != 6:
-            raise ValueError(f"actions must be [sum rows, h, 6], got {tuple(actions.shape)}")
+        if actions.ndim != 3 or actions.shape[2] != self.act_dim:
+            raise ValueError(f"actions must be [sum rows, h, {self.act_dim}], got {tuple(actions.shape)}")
         if sum(rows) != actions.shape[0]:
             raise ValueError(f"rows sum to {sum(rows)} but actions has {actions.shape[0]} rows")
         on_device = isinstance(observations, torch.Tensor) and observations.is_cuda
@@ -371,9 +383,9 @@ class DeviceRSSMModel(ForwardModel):
         actions = actions.to(torch.float32).contiguous()
         costs = torch.empty((actions.shape[0],), dtype=torch.float32, device=self.device)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.check(self.lib.icem_rssm_rollout_cost_batch(len(rows), (C.c_int32 * len(rows))(*rows), actions.shape[1], cost_mode,
-                                                      C.c_void_p(self.params.data_ptr()), C.c_void_p(o.data_ptr()),
-                                                      C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
+        L.check(self.lib.icem_rssm_rollout_cost_batch_w(len(rows), (C.c_int32 * len(rows))(*rows), actions.shape[1], self.act_dim, cost_mode,
+                                                        C.c_void_p(self.params.data_ptr()), C.c_void_p(o.data_ptr()),
+                                                        C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()), st))
         return costs
 
     def predict(self, *, observations, states, actions):

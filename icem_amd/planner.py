@@ -519,10 +519,30 @@ class IcemPlanner:
         return int(self.lib.icem_batch_f64_launches(self._h))
 
     # ------------------------------------------------------------------ the learned-dynamics step (declared RSSM)
-    def learned_step_ok(self) -> bool:
-        """Does ``icem_plan_step_learned`` serve THIS handle?  (f32, one GPU, six action dimensions, a horizon of the folded
-        sampler, the default generator, option ``learned_step`` on ...: asked of the handle.)"""
-        return bool(self.lib.icem_plan_step_learned_ok(self._h))
+    def _bind_rssm(self, model) -> bool:
+        """Tell the handle the action width of ``model`` (``icem_set_rssm_act_dim``) where that is the planner's own -- the
+        library cannot see the width a ``params`` buffer was packed at, and serves a handle that was never told at the declared
+        six only.  A model of another width (or none: no ``act_dim``) leaves the handle alone, so the entry refuses it as it
+        always has.  Returns whether the handle is now bound to ``model``'s width."""
+        w = getattr(model, "act_dim", None)
+        if w is None or int(w) != self.d or not 1 <= int(w) <= 32:
+            return False
+        if int(self.lib.icem_rssm_act_dim(self._h)) != int(w):
+            L.check(self.lib.icem_set_rssm_act_dim(self._h, int(w)))
+        return True
+
+    def _learned_ok(self, ask, model) -> bool:
+        """``ask(handle)`` as it stands (``model`` None), or for a step through ``model``: false where its width is not the
+        planner's, else asked of the handle bound to that width (as the step itself would bind it)."""
+        if model is not None and not self._bind_rssm(model):
+            return False
+        return bool(ask(self._h))
+
+    def learned_step_ok(self, model=None) -> bool:
+        """Does ``icem_plan_step_learned`` serve THIS handle?  (f32, one GPU, the RSSM's action width -- six unless the handle is
+        bound to its own, 1 .. 32 --, a horizon of the folded sampler, the default generator, option ``learned_step`` on ...:
+        asked of the handle.)  ``model``: ask for a step through this model, whose ``act_dim`` must be the planner's."""
+        return self._learned_ok(self.lib.icem_plan_step_learned_ok, model)
 
     @property
     def learned_step_launches(self) -> int:
@@ -549,6 +569,7 @@ class IcemPlanner:
             raise ValueError(f"expected an observation of shape ({L.RSSM_OBS_DIM},)")
         self.obs_rssm.copy_(torch.as_tensor(ob), non_blocking=False)
         cb = self._learned_buffers(self.obs_rssm.data_ptr())
+        self._bind_rssm(model)
         L.check(self.lib.icem_plan_step_learned(self._h, C.byref(cb), C.c_void_p(model.params.data_ptr()), self.mpc_step,
                                                 self._stream()))
         self.mpc_step += 1
@@ -574,6 +595,8 @@ class IcemPlanner:
         bs = (L.IcemPlanBuffersC * n)(*[pl._learned_buffers(obs_dev[i].data_ptr()) for i, pl in enumerate(pls)])
         steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
         results = torch.empty((n, p0.d + 1), dtype=torch.float32, device=p0.device)
+        for pl in pls:
+            pl._bind_rssm(model)
         L.check(p0.lib.icem_plan_step_learned_batch(hs, n, bs, C.c_void_p(model.params.data_ptr()), steps, _ptr(results), p0._stream()))
         for pl in pls:
             pl.mpc_step += 1
@@ -789,10 +812,11 @@ class IcemPlanner:
 
     random_batch_results = property(lambda self: getattr(self, "_random_batch_results", None))
 
-    def random_learned_step_ok(self) -> bool:
-        """Does ``icem_plan_step_random_learned`` serve THIS handle?  (:meth:`random_step_ok`'s conditions, f32, six action
-        dimensions, a population the RSSM's split launch takes: asked of the handle.)"""
-        return bool(self.lib.icem_plan_step_random_learned_ok(self._h))
+    def random_learned_step_ok(self, model=None) -> bool:
+        """Does ``icem_plan_step_random_learned`` serve THIS handle?  (:meth:`random_step_ok`'s conditions, f32, the RSSM's
+        action width -- six unless the handle is bound to its own, 1 .. 32 --, a population the RSSM's split launch takes: asked
+        of the handle.)  ``model``: as :meth:`learned_step_ok`'s."""
+        return self._learned_ok(self.lib.icem_plan_step_random_learned_ok, model)
 
     def plan_step_random_learned(self, model, obs, call_offset: int, change_freq: int) -> torch.Tensor:
         """:meth:`plan_step_random` through ``model`` (a ``DeviceRSSMModel``: its packed ``params``) as
@@ -802,6 +826,7 @@ class IcemPlanner:
         (``sample_piecewise``, ``model.rollout_cost``, ``topk_sorted(costs, 1)`` and the gathers).  Raises ``IcemError``
         before anything runs where the step is refused."""
         cb = self._random_cb(obs, "obs_rssm")
+        self._bind_rssm(model)
         L.check(self.lib.icem_plan_step_random_learned(self._h, C.byref(cb), C.c_void_p(model.params.data_ptr()), int(change_freq),
                                                        int(call_offset), self._stream()))
         return self._random_buffers()["result"][:self.d]
@@ -829,15 +854,18 @@ class IcemPlanner:
         res = getattr(p0, "_random_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
         if res is None or res.shape[0] != n:
             res = p0._random_batch_results = torch.zeros((n, p0.d + 2), dtype=p0.dt, device=p0.device)
+        for pl in pls:
+            pl._bind_rssm(model)
         L.check(p0.lib.icem_plan_step_random_learned_batch(hs, n, bs, C.c_void_p(model.params.data_ptr()), int(change_freq), offs,
                                                            _ptr(res), p0._stream()))
         return res[:, :p0.d]
 
     # ------------------------------------------------------------------ ... through the learned dynamics (declared RSSM)
-    def cem_learned_step_ok(self) -> bool:
-        """Does ``icem_plan_step_cem_learned`` serve THIS handle?  (:meth:`cem_step_ok`'s conditions, f32, six action
-        dimensions, a population the RSSM's split launch takes: asked of the handle.)"""
-        return bool(self.lib.icem_plan_step_cem_learned_ok(self._h))
+    def cem_learned_step_ok(self, model=None) -> bool:
+        """Does ``icem_plan_step_cem_learned`` serve THIS handle?  (:meth:`cem_step_ok`'s conditions, f32, the RSSM's action
+        width -- six unless the handle is bound to its own, 1 .. 32 --, a population the RSSM's split launch takes: asked of the
+        handle.)  ``model``: as :meth:`learned_step_ok`'s."""
+        return self._learned_ok(self.lib.icem_plan_step_cem_learned_ok, model)
 
     def plan_step_cem_learned(self, model, obs, mean: torch.Tensor, std: torch.Tensor, lower: torch.Tensor, upper: torch.Tensor, *,
                               like_levine: bool, shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
@@ -849,6 +877,7 @@ class IcemPlanner:
         (``ICEM_E_UNSUPPORTED``) before anything runs where :meth:`cem_learned_step_ok` is false."""
         cb = self._cem_cb(obs, mean, std, lower, upper, "obs_rssm")
         prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        self._bind_rssm(model)
         L.check(self.lib.icem_plan_step_cem_learned(self._h, C.byref(cb), C.byref(prm), C.c_void_p(model.params.data_ptr()),
                                                     self.mpc_step, self._stream()))
         self.mpc_step += 1
@@ -896,6 +925,8 @@ class IcemPlanner:
         if res is None or res.shape[0] != n:
             res = p0._cem_batch_results = torch.zeros((n, p0.d + 1), dtype=p0.dt, device=p0.device)
         prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        for pl in pls:
+            pl._bind_rssm(model)
         L.check(p0.lib.icem_plan_step_cem_learned_batch(hs, n, bs, C.byref(prm), C.c_void_p(model.params.data_ptr()), steps, _ptr(res),
                                                         p0._stream()))
         for pl in pls:

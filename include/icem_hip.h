@@ -293,7 +293,8 @@ int64_t icem_cem_batch_launches(const icem_handle* h); /* kernel launches of the
  * not be adjacent: the first iteration's sampler launch gathers them into the pool's [n, 230] table.  The batch's argument blocks
  * live in a device array of handles[0] and are uploaded only when a byte changed (icem_batch_uploads: the steady state uploads
  * nothing).  n == 1 is the solo step plus the results row.
- *   Served: f32 handles, world == 1, act_dim == 6, rng_rounds 7 or 10, profiling off, factor_decrease == 1, keep_previous_elites and
+ *   Served: f32 handles, world == 1, act_dim == the RSSM's action width (6, or the handle's own 1 .. 32 once icem_set_rssm_act_dim has bound it),
+ * rng_rounds 7 or 10, profiling off, factor_decrease == 1, keep_previous_elites and
  * shift_elites off, icem_update_distribution_ok(num_traj, K), a row that fits the step's sampler, a population the RSSM's split
  * launch takes (for a batch: all problems' tiles together), any horizon the handle and that launch accept.  Development option
  * cem_step = 0 switches these entries off too.  ICEM_E_INVALID: a NULL handle / buffers / flags / params, a negative step, a NULL
@@ -387,7 +388,8 @@ int64_t icem_random_batch_launches(const icem_handle* h); /* kernel launches of 
  * problems' obs0 buffers need not be adjacent: the sampler launch gathers them into the pool's [n, 230] table.  The argument blocks
  * are those of icem_plan_step_random_batch, in the same device array of handles[0], uploaded only when a byte changed.  n == 1 is
  * the solo step plus the results row.
- *   Served: whatever icem_plan_step_random_ok asks of the handle, f32, act_dim == 6, a population the RSSM's split launch takes (for
+ *   Served: whatever icem_plan_step_random_ok asks of the handle, f32,
+ * act_dim == the RSSM's action width (6, or the handle's own 1 .. 32 once icem_set_rssm_act_dim has bound it), a population the RSSM's split launch takes (for
  * a batch: all problems' tiles together; development option rssm_split = 0 switches the entries off, as random_step = 0 does), any
  * horizon that launch accepts.  ICEM_E_INVALID: a NULL handle / buffers / params, a NULL buffer, change_freq < 0 or >= horizon, a
  * negative call offset, n outside [1, 32], a handle twice, unequal configurations; ICEM_E_UNSUPPORTED: anything not served;
@@ -658,7 +660,8 @@ int64_t icem_batch_f64_launches(const icem_handle* h); /* kernel launches of the
  * count since the last reset -- per problem in a batch (mpc_steps_host[n], host memory): a planner reset later than its peers
  * has no shifted elites and fewer rows.  results (device, may be NULL): [n, act_dim + 1] f32, row p = problem p's executed
  * action | best cost.
- *   Served: f32, world == 1, act_dim == 6, the handle's fast path on, profiling off, rng_rounds 10, a horizon of the folded
+ *   Served: f32, world == 1, act_dim == the RSSM's action width (6, or the handle's own 1 .. 32 once icem_set_rssm_act_dim has bound it),
+ * horizon * act_dim <= 512, the handle's fast path on, profiling off, rng_rounds 10, a horizon of the folded
  * sampler (30, 12, 13, 10), at most 16 384 candidates and 32 elites per update, and all problems' 16-row tiles together within
  * the split launch's limit; development option learned_step = 0 switches the entries off.  Anything else is
  * ICEM_E_UNSUPPORTED; mismatched configurations (everything but the seed must agree), the same handle twice, n outside
@@ -802,7 +805,7 @@ size_t icem_record_bytes(const icem_handle* h);
 
 /* Learned-dynamics rollout (BASELINE configs[4]; the reference has no model code for it, README.md:21-29): the
  * recurrent state-space model declared in icem_amd/models.py::declared_rssm, rolled out on its prior mean from
- * obs0 = [h (200) | z (30)] (f32) along actions [n, horizon, 6] (f32) in ONE launch on the bf16 matrix cores
+ * obs0 = [h (200) | z (30)] (f32) along actions [n, horizon, 6] (f32; any other width 1 .. 32: icem_rssm_rollout_cost_w below) in ONE launch on the bf16 matrix cores
  * (f32 accumulation, f32 recurrent state); costs[i] (f32) = reduce_t -reward(state_t) with cost_mode = ICEM_COST_*.
  * params: the packed bf16 parameter buffer of icem_rssm_param_elems() elements (layout: icem_amd/csrc/icem_rssm.h;
  * packer: icem_amd.models.pack_rssm).  No handle.  Populations of up to 65 536 rows take a launch in which the
@@ -820,13 +823,32 @@ int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const 
                            const void* actions, void* costs, void* stream);
 /* B planners' populations through the declared RSSM in ONE launch (the reference's parallel episodes, each with its own
  * start state: icem/misc/rollout_utils.py:46-58, 129-152).  rows_host[p] >= 1 trajectories of problem p, back to back in
- * actions [sum rows, horizon, 6] / costs [sum rows]; obs0 [n_problems, 230] (f32, device); one params buffer for all.
+ * actions [sum rows, horizon, 6] (another width: icem_rssm_rollout_cost_batch_w) / costs [sum rows]; obs0 [n_problems, 230] (f32, device); one params buffer for all.
  * costs of problem p: bit for bit icem_rssm_rollout_cost(rows_host[p], ..., obs0 + 230 p, its actions).
  * n_problems in [1, 32].  Served by the split launch only: the sum over p of ceil(rows/16) tiles beyond its limit, or the
  * split launch switched off: ICEM_E_UNSUPPORTED, nothing launched.  Staging / capture / ICEM_E_STATE rules of
  * icem_rssm_rollout_cost. */
 int icem_rssm_rollout_cost_batch(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t cost_mode,
                                  const void* params, const void* obs0, const void* actions, void* costs, void* stream);
+/* The two entries above at any action width act_dim in [1, ICEM_RSSM_MAX_ACT_DIM] (the other sizes stay 200 / 30 / 200):
+ * actions is [n, horizon, act_dim] resp. [sum rows, horizon, act_dim], params a buffer packed from a model of THAT width --
+ * the same icem_rssm_param_elems() elements, the action columns of the input layer at 32 .. 32 + act_dim of its [z | a]
+ * contraction, zeros behind them (pack_rssm).  Only the act_dim entries a row owns per step are ever read.  act_dim outside
+ * the range: ICEM_E_UNSUPPORTED, nothing launched.  The entries above are these at act_dim = 6, bit for bit. */
+#define ICEM_RSSM_MAX_ACT_DIM 32
+int icem_rssm_rollout_cost_w(int32_t n, int32_t horizon, int32_t act_dim, int32_t cost_mode, const void* params, const void* obs0,
+                             const void* actions, void* costs, void* stream);
+int icem_rssm_rollout_cost_batch_w(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t act_dim, int32_t cost_mode,
+                                   const void* params, const void* obs0, const void* actions, void* costs, void* stream);
+/* Binds a handle to an RSSM of action width act_dim for the learned-dynamics steps (icem_plan_step_learned*,
+ * icem_plan_step_cem_learned*, icem_plan_step_random_learned* and their *_ok): the width of the model whose packed `params` the
+ * caller will pass.  act_dim must equal the handle's cfg.act_dim (ICEM_E_INVALID) and lie in [1, ICEM_RSSM_MAX_ACT_DIM]
+ * (ICEM_E_UNSUPPORTED); a refused call leaves the handle as it was.  A handle never bound is served at the declared width 6
+ * only -- the library cannot see the width of a `params` buffer, so it is never guessed from cfg.act_dim.  A batch shares one
+ * model: handles of one batch that are bound to different widths are an unequal configuration (ICEM_E_INVALID).
+ * icem_rssm_act_dim: the bound width (6 for a handle never bound, 0 for a null handle). */
+int icem_set_rssm_act_dim(icem_handle* h, int32_t act_dim);
+int32_t icem_rssm_act_dim(const icem_handle* h);
 
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action
