@@ -87,6 +87,14 @@ class IcemRandomBuffersC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("low", "high", "obs0", "actions", "costs", "best_actions", "result")]
 
 
+class IcemRssmProblemC(C.Structure):
+    """include/icem_hip.h: struct icem_rssm_problem."""
+    _fields_ = [("params", C.c_void_p), ("action_row0", C.c_int64), ("rows", C.c_int32), ("obs_row", C.c_int32)]
+
+
+RSSM_REDUCE = {"mean": 0, "max": 1}   # include/icem_hip.h: ICEM_RSSM_REDUCE_*
+RSSM_BATCH_MAX = 32                   # problems / members of one learned-dynamics launch
+
 # every symbol include/icem_hip.h declares: (name, restype, argtypes)
 _VP, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 _H = C.c_void_p
@@ -106,6 +114,9 @@ SYMBOLS = [
     ("icem_rssm_rollout_cost_batch", C.c_int, [_I32, C.POINTER(_I32), _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     ("icem_rssm_rollout_cost_w", C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     ("icem_rssm_rollout_cost_batch_w", C.c_int, [_I32, C.POINTER(_I32), _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_rssm_rollout_cost_models", C.c_int, [_I32, C.POINTER(IcemRssmProblemC), _I32, _I32, _I32, _VP, _I32, _VP, _I64, _VP, _VP]),
+    ("icem_rssm_ensemble_reduce", C.c_int, [_I32, _I64, _I32, _VP, _VP, _VP]),
+    ("icem_rssm_rollout_cost_ensemble", C.c_int, [_I32, C.POINTER(_VP), _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     ("icem_set_rssm_act_dim", C.c_int, [_VP, _I32]),
     ("icem_rssm_act_dim", _I32, [_VP]),
     ("icem_get_action", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .envs import Box, Discrete
-from .models import DeviceSyntheticModel, TrajectoryBatch
+from .models import DeviceSyntheticModel, TrajectoryBatch, rssm_rollout_cost_models
 from .planner import IcemConfig, IcemPlanner
 from ._lib import COST_MODES as L_COST_MODES
 
@@ -605,7 +605,7 @@ class MpcICemHip(MpcController):
         return executed_action
 
     @staticmethod
-    def get_action_batch(controllers, observations, states=None, mode="train"):
+    def get_action_batch(controllers, observations, states=None, mode="train", own_models=False):
         """``get_action`` of several controllers of ONE configuration at once -- the reference's parallel episodes, each
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152) -- through ``icem_plan_step_batch``:
         every stage of the planning step is one launch for all of them.  Each controller ends in exactly the state its own
@@ -614,8 +614,12 @@ class MpcICemHip(MpcController):
         GEMM kernels at h = 30: HumanoidStandup at o = 378, Humanoid, Ant, Hopper, Reacher, FetchReach); or controllers of the learned-dynamics path (``DeviceRSSMModel``) that share one parameter buffer and
         one configuration: the whole step is ``icem_plan_step_learned_batch``, every stage one launch for all of them (where
         that entry does not serve them -- another horizon, f64 ... -- ONE ``rollout_cost_batch`` launch per CEM iteration scores
-        their populations and sampling and the distribution update stay one launch per controller).  Anything else: call
-        ``get_action`` per controller."""
+        their populations and sampling and the distribution update stay one launch per controller; a ``DeviceRSSMEnsemble``
+        they all share is stepped the same way); or, with ``own_models=True``, learned-dynamics controllers of one
+        configuration with a plain ``DeviceRSSMModel`` EACH (one action width, one device): that stage-wise step, its one
+        scoring launch per iteration reading every problem's own parameters (``rssm_rollout_cost_models``).  Without the
+        keyword, controllers whose parameter buffers differ are refused as they always were: two copies of one model are
+        more often a mistake than a wish.  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)
         n = len(ctrls)
         states = [None] * n if states is None else list(states)
@@ -624,7 +628,7 @@ class MpcICemHip(MpcController):
                 raise AttributeError("beginning_of_rollout() needs to be called before")
         rssm = any(c.rssm_path for c in ctrls)   # learned dynamics: the stage-wise step around one cost launch per iteration
         if rssm:
-            why = MpcICemHip._rssm_batch_refusal(ctrls)
+            why = MpcICemHip._rssm_batch_refusal(ctrls, own_models)
             if why:
                 raise NotImplementedError("get_action_batch: " + why)
         elif any(not c.device_path or c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose for c in ctrls):
@@ -632,7 +636,8 @@ class MpcICemHip(MpcController):
         for c, ob, stt in zip(ctrls, observations, states):
             c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
                 observation=ob, env_state=stt, model_state=c.forward_model_state)
-        if rssm and all(c._learned_step_ok(None) for c in ctrls):
+        shared = rssm and all(MpcICemHip._share_params(c.forward_model, ctrls[0].forward_model) for c in ctrls)
+        if shared and all(c._learned_step_ok(None) for c in ctrls):   # (the fused step knows ONE parameter buffer)
             host = MpcICemHip._get_action_batch_learned(ctrls, observations)
         elif rssm:
             host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
@@ -813,8 +818,13 @@ class MpcICemHip(MpcController):
         return results.cpu().numpy().astype(np.float64)
 
     @staticmethod
-    def _rssm_batch_refusal(ctrls):
-        """Why these controllers' steps cannot share ``rollout_cost_batch`` launches (None: they can)."""
+    def _share_params(m, m0) -> bool:
+        return m is m0 or (m.params.data_ptr() == m0.params.data_ptr() and m.params.numel() == m0.params.numel())
+
+    @staticmethod
+    def _rssm_batch_refusal(ctrls, own_models=False):
+        """Why these controllers' steps cannot share ``rollout_cost_batch`` launches (None: they can).  ``own_models``: the
+        caller asked for controllers with a model each to be served (``get_action_batch(..., own_models=True)``)."""
         c0 = ctrls[0]
         if not all(c.rssm_path for c in ctrls):
             return "learned-dynamics controllers cannot be mixed with controllers of another path"
@@ -824,8 +834,13 @@ class MpcICemHip(MpcController):
             if c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose:
                 return "Philox noise, one GPU, not verbose"
             m, m0 = c.forward_model, c0.forward_model
-            if m is not m0 and not (m.params.data_ptr() == m0.params.data_ptr() and m.params.numel() == m0.params.numel()):
-                return "learned-dynamics controllers must share one parameter buffer (the same DeviceRSSMModel, or the same params storage)"
+            if not MpcICemHip._share_params(m, m0):
+                # a model each: served on request while every model is the library's own RSSM (one launch reads B parameter buffers)
+                if not own_models or not all(k._model_is_the_library_rssm() for k in ctrls):
+                    return ("learned-dynamics controllers must share one parameter buffer (the same DeviceRSSMModel, or the same params "
+                            "storage); controllers with a plain DeviceRSSMModel each are stepped together with own_models=True")
+                if m.act_dim != m0.act_dim or m.params.device != m0.params.device:
+                    return "learned-dynamics controllers with a model each need models of one action width on one device"
             # (everything but the seed: IcemConfig is a dataclass, and rank / world are 0 / 1 here)
             if replace(c.planner.cfg, seed=0) != replace(c0.planner.cfg, seed=0) or c.planner.device != c0.planner.device:
                 return "one configuration (horizon, populations, elites, iterations, cost mode, flags) on one device"
@@ -837,6 +852,8 @@ class MpcICemHip(MpcController):
         slice of one buffer, ONE launch scores all slices, every controller updates from its slice.  -> [B, d + 1] host
         array of executed actions and best costs (one device-to-host copy, one synchronisation)."""
         p0, m = ctrls[0].planner, ctrls[0].forward_model
+        # a model each (plain DeviceRSSMModels, _rssm_batch_refusal): the one launch reads every problem's own parameters
+        own = not all(MpcICemHip._share_params(c.forward_model, m) for c in ctrls)
         obs_dev = torch.as_tensor(np.asarray(observations, dtype=np.float32).reshape(len(ctrls), -1), device=m.device)
         for i in range(len(p0.population_sizes)):
             rows = [c._stage_rows(i) for c in ctrls]   # (a controller reset later than its peers has no shifted elites)
@@ -844,7 +861,11 @@ class MpcICemHip(MpcController):
             slices = list(torch.split(actions, rows))
             for c, a in zip(ctrls, slices):
                 c._stage_sample(i, None, a)
-            costs = m.rollout_cost_batch(obs_dev, actions, rows, L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
+            if own:
+                costs = rssm_rollout_cost_models([c.forward_model for c in ctrls], obs_dev, actions, rows, None,
+                                                 L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
+            else:
+                costs = m.rollout_cost_batch(obs_dev, actions, rows, L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
             for c, a, k in zip(ctrls, slices, torch.split(costs, rows)):
                 c._stage_update(i, k, a)
         return torch.stack([c._stage_finish() for c in ctrls]).cpu().numpy().astype(np.float64)

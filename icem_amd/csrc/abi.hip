@@ -966,4 +966,68 @@ int icem_rssm_rollout_cost_batch_w(int32_t n_problems, const int32_t* rows_host,
                                                       (const float*)obs0, (const float*)actions, (float*)costs, (hipStream_t)stream));
 }
 
+// admission of a launch of problems with a model each (both entries below): everything that is refused, before any device call
+static int admit_rssm_models(const char* who, int32_t n_problems, const icem_rssm_problem* pr, int32_t horizon, int32_t act_dim,
+                             int32_t cost_mode, int32_t n_obs, int64_t n_action_rows, rssm::Problem* out) {
+    auto say = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+    if (n_problems < 1 || n_problems > rssm::BATCH_MAX) return say(ICEM_E_INVALID, "n_problems / members must be in [1, 32]");
+    for (int p = 0; p < n_problems; ++p) {
+        if (!pr[p].params) return say(ICEM_E_INVALID, "null params entry");
+        if (pr[p].rows < 1) return say(ICEM_E_INVALID, "every problem needs at least one row");
+        if (pr[p].action_row0 < 0 || pr[p].action_row0 + pr[p].rows > n_action_rows)
+            return say(ICEM_E_INVALID, "a problem's action rows (action_row0 .. action_row0 + rows) must lie inside [0, n_action_rows]");
+        if (pr[p].obs_row < 0 || pr[p].obs_row >= n_obs) return say(ICEM_E_INVALID, "obs_row must be in [0, n_obs)");
+        out[p] = {(const unsigned short*)pr[p].params, (long long)pr[p].action_row0, pr[p].rows, pr[p].obs_row};
+    }
+    if (horizon < 1) return say(ICEM_E_INVALID, "horizon must be >= 1");
+    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return say(ICEM_E_INVALID, "bad cost_mode");
+    if (act_dim < 1 || act_dim > rssm::ACT_MAX) return say(ICEM_E_UNSUPPORTED, "act_dim must be in [1, 32]");
+    const int tiles = rssm_models_tiles(n_problems, out);
+    if (tiles < 0 || !rssm_split_batch_ok(tiles, horizon))
+        return say(ICEM_E_UNSUPPORTED, "the problems' tiles (the sum over the problems of ceil(rows / 16)) exceed the split launch's "
+                                       "limit, or the split launch is switched off; nothing was launched");
+    return ICEM_OK;
+}
+
+int icem_rssm_rollout_cost_models(int32_t n_problems, const icem_rssm_problem* problems_host, int32_t horizon, int32_t act_dim,
+                                  int32_t cost_mode, const void* obs0, int32_t n_obs, const void* actions, int64_t n_action_rows,
+                                  void* costs, void* stream) {
+    if (!problems_host || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_models: null pointer");
+    rssm::Problem pr[rssm::BATCH_MAX];
+    if (int rc = admit_rssm_models("icem_rssm_rollout_cost_models", n_problems, problems_host, horizon, act_dim, cost_mode, n_obs,
+                                   n_action_rows, pr))
+        return rc;
+    return rssm_launch_result(launch_rssm_split_models(n_problems, pr, horizon, act_dim, cost_mode, (const float*)obs0, (const float*)actions,
+                                                       (float*)costs, (hipStream_t)stream));
+}
+
+int icem_rssm_ensemble_reduce(int32_t members, int64_t n, int32_t reduce, const void* member_costs, void* costs, void* stream) {
+    if (!member_costs || !costs) return fail(ICEM_E_INVALID, "icem_rssm_ensemble_reduce: null pointer");
+    if (members < 1 || members > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_rssm_ensemble_reduce: members must be in [1, 32]");
+    if (n < 1) return fail(ICEM_E_INVALID, "icem_rssm_ensemble_reduce: n must be >= 1");
+    if (reduce != ICEM_RSSM_REDUCE_MEAN && reduce != ICEM_RSSM_REDUCE_MAX)
+        return fail(ICEM_E_INVALID, "icem_rssm_ensemble_reduce: reduce must be ICEM_RSSM_REDUCE_MEAN or ICEM_RSSM_REDUCE_MAX");
+    ICEM_HIP_TRY(launch_rssm_ensemble_reduce(members, n, reduce, (const float*)member_costs, (float*)costs, (hipStream_t)stream));
+    return ICEM_OK;
+}
+
+int icem_rssm_rollout_cost_ensemble(int32_t members, const void* const* params_host, int32_t n, int32_t horizon, int32_t act_dim,
+                                    int32_t cost_mode, int32_t reduce, const void* obs0, const void* actions, void* member_costs,
+                                    void* costs, void* stream) {
+    if (!params_host || !obs0 || !actions || !member_costs || !costs) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_ensemble: null pointer");
+    if (members < 1 || members > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_ensemble: members must be in [1, 32]");
+    if (n < 1) return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_ensemble: n (rows) must be >= 1");
+    if (reduce != ICEM_RSSM_REDUCE_MEAN && reduce != ICEM_RSSM_REDUCE_MAX)
+        return fail(ICEM_E_INVALID, "icem_rssm_rollout_cost_ensemble: reduce must be ICEM_RSSM_REDUCE_MEAN or ICEM_RSSM_REDUCE_MAX");
+    icem_rssm_problem in[rssm::BATCH_MAX];
+    for (int e = 0; e < members; ++e) in[e] = {params_host[e], 0, n, 0};   // every member: all n rows, from the one observation
+    rssm::Problem pr[rssm::BATCH_MAX];
+    if (int rc = admit_rssm_models("icem_rssm_rollout_cost_ensemble", members, in, horizon, act_dim, cost_mode, 1, n, pr)) return rc;
+    if (int rc = rssm_launch_result(launch_rssm_split_models(members, pr, horizon, act_dim, cost_mode, (const float*)obs0,
+                                                             (const float*)actions, (float*)member_costs, (hipStream_t)stream)))
+        return rc;
+    ICEM_HIP_TRY(launch_rssm_ensemble_reduce(members, n, reduce, (const float*)member_costs, (float*)costs, (hipStream_t)stream));
+    return ICEM_OK;
+}
+
 }  // extern "C"

@@ -56,4 +56,16 @@ bool rssm_split_batch_ok(int tiles, int horizon);
 hipError_t rssm_split_prepare(int tiles, int horizon, hipStream_t st);   // staging + status check of such a launch, no kernel
 hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon, int act_dim, int cost_mode, const unsigned short* params,
                                    const float* obs0, const float* actions, float* costs, hipStream_t st);
+// B <= BATCH_MAX problems with a MODEL EACH in one split launch (an ensemble's members, parallel episodes that own their
+// trained models): problem p rolls its `rows` action rows action_row0 .. (several problems may name the same rows) out from
+// row obs_row of obs0 through its own packed `params`; costs [sum rows] takes the problems' rows back to back in problem
+// order, each bit for bit what launch_rssm_split gives for that problem alone.
+namespace rssm {
+struct Problem { const unsigned short* params; long long action_row0; int rows, obs_row; };
+}
+int rssm_models_tiles(int n_problems, const rssm::Problem* problems);   // (-1: more than the staging bookkeeping could ever hold)
+hipError_t launch_rssm_split_models(int n_problems, const rssm::Problem* problems, int horizon, int act_dim, int cost_mode, const float* obs0,
+                                    const float* actions, float* costs, hipStream_t st);
+// costs [n] = the mean (reduce 0) or the maximum (1) over e of member_costs [members, n], members in ascending order
+hipError_t launch_rssm_ensemble_reduce(int members, long long n, int reduce, const float* member_costs, float* costs, hipStream_t st);
 }  // namespace icem

@@ -498,23 +498,10 @@ __device__ __forceinline__ void recurrence(ProducerLds<TT>& s, bool first_wg, in
     else recurrence_steps<false, TT, AW>(s, w, lane, base, row_end, horizon, d, Pg, actions, items, tile_stride, flag, ntl, stamps, stamp);
 }
 
-// tiles first, first + stride, ...: one tile per workgroup while both workgroup kinds fit the chip together, several for
-// the large populations whose reward workgroups run behind the recurrence workgroups (the head's weights are loaded once).
-// rows_of(tile, base, end): trajectory j of launch-global tile `tile` is row base + j of costs if that is below end
-// (asked once per tile, in ascending tile order, at the store).
-template <class RowsOf>
-__device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int stride, int tiles, RowsOf rows_of, int horizon, int cost_mode,
-                                            const unsigned short* __restrict__ Pg, float* __restrict__ costs,
-                                            const unsigned short* stage, unsigned* flags, unsigned* status, long long* stamps) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 15, g = lane >> 4;
-    const bool stamp = stamps && first == 0 && tid == 0;
-    if (stamp) stamps[8] = wall_clock64();
+// the reward head's weights and biases of ONE model into the wave's registers (148 + 20 per lane)
+__device__ __forceinline__ void load_head(const unsigned short* Pg, int lane, int w, int g, v4i (&A6)[NOB][K6K],
+                                          v4i (&A7)[NOB][HIDK], v4i (&A8)[HIDK], v4f (&b6)[NOB], v4f (&b7)[NOB], v4f& b8) {
     gptr Plane = (gptr)Pg + lane * 8;
-    // the head's weights and biases, once
-    v4i A6[NOB][K6K], A7[NOB][HIDK], A8[HIDK];
-    v4f b6[NOB], b7[NOB];
 #pragma unroll
     for (int i = 0; i < NOB; ++i) {
         const int ob = own_block(w, i);
@@ -524,7 +511,43 @@ __device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int strid
         b7[i] = *reinterpret_cast<const v4f*>(reinterpret_cast<const float*>(Pg + B7) + ob * 16 + 4 * g);
     }
     request<HIDK>(Plane + W8, A8);
-    const v4f b8 = *reinterpret_cast<const v4f*>(reinterpret_cast<const float*>(Pg + B8) + 4 * g);
+    b8 = *reinterpret_cast<const v4f*>(reinterpret_cast<const float*>(Pg + B8) + 4 * g);
+}
+// the launches of ONE model: a walking workgroup keeps the weights it loaded in front of its first tile
+struct SameModel {
+    static constexpr bool PER_TILE = false;
+    __device__ const unsigned short* operator()(int) const { return nullptr; }
+};
+// a model per problem: of(tile) -> the packed parameters of the tile's problem
+template <class F>
+struct PerTile {
+    static constexpr bool PER_TILE = true;
+    F& of;
+    __device__ const unsigned short* operator()(int tile) const { return of(tile); }
+};
+
+// tiles first, first + stride, ...: one tile per workgroup while both workgroup kinds fit the chip together, several for
+// the large populations whose reward workgroups run behind the recurrence workgroups (the head's weights are loaded once).
+// rows_of(tile, base, end): trajectory j of launch-global tile `tile` is row base + j of costs if that is below end
+// (asked once per tile, in ascending tile order, at the store).
+// Pg: the model of tile `first`.  PER_TILE launches (problems with a model each): params_of(tile), asked once per tile in
+// ascending tile order in front of rows_of, names the tile's model; a walking workgroup reloads ALL of the head's weights
+// and biases when the pointer differs from the one it holds (a wave-uniform comparison: both come out of scalar
+// registers), and loads nothing when it is the same.
+template <class RowsOf, class ParamsOf>
+__device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int stride, int tiles, RowsOf rows_of, ParamsOf params_of, int horizon,
+                                            int cost_mode, const unsigned short* __restrict__ Pg, float* __restrict__ costs,
+                                            const unsigned short* stage, unsigned* flags, unsigned* status, long long* stamps) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const bool stamp = stamps && first == 0 && tid == 0;
+    if (stamp) stamps[8] = wall_clock64();
+    // the head's weights and biases, once (per model)
+    v4i A6[NOB][K6K], A7[NOB][HIDK], A8[HIDK];
+    v4f b6[NOB], b7[NOB], b8;
+    load_head(Pg, lane, w, g, A6, A7, A8, b6, b7, b8);
+    const unsigned short* held = Pg;   // (PER_TILE) the model whose head the registers hold
     for (int e = tid; e < 2 * 16 * RS; e += NTHR) { (&s.r1[0][0])[e] = 0; (&s.r2[0][0])[e] = 0; }   // the K padding of the rows
     // A reward workgroup that gave up in an EARLIER launch left this staging area's flags in an unknown state (its stalled
     // producer kept storing behind the reset): the status word stays raised until the host has zeroed the flags
@@ -534,6 +557,13 @@ __device__ __forceinline__ void reward_head(ConsumerLds& s, int first, int strid
     const int xr = j * RS + 8 * g, xo = j * RS + 4 * g;
     if (stamp) stamps[9] = wall_clock64();
     for (int tile = first; tile < tiles; tile += stride) {
+    if constexpr (ParamsOf::PER_TILE) {
+        const unsigned short* mine = params_of(tile);
+        if (mine != held) {   // (uniform; the registers are the wave's own: it is past its MFMAs of the tile before)
+            held = mine;
+            load_head(held, lane, w, g, A6, A7, A8, b6, b7, b8);
+        }
+    }
     const unsigned short* items = stage + (size_t)tile * horizon * ITEM;
     unsigned* flag = flags + tile;
     float acc_cost = 0.f;
@@ -637,7 +667,8 @@ __global__ __launch_bounds__(NTHR) void rssm_split_kernel(int n, int horizon, in
                             ACT, Pg, obs0, actions, stage, flags, stamps);
     } else {
         reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
-                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, SameModel{}, horizon, cost_mode, Pg, costs, stage, flags,
+                    status, stamps);
     }
 }
 // ... at any action width d in [1, ACT_MAX]: the recurrence stages d entries per row and step (row stride horizon * d); the
@@ -655,7 +686,8 @@ __global__ __launch_bounds__(NTHR) void rssm_split_w_kernel(int n, int horizon, 
                           d, Pg, obs0, actions, stage, flags, stamps);
     } else {
         reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
-                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+                    [n](int tile, int& base, int& end) { base = tile * 16; end = n; }, SameModel{}, horizon, cost_mode, Pg, costs, stage, flags,
+                    status, stamps);
     }
 }
 
@@ -695,7 +727,7 @@ __global__ __launch_bounds__(NTHR) void rssm_split_batch_kernel(const BatchTable
                         base = tab.row0[p] + (tile - tab.tile0[p]) * 16;
                         end = tab.row0[p] + tab.rows[p];
                     },
-                    horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+                    SameModel{}, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
     }
 }
 // ... at any action width d in [1, ACT_MAX] (rssm_split_w_kernel)
@@ -722,8 +754,88 @@ __global__ __launch_bounds__(NTHR) void rssm_split_batch_w_kernel(const BatchTab
                         base = tab.row0[p] + (tile - tab.tile0[p]) * 16;
                         end = tab.row0[p] + tab.rows[p];
                     },
-                    horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
+                    SameModel{}, horizon, cost_mode, Pg, costs, stage, flags, status, stamps);
     }
+}
+
+// The problems of a launch in which every problem names its OWN model, by value in the kernel arguments as BatchTable is
+// (1152 bytes).  Problem p owns the launch-global tiles tile0[p] .. and the recurrence workgroups wg0[p] ..; its rows[p]
+// trajectories are the ACTION rows arow0[p] .. (several problems may name the same rows: an ensemble's members score one
+// population) and the COST rows crow0[p] .. (back to back in problem order); it starts from row obs[p] of the observation
+// table and runs through the packed parameter buffer params[p].  The pointers are declared in the global address space:
+// read out of the kernel arguments as generic ones, every weight access behind them would be a FLAT access.
+struct ModelsTable {
+    gptr params[rssm::BATCH_MAX];
+    long long arow0[rssm::BATCH_MAX];
+    int tile0[rssm::BATCH_MAX], wg0[rssm::BATCH_MAX], rows[rssm::BATCH_MAX], crow0[rssm::BATCH_MAX], obs[rssm::BATCH_MAX];
+};
+
+// rssm_split_batch_kernel for problems with a model each (AW: recurrence): the same two device bodies.  A recurrence
+// workgroup's tiles are all of ONE problem, hence of one model; its actions start at the problem's first action row (the
+// padding rows of the problem's last tile repeat ITS last row).  A reward workgroup that scores one tile loads that
+// tile's model; one that walks the tiles holds a model's head until a tile names another (reward_head).
+template <int TT, int AW>
+__device__ __forceinline__ void split_models(unsigned char* smem, const ModelsTable& tab, int n_problems, int horizon, int d, int cost_mode,
+                                             const float* __restrict__ obs0, const float* __restrict__ actions, float* __restrict__ costs,
+                                             unsigned short* stage, unsigned* flags, unsigned* status, int tiles, int prods,
+                                             long long* stamps) {
+    const int b = blockIdx.x;
+    if (b < prods) {
+        int p = 0;
+        for (int q = 1; q < n_problems; ++q) p = b >= tab.wg0[q] ? q : p;
+        const int lt0 = (b - tab.wg0[p]) * TT;
+        const int left = (tab.rows[p] + 15) / 16 - lt0;
+        recurrence<TT, AW>(*reinterpret_cast<ProducerLds<TT>*>(smem), b == 0, tab.tile0[p] + lt0, left < TT ? left : TT, lt0 * 16, tab.rows[p],
+                           horizon, d, (const unsigned short*)tab.params[p], obs0 + (size_t)tab.obs[p] * (DET + STOCH),
+                           actions + (size_t)tab.arow0[p] * horizon * (AW ? AW : d), stage, flags, stamps);
+    } else {
+        int p = 0;   // (a walking workgroup's tiles ascend: the scan goes on from the problem of the tile before)
+        auto params_of = [&tab, &p, n_problems](int tile) {
+            while (p + 1 < n_problems && tile >= tab.tile0[p + 1]) ++p;
+            return (const unsigned short*)tab.params[p];
+        };
+        const unsigned short* first_model = params_of(b - prods);
+        reward_head(*reinterpret_cast<ConsumerLds*>(smem), b - prods, (int)gridDim.x - prods, tiles,
+                    [&tab, &p](int tile, int& base, int& end) {   // (behind params_of(tile): p is the tile's problem)
+                        base = tab.crow0[p] + (tile - tab.tile0[p]) * 16;
+                        end = tab.crow0[p] + tab.rows[p];
+                    },
+                    PerTile<decltype(params_of)>{params_of}, horizon, cost_mode, first_model, costs, stage, flags, status, stamps);
+    }
+}
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_split_models_kernel(const ModelsTable tab, int n_problems, int horizon, int cost_mode,
+                                                                const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                                float* __restrict__ costs, unsigned short* stage, unsigned* flags,
+                                                                unsigned* status, int tiles, int prods, long long* stamps) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
+    split_models<TT, ACT>(smem, tab, n_problems, horizon, ACT, cost_mode, obs0, actions, costs, stage, flags, status, tiles, prods, stamps);
+}
+// ... at any action width d in [1, ACT_MAX] (rssm_split_w_kernel)
+template <int TT>
+__global__ __launch_bounds__(NTHR) void rssm_split_models_w_kernel(const ModelsTable tab, int n_problems, int horizon, int d, int cost_mode,
+                                                                  const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                                  float* __restrict__ costs, unsigned short* stage, unsigned* flags,
+                                                                  unsigned* status, int tiles, int prods, long long* stamps) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[lds_bytes<TT>()];
+    split_models<TT, 0>(smem, tab, n_problems, horizon, d, cost_mode, obs0, actions, costs, stage, flags, status, tiles, prods, stamps);
+}
+
+// costs[i] = the mean (reduce 0) or the worst (1) of member_costs[e][i] over the members, one thread per row, the members
+// in the order e = 0, 1, ..: no atomics, no division (inv = (float)(1.0 / members) comes from the host), so the bits are
+// those of the same three float32 operations anywhere.  A NaN member makes the row NaN under both (max: the rule of
+// reward_head's `best` mode).
+__global__ __launch_bounds__(256) void rssm_ensemble_reduce_kernel(int members, long long n, int reduce, float inv,
+                                                                  const float* __restrict__ member_costs, float* __restrict__ costs) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float acc = member_costs[i];
+    for (int e = 1; e < members; ++e) {
+        const float c = member_costs[(size_t)e * n + i];
+        if (reduce == 0) acc = acc + c;
+        else acc = (c > acc || c != c) ? c : acc;
+    }
+    costs[i] = reduce == 0 ? acc * inv : acc;
 }
 
 // One staging area per (device, stream): launches on a stream are ordered, so they may share it.  (Areas live until
@@ -907,6 +1019,55 @@ hipError_t launch_rssm_split_batch(int n_problems, const int* rows, int horizon,
     else
         hipLaunchKernelGGL(rssm_split_batch_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, params,
                            obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    return hipGetLastError();
+}
+
+int rssm_models_tiles(int n_problems, const rssm::Problem* problems) {
+    long long tiles = 0;
+    for (int p = 0; p < n_problems; ++p) tiles += ((long long)problems[p].rows + 15) / 16;
+    return tiles > rssm::SPLIT_TILE_LIMIT ? -1 : (int)tiles;
+}
+
+hipError_t launch_rssm_split_models(int n_problems, const rssm::Problem* problems, int horizon, int act_dim, int cost_mode, const float* obs0,
+                                    const float* actions, float* costs, hipStream_t st) {
+    const int tiles = rssm_models_tiles(n_problems, problems);
+    if (n_problems < 1 || n_problems > rssm::BATCH_MAX || tiles < 1 || act_dim < 1 || act_dim > ACT_MAX) return hipErrorInvalidValue;
+    const Arrangement a = arrangement(tiles);
+    ModelsTable tab{};
+    int prods = 0;
+    for (int p = 0, tile = 0, row = 0; p < n_problems; ++p) {
+        const rssm::Problem& q = problems[p];
+        if (!q.params || q.rows < 1 || q.action_row0 < 0 || q.obs_row < 0) return hipErrorInvalidValue;
+        const int pt = (q.rows + 15) / 16;
+        tab.params[p] = (gptr)q.params; tab.arow0[p] = q.action_row0; tab.obs[p] = q.obs_row;
+        tab.tile0[p] = tile; tab.wg0[p] = prods; tab.crow0[p] = row; tab.rows[p] = q.rows;
+        tile += pt; prods += (pt + a.tt - 1) / a.tt; row += q.rows;
+    }
+    std::unique_lock<std::mutex> lk;
+    const Staging* sg = nullptr;
+    const hipError_t e = staging_for(tiles, horizon, st, lk, sg);
+    if (e != hipSuccess) return e;
+    if (act_dim != ACT) {   // the runtime-width twins
+        if (a.tt == 2)
+            hipLaunchKernelGGL(rssm_split_models_w_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, act_dim, cost_mode,
+                               obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+        else
+            hipLaunchKernelGGL(rssm_split_models_w_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, act_dim, cost_mode,
+                               obs0, actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    } else if (a.tt == 2)
+        hipLaunchKernelGGL(rssm_split_models_kernel<2>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, obs0,
+                           actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    else
+        hipLaunchKernelGGL(rssm_split_models_kernel<1>, dim3(prods + a.heads), dim3(NTHR), 0, st, tab, n_problems, horizon, cost_mode, obs0,
+                           actions, costs, sg->stage, sg->flags, sg->status_dev, tiles, prods, g_stamps);
+    return hipGetLastError();
+}
+
+hipError_t launch_rssm_ensemble_reduce(int members, long long n, int reduce, const float* member_costs, float* costs, hipStream_t st) {
+    if (members < 1 || n < 1 || reduce < 0 || reduce > 1) return hipErrorInvalidValue;
+    const float inv = (float)(1.0 / members);
+    hipLaunchKernelGGL(rssm_ensemble_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, members, n, reduce, inv, member_costs,
+                       costs);
     return hipGetLastError();
 }
 }  // namespace icem

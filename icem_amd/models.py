@@ -390,3 +390,183 @@ class DeviceRSSMModel(ForwardModel):
 
     def predict(self, *, observations, states, actions):
         return self._tm.predict(observations=observations, states=states, actions=actions)
+
+
+def _rssm_models_launch(lib, device, act_dim, params_ptrs, obs_rows, arow0, rows, obs_dev, n_obs, actions, cost_mode, out=None):
+    """One ``icem_rssm_rollout_cost_models`` launch: problem p = (params_ptrs[p], obs_rows[p], arow0[p], rows[p]) over the f32
+    device tensors ``obs_dev [n_obs, 230]`` and ``actions [n_action_rows, h, act_dim]`` -> costs ``[sum rows]`` (``out``, or new)."""
+    import ctypes as C
+    import torch
+    from . import _lib as L
+    n = len(rows)
+    costs = torch.empty((sum(rows),), dtype=torch.float32, device=device) if out is None else out
+    problems = (L.IcemRssmProblemC * n)(*[L.IcemRssmProblemC(int(params_ptrs[p]), int(arow0[p]), int(rows[p]), int(obs_rows[p]))
+                                           for p in range(n)])
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    L.check(lib.icem_rssm_rollout_cost_models(n, problems, actions.shape[1], act_dim, cost_mode, C.c_void_p(obs_dev.data_ptr()), n_obs,
+                                              C.c_void_p(actions.data_ptr()), actions.shape[0], C.c_void_p(costs.data_ptr()), st))
+    return costs
+
+
+def _check_problem_shapes(act_dim, n_problems, observations, actions, rows, action_row0):
+    """The shape checks of ``rollout_cost_batch`` for problems that may share action rows (needs nothing of a device).
+    -> (rows, action_row0, observations: a device tensor as it came, or an f32 array)."""
+    import torch
+    rows = [int(r) for r in rows]
+    if len(rows) != n_problems:
+        raise ValueError(f"{n_problems} problems but {len(rows)} row counts")
+    if actions.ndim != 3 or actions.shape[2] != act_dim:
+        raise ValueError(f"actions must be [rows, h, {act_dim}], got {tuple(actions.shape)}")
+    if any(r < 1 for r in rows):
+        raise ValueError(f"every problem needs at least one row, got {rows}")
+    if action_row0 is None:   # back to back
+        if sum(rows) != actions.shape[0]:
+            raise ValueError(f"rows sum to {sum(rows)} but actions has {actions.shape[0]} rows")
+        action_row0 = [sum(rows[:p]) for p in range(len(rows))]
+    else:
+        action_row0 = [int(a) for a in action_row0]
+        if len(action_row0) != len(rows):
+            raise ValueError(f"{len(rows)} row counts but {len(action_row0)} first action rows")
+        for a, r in zip(action_row0, rows):
+            if a < 0 or a + r > actions.shape[0]:
+                raise ValueError(f"action rows {a} .. {a + r} lie outside actions' {actions.shape[0]} rows")
+    on_device = isinstance(observations, torch.Tensor) and observations.is_cuda
+    if not on_device:
+        observations = np.asarray(observations, dtype=np.float32)
+    if tuple(observations.shape) != (len(rows), 230):
+        raise ValueError(f"observations must be [{len(rows)}, 230] (one start state per problem), got {tuple(observations.shape)}")
+    if on_device and (observations.dtype != torch.float32 or not observations.is_contiguous()):
+        raise ValueError("a device tensor of observations must be contiguous float32")
+    return rows, action_row0, observations
+
+
+def rssm_rollout_cost_models(models, observations, actions, rows, action_row0=None, cost_mode: int = 0):
+    """``DeviceRSSMModel.rollout_cost`` of B problems with a MODEL EACH in ONE launch (``icem_rssm_rollout_cost_models``; the
+    reference's parallel episodes, icem/misc/rollout_utils.py:46-58, 129-152, each with its own trained model): problem p
+    scores ``rows[p]`` action sequences of ``actions [n, h, act_dim]`` (f32 device tensor) -- from row ``action_row0[p]`` on, or
+    back to back with ``action_row0=None``; the rows of different problems may overlap or coincide -- from ``observations[p]``
+    (``[B, 230]`` array-like, or an f32 device tensor that is used as is) through ``models[p]`` (``DeviceRSSMModel``s of one
+    action width on one device; the same model may serve several problems).  -> costs ``[sum rows]``, problem p's rows back
+    to back in problem order, each bit for bit what ``models[p].rollout_cost`` gives for it alone.  B <= 32."""
+    import torch
+    models = list(models)
+    if not 1 <= len(models) <= 32:
+        raise ValueError(f"one launch takes 1 to 32 problems, not {len(models)}")
+    act_dim = models[0].act_dim
+    if any(m.act_dim != act_dim for m in models):
+        raise ValueError(f"the models must share one action width, got {[m.act_dim for m in models]}")
+    rows, action_row0, observations = _check_problem_shapes(act_dim, len(models), observations, actions, rows, action_row0)
+    m0 = models[0]
+    if any(m.params.device != m0.params.device for m in models):
+        raise ValueError("the models' parameter buffers must be on one device")
+    o = observations if isinstance(observations, torch.Tensor) else torch.as_tensor(observations, device=m0.device)
+    actions = actions.to(torch.float32).contiguous()
+    return _rssm_models_launch(m0.lib, m0.device, act_dim, [m.params.data_ptr() for m in models], range(len(models)), action_row0, rows,
+                               o, len(models), actions, cost_mode)
+
+
+class DeviceRSSMEnsemble(ForwardModel):
+    """E ``DeviceRSSMModel``s that score every candidate plan together (the model loop of the reference's
+    icem/models/abstract_models.py:17-53, with members trained from different seeds): a plan's cost is the members' mean
+    (``reduce="mean"``) or the worst member's (``"max"``, the cautious planner), so that one model's error is not exploited.
+    Built from ``models=[DeviceRSSMModel, ...]`` or from ``seeds=[...]`` (+ ``act_dim``, default: the models' width, or 6);
+    1 to 32 members of one action width.  ``rollout_cost`` is ONE learned-dynamics launch for all members
+    (``icem_rssm_rollout_cost_ensemble``) + the reduction; ``member_costs`` holds the last ``[E, n]`` (row e: member e alone,
+    bit for bit).  ``params`` are the members' packed buffers stacked ``[E, elems]`` on one device -- the launch reads these.
+
+    Every controller plans through it with its stage-wise loop: it is deliberately NOT a ``DeviceRSSMModel`` (the library's
+    fused ``*_learned`` steps know one parameter buffer).  ``predict`` -- the reference-style interface needs ONE successor
+    state -- delegates to member 0."""
+
+    obs_dim = 230
+
+    def __init__(self, models=None, seeds=None, act_dim=None, reduce: str = "mean", device="cuda:0", env=None):
+        super().__init__(env=env)
+        import torch
+        from . import _lib as L
+        if reduce not in L.RSSM_REDUCE:
+            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        if (models is None) == (seeds is None):
+            raise ValueError("give either models=[DeviceRSSMModel, ...] or seeds=[...]")
+        count = len(models) if models is not None else len(seeds)
+        if not 1 <= count <= L.RSSM_BATCH_MAX:
+            raise ValueError(f"an ensemble has 1 to {L.RSSM_BATCH_MAX} members (one launch serves them all), not {count}")
+        if models is None:
+            models = [DeviceRSSMModel(seed=int(s), device=device, env=env, act_dim=6 if act_dim is None else int(act_dim)) for s in seeds]
+        models = list(models)
+        if not all(isinstance(m, DeviceRSSMModel) for m in models):
+            raise ValueError("the members of a DeviceRSSMEnsemble are DeviceRSSMModels")
+        widths = sorted({m.act_dim for m in models})
+        if len(widths) != 1 or (act_dim is not None and widths[0] != int(act_dim)):
+            raise ValueError(f"the members must share one action width{'' if act_dim is None else f' ({act_dim})'}, got {widths}")
+        self.models, self.members, self.reduce = models, len(models), reduce
+        self.act_dim = widths[0]
+        self.device = models[0].device
+        self.params = torch.stack([m.params.to(self.device) for m in models])
+        self.lib = models[0].lib
+        self.member_costs = None
+        self._obs_host = self._obs_dev = None
+
+    def _param_ptrs(self):
+        stride = self.params.shape[1] * self.params.element_size()
+        return [self.params.data_ptr() + e * stride for e in range(self.members)]
+
+    def rollout_cost(self, obs, actions, cost_mode: int = 0):
+        """costs ``[n]`` (f32 device tensor): the members' reduced costs of f32 device action sequences ``[n, h, act_dim]`` from
+        observation ``obs [230]``; ``member_costs [E, n]`` is kept."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        if actions.ndim != 3 or actions.shape[2] != self.act_dim:
+            raise ValueError(f"actions must be [n, h, {self.act_dim}], got {tuple(actions.shape)}")
+        if actions.shape[0] < 1:
+            raise ValueError("actions must have at least one row")
+        ob = np.asarray(obs, dtype=np.float32)
+        if ob.shape != (230,):
+            raise ValueError(f"obs must be [230], got {ob.shape}")
+        actions = actions.to(torch.float32).contiguous()
+        n, h, _ = actions.shape
+        if self._obs_host is None or not np.array_equal(ob, self._obs_host):   # the CEM iterations of a step share it
+            self._obs_host, self._obs_dev = ob.copy(), torch.as_tensor(ob, device=self.device)
+        member_costs = torch.empty((self.members, n), dtype=torch.float32, device=self.device)
+        costs = torch.empty((n,), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_rssm_rollout_cost_ensemble(self.members, (C.c_void_p * self.members)(*self._param_ptrs()), n, h, self.act_dim,
+                                                         cost_mode, L.RSSM_REDUCE[self.reduce], C.c_void_p(self._obs_dev.data_ptr()),
+                                                         C.c_void_p(actions.data_ptr()), C.c_void_p(member_costs.data_ptr()),
+                                                         C.c_void_p(costs.data_ptr()), st))
+        self.member_costs = member_costs
+        return costs
+
+    def rollout_cost_batch(self, observations, actions, rows, cost_mode: int = 0):
+        """``rollout_cost`` of B planners in ONE launch of B x E problems (+ one reduction): planner b scores its ``rows[b]``
+        action sequences -- back to back in ``actions [sum rows, h, act_dim]`` -- from ``observations[b]`` through every
+        member.  -> costs ``[sum rows]``; ``member_costs [E, sum rows]`` is kept.  One launch holds 32 problems: B x E beyond
+        that raises a ``ValueError`` (step fewer planners together)."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        rows = [int(r) for r in rows]
+        if len(rows) * self.members > L.RSSM_BATCH_MAX:
+            raise ValueError(f"{len(rows)} planners x {self.members} members = {len(rows) * self.members} problems, but one "
+                             f"learned-dynamics launch holds {L.RSSM_BATCH_MAX}: step at most {L.RSSM_BATCH_MAX // self.members} planners together")
+        rows, row0, observations = _check_problem_shapes(self.act_dim, len(rows), observations, actions, rows, None)
+        o = observations if isinstance(observations, torch.Tensor) else torch.as_tensor(observations, device=self.device)
+        actions = actions.to(torch.float32).contiguous()
+        B, total = len(rows), sum(rows)
+        member_costs = torch.empty((self.members, total), dtype=torch.float32, device=self.device)
+        ptrs = self._param_ptrs()
+        # member-major: problem e * B + b writes member_costs[e, row0[b] : row0[b] + rows[b]]
+        _rssm_models_launch(self.lib, self.device, self.act_dim, [ptrs[e] for e in range(self.members) for _ in range(B)],
+                            list(range(B)) * self.members, row0 * self.members, rows * self.members, o, B, actions, cost_mode,
+                            out=member_costs.view(-1))
+        costs = torch.empty((total,), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_rssm_ensemble_reduce(self.members, total, L.RSSM_REDUCE[self.reduce], C.c_void_p(member_costs.data_ptr()),
+                                                   C.c_void_p(costs.data_ptr()), st))
+        self.member_costs = member_costs
+        return costs
+
+    def predict(self, *, observations, states, actions):
+        """Member 0's successor state (the reference-style interface returns one; the planning costs are the ensemble's)."""
+        return self.models[0].predict(observations=observations, states=states, actions=actions)

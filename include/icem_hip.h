@@ -850,6 +850,45 @@ int icem_rssm_rollout_cost_batch_w(int32_t n_problems, const int32_t* rows_host,
 int icem_set_rssm_act_dim(icem_handle* h, int32_t act_dim);
 int32_t icem_rssm_act_dim(const icem_handle* h);
 
+/* Problems with a MODEL EACH in one launch of the learned-dynamics rollout: the reference's parallel episodes
+ * (icem/misc/rollout_utils.py:46-58, 129-152) when every episode owns its trained model, and the members of a model
+ * ensemble, which the reference's model loop (icem/models/abstract_models.py:17-53) would visit one after the other.
+ * Problem p rolls the rows action_row0 .. action_row0 + rows of actions [n_action_rows, horizon, act_dim] (f32, device; the
+ * rows of different problems may overlap or coincide, and are only read) out from row obs_row of obs0 [n_obs, 230] (f32,
+ * device) through its own packed parameter buffer (device; icem_rssm_param_elems() 16-bit words packed at width act_dim).
+ * costs [sum rows] (f32): problem p's rows back to back in problem order, each bit for bit what icem_rssm_rollout_cost_w
+ * gives for that problem alone with its params.  n_problems in [1, 32]; problems_host is read before the call returns.
+ *   ICEM_E_INVALID: a NULL pointer or a NULL params entry, n_problems outside [1, 32], rows < 1, action_row0 < 0 or
+ * action_row0 + rows > n_action_rows, obs_row outside [0, n_obs), horizon < 1, a bad cost_mode.  ICEM_E_UNSUPPORTED:
+ * act_dim outside [1, ICEM_RSSM_MAX_ACT_DIM]; all problems' tiles together (the sum of ceil(rows / 16)) beyond the split
+ * launch's limit, or the split launch switched off.  Whatever is refused is refused before anything is launched.  Staging /
+ * capture / ICEM_E_STATE rules of icem_rssm_rollout_cost (the first call of a size not inside a stream capture). */
+typedef struct icem_rssm_problem {
+    const void* params;   /* this problem's packed RSSM (icem_rssm_param_elems() 16-bit words) */
+    int64_t action_row0;  /* its first row of `actions`; problems may overlap or coincide */
+    int32_t rows;         /* >= 1 */
+    int32_t obs_row;      /* its start state: row of obs0 [n_obs, 230] */
+} icem_rssm_problem;
+int icem_rssm_rollout_cost_models(int32_t n_problems, const icem_rssm_problem* problems_host, int32_t horizon, int32_t act_dim,
+                                  int32_t cost_mode, const void* obs0, int32_t n_obs, const void* actions, int64_t n_action_rows,
+                                  void* costs, void* stream);
+/* costs [n] (f32, device) out of member_costs [members, n] (f32, device), the members visited in the order 0 .. members - 1
+ * (the model loop of icem/models/abstract_models.py:17-53, reduced): ICEM_RSSM_REDUCE_MEAN is ((c_0 + c_1) + ...) * inv with
+ * inv = (float)(1.0 / members) computed on the host -- no division on the device, no atomics: float32 arithmetic restates
+ * it bit for bit; ICEM_RSSM_REDUCE_MAX is the worst member, and a NaN member makes the row NaN under both.  members in
+ * [1, 32], n >= 1, otherwise (or a NULL pointer, a bad reduce) ICEM_E_INVALID. */
+enum { ICEM_RSSM_REDUCE_MEAN = 0, ICEM_RSSM_REDUCE_MAX = 1 };
+int icem_rssm_ensemble_reduce(int32_t members, int64_t n, int32_t reduce, const void* member_costs, void* costs, void* stream);
+/* An ensemble of `members` models (params_host [members]: host array of device pointers, read before the call returns)
+ * scores the SAME n rows of actions [n, horizon, act_dim] from one observation obs0 [230]: ONE split launch of
+ * members problems that share the action rows, then the reduction.  member_costs [members, n] is an OUTPUT (row e: member
+ * e alone, bit for bit icem_rssm_rollout_cost_w with its params), costs [n] their icem_rssm_ensemble_reduce.  members == 1
+ * gives the solo launch's bits in both.  Refusals as above (members outside [1, 32], n < 1: ICEM_E_INVALID; members x
+ * ceil(n / 16) tiles beyond the limit: ICEM_E_UNSUPPORTED), before anything is launched. */
+int icem_rssm_rollout_cost_ensemble(int32_t members, const void* const* params_host, int32_t n, int32_t horizon, int32_t act_dim,
+                                    int32_t cost_mode, int32_t reduce, const void* obs0, const void* actions, void* member_costs,
+                                    void* costs, void* stream);
+
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action
  * [act_dim] (+ the best cost of the last pool, if best_cost_host != NULL) comes back as float64 after ONE stream
