@@ -198,6 +198,9 @@ SYMBOLS = [
     ("icem_plan_step_learned", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _VP, _I32, _VP]),
     ("icem_plan_step_learned_batch", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _VP, C.POINTER(_I32), _VP, _VP]),
     ("icem_learned_step_launches", C.c_int64, [_H]),
+    ("icem_plan_step_learned_models_ok", C.c_int, [_H, _I32, _I32]),
+    ("icem_plan_step_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(_VP), _I32,
+                                                C.POINTER(_I32), _VP, _VP, _VP]),
     ("icem_tile_growth", C.c_double, [_H]),
     ("icem_nonfinite_costs", C.c_int, [_H, C.POINTER(C.c_int64), _VP]),
     ("icem_set_option", C.c_int, [C.c_char_p, C.c_double]),

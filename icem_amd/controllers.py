@@ -332,6 +332,18 @@ class MpcController(ModelBasedController, StatefulController, ABC):
                 and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
                 and m.params.device == self.planner.device)
 
+    def _model_is_the_library_ensemble(self) -> bool:
+        """The sibling of :meth:`_model_is_the_library_rssm` for ``icem_plan_step_learned_models``: the model is a
+        ``DeviceRSSMEnsemble`` whose ``rollout_cost`` / ``rollout_cost_batch`` are the class's own, on the type and on the
+        instance -- an ensemble that was instrumented (a method replaced to time, count or record the rollouts) is called
+        stage by stage, as it asks to be."""
+        from .models import DeviceRSSMEnsemble
+        m = self.forward_model
+        return (isinstance(m, DeviceRSSMEnsemble) and type(m).rollout_cost is DeviceRSSMEnsemble.rollout_cost
+                and type(m).rollout_cost_batch is DeviceRSSMEnsemble.rollout_cost_batch
+                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
+                and m.params.device == self.planner.device)
+
     def _costs_of(self, obs, actions: torch.Tensor) -> torch.Tensor:
         """Per-trajectory costs (device tensor) of a batch of device action sequences, through whichever
         model this controller was given."""
@@ -582,6 +594,8 @@ class MpcICemHip(MpcController):
             executed_action, self.last_min_cost = host[:-1], float(host[-1])
         elif self._learned_step_ok(noise):
             executed_action = self._get_action_learned(obs)   # the whole step one library call (icem_plan_step_learned)
+        elif self._learned_models_ok(noise, 1):
+            executed_action = self._get_action_learned_models(obs)   # ... through an ensemble (icem_plan_step_learned_models)
         else:
             executed_action = self._get_action_stagewise(obs, noise)
         return self._finish_action(obs, executed_action)
@@ -617,7 +631,11 @@ class MpcICemHip(MpcController):
         their populations and sampling and the distribution update stay one launch per controller; a ``DeviceRSSMEnsemble``
         they all share is stepped the same way); or, with ``own_models=True``, learned-dynamics controllers of one
         configuration with a plain ``DeviceRSSMModel`` EACH (one action width, one device): that stage-wise step, its one
-        scoring launch per iteration reading every problem's own parameters (``rssm_rollout_cost_models``).  Without the
+        scoring launch per iteration reading every problem's own parameters (``rssm_rollout_cost_models``).  Both of these --
+        controllers on one ``DeviceRSSMEnsemble``, controllers with a plain model each -- take ``icem_plan_step_learned_models``
+        where it serves them (``IcemPlanner.learned_models_step_ok``): the whole step in the library, 3 launches per iteration
+        for all controllers and members, the same bits; an ensemble whose rollout was instrumented is still called stage by
+        stage, and controllers that each own an ENSEMBLE are not offered here (the C entry serves them).  Without the
         keyword, controllers whose parameter buffers differ are refused as they always were: two copies of one model are
         more often a mistake than a wish.  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)
@@ -639,6 +657,12 @@ class MpcICemHip(MpcController):
         shared = rssm and all(MpcICemHip._share_params(c.forward_model, ctrls[0].forward_model) for c in ctrls)
         if shared and all(c._learned_step_ok(None) for c in ctrls):   # (the fused step knows ONE parameter buffer)
             host = MpcICemHip._get_action_batch_learned(ctrls, observations)
+        elif shared and all(c.forward_model is ctrls[0].forward_model and c._learned_models_ok(None, n) for c in ctrls):
+            # one ensemble for all of them: icem_plan_step_learned_models, the members' pointers repeated per problem
+            host = MpcICemHip._get_action_batch_learned_models(ctrls, observations, ctrls[0].forward_model)
+        elif rssm and not shared and all(c._learned_models_ok(None, n) for c in ctrls):
+            # a plain model each (own_models=True, or the batch was refused above): the same entry with one member per problem
+            host = MpcICemHip._get_action_batch_learned_models(ctrls, observations, [c.forward_model for c in ctrls])
         elif rssm:
             host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
         else:
@@ -809,6 +833,51 @@ class MpcICemHip(MpcController):
             c._elites_into_planner()
         try:
             results = IcemPlanner.plan_step_learned_batch([c.planner for c in ctrls], ctrls[0].forward_model, observations)
+        except IcemError as e:
+            if e.code != ICEM_E_UNSUPPORTED:
+                raise
+            return MpcICemHip._get_action_batch_rssm(ctrls, observations)   # (refused before anything ran)
+        for c in ctrls:
+            c._elites_from_planner()
+        return results.cpu().numpy().astype(np.float64)
+
+    # -- ... through an ensemble, or through a model per controller (icem_plan_step_learned_models): the same bits again
+    def _learned_models_ok(self, noise, n) -> bool:
+        """Does ``icem_plan_step_learned_models`` serve ``n`` controllers like this one -- through the library's own ensemble
+        they plan with, or, with a plain ``DeviceRSSMModel``, through a model each?"""
+        if not (self.rssm_path and not self.device_path and noise is None and self.planner.cfg.world == 1 and not self.verbose):
+            return False
+        if self._model_is_the_library_ensemble():
+            members = self.forward_model.members
+        elif self._model_is_the_library_rssm():
+            members = 1
+        else:
+            return False
+        return bool(self.planner._bind_rssm(self.forward_model) and self.planner.learned_models_step_ok(n, members))
+
+    def _get_action_learned_models(self, obs):
+        from ._lib import IcemError, ICEM_E_UNSUPPORTED
+        self._elites_into_planner()
+        try:
+            results = IcemPlanner.plan_step_learned_models([self.planner], self.forward_model, [obs])
+        except IcemError as e:
+            if e.code != ICEM_E_UNSUPPORTED:
+                raise
+            return self._get_action_stagewise(obs, None)   # (refused before anything ran)
+        self._elites_from_planner()
+        host = results[0].cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+        self.last_min_cost = float(host[-1])
+        return host[:-1]
+
+    @staticmethod
+    def _get_action_batch_learned_models(ctrls, observations, models):
+        """-> [B, d + 1] host array of executed actions and best costs (one device-to-host copy, one synchronisation); a
+        batch the entry does not serve as a whole steps stage-wise, as :meth:`_get_action_batch_learned`'s does."""
+        from ._lib import IcemError, ICEM_E_UNSUPPORTED
+        for c in ctrls:
+            c._elites_into_planner()
+        try:
+            results = IcemPlanner.plan_step_learned_models([c.planner for c in ctrls], models, observations)
         except IcemError as e:
             if e.code != ICEM_E_UNSUPPORTED:
                 raise

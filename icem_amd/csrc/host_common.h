@@ -82,9 +82,25 @@ struct LearnedCtx {
     float* pool_actions() const { return pool; }
     float* pool_costs(int hd) const { return pool ? pool + pool_rows * (size_t)hd : nullptr; }
     float* pool_obs(int hd) const { return pool ? pool + pool_rows * (size_t)(hd + 1) : nullptr; }
+    // icem_plan_step_learned_models whose caller brought no member_costs: [members, rows] of one iteration; grows like the pool
+    float* member_costs = nullptr;
+    size_t member_cap = 0;
+    hipError_t reserve_members(size_t floats, hipStream_t st) {
+        if (member_cap >= floats) return hipSuccess;
+        if (member_costs) {
+            if (hipError_t e = hipStreamSynchronize(st)) return e;
+            (void)hipFree(member_costs);
+            member_costs = nullptr;
+            member_cap = 0;
+        }
+        if (hipError_t e = hipMalloc((void**)&member_costs, floats * sizeof(float))) return e;
+        member_cap = floats;
+        return hipSuccess;
+    }
     ~LearnedCtx() {
         if (pool) (void)hipFree(pool);
         if (idx) (void)hipFree(idx);
+        if (member_costs) (void)hipFree(member_costs);
     }
 };
 

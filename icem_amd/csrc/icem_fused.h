@@ -258,6 +258,20 @@ struct UpdateFinishArgs {
     float* result;
 };
 void launch_update_small_batch(const UpdateFinishArgs* args_dev, int n, bool finish, hipStream_t st);
+// ... whose pool costs are not in memory yet: the update reduces them itself from the members' (icem_plan_step_learned_models).
+// Candidate i of the problem costs reduce_e member_costs[e * stride + row0 + i], e = 0 .. members - 1, in the arithmetic of
+// rssm_ensemble_reduce_kernel operation for operation (mean: ((c_0 + c_1) + ..) * inv with inv = (float)(1.0 / members) from the
+// host; max: (c > acc || c != c) ? c : acc; a NaN member makes the row NaN); the reduced cost is also written to costs[i], where
+// the single-model step leaves it.  Everything behind the keys is launch_update_small_batch's.  members in [1, 32].
+struct UpdateMembersArgs {
+    UpdateFinishArgs f;          // (f.u.costs: unused -- the costs come from member_costs)
+    const float* member_costs;   // [members, stride]
+    float* costs;                // [f.u.n] out: the reduced costs
+    int members, reduce;         // reduce: ICEM_RSSM_REDUCE_MEAN / _MAX
+    int stride, row0;            // the member stride (all problems' rows of this iteration) and this problem's first row
+    float inv;                   // (float)(1.0 / members)
+};
+void launch_update_small_members_batch(const UpdateMembersArgs* args_dev, int n, bool finish, hipStream_t st);
 // sorted top-K of a small f32 cost array in one launch (icem_topk_sorted's fast path)
 bool topk_small_ok(int n, int K);
 void launch_topk_small(const float* costs, int n, int K, float* out_c, int* out_i, hipStream_t st);

@@ -289,6 +289,14 @@ __global__ __launch_bounds__(1024) void update_small_batch_kernel(const UpdateFi
     update_small_body<FINISH>(g.u, &g);
 }
 
+// ... with the pool's costs still in the members' rows (icem_plan_step_learned_models): the same body, its keys out of the
+// members' reduction (MemberCosts, update_small_body.h) -- the launch that reduced them first is gone
+template <bool FINISH>
+__global__ __launch_bounds__(1024) void update_small_members_batch_kernel(const UpdateMembersArgs* __restrict__ args) {
+    const UpdateMembersArgs g = args[blockIdx.x];
+    update_small_body<FINISH>(g.f.u, &g.f, MemberCosts{g.member_costs + g.row0, g.costs, (unsigned)g.stride, g.members, g.reduce, g.inv});
+}
+
 }  // namespace
 
 void launch_update_small(const UpdateSmallArgs& a, hipStream_t st) {
@@ -298,6 +306,11 @@ void launch_update_small(const UpdateSmallArgs& a, hipStream_t st) {
 void launch_update_small_batch(const UpdateFinishArgs* args_dev, int n, bool finish, hipStream_t st) {
     if (finish) hipLaunchKernelGGL(update_small_batch_kernel<true>, dim3(n), dim3(1024), 0, st, args_dev);
     else hipLaunchKernelGGL(update_small_batch_kernel<false>, dim3(n), dim3(1024), 0, st, args_dev);
+}
+
+void launch_update_small_members_batch(const UpdateMembersArgs* args_dev, int n, bool finish, hipStream_t st) {
+    if (finish) hipLaunchKernelGGL(update_small_members_batch_kernel<true>, dim3(n), dim3(1024), 0, st, args_dev);
+    else hipLaunchKernelGGL(update_small_members_batch_kernel<false>, dim3(n), dim3(1024), 0, st, args_dev);
 }
 
 bool topk_small_ok(int n, int K) { return n >= 1 && n <= 16384 && K >= 1 && K <= 32; }

@@ -17,6 +17,11 @@
 // are host_common.h's call_base, shift_rows and elite_parity, so a controller may alternate between the two steps.  A batch's
 // rows sit back to back in a pool of the first handle's (LearnedCtx: the batched rollout wants them contiguous); one problem
 // alone uses its own actions / costs buffers.
+//
+// icem_plan_step_learned_models is the same step for problems that roll out through models of their own (an ensemble's members,
+// a trained model per episode): the rollout is launch_rssm_split_models over n * members problems in member-major order, and
+// the update is update_small_members_batch_kernel, which reduces the members' costs while it builds its keys -- still 3
+// launches per iteration, and the same code below (StepModels).
 #include "block_layout.h"
 #include "host_common.h"
 #include "icem_rssm.h"
@@ -51,8 +56,27 @@ const char* learned_unserved(const icem_handle* h) {
     return nullptr;
 }
 
+// icem_plan_step_learned_models: every problem rolls out through `members` models of its own instead of the one shared buffer
+struct StepModels {
+    int members, reduce;
+    const void* const* params;   // [n * members], problem-major
+    float* member_costs;         // the caller's [members * n * max_rows], or nullptr: the context's scratch
+};
+
+// the rollout of such a step's iteration: n * members problems in member-major order -- problem e * n + p reads problem p's
+// action rows and observation row p, so that the costs land as [members, the iteration's rows of all problems]
+void models_problems(const StepModels& mo, int n, const int* rows, rssm::Problem* out) {
+    for (int e = 0; e < mo.members; ++e) {
+        long long row0 = 0;
+        for (int p = 0; p < n; ++p) {
+            out[e * n + p] = {(const unsigned short*)mo.params[(size_t)p * mo.members + e], row0, rows[p], p};
+            row0 += rows[p];
+        }
+    }
+}
+
 int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
-                 void* results, hipStream_t st) {
+                 void* results, hipStream_t st, const StepModels* mo = nullptr) {
     icem_handle* h0 = handles[0];
     const icem_config& c = h0->cfg;
     const int H = c.horizon, d = c.act_dim, hd = h0->hd, K = c.num_elites, iters = c.opt_iters, n_reuse = std::max(0, h0->n_reuse);
@@ -69,7 +93,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         if (b.z_r || b.z_i || b.z_r_shift || b.z_i_shift) return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned: external noise (z_*) is not served");
     }
     // rows of every problem and iteration; the largest launch's tiles
-    std::vector<int> rows((size_t)iters * n);
+    std::vector<int> rows((size_t)iters * n), all_rows((size_t)iters);
     int tiles_max = 0, shift_max = 0;
     size_t rows_max = 0;
     for (int it = 0; it < iters; ++it) {
@@ -79,12 +103,23 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             all += rows[(size_t)it * n + p];
             shift_max = std::max(shift_max, shift_rows(handles[p], steps[p], it));
         }
-        const int tiles = rssm_batch_tiles(n, &rows[(size_t)it * n]);
-        if (tiles < 0 || !rssm_split_batch_ok(tiles, H))
-            return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_batch: the batch's tiles (the sum over the problems of ceil(rows / 16)) exceed "
-                                            "the split launch's limit; nothing was launched");
+        int tiles;
+        if (mo) {
+            rssm::Problem pr[rssm::BATCH_MAX];
+            models_problems(*mo, n, &rows[(size_t)it * n], pr);
+            tiles = rssm_models_tiles(n * mo->members, pr);
+            if (tiles < 0 || !rssm_split_batch_ok(tiles, H))
+                return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_models: the tiles of an iteration (members x the sum over the problems of "
+                                                "ceil(rows / 16)) exceed the split launch's limit; nothing was launched");
+        } else {
+            tiles = rssm_batch_tiles(n, &rows[(size_t)it * n]);
+            if (tiles < 0 || !rssm_split_batch_ok(tiles, H))
+                return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_batch: the batch's tiles (the sum over the problems of ceil(rows / 16)) exceed "
+                                                "the split launch's limit; nothing was launched");
+        }
         tiles_max = std::max(tiles_max, tiles);
         rows_max = std::max(rows_max, all);
+        all_rows[it] = (int)all;
     }
     // the rollout's staging area and its host-visible status word, BEFORE the first launch: a refused step leaves everything as it was
     if (int rc = rssm_launch_result(rssm_split_prepare(tiles_max, H, st))) return rc;
@@ -96,8 +131,14 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     float* pool_a = ctx->pool_actions();
     float* pool_c = ctx->pool_costs(hd);
     float* pool_o = ctx->pool_obs(hd);
+    // (a models step: the members' costs of one iteration, [members, its rows] -- the caller's buffer, or scratch that only grows)
+    float* member_costs = mo ? mo->member_costs : nullptr;
+    if (mo && !member_costs) {
+        ICEM_HIP_TRY(ctx->reserve_members((size_t)mo->members * cap_rows, st));
+        member_costs = ctx->member_costs;
+    }
     // ---- argument blocks (block_layout.h): per iteration [sample x n | update x n], then [shift x n] ----
-    const size_t sb = sizeof(FastSampleArgs), ub = sizeof(UpdateFinishArgs), hb = gk_shift_sample_block_bytes();
+    const size_t sb = sizeof(FastSampleArgs), ub = mo ? sizeof(UpdateMembersArgs) : sizeof(UpdateFinishArgs), hb = gk_shift_sample_block_bytes();
     BlockLayout part(n, ICEM_MAX_BATCH), tail(n, ICEM_MAX_BATCH);
     part.add(sb);   // (at 0)
     const size_t at_update = part.add(ub), per_it = part.bytes(), at_shift = per_it * iters;
@@ -113,6 +154,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             const int n_it = h0->pop[it], n_shift = shift_rows(h, steps[p], it), n_rows = n_it + n_shift;
             float* acts = n == 1 ? (float*)b.actions : pool_a + row0 * hd;
             float* csts = n == 1 ? (float*)b.costs : pool_c + row0;
+            const size_t first_row = row0;
             row0 += n_rows;
             const int r = elite_parity(h, steps[p], it), w = r ^ 1;
             float* el = (float*)b.elites;
@@ -132,7 +174,14 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             if (it == 0)
                 gk_shift_sample_block(h, n_shift, b.mean, b.std, b.low, b.high, (uint64_t)iters, el_r, acts + (size_t)n_it * hd,
                                       blob.data() + at_shift + hb * p);
-            UpdateFinishArgs& u = *(UpdateFinishArgs*)(blob.data() + per_it * it + at_update + ub * p);
+            UpdateFinishArgs& u = *(UpdateFinishArgs*)(blob.data() + per_it * it + at_update + ub * p);   // (UpdateMembersArgs begins with one)
+            if (mo) {
+                UpdateMembersArgs& m = *(UpdateMembersArgs*)(blob.data() + per_it * it + at_update + ub * p);
+                m.member_costs = member_costs, m.costs = csts;
+                m.members = mo->members, m.reduce = mo->reduce;
+                m.stride = all_rows[it], m.row0 = (int)first_row;
+                m.inv = (float)(1.0 / mo->members);
+            }
             const bool keep = it > 0 && c.keep_previous_elites && n_reuse > 0;
             u.u.costs = csts, u.u.pool = acts;
             u.u.keep_costs = keep ? ec_r : nullptr, u.u.keep_actions = keep ? el_r : nullptr;
@@ -174,14 +223,20 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             ++launches;
         }
         hipError_t e;
-        if (n == 1)
+        if (mo) {
+            rssm::Problem pr[rssm::BATCH_MAX];
+            models_problems(*mo, n, &rows[(size_t)it * n], pr);
+            e = launch_rssm_split_models(n * mo->members, pr, H, d, c.cost_mode, n == 1 ? (const float*)buffers[0].obs0 : pool_o,
+                                         n == 1 ? (const float*)buffers[0].actions : pool_a, member_costs, st);
+        } else if (n == 1)
             e = launch_rssm_rollout(rows[it], H, d, c.cost_mode, (const unsigned short*)params, (const float*)buffers[0].obs0,
                                     (const float*)buffers[0].actions, (float*)buffers[0].costs, st);
         else
             e = launch_rssm_split_batch(n, &rows[(size_t)it * n], H, d, c.cost_mode, (const unsigned short*)params, pool_o, pool_a, pool_c, st);
         if (int rc = rssm_launch_result(e)) return rc;
         ++launches;
-        launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + at_update), n, it == iters - 1, st);
+        if (mo) launch_update_small_members_batch((const UpdateMembersArgs*)(dev + per_it * it + at_update), n, it == iters - 1, st);
+        else launch_update_small_batch((const UpdateFinishArgs*)(dev + per_it * it + at_update), n, it == iters - 1, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
     }
@@ -211,5 +266,34 @@ int icem_plan_step_learned(icem_handle* h, const icem_plan_buffers* b, const voi
 }
 
 int64_t icem_learned_step_launches(const icem_handle* h) { return h ? (int64_t)h->learned.launches : 0; }
+
+// would a batch of n handles like `h` with `members` models per problem be served?  (the tiles: every problem with its shifted elites)
+int icem_plan_step_learned_models_ok(const icem_handle* h, int32_t n, int32_t members) {
+    if (!h || learned_unserved(h) || n < 1 || n > ICEM_MAX_BATCH || members < 1 || members > rssm::BATCH_MAX || n * members > rssm::BATCH_MAX)
+        return 0;
+    const long long tiles = (long long)n * members * ((max_rows(h) + 15) / 16);
+    return tiles <= rssm::SPLIT_TILE_LIMIT && rssm_split_batch_ok((int)tiles, h->cfg.horizon) ? 1 : 0;
+}
+
+int icem_plan_step_learned_models(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t members,
+                                  const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host, void* member_costs,
+                                  void* results, void* stream) {
+    const char* config_msg = "icem_plan_step_learned_models: the handles must share one configuration (everything but the seed)";
+    // (what the counts and the table alone decide comes first: no handle has been looked at when n x members is refused)
+    if (!handles || !buffers || !params_host || !mpc_steps_host || n < 1 || n > ICEM_MAX_BATCH)
+        return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: null argument / n outside [1, 32]");
+    if (members < 1 || members > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: members must be in [1, 32]");
+    if (reduce != ICEM_RSSM_REDUCE_MEAN && reduce != ICEM_RSSM_REDUCE_MAX)
+        return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: reduce must be ICEM_RSSM_REDUCE_MEAN or ICEM_RSSM_REDUCE_MAX");
+    for (int i = 0; i < n * members; ++i)
+        if (!params_host[i]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: null params entry");
+    if (n * members > rssm::BATCH_MAX)
+        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_models: n x members problems, but one learned-dynamics launch holds 32 "
+                                        "(its table travels in the kernel arguments); nothing was launched");
+    if (int rc = admit_batch(handles, n, true, true, "icem_plan_step_learned_models: ", config_msg)) return rc;
+    if (int rc = admit_rssm_binding(handles, n, config_msg)) return rc;
+    const StepModels mo{members, reduce, params_host, (float*)member_costs};
+    return learned_step(handles, n, buffers, nullptr, mpc_steps_host, results, (hipStream_t)stream, &mo);
+}
 
 }  // extern "C"

@@ -12,9 +12,54 @@ namespace icem {
 // topk_small_kernel's; the selection lands in LDS (wg_merge_emit's list 0 of 1, through a generic pointer).
 // (the body of update_small_kernel and of update_small_batch_kernel: one device function.  FINISH: the step's epilogue behind
 //  the refit -- the new mean goes through LDS and leaves shifted, std is reset (shift_kernel's arithmetic, icem.py:167-175),
-//  executed = elites[0, 0, :], best_cost = elite_costs[0], and both once more as the problem's row of `results`.)
-template <bool FINISH>
-__device__ __forceinline__ void update_small_body(const UpdateSmallArgs& a, const UpdateFinishArgs* f) {
+//  executed = elites[0, 0, :], best_cost = elite_costs[0], and both once more as the problem's row of `results`.
+//  Src: where candidate i < a.n gets its cost from -- PoolCosts, the plain load of a.costs[i], unless the caller says otherwise.)
+struct PoolCosts {
+    __device__ __forceinline__ float operator()(const UpdateSmallArgs& a, int i) const { return a.costs[i]; }
+};
+
+// ... or from the costs of an ensemble's members (update_small_members_batch_kernel; UpdateMembersArgs, icem_fused.h), reduced here
+// as rssm_ensemble_reduce_kernel reduces them -- the same float32 operations in the same order, no atomics, no division, the
+// mean's one multiply a rounding of its own -- and written to costs[i] as well.  `members` is uniform across the workgroup: a
+// row's loads are all requested before the first is consumed (one round trip to memory, not one per member), in a group of
+// up to 8 members or of up to 32.
+struct MemberCosts {
+    const float* mc;   // member 0's cost of this problem's row 0
+    float* out;
+    unsigned stride;   // (members * stride <= 32 * 16 384 floats: 32-bit offsets from the one base)
+    int members, reduce;
+    float inv;
+    template <int T>
+    __device__ __forceinline__ float reduced(unsigned i) const {
+        // (straight-line: a slot behind the last member loads the last member's cost again and is not consumed)
+        // (typed as global memory: a pointer read from the argument block is generic, and its loads were flat_load)
+        typedef const float __attribute__((address_space(1))) * GlobalF;
+        const GlobalF g = (GlobalF)mc;
+        float c[T];
+#pragma unroll
+        for (int e = 0; e < T; ++e) c[e] = g[(unsigned)(e < members ? e : members - 1) * stride + i];
+        float acc = c[0];
+        if (reduce == 0) {
+#pragma unroll
+            for (int e = 1; e < T; ++e) acc = e < members ? acc + c[e] : acc;
+            return __fmul_rn(acc, inv);   // (__fmul_rn: never contracted into the key's `+ 0.0f`)
+        }
+#pragma unroll
+        for (int e = 1; e < T; ++e) {
+            const bool worse = (c[e] > acc) | (c[e] != c[e]);
+            acc = ((e < members) & worse) ? c[e] : acc;
+        }
+        return acc;
+    }
+    __device__ __forceinline__ float operator()(const UpdateSmallArgs&, int i) const {
+        const float r = members <= 8 ? reduced<8>((unsigned)i) : reduced<32>((unsigned)i);
+        out[i] = r;
+        return r;
+    }
+};
+
+template <bool FINISH, class Src = PoolCosts>
+__device__ __forceinline__ void update_small_body(const UpdateSmallArgs& a, const UpdateFinishArgs* f, const Src src = Src()) {
     __shared__ unsigned long long wg_keys[2][16][32];
     __shared__ unsigned long long sel[32];
     __shared__ float shifted[FINISH ? UPDATE_FINISH_MAX_HD : 1];
@@ -25,7 +70,7 @@ __device__ __forceinline__ void update_small_body(const UpdateSmallArgs& a, cons
     for (int base = wave * 64; base < n_all; base += 1024) {
         const int i = base + lane;
         unsigned long long key = KEY_SENTINEL;
-        if (i < n_all) key = make_key(i < a.n ? a.costs[i] : a.keep_costs[i - a.n], i);
+        if (i < n_all) key = make_key(i < a.n ? src(a, i) : a.keep_costs[i - a.n], i);
         key = wave_sort64(key, lane);
         if (!first) {
             const unsigned long long prev = __shfl(run, lane - 32, 64);

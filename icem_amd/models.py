@@ -474,9 +474,12 @@ class DeviceRSSMEnsemble(ForwardModel):
     (``icem_rssm_rollout_cost_ensemble``) + the reduction; ``member_costs`` holds the last ``[E, n]`` (row e: member e alone,
     bit for bit).  ``params`` are the members' packed buffers stacked ``[E, elems]`` on one device -- the launch reads these.
 
-    Every controller plans through it with its stage-wise loop: it is deliberately NOT a ``DeviceRSSMModel`` (the library's
-    fused ``*_learned`` steps know one parameter buffer).  ``predict`` -- the reference-style interface needs ONE successor
-    state -- delegates to member 0."""
+    It is deliberately NOT a ``DeviceRSSMModel``: the library's fused ``*_learned`` steps know one parameter buffer, and the
+    CEM and random-shooting baselines plan through an ensemble with their stage-wise loops.  ``MpcICemHip`` takes the whole
+    MPC step through it as one library call (``icem_plan_step_learned_models``: the members' reduction inside the update
+    launch) where that entry serves the planner, and leaves ``member_costs`` as the stage-wise loop does: the last
+    iteration's ``[E, rows]``.  ``predict`` -- the reference-style interface needs ONE successor state -- delegates to
+    member 0."""
 
     obs_dim = 230
 

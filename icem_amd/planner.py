@@ -602,6 +602,94 @@ class IcemPlanner:
             pl.mpc_step += 1
         return results
 
+    # ------------------------------------------------------------------ ... through ensembles and a model per planner
+    def learned_models_step_ok(self, n: int = 1, members: int = 1) -> bool:
+        """Does ``icem_plan_step_learned_models`` serve a batch of ``n`` handles like THIS one through ``members`` models per
+        problem?  (:meth:`learned_step_ok`'s conditions of the handle as it is bound, ``n * members <= 32``, and the tiles of
+        every iteration of such a batch within the rollout's limit.)"""
+        return bool(self.lib.icem_plan_step_learned_models_ok(self._h, int(n), int(members)))
+
+    def _step_rows(self, it: int) -> int:
+        """Rows iteration ``it`` of this planner's NEXT step scores (the shifted elites behind iteration 0's population)."""
+        shift = it == 0 and self.cfg.shift_elites and self.mpc_step > 0 and self.n_reuse > 0
+        return self.population_sizes[it] + (self.n_reuse if shift else 0)
+
+    @staticmethod
+    def plan_step_learned_models(planners: Sequence["IcemPlanner"], models, observations, reduce=None, member_costs=None) -> torch.Tensor:
+        """One MPC step of every planner of ``planners`` (one configuration; seeds, episodes, step counts and observations of
+        their own) as ``icem_plan_step_learned_models``: :meth:`plan_step_learned_batch` with the rollout of every problem
+        through models of its own.  ``models``: a ``DeviceRSSMEnsemble`` every planner plans through; a list of
+        ``DeviceRSSMModel`` (one per planner); or a list of lists (every planner its own ensemble, all of one size).  A plan's
+        cost is the mean or the worst of its problem's members: ``reduce`` ``"mean"`` / ``"max"`` (None: the ensemble's own,
+        else ``"mean"``).  Every stage is one launch for all problems and members, 3 per CEM iteration (+ 1 in a step that
+        shifts elites).  Each planner's buffers afterwards are bit for bit those of its own step with its members.  Returns
+        the results ``[B, d + 1]`` (executed action | best cost per planner; device tensor, no host sync; kept with the first
+        planner -- its next call of this batch size overwrites it).  The members' costs
+        of the LAST iteration, ``[members, its rows of all planners]``, are left in ``member_costs`` (an f32 device tensor of
+        at least ``members * B * max rows`` elements) when one is given, and with a ``DeviceRSSMEnsemble`` in its
+        ``member_costs`` as its ``rollout_cost_batch`` leaves them.  Raises ``IcemError`` before anything runs -- and before
+        any planner has advanced -- where the batch is not served."""
+        from .models import DeviceRSSMEnsemble, DeviceRSSMModel
+        pls = list(planners)
+        n = len(pls)
+        ens = models if isinstance(models, DeviceRSSMEnsemble) else None
+        if ens is not None:
+            table = [ens._param_ptrs()] * n
+            width_of = ens
+            reduce = ens.reduce if reduce is None else reduce
+        else:
+            per = [[m] if isinstance(m, DeviceRSSMModel) else list(m) for m in models]
+            if len(per) != n:
+                raise ValueError(f"{n} planners but models for {len(per)}")
+            if n and (len(per[0]) < 1 or any(len(ms) != len(per[0]) for ms in per)):
+                raise ValueError(f"every planner needs the same number (>= 1) of models, got {[len(ms) for ms in per]}")
+            flat = [m for ms in per for m in ms]
+            if not all(isinstance(m, DeviceRSSMModel) for m in flat):
+                raise ValueError("the models of plan_step_learned_models are DeviceRSSMModels (or one DeviceRSSMEnsemble)")
+            if len({m.act_dim for m in flat}) > 1 or len({m.params.device for m in flat}) > 1:
+                raise ValueError("learned-dynamics models of one step need one action width on one device")
+            table = [[m.params.data_ptr() for m in ms] for ms in per]
+            width_of = flat[0] if flat else None
+            reduce = "mean" if reduce is None else reduce
+        if reduce not in L.RSSM_REDUCE:
+            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_learned_models(None, 0, None, 1, None, 0, None, None, None, None))
+        members = len(table[0])
+        p0 = pls[0]
+        obs = np.ascontiguousarray(np.asarray(observations, dtype=np.float32).reshape(n, -1))
+        if obs.shape[1] != L.RSSM_OBS_DIM:
+            raise ValueError(f"expected observations of shape ({n}, {L.RSSM_OBS_DIM})")
+        need = members * n * max(p0.population_sizes[it] + (p0.n_reuse if it == 0 else 0) for it in range(len(p0.population_sizes)))
+        if ens is not None and member_costs is None:   # (kept with the ensemble: its address sits in the step's argument blocks)
+            member_costs = getattr(ens, "_step_member_costs", None)
+            if member_costs is None or member_costs.numel() < need or member_costs.device != p0.device:
+                member_costs = ens._step_member_costs = torch.empty((need,), dtype=torch.float32, device=p0.device)
+        if member_costs is not None and (member_costs.dtype != torch.float32 or not member_costs.is_contiguous()
+                                         or member_costs.numel() < need or member_costs.device != p0.device):
+            raise ValueError(f"member_costs must be a contiguous float32 tensor of at least {need} elements on the planners' device")
+        # (the observations and the results of a batch size live with the first planner: the results' address sits in the argument blocks)
+        kept = p0.__dict__.setdefault("_models_step_io", {})
+        if n not in kept:
+            kept[n] = (torch.empty((n, L.RSSM_OBS_DIM), dtype=torch.float32, device=p0.device),
+                       torch.empty((n, p0.d + 1), dtype=torch.float32, device=p0.device))
+        obs_dev, results = kept[n]
+        obs_dev.copy_(torch.as_tensor(obs), non_blocking=False)   # one host-to-device copy for the whole batch
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemPlanBuffersC * n)(*[pl._learned_buffers(obs_dev[i].data_ptr()) for i, pl in enumerate(pls)])
+        steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
+        ptrs = (C.c_void_p * (n * members))(*[p for row in table for p in row])
+        last_rows = sum(pl._step_rows(len(pl.population_sizes) - 1) for pl in pls)
+        for pl in pls:
+            pl._bind_rssm(width_of)
+        L.check(p0.lib.icem_plan_step_learned_models(hs, n, bs, members, ptrs, L.RSSM_REDUCE[reduce], steps,
+                                                     None if member_costs is None else _ptr(member_costs), _ptr(results), p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        if ens is not None:
+            ens.member_costs = member_costs[:members * last_rows].view(members, last_rows)
+        return results
+
     # ------------------------------------------------------------------ the CEM baseline's step (MpcCemStd)
     def cem_step_ok(self) -> bool:
         """Does ``icem_plan_step_cem`` serve THIS handle?  (One GPU, profiling off, ``factor_decrease == 1``, no kept or

@@ -677,6 +677,38 @@ int icem_plan_step_learned(icem_handle* h, const icem_plan_buffers* b, const voi
 int icem_plan_step_learned_batch(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const void* params,
                                  const int32_t* mpc_steps_host, void* results, void* stream);
 int64_t icem_learned_step_launches(const icem_handle* h); /* kernel launches of the last learned step this handle led (handles[0]); measurement */
+/* icem_plan_step_learned_batch for problems that roll out through MODELS OF THEIR OWN: an ensemble whose members score every
+ * plan together (the model loop of icem/models/abstract_models.py:17-53), parallel episodes that each own a trained model
+ * (icem/misc/rollout_utils.py:46-58, 129-152), or both.  params_host [n * members] (host array of device pointers, problem-major,
+ * read before the call returns): problem p's members are params_host[p * members .. (p + 1) * members), each a packed buffer
+ * as icem_rssm_rollout_cost_models takes it.  A shared ensemble repeats the same `members` pointers for every problem; a model
+ * each is members == 1 with n pointers; an ensemble each names n * members buffers.  A plan's cost is the members'
+ * icem_rssm_ensemble_reduce (`reduce`: ICEM_RSSM_REDUCE_MEAN or _MAX; a NaN member makes the row NaN).
+ *   Semantics: icem_plan_step_learned_batch's -- noise offsets, elite halves, the shifted rows of a problem reset later than
+ * its peers, the epilogue, `results`, the buffers (n == 1 works in the problem's own actions / costs, a batch in a pool of
+ * handles[0]'s), option learned_step -- with two differences.  The rollout of an iteration is ONE launch of n * members problems
+ * in member-major order (problem e * n + p reads problem p's action rows and observation), so the members' costs land as
+ * [members, the iteration's rows of all problems]: the layout icem_rssm_rollout_cost_models gives such a launch.  And the
+ * update reduces them itself: problem p's candidate i costs the reduction over e of member_costs[e * stride + row0 + i]
+ * (stride: the iteration's rows of all problems, row0: p's first), in icem_rssm_ensemble_reduce's arithmetic operation for
+ * operation, and the reduced cost is written where the single-model step leaves its costs.  So still 3 launches per
+ * iteration, + 1 in a step that shifts elites, whatever n and members.  Every buffer of every problem is bit for bit what the
+ * stage-wise operators (sample, icem_rssm_rollout_cost_ensemble / _models, update, shift) give; members == 1 with equal pointers
+ * gives icem_plan_step_learned_batch's bits, with n == 1 icem_plan_step_learned's.
+ *   member_costs (device f32, may be NULL): at least members * n * (the largest iteration's rows of one problem) floats; after the
+ * call it holds the LAST iteration's [members, rows of all problems].  NULL: scratch of handles[0] (no allocation after the
+ * first call of a size).  Its address sits in the step's argument blocks: keep one buffer and the steady state uploads nothing.
+ *   ICEM_E_INVALID: a NULL argument or a NULL entry of params_host, n or members outside [1, 32], a bad reduce, the same handle
+ * twice, unequal configurations or RSSM widths.  ICEM_E_UNSUPPORTED: n * members > 32 (the launch's table travels in the
+ * kernel arguments); the tiles of an iteration (members x the sum over the problems of ceil(rows / 16)) beyond the split
+ * launch's limit; whatever icem_plan_step_learned_batch does not serve; a non-NULL z_*.  All of it before anything is launched
+ * or any handle touched; the learned-dynamics rollout's status word is looked at before the first launch (ICEM_E_STATE: nothing
+ * was launched).  icem_plan_step_learned_models_ok: would n handles like this one be served with `members` models each (every
+ * problem counted with its shifted elites)?  icem_learned_step_launches counts this entry's launches too. */
+int icem_plan_step_learned_models_ok(const icem_handle* h, int32_t n, int32_t members);
+int icem_plan_step_learned_models(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, int32_t members,
+                                  const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host, void* member_costs,
+                                  void* results, void* stream);
 
 /* Wide observations (32 < obs_dim <= 384; HumanoidStandup's o = 378, environments/mujoco.py:241-277): which matrix-pipe
  * arithmetic the rollout's model step (the GEMM of abstract_models.py:31-53's predict at this width) runs in.  The modes
