@@ -201,6 +201,12 @@ SYMBOLS = [
     ("icem_plan_step_learned_models_ok", C.c_int, [_H, _I32, _I32]),
     ("icem_plan_step_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(_VP), _I32,
                                                 C.POINTER(_I32), _VP, _VP, _VP]),
+    ("icem_plan_step_cem_learned_models_ok", C.c_int, [_H, _I32, _I32]),
+    ("icem_plan_step_cem_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _I32,
+                                                    C.POINTER(_VP), _I32, C.POINTER(_I32), _VP, _VP, _VP]),
+    ("icem_plan_step_random_learned_models_ok", C.c_int, [_H, _I32, _I32]),
+    ("icem_plan_step_random_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemRandomBuffersC), _I32, C.POINTER(_VP), _I32,
+                                                       _I32, C.POINTER(_I64), _VP, _VP, _VP]),
     ("icem_tile_growth", C.c_double, [_H]),
     ("icem_nonfinite_costs", C.c_int, [_H, C.POINTER(C.c_int64), _VP]),
     ("icem_set_option", C.c_int, [C.c_char_p, C.c_double]),

@@ -344,6 +344,34 @@ class MpcController(ModelBasedController, StatefulController, ABC):
                 and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
                 and m.params.device == self.planner.device)
 
+    def _steps_through_an_ensemble(self) -> bool:
+        """The fused step of this (baseline) controller is the one through models of their own: its model is the library's
+        own ensemble (``icem_plan_step_cem_learned_models`` / ``icem_plan_step_random_learned_models``)."""
+        return bool(self.rssm_path and not self.device_path and self._model_is_the_library_ensemble())
+
+    @staticmethod
+    def _batch_models(ctrls, own_models):
+        """How a batch of learned-dynamics baseline controllers (every one the library's RSSM or the library's ensemble) names
+        its models to the library -> ``(models, members, why)``: ``models`` None where all share one ``DeviceRSSMModel`` (the
+        ``*_learned_batch`` entries), the shared ``DeviceRSSMEnsemble``, or -- ``own_models`` -- the list of every controller's
+        plain model / ensemble (the ``*_learned_models`` entries); ``why``: the refusal, else None."""
+        c0 = ctrls[0]
+        ens = [c._steps_through_an_ensemble() for c in ctrls]
+        if any(ens) and not all(ens):
+            return None, 0, "controllers on an ensemble cannot be mixed with controllers on a plain model"
+        m0 = c0.forward_model
+        if all(c.forward_model is m0 for c in ctrls):
+            return (m0, m0.members, None) if ens[0] else (None, 1, None)
+        if not own_models:
+            return None, 0, ("learned-dynamics controllers must share one DeviceRSSMModel (or one DeviceRSSMEnsemble); controllers with "
+                             "a model or an ensemble each are stepped together by get_action_batch_own_models")
+        ms = [c.forward_model for c in ctrls]
+        if any(m.act_dim != m0.act_dim or m.params.device != m0.params.device for m in ms):
+            return None, 0, "learned-dynamics controllers with a model each need models of one action width on one device"
+        if ens[0] and any(m.members != m0.members or m.reduce != m0.reduce for m in ms):
+            return None, 0, "controllers with an ensemble each need ensembles of one size and one reduction"
+        return ms, (m0.members if ens[0] else 1), None
+
     def _costs_of(self, obs, actions: torch.Tensor) -> torch.Tensor:
         """Per-trajectory costs (device tensor) of a batch of device action sequences, through whichever
         model this controller was given."""
@@ -635,7 +663,8 @@ class MpcICemHip(MpcController):
         controllers on one ``DeviceRSSMEnsemble``, controllers with a plain model each -- take ``icem_plan_step_learned_models``
         where it serves them (``IcemPlanner.learned_models_step_ok``): the whole step in the library, 3 launches per iteration
         for all controllers and members, the same bits; an ensemble whose rollout was instrumented is still called stage by
-        stage, and controllers that each own an ENSEMBLE are not offered here (the C entry serves them).  Without the
+        stage; controllers that each own an ENSEMBLE (one size, one reduction) are served by the same entry with ``own_models=True``
+        where it serves the batch, and refused elsewhere.  Without the
         keyword, controllers whose parameter buffers differ are refused as they always were: two copies of one model are
         more often a mistake than a wish.  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)
@@ -881,6 +910,9 @@ class MpcICemHip(MpcController):
         except IcemError as e:
             if e.code != ICEM_E_UNSUPPORTED:
                 raise
+            if IcemPlanner._ensembles_each(models):   # (the stage-wise step has no launch for an ensemble each)
+                raise NotImplementedError(f"get_action_batch: the library does not serve these controllers with an ensemble each ({e}); "
+                                          "call get_action per controller") from e
             return MpcICemHip._get_action_batch_rssm(ctrls, observations)   # (refused before anything ran)
         for c in ctrls:
             c._elites_from_planner()
@@ -905,9 +937,18 @@ class MpcICemHip(MpcController):
             m, m0 = c.forward_model, c0.forward_model
             if not MpcICemHip._share_params(m, m0):
                 # a model each: served on request while every model is the library's own RSSM (one launch reads B parameter buffers)
-                if not own_models or not all(k._model_is_the_library_rssm() for k in ctrls):
+                # -- or every model the library's own ensemble, where icem_plan_step_learned_models serves the batch (the stage-wise
+                # step has no launch for an ensemble each)
+                each_ens = all(k._model_is_the_library_ensemble() for k in ctrls)
+                if not own_models or not (each_ens or all(k._model_is_the_library_rssm() for k in ctrls)):
                     return ("learned-dynamics controllers must share one parameter buffer (the same DeviceRSSMModel, or the same params "
-                            "storage); controllers with a plain DeviceRSSMModel each are stepped together with own_models=True")
+                            "storage); controllers with a plain DeviceRSSMModel each, or a DeviceRSSMEnsemble each, are stepped together "
+                            "with own_models=True")
+                if each_ens and (m.members != m0.members or m.reduce != m0.reduce):
+                    return "learned-dynamics controllers with an ensemble each need ensembles of one size and one reduction"
+                if each_ens and not all(k._learned_models_ok(None, len(ctrls)) for k in ctrls):
+                    return ("the library does not serve these controllers with an ensemble each in one call "
+                            "(IcemPlanner.learned_models_step_ok): call get_action per controller")
                 if m.act_dim != m0.act_dim or m.params.device != m0.params.device:
                     return "learned-dynamics controllers with a model each need models of one action width on one device"
             # (everything but the seed: IcemConfig is a dataclass, and rank / world are 0 / 1 here)
@@ -958,6 +999,11 @@ class MpcCemStdHip(MpcController):
     else it is the stage-wise loop over the operators -- the same bits.  With a ``DeviceRSSMModel`` whose ``rollout_cost``
     is its own (learned dynamics: the planner PlaNet uses) the same holds through ``icem_plan_step_cem_learned`` /
     ``icem_plan_step_cem_learned_batch`` where ``IcemPlanner.cem_learned_step_ok()``; a batch then shares one model.
+    With a ``DeviceRSSMEnsemble`` whose methods are its own -- CEM through an ensemble, the planner of PETS -- ``get_action`` is
+    ``icem_plan_step_cem_learned_models`` where ``IcemPlanner.cem_learned_models_step_ok()``: one rollout launch for all members,
+    their reduction inside the update launch, still 3 launches per iteration; measured (EXPERIMENTS R26.1; N = 1024, h = 12,
+    K = 10, 5 iterations) 0.57 against 0.65 ms for the loop at E = 2, so ``fused_step=None`` takes it.  ``get_action_batch``
+    takes the same entry for controllers on one ensemble, ``get_action_batch_own_models`` for a model or an ensemble each.
     ``fused_step``: None (the rule above), False (always the loop) or True (raise where the fused step is not served)."""
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
@@ -1065,9 +1111,10 @@ class MpcCemStdHip(MpcController):
         return executed_action
 
     @staticmethod
-    def _batch_refusal(ctrls):
+    def _batch_refusal(ctrls, own_models=False):
         """Why ``icem_plan_step_cem_batch`` cannot run these controllers' steps as one call (None: it can, as far as the
-        controllers can tell -- the library has the last word)."""
+        controllers can tell -- the library has the last word).  ``own_models``: the caller asked for controllers with a model
+        or an ensemble each to be served."""
         import dataclasses
         for c in ctrls:
             if c.fused_step is False:
@@ -1082,16 +1129,34 @@ class MpcCemStdHip(MpcController):
             return "the controllers differ in configuration (everything but the seed must be equal) or in their flags"
         if len({id(c.planner) for c in ctrls}) != len(ctrls):
             return "a controller appears twice"
-        learned = [c._steps_through_the_rssm() for c in ctrls]
-        if any(learned):   # one launch rolls every problem's rows out through ONE parameter buffer
+        learned = [c._steps_through_the_rssm() or c._steps_through_an_ensemble() for c in ctrls]
+        if any(learned):
             if not all(learned):
                 return "learned-dynamics controllers cannot be mixed with controllers of the built-in model"
-            if any(c.forward_model is not c0.forward_model for c in ctrls[1:]):
-                return "learned-dynamics controllers must share one DeviceRSSMModel"
+            # one parameter buffer for every problem's rows, or (the *_learned_models entry) a table of them
+            models, members, why = MpcController._batch_models(ctrls, own_models)
+            if why is not None:
+                return why
+            if models is not None and not c0.planner.cem_learned_models_step_ok(len(ctrls), members):
+                return (f"the library does not serve {len(ctrls)} such controllers x {members} models in one call "
+                        "(IcemPlanner.cem_learned_models_step_ok)")
         return None
 
     @staticmethod
+    def get_action_batch_own_models(controllers, observations, states=None, mode="train"):
+        """:meth:`get_action_batch` for learned-dynamics controllers that each own their model -- a plain ``DeviceRSSMModel``
+        each, or a ``DeviceRSSMEnsemble`` each (one size, one reduction): ``own_models=True`` as ``MpcICemHip.get_action_batch``
+        spells it (a method of its own here: the parameter list of :meth:`get_action_batch` is held by the suite).  ONE
+        ``icem_plan_step_cem_learned_models`` call where it serves them; everything else as :meth:`get_action_batch`."""
+        return MpcCemStdHip._get_action_batch(controllers, observations, states, mode, True)
+
+    @staticmethod
     def get_action_batch(controllers, observations, states=None, mode="train"):
+        """:meth:`_get_action_batch` (which see) for controllers that share their model, or have the built-in one each."""
+        return MpcCemStdHip._get_action_batch(controllers, observations, states, mode, False)
+
+    @staticmethod
+    def _get_action_batch(controllers, observations, states=None, mode="train", own_models=False):
         """``get_action`` of several controllers at once -- the reference steps its CEM baseline's episodes side by side, each
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152; mpc.py:200-262) -- as ONE library call
         (``icem_plan_step_cem_batch``: 3 launches per CEM iteration for all of them, one device-to-host copy) where every
@@ -1099,7 +1164,9 @@ class MpcCemStdHip(MpcController):
         and flags; seeds, episodes and step counts are their own.  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves (same executed action, bit for bit; same bookkeeping).  Where the
         batch is not served each controller's own planning step runs, in order, with the same results; a controller with
-        ``fused_step=True`` makes that a ``RuntimeError`` naming the reason."""
+        ``fused_step=True`` makes that a ``RuntimeError`` naming the reason.  Controllers that share one ``DeviceRSSMEnsemble``
+        take ``icem_plan_step_cem_learned_models``; ``own_models`` (:meth:`get_action_batch_own_models`; the keyword's meaning
+        on ``MpcICemHip``) serves controllers with a plain ``DeviceRSSMModel`` each, or an ensemble each, through the same entry."""
         from ._lib import ICEM_E_INVALID, ICEM_E_STATE, ICEM_E_UNSUPPORTED, IcemError
         ctrls = list(controllers)
         n = len(ctrls)
@@ -1115,14 +1182,17 @@ class MpcCemStdHip(MpcController):
         for c, ob, stt in zip(ctrls, observations, states):
             c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
                 observation=ob, env_state=stt, model_state=c.forward_model_state)
-        why = MpcCemStdHip._batch_refusal(ctrls)
+        why = MpcCemStdHip._batch_refusal(ctrls, own_models)
         host = None
         if why is None:
             c0 = ctrls[0]
             pls, dists = [c.planner for c in ctrls], [(c._mean, c._std, c._lower, c._upper) for c in ctrls]
             flags = dict(like_levine=c0.like_levine, shift_means=c0.shift_means, execute_best_elite=c0.execute_best_elite)
             try:
-                if c0._steps_through_the_rssm():
+                models = MpcController._batch_models(ctrls, own_models)[0] if c0.rssm_path and not c0.device_path else None
+                if models is not None:
+                    res = IcemPlanner.plan_step_cem_learned_models(pls, models, observations, dists, **flags)
+                elif c0._steps_through_the_rssm():
                     res = IcemPlanner.plan_step_cem_learned_batch(pls, c0.forward_model, observations, dists, **flags)
                 else:
                     res = IcemPlanner.plan_step_cem_batch(pls, observations, dists, **flags)
@@ -1148,8 +1218,8 @@ class MpcCemStdHip(MpcController):
     def _fused_step_refusal(self):
         """Why ``icem_plan_step_cem`` -- ``icem_plan_step_cem_learned`` where the model is the library's own RSSM -- cannot
         run this controller's step (None: it can)."""
-        learned = self._steps_through_the_rssm()
-        if not self.device_path and not learned:
+        learned, ens = self._steps_through_the_rssm(), self._steps_through_an_ensemble()
+        if not self.device_path and not learned and not ens:
             if self.rssm_path:
                 return "the learned-dynamics model is not the library's own RSSM (its rollout_cost is called stage by stage)"
             return "the model is not the device's built-in one"
@@ -1159,9 +1229,12 @@ class MpcCemStdHip(MpcController):
             return "compute_new_mean is overridden"
         if self.verbose:
             return "the controller is verbose"
+        if ens and not (self.planner._bind_rssm(self.forward_model)
+                        and self.planner.cem_learned_models_step_ok(1, self.forward_model.members)):
+            return "the library does not serve this handle through this ensemble (IcemPlanner.cem_learned_models_step_ok)"
         if learned and not self.planner.cem_learned_step_ok(self.forward_model):
             return "the library does not serve this handle through the learned dynamics (IcemPlanner.cem_learned_step_ok)"
-        if not learned and not self.planner.cem_step_ok():
+        if not learned and not ens and not self.planner.cem_step_ok():
             return "the library does not serve this handle (IcemPlanner.cem_step_ok)"
         return None
 
@@ -1182,7 +1255,9 @@ class MpcCemStdHip(MpcController):
         RSSM); one device-to-host copy of ``[executed | best_cost]``."""
         p = self.planner
         flags = dict(like_levine=self.like_levine, shift_means=self.shift_means, execute_best_elite=self.execute_best_elite)
-        if self._steps_through_the_rssm():
+        if self._steps_through_an_ensemble():   # (icem_plan_step_cem_learned_models, one problem: the same buffers)
+            IcemPlanner.plan_step_cem_learned_models([p], self.forward_model, [obs], [(self._mean, self._std, self._lower, self._upper)], **flags)
+        elif self._steps_through_the_rssm():
             p.plan_step_cem_learned(self.forward_model, obs, self._mean, self._std, self._lower, self._upper, **flags)
         else:
             p.plan_step_cem(obs, self._mean, self._std, self._lower, self._upper, **flags)
@@ -1250,7 +1325,12 @@ class MpcRandomHip(MpcController):
     ``icem_plan_step_random_learned`` / ``icem_plan_step_random_learned_batch`` and ``IcemPlanner.random_learned_step_ok()``;
     the controllers of a batch then share ONE model object.  ``fused_step=None`` takes the library step there too: measured
     (EXPERIMENTS R22.1; N = 1024, h = 12, hold 4) 0.123 ms per ``get_action`` against 0.148 ms for the chain in one process
-    -- the rollout's 74 us are common to both --, and sixteen controllers 0.43 ms per step of the batch against 1.34 ms."""
+    -- the rollout's 74 us are common to both --, and sixteen controllers 0.43 ms per step of the batch against 1.34 ms.
+    With a ``DeviceRSSMEnsemble`` whose methods are its own -- random shooting through an ensemble, as PETS plans --
+    ``get_action`` is ``icem_plan_step_random_learned_models`` where ``IcemPlanner.random_learned_models_step_ok()``: one
+    rollout launch for all members, their reduction inside the selection launch, still 3 launches; measured (EXPERIMENTS
+    R26.1, same shape) 0.13 against 0.15 ms for the chain at E = 2, so ``fused_step=None`` takes it.  ``get_action_batch``
+    takes the same entry for controllers on one ensemble, ``get_action_batch_own_models`` for a model or an ensemble each."""
 
     def __init__(self, *, action_sampler_params, dtype="f32", seed=0, rng_rounds=10, device="cuda:0",
                  noise_source: Union[str, Callable] = "philox", fused_step=None, **kwargs):
@@ -1323,8 +1403,8 @@ class MpcRandomHip(MpcController):
     def _fused_step_refusal(self):
         """Why ``icem_plan_step_random`` -- ``icem_plan_step_random_learned`` where the model is the library's own RSSM --
         cannot run this controller's step (None: it can)."""
-        learned = self._steps_through_the_rssm()
-        if not self.device_path and not learned:
+        learned, ens = self._steps_through_the_rssm(), self._steps_through_an_ensemble()
+        if not self.device_path and not learned and not ens:
             if self.rssm_path:
                 return "the learned-dynamics model is not the library's own RSSM (its rollout_cost is called stage by stage)"
             return "the model is not the device's built-in one"
@@ -1332,9 +1412,12 @@ class MpcRandomHip(MpcController):
             return "the noise source is not the device's (external uniforms keep the operator chain)"
         if self.verbose:
             return "the controller is verbose"
+        if ens and not (self.planner._bind_rssm(self.forward_model)
+                        and self.planner.random_learned_models_step_ok(1, self.forward_model.members)):
+            return "the library does not serve this handle through this ensemble (IcemPlanner.random_learned_models_step_ok)"
         if learned and not self.planner.random_learned_step_ok(self.forward_model):
             return "the library does not serve this handle through the learned dynamics (IcemPlanner.random_learned_step_ok)"
-        if not learned and not self.planner.random_step_ok():
+        if not learned and not ens and not self.planner.random_step_ok():
             return "the library does not serve this handle (IcemPlanner.random_step_ok)"
         return None
 
@@ -1363,7 +1446,9 @@ class MpcRandomHip(MpcController):
         """The whole step in the library (``icem_plan_step_random``, or ``icem_plan_step_random_learned`` through the library's
         RSSM); one device-to-host copy of ``result``."""
         p = self.planner
-        if self._steps_through_the_rssm():
+        if self._steps_through_an_ensemble():   # (icem_plan_step_random_learned_models, one problem: the same buffers)
+            IcemPlanner.plan_step_random_learned_models([p], self.forward_model, [obs], [self.calls], self.action_change_frequency)
+        elif self._steps_through_the_rssm():
             p.plan_step_random_learned(self.forward_model, obs, self.calls, self.action_change_frequency)
         else:
             p.plan_step_random(obs, self.calls, self.action_change_frequency)
@@ -1380,9 +1465,10 @@ class MpcRandomHip(MpcController):
         return actions[self.best_traj_idx, 0].cpu().numpy().astype(np.float64)
 
     @staticmethod
-    def _batch_refusal(ctrls):
+    def _batch_refusal(ctrls, own_models=False):
         """Why ``icem_plan_step_random_batch`` cannot run these controllers' steps as one call (None: it can, as far as the
-        controllers can tell -- the library has the last word)."""
+        controllers can tell -- the library has the last word).  ``own_models``: the caller asked for controllers with a model
+        or an ensemble each to be served."""
         import dataclasses
         for c in ctrls:
             if c.fused_step is False:
@@ -1396,16 +1482,34 @@ class MpcRandomHip(MpcController):
             return "the controllers differ in configuration (everything but the seed must be equal) or in action_change_frequency"
         if len({id(c.planner) for c in ctrls}) != len(ctrls):
             return "a controller appears twice"
-        learned = [c._steps_through_the_rssm() for c in ctrls]
-        if any(learned):   # one launch rolls every problem's rows out through ONE parameter buffer
+        learned = [c._steps_through_the_rssm() or c._steps_through_an_ensemble() for c in ctrls]
+        if any(learned):
             if not all(learned):
                 return "learned-dynamics controllers cannot be mixed with controllers of the built-in model"
-            if any(c.forward_model is not c0.forward_model for c in ctrls[1:]):
-                return "learned-dynamics controllers must share one DeviceRSSMModel"
+            # one parameter buffer for every problem's rows, or (the *_learned_models entry) a table of them
+            models, members, why = MpcController._batch_models(ctrls, own_models)
+            if why is not None:
+                return why
+            if models is not None and not c0.planner.random_learned_models_step_ok(len(ctrls), members):
+                return (f"the library does not serve {len(ctrls)} such controllers x {members} models in one call "
+                        "(IcemPlanner.random_learned_models_step_ok)")
         return None
 
     @staticmethod
+    def get_action_batch_own_models(controllers, observations, states=None, mode="train"):
+        """:meth:`get_action_batch` for learned-dynamics controllers that each own their model -- a plain ``DeviceRSSMModel``
+        each, or a ``DeviceRSSMEnsemble`` each (one size, one reduction): ``own_models=True`` as ``MpcICemHip.get_action_batch``
+        spells it (a method of its own here: the parameter list of :meth:`get_action_batch` is held by the suite).  ONE
+        ``icem_plan_step_random_learned_models`` call where it serves them; everything else as :meth:`get_action_batch`."""
+        return MpcRandomHip._get_action_batch(controllers, observations, states, mode, True)
+
+    @staticmethod
     def get_action_batch(controllers, observations, states=None, mode="train"):
+        """:meth:`_get_action_batch` (which see) for controllers that share their model, or have the built-in one each."""
+        return MpcRandomHip._get_action_batch(controllers, observations, states, mode, False)
+
+    @staticmethod
+    def _get_action_batch(controllers, observations, states=None, mode="train", own_models=False):
         """``get_action`` of several controllers at once -- the reference steps its baseline's episodes side by side, each
         controller its own ``get_action`` (icem/misc/rollout_utils.py:46-58, 129-152; mpc.py:114-138) -- as ONE library call
         (``icem_plan_step_random_batch``: the step's launches once for all of them, one device-to-host copy) where every
@@ -1413,7 +1517,10 @@ class MpcRandomHip(MpcController):
         seeds, models and call counters are their own (through the library's RSSM: ``icem_plan_step_random_learned_batch``,
         ONE model object for all of them).  Each controller ends in exactly the state its own
         ``get_action(observations[i], states[i])`` leaves.  Where the batch is not served each controller's own step runs, in
-        order, with the same results; a controller with ``fused_step=True`` makes that a ``RuntimeError`` naming the reason."""
+        order, with the same results; a controller with ``fused_step=True`` makes that a ``RuntimeError`` naming the reason.
+        Controllers that share one ``DeviceRSSMEnsemble`` take ``icem_plan_step_random_learned_models``; ``own_models``
+        (:meth:`get_action_batch_own_models`; the keyword's meaning on ``MpcICemHip``) serves controllers with a plain
+        ``DeviceRSSMModel`` each, or an ensemble each, through the same entry."""
         from ._lib import ICEM_E_INVALID, ICEM_E_STATE, ICEM_E_UNSUPPORTED, IcemError
         ctrls = list(controllers)
         n = len(ctrls)
@@ -1426,12 +1533,15 @@ class MpcRandomHip(MpcController):
         for c, ob, stt in zip(ctrls, observations, states):
             c.forward_model_state = c.forward_model.got_actual_observation_and_env_state(
                 observation=ob, env_state=stt, model_state=c.forward_model_state)
-        why = MpcRandomHip._batch_refusal(ctrls)
+        why = MpcRandomHip._batch_refusal(ctrls, own_models)
         host = None
         if why is None:
             try:
                 pls, offs, c0 = [c.planner for c in ctrls], [c.calls for c in ctrls], ctrls[0]
-                if c0._steps_through_the_rssm():
+                models = MpcController._batch_models(ctrls, own_models)[0] if c0.rssm_path and not c0.device_path else None
+                if models is not None:
+                    IcemPlanner.plan_step_random_learned_models(pls, models, observations, offs, c0.action_change_frequency)
+                elif c0._steps_through_the_rssm():
                     IcemPlanner.plan_step_random_learned_batch(pls, c0.forward_model, observations, offs, c0.action_change_frequency)
                 else:
                     IcemPlanner.plan_step_random_batch(pls, observations, offs, c0.action_change_frequency)

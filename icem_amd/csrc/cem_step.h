@@ -55,4 +55,17 @@ void launch_cem_sample_gather_batch(const icem_handle* h, int n_rows, const void
 void launch_cem_update_batch(const CemUpdateF32Args* args_dev, int n_problems, int hd, hipStream_t st);
 void launch_cem_update_batch(const CemUpdateF64Args* args_dev, int n_problems, int hd, hipStream_t st);
 
+// ---- icem_plan_step_cem_learned_models: the f32 update whose pool costs are not in memory yet -- it reduces them itself from the
+// members' (UpdateMembersArgs, icem_fused.h: the same fields with the same meaning, the same arithmetic -- MemberCosts,
+// update_small_body.h) and leaves the reduced cost in costs[i] as well.  u.u.costs is unused.
+struct CemUpdateMembersArgs {
+    CemUpdateF32Args c;
+    const float* member_costs;   // [members, stride]
+    float* costs;                // [c.u.n] out: the reduced costs
+    int members, reduce;         // reduce: ICEM_RSSM_REDUCE_MEAN / _MAX
+    int stride, row0;            // the member stride (all problems' rows) and this problem's first row
+    float inv;                   // (float)(1.0 / members)
+};
+void launch_cem_update_members_batch(const CemUpdateMembersArgs* args_dev, int n_problems, int hd, hipStream_t st);
+
 }  // namespace icem

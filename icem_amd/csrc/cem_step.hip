@@ -18,9 +18,16 @@
 // BASELINE configs[4]) -- the planner PlaNet uses: the sampler and the update above around launch_rssm_rollout (one problem) /
 // launch_rssm_split_batch (several, their rows back to back in the learned step's pool of the first handle, icem_plan_step_learned_batch's
 // arrangement).  The refusals, the block filling and the update launch are the ones above.
+//
+// icem_plan_step_cem_learned_models is that batched step for problems that roll out through models of their own (an ensemble's
+// members, a trained model per controller): cem_step_batch with the rollout ONE launch_rssm_split_models of n * members problems in
+// member-major order (step_models.h, shared with learned_step.hip) and the update cem_update_members_batch_kernel
+// (k_cem_members.hip), which reduces the members' costs while it builds its keys -- still 3 launches per iteration.  One problem
+// works in its own actions / costs.
 #include "cem_step.h"
 #include "icem_rssm.h"
 #include "recorded_batch.h"
+#include "step_models.h"
 
 using namespace icem;
 
@@ -176,8 +183,11 @@ int cem_step_solo(icem_handle* h, const icem_cem_buffers* b, const icem_cem_para
 // cem_batch_launches, written behind the last launch only, and through the RSSM its learned-step pool.  Recording a handle's rollout
 // may upload that handle's packed model (ensure_fast_model: idempotent, what its next solo step would do first).  So a HIP call
 // that fails anywhere below leaves every handle as it was.
+// mo (icem_plan_step_cem_learned_models; params == nullptr): every problem rolls out through models of its own -- the rollout is
+// ONE launch_rssm_split_models of n * members problems, the update reduces the members' costs itself; n == 1 then works in the
+// problem's own actions / costs and needs no pool.
 int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* buffers, const icem_cem_params& p, const void* params,
-                   const int32_t* steps, void* results, hipStream_t st) {
+                   const int32_t* steps, void* results, hipStream_t st, const StepModels* mo = nullptr) {
     const std::string who = "icem_plan_step_cem_batch: ";
     icem_handle* h0 = handles[0];
     const icem_config& c = h0->cfg;
@@ -186,15 +196,25 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
     // ---- the rollout.  Through the RSSM: problem i's rows are drawn into the slice [i * N, (i + 1) * N) of the first handle's
     // learned-step pool, ONE split launch scores the pool, every update reads its slice; the first sampler launch also gathers the
     // observations into the pool's [n, 230] table.  Else: every problem's rollout launch, recorded and compared (recorded_batch.h) ----
-    RecordedBatch rb(params ? 0 : n);
-    float *pool_a = nullptr, *pool_c = nullptr;
+    const bool learned = params || mo, pooled = learned && n > 1;
+    RecordedBatch rb(learned ? 0 : n);
+    float *pool_a = nullptr, *pool_c = nullptr, *member_costs = mo ? mo->member_costs : nullptr;
     ObsGather og{};
-    if (params) {
+    if (learned) {
         LearnedCtx& ctx = h0->learned;
-        ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
-        pool_a = ctx.pool_actions(), pool_c = ctx.pool_costs(hd);
-        og.dst = ctx.pool_obs(hd), og.width = ICEM_RSSM_OBS_DIM;
-        for (int i = 0; i < n; ++i) og.src[i] = (const float*)buffers[i].obs0;
+        if (pooled) {
+            ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
+            pool_a = ctx.pool_actions(), pool_c = ctx.pool_costs(hd);
+            og.dst = ctx.pool_obs(hd), og.width = ICEM_RSSM_OBS_DIM;
+            for (int i = 0; i < n; ++i) og.src[i] = (const float*)buffers[i].obs0;
+        } else {   // (one problem: its own rows, its own observation)
+            pool_a = (float*)buffers[0].actions, pool_c = (float*)buffers[0].costs;
+            og.dst = (float*)const_cast<void*>(buffers[0].obs0);
+        }
+        if (mo && !member_costs) {   // (the members' costs of one iteration: scratch that only grows)
+            ICEM_HIP_TRY(ctx.reserve_members((size_t)mo->members * n * N, st));
+            member_costs = ctx.member_costs;
+        }
     } else {
         if (!cem_sample_ok(h0))
             return fail(ICEM_E_UNSUPPORTED, who + "a row of this shape does not fit the step's sampler (its three probability tables and one row in LDS): "
@@ -204,7 +224,7 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
         if (int rc = rb.check(who)) return rc;
     }
     // ---- argument blocks: per iteration [sample x n | rollout launch(es) x n | update x n]; no step-dependent value in them ----
-    const size_t sb = cem_sample_block_bytes(h0), ub = f64 ? sizeof(CemUpdateF64Args) : sizeof(CemUpdateF32Args);
+    const size_t sb = cem_sample_block_bytes(h0), ub = mo ? sizeof(CemUpdateMembersArgs) : f64 ? sizeof(CemUpdateF64Args) : sizeof(CemUpdateF32Args);
     BlockLayout layout(n, ICEM_MAX_BATCH);
     layout.add(sb);   // (at 0)
     rb.place(layout);
@@ -216,11 +236,18 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
         unsigned char* part = blob.data() + per_it * it;
         for (int i = 0; i < n; ++i) {
             icem_cem_buffers b = buffers[i];
-            if (params) b.actions = pool_a + (size_t)i * N * hd, b.costs = pool_c + (size_t)i * N;   // (the problem's own, but its pool: the slice)
+            if (pooled) b.actions = pool_a + (size_t)i * N * hd, b.costs = pool_c + (size_t)i * N;   // (the problem's own, but its pool: the slice)
             cem_sample_block(handles[i], N, b.mean, b.std, b.lower, b.upper, (uint64_t)it, b.actions, part + sb * i);
             rb.copy(i, part);
             void* row = results_row(results, i, (size_t)(c.act_dim + 1) * h0->tsize);
-            if (f64) fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF64Args*)(part + at_update + ub * i));
+            if (mo) {   // (CemUpdateMembersArgs begins with a CemUpdateF32Args)
+                CemUpdateMembersArgs& m = *(CemUpdateMembersArgs*)(part + at_update + ub * i);
+                fill_update(handles[i], b, p, it == iters - 1, row, m.c);
+                m.member_costs = member_costs, m.costs = (float*)b.costs;
+                m.members = mo->members, m.reduce = mo->reduce;
+                m.stride = n * N, m.row0 = i * N;
+                m.inv = (float)(1.0 / mo->members);
+            } else if (f64) fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF64Args*)(part + at_update + ub * i));
             else fill_update(handles[i], b, p, it == iters - 1, row, *(CemUpdateF32Args*)(part + at_update + ub * i));
         }
     }
@@ -228,20 +255,25 @@ int cem_step_batch(icem_handle* const* handles, int n, const icem_cem_buffers* b
     ICEM_HIP_TRY(h0->cem_batch_args.put(slot, blob, layout.room() * iters, st, &h0->batch_uploads));
     // ---- the launches: 3 per iteration (+ the GEMM path's row tail, which a CEM step never has: no shifted rows) ----
     const unsigned char* dev = (const unsigned char*)h0->cem_batch_args.dev(slot);
-    const std::vector<int> rows(params ? n : 0, N);
+    const std::vector<int> rows(learned ? n : 0, N);
+    rssm::Problem pr[rssm::BATCH_MAX];
+    if (mo) models_problems(*mo, n, rows.data(), pr);
     long long launches = 0;
     for (int it = 0; it < iters; ++it) {
         const unsigned char* part = dev + per_it * it;
-        if (params && it == 0) launch_cem_sample_gather_batch(h0, N, part, bases, og, n, st);
+        if (pooled && it == 0) launch_cem_sample_gather_batch(h0, N, part, bases, og, n, st);
         else launch_cem_sample_batch(h0, N, part, bases, n, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
-        if (int rc = params ? rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params,
-                                                                         og.dst, pool_a, pool_c, st))
-                            : rb.launch(part, bases, st, &launches))
+        if (int rc = mo       ? rssm_launch_result(launch_rssm_split_models(n * mo->members, pr, c.horizon, c.act_dim, c.cost_mode, og.dst, pool_a,
+                                                                            member_costs, st))
+                     : params ? rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params,
+                                                                           og.dst, pool_a, pool_c, st))
+                              : rb.launch(part, bases, st, &launches))
             return rc;
-        if (params) ++launches;
-        if (f64) launch_cem_update_batch((const CemUpdateF64Args*)(part + at_update), n, hd, st);
+        if (learned) ++launches;
+        if (mo) launch_cem_update_members_batch((const CemUpdateMembersArgs*)(part + at_update), n, hd, st);
+        else if (f64) launch_cem_update_batch((const CemUpdateF64Args*)(part + at_update), n, hd, st);
         else launch_cem_update_batch((const CemUpdateF32Args*)(part + at_update), n, hd, st);
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
@@ -319,6 +351,36 @@ int icem_plan_step_cem_learned_batch(icem_handle* const* handles, int32_t n, con
         return rc;
     }
     return cem_step_batch(handles, n, buffers, *p, params, mpc_steps_host, results, (hipStream_t)stream);
+}
+
+// would a batch of n handles like `h` with `members` models per problem be served?
+int icem_plan_step_cem_learned_models_ok(const icem_handle* h, int32_t n, int32_t members) {
+    if (!h || cem_learned_unserved(h) || n < 1 || n > ICEM_MAX_BATCH || members < 1 || members > rssm::BATCH_MAX || n * members > rssm::BATCH_MAX)
+        return 0;
+    const long long tiles = (long long)n * members * ((h->cfg.num_traj + 15) / 16);
+    return tiles <= rssm::SPLIT_TILE_LIMIT && rssm_split_batch_ok((int)tiles, h->cfg.horizon) ? 1 : 0;
+}
+
+int icem_plan_step_cem_learned_models(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
+                                      int32_t members, const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host,
+                                      void* member_costs, void* results, void* stream) {
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    const std::string who = "icem_plan_step_cem_learned_models: ";
+    const std::string config_msg = who + "the handles must share one configuration (everything but the seed)";
+    // (what the counts and the table alone decide comes first: no handle has been looked at when n x members is refused)
+    if (int rc = models_args_refusal(who, handles && buffers && p && mpc_steps_host, n, members, params_host, reduce)) return rc;
+    if (int rc = admit_batch(handles, n, true, true, who.c_str(), config_msg.c_str())) return rc;
+    if (int rc = admit_rssm_binding(handles, n, config_msg.c_str())) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = cem_refusal(handles[i], buffers[i], mpc_steps_host[i], who, true)) return rc;
+    const icem_config& c = handles[0]->cfg;
+    const StepModels mo{members, reduce, params_host, (float*)member_costs};
+    const int tiles = models_tiles_uniform(mo, n, c.num_traj, c.horizon);
+    if (tiles < 0)
+        return fail(ICEM_E_UNSUPPORTED, who + "the tiles of a rollout (members x the sum over the problems of ceil(num_traj / 16)) exceed the "
+                                              "split launch's limit; nothing was launched");
+    if (int rc = rssm_launch_result(rssm_split_prepare(tiles, c.horizon, (hipStream_t)stream))) return rc;
+    return cem_step_batch(handles, n, buffers, *p, nullptr, mpc_steps_host, results, (hipStream_t)stream, &mo);
 }
 
 int64_t icem_cem_step_launches(const icem_handle* h) { return h ? (int64_t)h->cem_launches : 0; }

@@ -10,9 +10,12 @@
 // The arithmetic of every value is a device function shared with the operator that computes it: the step's bits are theirs.
 // icem_plan_step_cem_learned* (the same step through the declared RSSM) launches these kernels around the RSSM's rollout;
 // its batch's first sampler launch is cem_sample_gather_batch_kernel, which also builds the batch's observation table.
+// icem_plan_step_cem_learned_models' update kernel, which reduces an ensemble's member costs on the way to its keys, is
+// k_cem_members.hip's: a unit of its own, so that the code of the kernels here is what it was.
 #include "update_small_body.h"
 #include "generic_dev.h"
 #include "cem_step.h"
+#include "cem_update_dev.h"   // from_device of the f32 update's blocks
 
 namespace icem {
 
@@ -68,21 +71,6 @@ __device__ __forceinline__ CemSampleArgs<T> from_device(const CemSampleArgs<T>& 
     CemSampleArgs<T> a = m;
     a.mean = gptr(m.mean), a.std = gptr(m.std), a.lower = gptr(m.lower), a.upper = gptr(m.upper), a.out = gptr(m.out);
     return a;
-}
-template <typename T>
-__device__ __forceinline__ CemTailArgs<T> from_device(const CemTailArgs<T>& m) {
-    CemTailArgs<T> t = m;
-    t.mean = gptr(m.mean), t.std = gptr(m.std), t.low = gptr(m.low), t.high = gptr(m.high), t.lower = gptr(m.lower), t.upper = gptr(m.upper);
-    t.elites = gptr(m.elites), t.elite_costs = gptr(m.elite_costs), t.executed = gptr(m.executed), t.best_cost = gptr(m.best_cost);
-    t.result = gptr(m.result);
-    return t;
-}
-__device__ __forceinline__ UpdateSmallArgs from_device(const UpdateSmallArgs& m) {
-    UpdateSmallArgs u = m;
-    u.costs = gptr(m.costs), u.pool = gptr(m.pool), u.keep_costs = gptr(m.keep_costs), u.keep_actions = gptr(m.keep_actions);
-    u.mean = gptr(m.mean), u.std = gptr(m.std), u.elites_out = gptr(m.elites_out), u.elite_costs_out = gptr(m.elite_costs_out);
-    u.idx_out = gptr(m.idx_out);
-    return u;
 }
 // (the CEM step's selection: every row a sampled one, no kept elites, nothing to wait for, never the step's "last")
 __device__ __forceinline__ SelectArgs<double> from_device(const SelectArgs<double>& m) {

@@ -7,6 +7,8 @@
 //                                       the pool's [n, 230] table (as cem_sample_gather_batch_kernel, k_cem.hip)
 //   random_select_pool_batch_kernel     random_select_body on the slice's costs and actions, every cost it reads stored into the
 //                                       problem's own `costs`
+// (icem_plan_step_random_learned_models' selection, which reduces an ensemble's member costs on the way to its keys, is
+//  k_random_members.hip's: a unit of its own.)
 // The argument blocks are byte for byte those of icem_plan_step_random_batch (the problem's OWN buffers); the pool's pointers travel
 // by value and the slices follow from blockIdx.y.  The solo step launches the kernels of k_random.hip.
 #include "random_dev.h"

@@ -21,10 +21,12 @@
 // icem_plan_step_learned_models is the same step for problems that roll out through models of their own (an ensemble's members,
 // a trained model per episode): the rollout is launch_rssm_split_models over n * members problems in member-major order, and
 // the update is update_small_members_batch_kernel, which reduces the members' costs while it builds its keys -- still 3
-// launches per iteration, and the same code below (StepModels).
+// launches per iteration, and the same code below (StepModels, step_models.h: shared with the two baselines' steps through such
+// models, cem_step.hip and random_step.hip).
 #include "block_layout.h"
 #include "host_common.h"
 #include "icem_rssm.h"
+#include "step_models.h"
 
 using namespace icem;
 
@@ -54,25 +56,6 @@ const char* learned_unserved(const icem_handle* h) {
     if (!topk_small_ok(max_rows(h) + std::max(0, h->n_reuse), c.num_elites)) return "the one-launch update does not take this pool / num_elites (<= 16384 candidates, <= 32 elites)";
     if (!rssm_split_ok(max_rows(h), c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
     return nullptr;
-}
-
-// icem_plan_step_learned_models: every problem rolls out through `members` models of its own instead of the one shared buffer
-struct StepModels {
-    int members, reduce;
-    const void* const* params;   // [n * members], problem-major
-    float* member_costs;         // the caller's [members * n * max_rows], or nullptr: the context's scratch
-};
-
-// the rollout of such a step's iteration: n * members problems in member-major order -- problem e * n + p reads problem p's
-// action rows and observation row p, so that the costs land as [members, the iteration's rows of all problems]
-void models_problems(const StepModels& mo, int n, const int* rows, rssm::Problem* out) {
-    for (int e = 0; e < mo.members; ++e) {
-        long long row0 = 0;
-        for (int p = 0; p < n; ++p) {
-            out[e * n + p] = {(const unsigned short*)mo.params[(size_t)p * mo.members + e], row0, rows[p], p};
-            row0 += rows[p];
-        }
-    }
 }
 
 int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
@@ -280,16 +263,7 @@ int icem_plan_step_learned_models(icem_handle* const* handles, int32_t n, const 
                                   void* results, void* stream) {
     const char* config_msg = "icem_plan_step_learned_models: the handles must share one configuration (everything but the seed)";
     // (what the counts and the table alone decide comes first: no handle has been looked at when n x members is refused)
-    if (!handles || !buffers || !params_host || !mpc_steps_host || n < 1 || n > ICEM_MAX_BATCH)
-        return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: null argument / n outside [1, 32]");
-    if (members < 1 || members > rssm::BATCH_MAX) return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: members must be in [1, 32]");
-    if (reduce != ICEM_RSSM_REDUCE_MEAN && reduce != ICEM_RSSM_REDUCE_MAX)
-        return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: reduce must be ICEM_RSSM_REDUCE_MEAN or ICEM_RSSM_REDUCE_MAX");
-    for (int i = 0; i < n * members; ++i)
-        if (!params_host[i]) return fail(ICEM_E_INVALID, "icem_plan_step_learned_models: null params entry");
-    if (n * members > rssm::BATCH_MAX)
-        return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned_models: n x members problems, but one learned-dynamics launch holds 32 "
-                                        "(its table travels in the kernel arguments); nothing was launched");
+    if (int rc = models_args_refusal("icem_plan_step_learned_models: ", handles && buffers && mpc_steps_host, n, members, params_host, reduce)) return rc;
     if (int rc = admit_batch(handles, n, true, true, "icem_plan_step_learned_models: ", config_msg)) return rc;
     if (int rc = admit_rssm_binding(handles, n, config_msg)) return rc;
     const StepModels mo{members, reduce, params_host, (float*)member_costs};

@@ -1,16 +1,19 @@
 // random_dev.h -- the device bodies of the random-shooting step's kernels, shared by k_random.hip (the built-in model's step:
-// icem_plan_step_random*) and k_random_learned.hip (the step through the learned dynamics: icem_plan_step_random_learned_batch).
+// icem_plan_step_random*), k_random_learned.hip (the step through the learned dynamics: icem_plan_step_random_learned_batch) and
+// k_random_members.hip (that step through an ensemble's members: icem_plan_step_random_learned_models).
 //   random_sample_body   icem_sample_piecewise's pool (mpc.py:96-109): a workgroup owns RANDOM_SPAN consecutive elements, draws
 //                        each (block, dimension) value they need once into LDS -- the operator's arithmetic, the same bits --
 //                        and stores its span from there, four elements per store
 //   random_select_body   np.argmin(costs) (mpc.py:122) as icem_topk_sorted(costs, 1) gives it, the gathers behind it
 // MIRROR (compile time, false in every kernel of k_random.hip): the body works on a slice of a pool and writes what it stores
 // (the sampler) or reads (the selection's costs) into the problem's own buffer as well.
+// Src (compile time, the plain load in every kernel but one): where the selection gets a row's cost from.
 // Internal; device code only.
 #pragma once
 #include "fused_dev.h"     // gptr
 #include "generic_dev.h"   // key_less, nan_to_inf, wave_min_key, fmad, row_stream
 #include "random_step.h"
+#include "update_small_body.h"   // MemberCosts
 
 namespace icem {
 
@@ -142,9 +145,18 @@ __device__ __forceinline__ void wg_min_key(T& c, int& i, T* red_c, int* red_i) {
     __syncthreads();
 }
 
-// MIRROR: every cost read from a.costs is stored, as read, at the same index of mirror_costs
-template <typename T, bool MIRROR = false>
-__device__ __forceinline__ void random_select_body(const RandomSelectArgs<T>& a, T* mirror_costs = nullptr) {
+// where row i of the slice gets its cost from: the plain load of a.costs[i] ...
+template <typename T>
+struct SliceCosts {
+    __device__ __forceinline__ T operator()(const RandomSelectArgs<T>& a, int i) const { return a.costs[i]; }
+};
+// ... or (random_select_members_batch_kernel, k_random_members.hip) the costs of an ensemble's members: MemberCosts
+// (update_small_body.h), which reduces them as rssm_ensemble_reduce_kernel does -- all of a row's loads requested before the
+// first is consumed -- and stores the reduced cost, as computed, where a.costs[i] would have been read
+
+// MIRROR: every cost the source gives is stored, as given, at the same index of mirror_costs
+template <typename T, bool MIRROR = false, class Src = SliceCosts<T>>
+__device__ __forceinline__ void random_select_body(const RandomSelectArgs<T>& a, T* mirror_costs = nullptr, const Src src = Src()) {
     constexpr int NW = RANDOM_SELECT_NT / 64;
     __shared__ T red_c[NW];
     __shared__ int red_i[NW];
@@ -155,7 +167,7 @@ __device__ __forceinline__ void random_select_body(const RandomSelectArgs<T>& a,
     T bc = inf_v<T>();
     int bi = INT_MAX;
     for (int i = lo + tid; i < hi; i += RANDOM_SELECT_NT) {
-        const T raw = a.costs[i];
+        const T raw = src(a, i);
         if constexpr (MIRROR) mirror_costs[i] = raw;
         const T c = nan_to_inf(raw);
         if (key_less(c, i, bc, bi)) bc = c, bi = i;

@@ -71,5 +71,17 @@ void launch_random_sample_gather_batch(const icem_handle* h, const void* args_de
                                        const RandomPool<float>& pool, int n_problems, hipStream_t st);
 // the batched selection on the pool's slices, every cost it reads stored into the problem's own costs
 void launch_random_select_pool_batch(const icem_handle* h, const void* args_dev, const RandomPool<float>& pool, int n_problems, hipStream_t st);
+// ... whose costs are still the members' (icem_plan_step_random_learned_models): member e's cost of problem p's row i is
+// member_costs[e * stride + p * N + i]; the selection reduces them (mean: ((c_0 + c_1) + ..) * inv, max: a NaN member wins),
+// stores the reduced cost to the pool's slice and to the problem's own costs, and selects on it.  With one problem the pool may
+// BE the problem's own actions / costs.
+struct RandomMembers {
+    const float* member_costs;   // [members, stride]
+    int members, reduce;         // reduce: ICEM_RSSM_REDUCE_MEAN / _MAX
+    int stride;                  // n * N
+    float inv;                   // (float)(1.0 / members)
+};
+void launch_random_select_members_batch(const icem_handle* h, const void* args_dev, const RandomPool<float>& pool, const RandomMembers& mb,
+                                        int n_problems, hipStream_t st);
 
 }  // namespace icem

@@ -17,9 +17,16 @@
 // Unlike the CEM step's, a problem's own pool is NOT scratch here -- a controller keeps it (MpcRandomHip._last_actions / _last_costs)
 // -- so the batch's sampler and selection (k_random_learned.hip) work on the pool's slices and mirror the rows they store and the
 // costs they read into the problem's own buffers: 3 launches whatever B, every buffer of every problem its solo step's.
+//
+// icem_plan_step_random_learned_models is that batched step for problems that roll out through models of their own (an ensemble's
+// members, a trained model per controller): random_learned_step_batch with the rollout ONE launch_rssm_split_models of n * members
+// problems in member-major order (step_models.h, shared with learned_step.hip) and the selection
+// random_select_members_batch_kernel (k_random_members.hip), which reduces the members' costs on the way to its keys -- still 3 launches.  One problem
+// works in its own actions / costs.
 #include "random_step.h"
 #include "icem_rssm.h"
 #include "recorded_batch.h"
+#include "step_models.h"
 
 using namespace icem;
 
@@ -164,17 +171,27 @@ int random_step_batch(icem_handle* const* handles, int n, const icem_random_buff
 // drawn into the slice [i * N, (i + 1) * N) of the first handle's learned-step pool AND into its own actions, ONE split launch
 // scores the pool, the selection reads the slices and leaves every cost in the problem's own costs as well.  Host state: as
 // random_step_batch's, and the first handle's pool.
+// mo (icem_plan_step_random_learned_models; params == nullptr): every problem rolls out through models of its own -- the rollout is
+// ONE launch_rssm_split_models of n * members problems, the selection reduces the members' costs itself; n == 1 then works in the
+// problem's own actions / costs (the pool IS those) and its sampler is the built-in step's batched one.
 int random_learned_step_batch(icem_handle* const* handles, int n, const icem_random_buffers* buffers, const void* params, int32_t change_freq,
-                              const int64_t* offsets, void* results, hipStream_t st) {
+                              const int64_t* offsets, void* results, hipStream_t st, const StepModels* mo = nullptr) {
     icem_handle* h0 = handles[0];
     const icem_config& c = h0->cfg;
     const int N = c.num_traj, hd = h0->hd;
     LearnedCtx& ctx = h0->learned;
-    ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
-    const RandomPool<float> pool{ctx.pool_actions(), ctx.pool_costs(hd)};
+    const bool pooled = n > 1;
+    if (pooled) ICEM_HIP_TRY(ctx.reserve((size_t)n * N, n, hd, st));
+    const RandomPool<float> pool = pooled ? RandomPool<float>{ctx.pool_actions(), ctx.pool_costs(hd)}
+                                          : RandomPool<float>{(float*)buffers[0].actions, (float*)buffers[0].costs};
     ObsGather og{};
-    og.dst = ctx.pool_obs(hd), og.width = ICEM_RSSM_OBS_DIM;
+    og.dst = pooled ? ctx.pool_obs(hd) : (float*)const_cast<void*>(buffers[0].obs0), og.width = ICEM_RSSM_OBS_DIM;
     for (int i = 0; i < n; ++i) og.src[i] = (const float*)buffers[i].obs0;
+    float* member_costs = mo ? mo->member_costs : nullptr;
+    if (mo && !member_costs) {   // (the members' costs of the rollout: scratch that only grows)
+        ICEM_HIP_TRY(ctx.reserve_members((size_t)mo->members * n * N, st));
+        member_costs = ctx.member_costs;
+    }
     for (int i = 0; i < n; ++i)
         if (int rc = reserve_ws(handles[i], st)) return rc;
     // ---- argument blocks: [sample x n | select x n], those of icem_plan_step_random_batch (the problems' OWN buffers) ----
@@ -192,13 +209,24 @@ int random_learned_step_batch(icem_handle* const* handles, int n, const icem_ran
     ICEM_HIP_TRY(h0->random_batch_args.put(0, blob, layout.room(), st, &h0->batch_uploads));
     // ---- the launches ----
     const unsigned char* dev = (const unsigned char*)h0->random_batch_args.dev(0);
-    launch_random_sample_gather_batch(h0, dev, bases, og, pool, n, st);
+    if (pooled) launch_random_sample_gather_batch(h0, dev, bases, og, pool, n, st);
+    else launch_random_sample_batch(h0, dev, bases, n, st);
     ICEM_HIP_TRY(hipGetLastError());
     const std::vector<int> rows(n, N);
-    if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params, og.dst,
-                                                            pool.actions, pool.costs, st)))
-        return rc;
-    launch_random_select_pool_batch(h0, dev + at_select, pool, n, st);
+    if (mo) {
+        rssm::Problem pr[rssm::BATCH_MAX];
+        models_problems(*mo, n, rows.data(), pr);
+        if (int rc = rssm_launch_result(launch_rssm_split_models(n * mo->members, pr, c.horizon, c.act_dim, c.cost_mode, og.dst, pool.actions,
+                                                                 member_costs, st)))
+            return rc;
+        launch_random_select_members_batch(h0, dev + at_select, pool, RandomMembers{member_costs, mo->members, mo->reduce, n * N, (float)(1.0 / mo->members)},
+                                           n, st);
+    } else {
+        if (int rc = rssm_launch_result(launch_rssm_split_batch(n, rows.data(), c.horizon, c.act_dim, c.cost_mode, (const unsigned short*)params, og.dst,
+                                                                pool.actions, pool.costs, st)))
+            return rc;
+        launch_random_select_pool_batch(h0, dev + at_select, pool, n, st);
+    }
     ICEM_HIP_TRY(hipGetLastError());
     h0->random_batch_launches = 3;
     return ICEM_OK;
@@ -275,6 +303,38 @@ int icem_plan_step_random_learned_batch(icem_handle* const* handles, int32_t n, 
         return random_step_solo(handles[0], &buffers[0], change_freq, call_offsets_host[0], 0, nullptr, results, (hipStream_t)stream,
                                 &handles[0]->random_batch_launches, params);
     return random_learned_step_batch(handles, n, buffers, params, change_freq, call_offsets_host, results, (hipStream_t)stream);
+}
+
+// would a batch of n handles like `h` with `members` models per problem be served?
+int icem_plan_step_random_learned_models_ok(const icem_handle* h, int32_t n, int32_t members) {
+    if (!h || random_learned_unserved(h) || n < 1 || n > ICEM_MAX_BATCH || members < 1 || members > rssm::BATCH_MAX || n * members > rssm::BATCH_MAX)
+        return 0;
+    const long long tiles = (long long)n * members * ((h->cfg.num_traj + 15) / 16);
+    return tiles <= rssm::SPLIT_TILE_LIMIT && rssm_split_batch_ok((int)tiles, h->cfg.horizon) ? 1 : 0;
+}
+
+int icem_plan_step_random_learned_models(icem_handle* const* handles, int32_t n, const icem_random_buffers* buffers, int32_t members,
+                                         const void* const* params_host, int32_t reduce, int32_t change_freq, const int64_t* call_offsets_host,
+                                         void* member_costs, void* results, void* stream) {
+    // ---- refusals: all of them before anything is launched or any handle touched ----
+    const std::string who = "icem_plan_step_random_learned_models: ";
+    const std::string config_msg = who + "the handles must share one configuration (everything but the seed)";
+    // (what the counts and the table alone decide comes first: no handle has been looked at when n x members is refused)
+    if (int rc = models_args_refusal(who, handles && buffers && call_offsets_host, n, members, params_host, reduce)) return rc;
+    if (int rc = admit_batch(handles, n, true, true, who.c_str(), config_msg.c_str())) return rc;
+    if (int rc = admit_rssm_binding(handles, n, config_msg.c_str())) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = random_arg_refusal(buffers[i], change_freq, call_offsets_host[i], who)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = random_refusal(handles[i], change_freq, who, true)) return rc;
+    const icem_config& c = handles[0]->cfg;
+    const StepModels mo{members, reduce, params_host, (float*)member_costs};
+    const int tiles = models_tiles_uniform(mo, n, c.num_traj, c.horizon);
+    if (tiles < 0)
+        return fail(ICEM_E_UNSUPPORTED, who + "the tiles of the rollout (members x the sum over the problems of ceil(num_traj / 16)) exceed the "
+                                              "split launch's limit; nothing was launched");
+    if (int rc = rssm_launch_result(rssm_split_prepare(tiles, c.horizon, (hipStream_t)stream))) return rc;
+    return random_learned_step_batch(handles, n, buffers, nullptr, change_freq, call_offsets_host, results, (hipStream_t)stream, &mo);
 }
 
 int64_t icem_random_step_launches(const icem_handle* h) { return h ? (int64_t)h->random_launches : 0; }

@@ -18,7 +18,8 @@ struct PoolCosts {
     __device__ __forceinline__ float operator()(const UpdateSmallArgs& a, int i) const { return a.costs[i]; }
 };
 
-// ... or from the costs of an ensemble's members (update_small_members_batch_kernel; UpdateMembersArgs, icem_fused.h), reduced here
+// ... or from the costs of an ensemble's members (update_small_members_batch_kernel; UpdateMembersArgs, icem_fused.h -- and the two
+// baselines' cem_update_members_batch_kernel, k_cem_members.hip, and random_select_members_batch_kernel, random_dev.h), reduced here
 // as rssm_ensemble_reduce_kernel reduces them -- the same float32 operations in the same order, no atomics, no division, the
 // mean's one multiply a rounding of its own -- and written to costs[i] as well.  `members` is uniform across the workgroup: a
 // row's loads are all requested before the first is consumed (one round trip to memory, not one per member), in a group of
@@ -51,7 +52,9 @@ struct MemberCosts {
         }
         return acc;
     }
-    __device__ __forceinline__ float operator()(const UpdateSmallArgs&, int i) const {
+    // (Args: the argument block of the body that asks -- UpdateSmallArgs here, RandomSelectArgs<float> in random_dev.h; unused)
+    template <class Args>
+    __device__ __forceinline__ float operator()(const Args&, int i) const {
         const float r = members <= 8 ? reduced<8>((unsigned)i) : reduced<32>((unsigned)i);
         out[i] = r;
         return r;

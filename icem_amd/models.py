@@ -474,11 +474,12 @@ class DeviceRSSMEnsemble(ForwardModel):
     (``icem_rssm_rollout_cost_ensemble``) + the reduction; ``member_costs`` holds the last ``[E, n]`` (row e: member e alone,
     bit for bit).  ``params`` are the members' packed buffers stacked ``[E, elems]`` on one device -- the launch reads these.
 
-    It is deliberately NOT a ``DeviceRSSMModel``: the library's fused ``*_learned`` steps know one parameter buffer, and the
-    CEM and random-shooting baselines plan through an ensemble with their stage-wise loops.  ``MpcICemHip`` takes the whole
-    MPC step through it as one library call (``icem_plan_step_learned_models``: the members' reduction inside the update
-    launch) where that entry serves the planner, and leaves ``member_costs`` as the stage-wise loop does: the last
-    iteration's ``[E, rows]``.  ``predict`` -- the reference-style interface needs ONE successor state -- delegates to
+    It is deliberately NOT a ``DeviceRSSMModel``: the library's fused ``*_learned`` steps know one parameter buffer.
+    ``MpcICemHip`` takes the whole MPC step through it as one library call (``icem_plan_step_learned_models``: the members'
+    reduction inside the update launch) where that entry serves the planner, and so do the CEM and random-shooting baselines
+    (``icem_plan_step_cem_learned_models`` / ``icem_plan_step_random_learned_models``: the reduction inside the update /
+    the selection launch); all leave ``member_costs`` as the stage-wise loop does: the last iteration's ``[E, rows]`` (with
+    an ensemble per planner, each ensemble's is its planner's columns of the step's one table: a view).  ``predict`` -- the reference-style interface needs ONE successor state -- delegates to
     member 0."""
 
     obs_dim = 230

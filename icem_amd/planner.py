@@ -615,11 +615,81 @@ class IcemPlanner:
         return self.population_sizes[it] + (self.n_reuse if shift else 0)
 
     @staticmethod
+    def _ensembles_each(models):
+        """``models`` as the list of ``DeviceRSSMEnsemble`` it is where every planner plans through an ensemble of its own, else None."""
+        from .models import DeviceRSSMEnsemble
+        if isinstance(models, DeviceRSSMEnsemble):
+            return None
+        models = list(models)
+        return models if models and all(isinstance(m, DeviceRSSMEnsemble) for m in models) else None
+
+    @staticmethod
+    def _leave_member_costs(ens, models, member_costs, members: int, rows):
+        """What a step through ensembles leaves in their ``member_costs``, as their own ``rollout_cost`` calls would: the last
+        rollout's ``[members, rows of all planners]`` with a shared ensemble, planner p's columns of it (a view) with an
+        ensemble each."""
+        if member_costs is None:
+            return
+        total = sum(rows)
+        table = member_costs[:members * total].view(members, total)
+        if ens is not None:
+            ens.member_costs = table
+            return
+        row0 = 0
+        for m, r in zip(IcemPlanner._ensembles_each(models) or [], rows):
+            m.member_costs = table[:, row0:row0 + r]
+            row0 += r
+
+    @staticmethod
+    def _models_table(models, n: int, reduce, who: str):
+        """``models`` of a step through models of their own -> ``(ens, table, width_of, reduce)``: the shared
+        ``DeviceRSSMEnsemble`` or None, the parameter pointers ``[n][members]``, a model that stands for the action width, and
+        the reduction's name (None: the ensemble's own -- of the first where every planner has one --, else ``"mean"``)."""
+        from .models import DeviceRSSMEnsemble, DeviceRSSMModel
+        ens = models if isinstance(models, DeviceRSSMEnsemble) else None
+        if ens is not None:
+            table = [ens._param_ptrs()] * n
+            width_of = ens
+            reduce = ens.reduce if reduce is None else reduce
+        else:
+            models = list(models)
+            if models and all(isinstance(m, DeviceRSSMEnsemble) for m in models):   # an ensemble each: the launch reads its stacked params
+                if len(models) != n:
+                    raise ValueError(f"{n} planners but models for {len(models)}")
+                if len({m.reduce for m in models}) > 1 and reduce is None:
+                    raise ValueError("the planners' ensembles reduce differently: name one reduce for the step")
+                if len({m.members for m in models}) > 1:
+                    raise ValueError(f"every planner needs the same number (>= 1) of models, got {[m.members for m in models]}")
+                if len({m.act_dim for m in models}) > 1 or len({m.params.device for m in models}) > 1:
+                    raise ValueError("learned-dynamics models of one step need one action width on one device")
+                reduce = models[0].reduce if reduce is None else reduce
+                if reduce not in L.RSSM_REDUCE:
+                    raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+                return None, [m._param_ptrs() for m in models], models[0], reduce
+            per = [[m] if isinstance(m, DeviceRSSMModel) else list(m) for m in models]
+            if len(per) != n:
+                raise ValueError(f"{n} planners but models for {len(per)}")
+            if n and (len(per[0]) < 1 or any(len(ms) != len(per[0]) for ms in per)):
+                raise ValueError(f"every planner needs the same number (>= 1) of models, got {[len(ms) for ms in per]}")
+            flat = [m for ms in per for m in ms]
+            if not all(isinstance(m, DeviceRSSMModel) for m in flat):
+                raise ValueError(f"the models of {who} are DeviceRSSMModels (or one DeviceRSSMEnsemble)")
+            if len({m.act_dim for m in flat}) > 1 or len({m.params.device for m in flat}) > 1:
+                raise ValueError("learned-dynamics models of one step need one action width on one device")
+            table = [[m.params.data_ptr() for m in ms] for ms in per]
+            width_of = flat[0] if flat else None
+            reduce = "mean" if reduce is None else reduce
+        if reduce not in L.RSSM_REDUCE:
+            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        return ens, table, width_of, reduce
+
+    @staticmethod
     def plan_step_learned_models(planners: Sequence["IcemPlanner"], models, observations, reduce=None, member_costs=None) -> torch.Tensor:
         """One MPC step of every planner of ``planners`` (one configuration; seeds, episodes, step counts and observations of
         their own) as ``icem_plan_step_learned_models``: :meth:`plan_step_learned_batch` with the rollout of every problem
         through models of its own.  ``models``: a ``DeviceRSSMEnsemble`` every planner plans through; a list of
-        ``DeviceRSSMModel`` (one per planner); or a list of lists (every planner its own ensemble, all of one size).  A plan's
+        ``DeviceRSSMModel`` (one per planner); or a list of ``DeviceRSSMEnsemble`` / of lists (every planner its own ensemble, all
+        of one size; ensembles bring their stacked ``params`` and, unless ``reduce`` is given, their common reduction).  A plan's
         cost is the mean or the worst of its problem's members: ``reduce`` ``"mean"`` / ``"max"`` (None: the ensemble's own,
         else ``"mean"``).  Every stage is one launch for all problems and members, 3 per CEM iteration (+ 1 in a step that
         shifts elites).  Each planner's buffers afterwards are bit for bit those of its own step with its members.  Returns
@@ -629,30 +699,9 @@ class IcemPlanner:
         at least ``members * B * max rows`` elements) when one is given, and with a ``DeviceRSSMEnsemble`` in its
         ``member_costs`` as its ``rollout_cost_batch`` leaves them.  Raises ``IcemError`` before anything runs -- and before
         any planner has advanced -- where the batch is not served."""
-        from .models import DeviceRSSMEnsemble, DeviceRSSMModel
         pls = list(planners)
         n = len(pls)
-        ens = models if isinstance(models, DeviceRSSMEnsemble) else None
-        if ens is not None:
-            table = [ens._param_ptrs()] * n
-            width_of = ens
-            reduce = ens.reduce if reduce is None else reduce
-        else:
-            per = [[m] if isinstance(m, DeviceRSSMModel) else list(m) for m in models]
-            if len(per) != n:
-                raise ValueError(f"{n} planners but models for {len(per)}")
-            if n and (len(per[0]) < 1 or any(len(ms) != len(per[0]) for ms in per)):
-                raise ValueError(f"every planner needs the same number (>= 1) of models, got {[len(ms) for ms in per]}")
-            flat = [m for ms in per for m in ms]
-            if not all(isinstance(m, DeviceRSSMModel) for m in flat):
-                raise ValueError("the models of plan_step_learned_models are DeviceRSSMModels (or one DeviceRSSMEnsemble)")
-            if len({m.act_dim for m in flat}) > 1 or len({m.params.device for m in flat}) > 1:
-                raise ValueError("learned-dynamics models of one step need one action width on one device")
-            table = [[m.params.data_ptr() for m in ms] for ms in per]
-            width_of = flat[0] if flat else None
-            reduce = "mean" if reduce is None else reduce
-        if reduce not in L.RSSM_REDUCE:
-            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        ens, table, width_of, reduce = IcemPlanner._models_table(models, n, reduce, "plan_step_learned_models")
         if n == 0:   # (the entry's own refusal: n outside [1, 32])
             L.check(L.load_library().icem_plan_step_learned_models(None, 0, None, 1, None, 0, None, None, None, None))
         members = len(table[0])
@@ -661,13 +710,7 @@ class IcemPlanner:
         if obs.shape[1] != L.RSSM_OBS_DIM:
             raise ValueError(f"expected observations of shape ({n}, {L.RSSM_OBS_DIM})")
         need = members * n * max(p0.population_sizes[it] + (p0.n_reuse if it == 0 else 0) for it in range(len(p0.population_sizes)))
-        if ens is not None and member_costs is None:   # (kept with the ensemble: its address sits in the step's argument blocks)
-            member_costs = getattr(ens, "_step_member_costs", None)
-            if member_costs is None or member_costs.numel() < need or member_costs.device != p0.device:
-                member_costs = ens._step_member_costs = torch.empty((need,), dtype=torch.float32, device=p0.device)
-        if member_costs is not None and (member_costs.dtype != torch.float32 or not member_costs.is_contiguous()
-                                         or member_costs.numel() < need or member_costs.device != p0.device):
-            raise ValueError(f"member_costs must be a contiguous float32 tensor of at least {need} elements on the planners' device")
+        member_costs = IcemPlanner._models_member_costs(p0, ens, member_costs, need, models)
         # (the observations and the results of a batch size live with the first planner: the results' address sits in the argument blocks)
         kept = p0.__dict__.setdefault("_models_step_io", {})
         if n not in kept:
@@ -679,15 +722,14 @@ class IcemPlanner:
         bs = (L.IcemPlanBuffersC * n)(*[pl._learned_buffers(obs_dev[i].data_ptr()) for i, pl in enumerate(pls)])
         steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
         ptrs = (C.c_void_p * (n * members))(*[p for row in table for p in row])
-        last_rows = sum(pl._step_rows(len(pl.population_sizes) - 1) for pl in pls)
+        last_rows = [pl._step_rows(len(pl.population_sizes) - 1) for pl in pls]
         for pl in pls:
             pl._bind_rssm(width_of)
         L.check(p0.lib.icem_plan_step_learned_models(hs, n, bs, members, ptrs, L.RSSM_REDUCE[reduce], steps,
                                                      None if member_costs is None else _ptr(member_costs), _ptr(results), p0._stream()))
         for pl in pls:
             pl.mpc_step += 1
-        if ens is not None:
-            ens.member_costs = member_costs[:members * last_rows].view(members, last_rows)
+        IcemPlanner._leave_member_costs(ens, models, member_costs, members, last_rows)
         return results
 
     # ------------------------------------------------------------------ the CEM baseline's step (MpcCemStd)
@@ -972,22 +1014,10 @@ class IcemPlanner:
         return self._cem_buffers()["result"][:self.d]
 
     @staticmethod
-    def plan_step_cem_learned_batch(planners: Sequence["IcemPlanner"], model, observations, dists, *, like_levine: bool,
-                                    shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
-        """:meth:`plan_step_cem_learned` of every planner of ``planners`` (one configuration; seeds, episodes, step counts
-        and observations of their own) through the one ``model`` as ``icem_plan_step_cem_learned_batch``: every iteration 3
-        launches for all of them.  ``observations``: ``[B, 230]`` array-like -- one host-to-device copy for the batch -- or
-        an f32 device tensor, used where it lies.  ``dists[i]``: planner i's ``(mean, std, lower, upper)``, updated in
-        place.  Each planner's ``cem_elites`` / ``cem_elite_costs`` / ``cem_elite_idx`` / ``cem_result`` afterwards are bit
-        for bit those of its own :meth:`plan_step_cem_learned`; its ``cem_actions`` / ``cem_costs`` are scratch for B > 1
-        (the batch scores its rows in a pool of the first planner's handle).  Returns the executed actions ``[B, d]``, a
-        view of ``planners[0].cem_batch_results`` ``[B, d + 1]`` (kept per batch size).  Raises ``IcemError`` before anything
-        runs, and before any planner has advanced, where the batch is not served."""
-        pls = list(planners)
-        n = len(pls)
-        if n == 0:   # (the entry's own refusal: n outside [1, 32])
-            L.check(L.load_library().icem_plan_step_cem_learned_batch(None, 0, None, None, None, None, None, None))
-        p0 = pls[0]
+    def _cem_learned_batch_io(pls, observations, dists, like_levine, shift_means, execute_best_elite):
+        """What a batched learned-dynamics CEM step hands the library: the handles, every planner's ``icem_cem_buffers`` (the
+        observations in ONE table kept with the first planner), the step counts, the results tensor and the flags."""
+        p0, n = pls[0], len(pls)
         dists = list(dists)
         if len(dists) != n:
             raise ValueError("one (mean, std, lower, upper) per planner")
@@ -1013,6 +1043,124 @@ class IcemPlanner:
         if res is None or res.shape[0] != n:
             res = p0._cem_batch_results = torch.zeros((n, p0.d + 1), dtype=p0.dt, device=p0.device)
         prm = L.IcemCemParamsC(int(bool(like_levine)), int(bool(shift_means)), int(bool(execute_best_elite)), 0)
+        return hs, bs, steps, res, prm
+
+    # ------------------------------------------------------------------ ... through ensembles and a model per planner
+    def cem_learned_models_step_ok(self, n: int = 1, members: int = 1) -> bool:
+        """Does ``icem_plan_step_cem_learned_models`` serve a batch of ``n`` handles like THIS one through ``members`` models per
+        problem?  (:meth:`cem_learned_step_ok`'s conditions of the handle as it is bound, ``n * members <= 32``, the tiles of
+        such a rollout within the launch's limit.)"""
+        return bool(self.lib.icem_plan_step_cem_learned_models_ok(self._h, int(n), int(members)))
+
+    def random_learned_models_step_ok(self, n: int = 1, members: int = 1) -> bool:
+        """Does ``icem_plan_step_random_learned_models`` serve a batch of ``n`` handles like THIS one through ``members`` models
+        per problem?  (:meth:`random_learned_step_ok`'s conditions, ``n * members <= 32``, the rollout's tiles.)"""
+        return bool(self.lib.icem_plan_step_random_learned_models_ok(self._h, int(n), int(members)))
+
+    @staticmethod
+    def _models_member_costs(p0, ens, member_costs, need: int, models=None):
+        """The ``member_costs`` tensor of a step through models of their own: the caller's (checked), the one kept with a
+        shared ensemble -- or, where every planner has an ensemble of its own, with the first of them -- (its address sits in
+        the step's argument blocks), or None (the library's scratch: plain models keep no member costs)."""
+        if ens is None and models is not None:
+            each = IcemPlanner._ensembles_each(models)
+            ens = each[0] if each else None
+        if ens is not None and member_costs is None:
+            member_costs = getattr(ens, "_step_member_costs", None)
+            if member_costs is None or member_costs.numel() < need or member_costs.device != p0.device:
+                member_costs = ens._step_member_costs = torch.empty((need,), dtype=torch.float32, device=p0.device)
+        if member_costs is not None and (member_costs.dtype != torch.float32 or not member_costs.is_contiguous()
+                                         or member_costs.numel() < need or member_costs.device != p0.device):
+            raise ValueError(f"member_costs must be a contiguous float32 tensor of at least {need} elements on the planners' device")
+        return member_costs
+
+    @staticmethod
+    def plan_step_cem_learned_models(planners: Sequence["IcemPlanner"], models, observations, dists, *, like_levine: bool,
+                                     shift_means: bool, execute_best_elite: bool, reduce=None, member_costs=None) -> torch.Tensor:
+        """:meth:`plan_step_cem_learned_batch` with the rollout of every problem through models of its own, as
+        ``icem_plan_step_cem_learned_models``: the planner PETS and PlaNet use, through an ensemble.  ``models``, ``reduce`` and
+        ``member_costs`` as :meth:`plan_step_learned_models` takes them (a ``DeviceRSSMEnsemble`` for all planners, a list of
+        ``DeviceRSSMModel`` -- one each --, or a list of ``DeviceRSSMEnsemble`` / of lists -- an ensemble each, all of one size);
+        ``member_costs`` needs ``members * B * num_traj`` elements and holds the last iteration's ``[members, B * num_traj]``.
+        3 launches per CEM iteration whatever B and the member count (:attr:`cem_batch_launches` of the first planner); every
+        planner's ``mean`` / ``std`` / ``lower`` / ``upper``, ``cem_elites`` / ``cem_elite_costs`` / ``cem_elite_idx`` and its
+        row of the results are bit for bit the operator loop's through its members; with one planner ``cem_actions`` /
+        ``cem_costs`` hold the last pool as well, with more they are scratch.  Returns the executed actions ``[B, d]``, a view
+        of ``planners[0].cem_batch_results`` ``[B, d + 1]``.  Raises ``IcemError`` before anything runs, and before any planner
+        has advanced, where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        ens, table, width_of, reduce = IcemPlanner._models_table(models, n, reduce, "plan_step_cem_learned_models")
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_cem_learned_models(None, 0, None, None, 1, None, 0, None, None, None, None))
+        members = len(table[0])
+        p0 = pls[0]
+        member_costs = IcemPlanner._models_member_costs(p0, ens, member_costs, members * n * p0.cfg.num_traj, models)
+        hs, bs, steps, res, prm = IcemPlanner._cem_learned_batch_io(pls, observations, dists, like_levine, shift_means, execute_best_elite)
+        ptrs = (C.c_void_p * (n * members))(*[p for row in table for p in row])
+        for pl in pls:
+            pl._bind_rssm(width_of)
+        L.check(p0.lib.icem_plan_step_cem_learned_models(hs, n, bs, C.byref(prm), members, ptrs, L.RSSM_REDUCE[reduce], steps,
+                                                         None if member_costs is None else _ptr(member_costs), _ptr(res), p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        IcemPlanner._leave_member_costs(ens, models, member_costs, members, [p0.cfg.num_traj] * n)
+        return res[:, :p0.d]
+
+    @staticmethod
+    def plan_step_random_learned_models(planners: Sequence["IcemPlanner"], models, observations, call_offsets, change_freq: int,
+                                        reduce=None, member_costs=None) -> torch.Tensor:
+        """:meth:`plan_step_random_learned_batch` with the rollout of every problem through models of its own, as
+        ``icem_plan_step_random_learned_models``: random shooting through an ensemble (PETS), or with a trained model per
+        planner.  ``models``, ``reduce`` and ``member_costs`` as :meth:`plan_step_cem_learned_models` takes them.  3 launches
+        whatever B and the member count (:attr:`random_batch_launches` of the first planner); every planner's ``random_*``
+        views -- its pool and the reduced costs included -- are bit for bit the operator chain's through its members.  Returns
+        the executed actions ``[B, d]``, a view of ``planners[0].random_batch_results`` ``[B, d + 2]``.  Raises ``IcemError``
+        before anything runs where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        ens, table, width_of, reduce = IcemPlanner._models_table(models, n, reduce, "plan_step_random_learned_models")
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_random_learned_models(None, 0, None, 1, None, 0, 0, None, None, None, None))
+        members = len(table[0])
+        p0 = pls[0]
+        observations, call_offsets = list(observations), list(call_offsets)
+        if len(observations) != n or len(call_offsets) != n:
+            raise ValueError("one observation and one call offset per planner")
+        member_costs = IcemPlanner._models_member_costs(p0, ens, member_costs, members * n * p0.cfg.num_traj, models)
+        cbs = [pl._random_cb(ob, "obs_rssm") for pl, ob in zip(pls, observations)]
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemRandomBuffersC * n)(*cbs)
+        offs = (C.c_int64 * n)(*[int(o) for o in call_offsets])
+        res = getattr(p0, "_random_batch_results", None)   # (kept per batch size: a captured step replays into the same tensor)
+        if res is None or res.shape[0] != n:
+            res = p0._random_batch_results = torch.zeros((n, p0.d + 2), dtype=p0.dt, device=p0.device)
+        ptrs = (C.c_void_p * (n * members))(*[p for row in table for p in row])
+        for pl in pls:
+            pl._bind_rssm(width_of)
+        L.check(p0.lib.icem_plan_step_random_learned_models(hs, n, bs, members, ptrs, L.RSSM_REDUCE[reduce], int(change_freq), offs,
+                                                            None if member_costs is None else _ptr(member_costs), _ptr(res), p0._stream()))
+        IcemPlanner._leave_member_costs(ens, models, member_costs, members, [p0.cfg.num_traj] * n)
+        return res[:, :p0.d]
+
+    @staticmethod
+    def plan_step_cem_learned_batch(planners: Sequence["IcemPlanner"], model, observations, dists, *, like_levine: bool,
+                                    shift_means: bool, execute_best_elite: bool) -> torch.Tensor:
+        """:meth:`plan_step_cem_learned` of every planner of ``planners`` (one configuration; seeds, episodes, step counts
+        and observations of their own) through the one ``model`` as ``icem_plan_step_cem_learned_batch``: every iteration 3
+        launches for all of them.  ``observations``: ``[B, 230]`` array-like -- one host-to-device copy for the batch -- or
+        an f32 device tensor, used where it lies.  ``dists[i]``: planner i's ``(mean, std, lower, upper)``, updated in
+        place.  Each planner's ``cem_elites`` / ``cem_elite_costs`` / ``cem_elite_idx`` / ``cem_result`` afterwards are bit
+        for bit those of its own :meth:`plan_step_cem_learned`; its ``cem_actions`` / ``cem_costs`` are scratch for B > 1
+        (the batch scores its rows in a pool of the first planner's handle).  Returns the executed actions ``[B, d]``, a
+        view of ``planners[0].cem_batch_results`` ``[B, d + 1]`` (kept per batch size).  Raises ``IcemError`` before anything
+        runs, and before any planner has advanced, where the batch is not served."""
+        pls = list(planners)
+        n = len(pls)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_cem_learned_batch(None, 0, None, None, None, None, None, None))
+        p0 = pls[0]
+        hs, bs, steps, res, prm = IcemPlanner._cem_learned_batch_io(pls, observations, dists, like_levine, shift_means, execute_best_elite)
         for pl in pls:
             pl._bind_rssm(model)
         L.check(p0.lib.icem_plan_step_cem_learned_batch(hs, n, bs, C.byref(prm), C.c_void_p(model.params.data_ptr()), steps, _ptr(res),

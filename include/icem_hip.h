@@ -710,6 +710,44 @@ int icem_plan_step_learned_models(icem_handle* const* handles, int32_t n, const 
                                   const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host, void* member_costs,
                                   void* results, void* stream);
 
+/* The two baselines' MPC steps through MODELS OF THEIR OWN -- the planners the ensemble literature uses (PETS: CEM or random
+ * shooting through a probabilistic ensemble; PlaNet's planner is this CEM): icem_plan_step_cem_learned_batch and
+ * icem_plan_step_random_learned_batch with params_host, members, reduce and member_costs as icem_plan_step_learned_models takes
+ * them (a shared ensemble, a model each with members == 1, an ensemble each; member_costs NULL or at least members * n * num_traj
+ * floats, afterwards the LAST rollout's [members, rows of all problems]).
+ *   Semantics: those of the *_learned_batch entry -- stream offsets, call_offsets, the results rows ([n, d + 1] / [n, d + 2]), the
+ * argument array of handles[0] uploaded only when a byte changed, free alternation with the other entries on one handle -- with
+ * two differences.  The rollout is ONE launch of n * members problems in member-major order (icem_plan_step_learned_models'
+ * arrangement: member e's cost of problem p's row i at member_costs[e * n * num_traj + p * num_traj + i]).  And the launch behind
+ * it reduces the members' costs itself, in icem_rssm_ensemble_reduce's arithmetic operation for operation (a NaN member makes the
+ * row NaN), and writes the reduced cost where the single-model step leaves its costs: the CEM step's update
+ * (cem_update_members_batch_kernel) while it builds its keys, the random-shooting step's selection
+ * (random_select_members_batch_kernel) while it looks for the smallest (cost, index) pair with NaN counted as +inf.  So 3 launches
+ * per CEM iteration (icem_cem_batch_launches of handles[0]) and 3 launches per random-shooting step (icem_random_batch_launches of
+ * handles[0]) whatever n and members, no host synchronisation, no allocation after the first call of a size on a stream.
+ * n == 1 works in the problem's own actions / costs, n > 1 in the pool of handles[0].
+ *   CEM: every problem's mean, std, lower, upper, elites, elite_costs, elite_idx, executed, best_cost and its results row are bit
+ * for bit the operator loop's (icem_sample_truncnorm, icem_rssm_rollout_cost_ensemble / _models, icem_update_distribution,
+ * icem_cem_bounds); for n == 1 the last pool in actions / costs too, for n > 1 a problem's own pool is scratch.  Random shooting:
+ * EVERY buffer of every problem (actions, costs, best_actions, result, its results row) is bit for bit the chain's
+ * (icem_sample_piecewise, icem_rssm_rollout_cost_ensemble / _models, icem_topk_sorted(costs, 1), the gathers).  Both: members == 1
+ * with equal pointers gives the *_learned_batch entry's bits, with n == 1 the solo entry's.
+ *   ICEM_E_INVALID: a NULL argument or a NULL entry of params_host, n or members outside [1, 32], a bad reduce, a handle twice,
+ * unequal configurations or RSSM widths, and what the *_learned entries call invalid (a negative step or offset, change_freq < 0
+ * or >= horizon, a NULL buffer).  ICEM_E_UNSUPPORTED: n * members > 32; the tiles of a rollout (members x the sum over the
+ * problems of ceil(num_traj / 16)) beyond the split launch's limit; whatever icem_plan_step_cem_learned_ok /
+ * icem_plan_step_random_learned_ok does not serve (options cem_step / random_step / rssm_split = 0 among it).  ICEM_E_STATE: the
+ * learned-dynamics rollout's staging and status-word rules, looked at before the first launch.  All of it before anything is
+ * launched or any handle touched.  *_models_ok: would n handles like this one be served with `members` models each? */
+int icem_plan_step_cem_learned_models_ok(const icem_handle* h, int32_t n, int32_t members);
+int icem_plan_step_cem_learned_models(icem_handle* const* handles, int32_t n, const icem_cem_buffers* buffers, const icem_cem_params* p,
+                                      int32_t members, const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host,
+                                      void* member_costs, void* results, void* stream);
+int icem_plan_step_random_learned_models_ok(const icem_handle* h, int32_t n, int32_t members);
+int icem_plan_step_random_learned_models(icem_handle* const* handles, int32_t n, const icem_random_buffers* buffers, int32_t members,
+                                         const void* const* params_host, int32_t reduce, int32_t change_freq,
+                                         const int64_t* call_offsets_host, void* member_costs, void* results, void* stream);
+
 /* Wide observations (32 < obs_dim <= 384; HumanoidStandup's o = 378, environments/mujoco.py:241-277): which matrix-pipe
  * arithmetic the rollout's model step (the GEMM of abstract_models.py:31-53's predict at this width) runs in.  The modes
  * are NAMES, not an accuracy order:

@@ -27,6 +27,14 @@ with min and max over BLOCKS blocks.
                                                solo fused steps.  The solo leg also prints the device time per launch of the three
                                                stages (sampler, rollout, update + bounds: each operator launched back to back between
                                                two events).  --stagewise runs on the parent commit's library as above.
+  python tools/cem_step_bench.py --models [--cases 1x2,1x5,4x1,4x5] [--stagewise]
+                                               the learned shape through MODELS OF THEIR OWN (``icem_plan_step_cem_learned_models``): B
+                                               controllers x E members -- E > 1: one ``DeviceRSSMEnsemble`` of E seeds for all of them,
+                                               E = 1: a ``DeviceRSSMModel`` each (``get_action_batch_own_models``) -- ``fused_step=True`` against
+                                               ``fused_step=False`` (each controller's stage-wise loop: sampler, ensemble rollout +
+                                               reduction, update, bounds), ``get_action`` for B = 1 and ``get_action_batch`` beyond,
+                                               alternating blocks in one process.  --stagewise: the loop alone (also on the parent
+                                               commit's library).
 """
 import ctypes as C
 import os
@@ -40,7 +48,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from icem_amd import _lib as L  # noqa: E402
 
 H, D, O_, ITERS, SIZES = 30, 6, 17, 5, (512, 4096)
-LEARNED = "--learned" in sys.argv
+MODELS = "--models" in sys.argv
+LEARNED = "--learned" in sys.argv or MODELS
 if LEARNED:   # BASELINE configs[4]'s population on the CEM baseline; the RSSM's observation is [h (200) | z (30)]
     H, O_, SIZES = 12, 230, (1024,)
 WARMUP, BLOCK, BLOCKS, TRACE_STEPS = 20, 200, 9, 50
@@ -62,11 +71,12 @@ def rssm():
     return _rssm[0]
 
 
-def controller(n, fused):
+def controller(n, fused, model=None, seed=1):
     from icem_amd import DeviceSyntheticModel, MpcCemStdHip, halfcheetah_env
-    model = rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0)
+    if model is None:
+        model = rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0)
     c = MpcCemStdHip(env=halfcheetah_env(17 if LEARNED else O_), forward_model=model, horizon=H,
-                     num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=1,
+                     num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=seed,
                      **({"fused_step": fused} if fused is not None else {}),
                      action_sampler_params=dict(alpha=0.1, elites_size=10, opt_iterations=ITERS, init_std=0.5, shift_means=True,
                                                 execute_best_elite=True, bounds_like_levine=False))
@@ -243,10 +253,65 @@ def main():
             stage_times(n)
 
 
+MODELS_BLOCK, MODELS_BLOCKS = 100, 9
+
+
+def main_models():
+    from icem_amd import DeviceRSSMEnsemble, DeviceRSSMModel, MpcCemStdHip
+    stagewise_only = "--stagewise" in sys.argv
+    if stagewise_only:
+        bind_what_the_library_has()
+    lib = L.load_library()
+    n = SIZES[0]
+    cases = [tuple(int(x) for x in c.split("x")) for c in _arg("--cases", "1x2,1x5,4x1,4x5").split(",")]
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  N = {n}, h = {H}, d = {D}, K = 10, {ITERS} iterations, "
+          f"f32, models of their own; warm-up {WARMUP} steps; {MODELS_BLOCKS} blocks of {MODELS_BLOCK} steps per variant, alternating", flush=True)
+    for B, E in cases:
+        def group(fused):
+            if E == 1:
+                models = [DeviceRSSMModel(seed=3 + i) for i in range(B)]
+            else:
+                models = [DeviceRSSMEnsemble(seeds=list(range(3, 3 + E)))] * B
+            return [controller(n, fused, model=m, seed=1 + i) for i, m in enumerate(models)]
+        groups = {"stage-wise": group(False)}
+        if not stagewise_only:
+            groups = {"fused": group(True), **groups}
+        obs = [0.1 * np.random.RandomState(i).randn(O_) for i in range(B)]
+
+        def step(cs):   # (every step ends in its device-to-host copy of the result)
+            return [cs[0].get_action(obs[0], None)] if B == 1 else (MpcCemStdHip.get_action_batch_own_models if E == 1 else MpcCemStdHip.get_action_batch)(cs, obs)
+
+        def block(cs, reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                step(cs)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / reps * 1e3
+        for cs in groups.values():
+            block(cs, WARMUP)
+        extra = ""
+        if not stagewise_only:   # the same seeds, the same steps so far: the two groups agree bit for bit
+            got, want = step(groups["fused"]), step(groups["stage-wise"])
+            same = all(np.array_equal(a, b) for a, b in zip(got, want)) and all(np.array_equal(a.mean, b.mean) for a, b in zip(*groups.values()))
+            extra = f" | equal bits: {same}; launches per fused step {groups['fused'][0].planner.cem_batch_launches}"
+        t = {k: [] for k in groups}
+        for _ in range(MODELS_BLOCKS):
+            for k, cs in groups.items():
+                t[k].append(block(cs, MODELS_BLOCK))
+        line = " | ".join(f"{k} median {sorted(v)[len(v) // 2]:7.4f} ms per step (min {min(v):.4f}, max {max(v):.4f})" for k, v in t.items())
+        if not stagewise_only:
+            f, s_ = (sorted(t[k])[MODELS_BLOCKS // 2] for k in ("fused", "stage-wise"))
+            extra = f" | stage-wise / fused {s_ / f:.2f}x | fused median < stage-wise min: {f < min(t['stage-wise'])}" + extra
+        print(f"  B = {B} E = {E}: {line}{extra}", flush=True)
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures and has nothing to say without one")
-    if "--batch" in sys.argv:
+    if MODELS:
+        main_models()
+    elif "--batch" in sys.argv:
         main_batch()
     else:
         main()

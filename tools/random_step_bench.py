@@ -28,6 +28,13 @@ BLOCKS blocks.
                                                  the chain's sampler, rollout and selection one by one, the solo fused step as a
                                                  whole, and per B the batched step as a whole and its batched rollout alone (the
                                                  difference is the batch's sampler + selection)
+  python tools/random_step_bench.py --models [--cases 1x2,1x5,4x1,4x5] [--stagewise]
+                                                 the learned shape through MODELS OF THEIR OWN (``icem_plan_step_random_learned_models``):
+                                                 B controllers x E members -- E > 1: one ``DeviceRSSMEnsemble`` of E seeds for all of
+                                                 them, E = 1: a ``DeviceRSSMModel`` each (``get_action_batch_own_models``) -- ``fused_step=True``
+                                                 against ``fused_step=False`` (each controller's operator chain), ``get_action`` for
+                                                 B = 1 and ``get_action_batch`` beyond, alternating blocks in one process.
+                                                 --stagewise: the chain alone (also on the parent commit's library).
 """
 import ctypes as C
 import os
@@ -43,7 +50,8 @@ from icem_amd import _lib as L  # noqa: E402
 H, D, O_, FREQ, SIZES = 30, 6, 17, 4, (512, 4096)
 WARMUP, BLOCK, BLOCKS, TRACE_STEPS = 20, 200, 9, 50
 BATCH_BLOCK, BATCH_BLOCKS, BATCH_WARMUP = 30, 7, 10
-LEARNED = "--learned" in sys.argv
+MODELS = "--models" in sys.argv
+LEARNED = "--learned" in sys.argv or MODELS
 if LEARNED:   # the declared RSSM's shape (BASELINE configs[4])
     H, O_, SIZES = 12, 230, (1024,)
 EVENT_REPS, EVENT_BLOCKS = 50, 5
@@ -63,10 +71,12 @@ def bind_what_the_library_has():
     L.SYMBOLS[:] = [s for s in L.SYMBOLS if hasattr(have, s[0])]
 
 
-def controller(n, fused):
+def controller(n, fused, model=None, seed=1):
     from icem_amd import DeviceSyntheticModel, MpcRandomHip, halfcheetah_env
-    c = MpcRandomHip(env=halfcheetah_env(17 if LEARNED else O_), forward_model=rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0), horizon=H,
-                     num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=1, fused_step=fused,
+    if model is None:
+        model = rssm() if LEARNED else DeviceSyntheticModel.make(O_, D, kind=0)
+    c = MpcRandomHip(env=halfcheetah_env(17 if LEARNED else O_), forward_model=model, horizon=H,
+                     num_simulated_trajectories=n, cost_along_trajectory="sum", verbose=False, dtype="f32", seed=seed, fused_step=fused,
                      action_sampler_params=dict(action_change_frequency=FREQ))
     c.beginning_of_rollout(observation=np.zeros(O_), state=None, mode="train")
     return c
@@ -244,10 +254,66 @@ def main():
             print(f"  chain / fused at N = {n}: {s / f:.2f}x", flush=True)
 
 
+MODELS_BLOCK, MODELS_BLOCKS = 200, 9
+
+
+def main_models():
+    from icem_amd import DeviceRSSMEnsemble, DeviceRSSMModel, MpcRandomHip
+    stagewise_only = "--stagewise" in sys.argv
+    if stagewise_only:
+        bind_what_the_library_has()
+    lib = L.load_library()
+    n = SIZES[0]
+    cases = [tuple(int(x) for x in c.split("x")) for c in _arg("--cases", "1x2,1x5,4x1,4x5").split(",")]
+    print(f"build {lib.icem_build_hash().decode()}  device {torch.cuda.get_device_name(0)}  N = {n}, h = {H}, d = {D}, hold {FREQ}, f32, "
+          f"models of their own; warm-up {WARMUP} steps; {MODELS_BLOCKS} blocks of {MODELS_BLOCK} steps per variant, alternating", flush=True)
+    for B, E in cases:
+        def group(fused):
+            if E == 1:
+                models = [DeviceRSSMModel(seed=3 + i) for i in range(B)]
+            else:
+                models = [DeviceRSSMEnsemble(seeds=list(range(3, 3 + E)))] * B
+            return [controller(n, fused, model=m, seed=1 + i) for i, m in enumerate(models)]
+        groups = {"chain": group(False)}
+        if not stagewise_only:
+            groups = {"fused": group(True), **groups}
+        obs = [0.1 * np.random.RandomState(i).randn(O_) for i in range(B)]
+
+        def step(cs):   # (every step ends in its device-to-host copy of the result)
+            return [cs[0].get_action(obs[0], None)] if B == 1 else (MpcRandomHip.get_action_batch_own_models if E == 1 else MpcRandomHip.get_action_batch)(cs, obs)
+
+        def block(cs, reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                step(cs)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / reps * 1e3
+        for cs in groups.values():
+            block(cs, WARMUP)
+        extra = ""
+        if not stagewise_only:   # the same seeds, the same steps so far: the two groups agree bit for bit
+            got, want = step(groups["fused"]), step(groups["chain"])
+            same = all(np.array_equal(a, b) for a, b in zip(got, want)) and all(
+                a.best_traj_idx == b.best_traj_idx and torch.equal(a._last_costs, b._last_costs) for a, b in zip(*groups.values()))
+            extra = f" | equal bits: {same}; launches per fused step {groups['fused'][0].planner.random_batch_launches}"
+        t = {k: [] for k in groups}
+        for _ in range(MODELS_BLOCKS):
+            for k, cs in groups.items():
+                t[k].append(block(cs, MODELS_BLOCK))
+        line = " | ".join(f"{k} median {sorted(v)[len(v) // 2]:7.4f} ms per step (min {min(v):.4f}, max {max(v):.4f})" for k, v in t.items())
+        if not stagewise_only:
+            f, s_ = (sorted(t[k])[MODELS_BLOCKS // 2] for k in ("fused", "chain"))
+            extra = f" | chain / fused {s_ / f:.2f}x | fused median < chain min: {f < min(t['chain'])}" + extra
+        print(f"  B = {B} E = {E}: {line}{extra}", flush=True)
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures and has nothing to say without one")
-    if LEARNED and "--events" in sys.argv:
+    if MODELS:
+        main_models()
+    elif LEARNED and "--events" in sys.argv:
         main_events()
     elif "--batch" in sys.argv:
         main_batch()
