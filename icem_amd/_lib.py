@@ -94,6 +94,26 @@ class IcemRssmProblemC(C.Structure):
 
 RSSM_REDUCE = {"mean": 0, "max": 1}   # include/icem_hip.h: ICEM_RSSM_REDUCE_*
 RSSM_BATCH_MAX = 32                   # problems / members of one learned-dynamics launch
+MLP_ACTIVATIONS = {"relu": 0, "swish": 1}   # include/icem_hip.h: ICEM_MLP_RELU / ICEM_MLP_SWISH
+MLP_MAX_OBS_DIM, MLP_MAX_ACT_DIM, MLP_MAX_LAYERS, MLP_HIDDEN = 64, 32, 4, 200
+
+
+def cost_spec_structs(spec):
+    """``(IcemCostSpecC, IcemCostTermsC or None)`` of an ``envs.CostSpec``: what ``icem_set_cost`` + ``icem_set_cost_terms``
+    take from a handle's planner, for the entries that take the pair itself (``icem_mlp_rollout_cost``)."""
+    c = IcemCostSpecC(spec.ctrl_weight, spec.lin_weight, spec.flip_penalty, spec.flip_thresh, spec.lin_idx, spec.flip_idx)
+    if not getattr(spec, "extended", False):
+        return c, None
+    if len(spec.terms) > MAX_COST_TERMS:
+        raise ValueError(f"at most {MAX_COST_TERMS} cost terms")
+    t = IcemCostTermsC(diff_weight=spec.diff_weight, health_penalty=spec.health_penalty, health_lo=spec.health_lo,
+                       health_hi=spec.health_hi, box_lo=spec.box_lo, box_hi=spec.box_hi, diff_idx=spec.diff_idx,
+                       health_idx=spec.health_idx, health_closed=int(spec.health_closed), box_from=spec.box_from,
+                       n_terms=len(spec.terms))
+    for j, tm in enumerate(spec.terms):
+        t.terms[j] = IcemCostTermC(weight=tm.weight, thresh=tm.thresh, gate_thresh=tm.gate_thresh, kind=tm.kind,
+                                   a=tm.a, b=tm.b, len=tm.len, gate_idx=tm.gate_idx)
+    return c, t
 
 # every symbol include/icem_hip.h declares: (name, restype, argtypes)
 _VP, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
@@ -117,6 +137,9 @@ SYMBOLS = [
     ("icem_rssm_rollout_cost_models", C.c_int, [_I32, C.POINTER(IcemRssmProblemC), _I32, _I32, _I32, _VP, _I32, _VP, _I64, _VP, _VP]),
     ("icem_rssm_ensemble_reduce", C.c_int, [_I32, _I64, _I32, _VP, _VP, _VP]),
     ("icem_rssm_rollout_cost_ensemble", C.c_int, [_I32, C.POINTER(_VP), _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_mlp_param_elems", _SZ, [_I32, _I32, _I32]),
+    ("icem_mlp_rollout_cost", C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(IcemCostSpecC), C.POINTER(IcemCostTermsC),
+                                        _VP, _VP, _VP, _VP, _VP, _VP]),
     ("icem_set_rssm_act_dim", C.c_int, [_VP, _I32]),
     ("icem_rssm_act_dim", _I32, [_VP]),
     ("icem_get_action", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),

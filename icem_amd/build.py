@@ -19,7 +19,7 @@ UNITS = ["generic_kernels.hip", "plan.hip", "abi.hip", "exchange.hip", "k_sample
          "k_iter_small.hip", "icem_rssm.hip", "icem_rssm_split.hip", "k_rollout_wide.hip", "collective.hip", "k_rollout_ahead.hip",
          "k_rollout_wide_split.hip", "k_rollout_hn.hip", "learned_step.hip", "k_generic_batch.hip", "k_rollout_wide_batch.hip",
          "k_rollout_wide_split_batch.hip", "k_rollout_f64.hip", "cem_step.hip", "k_cem.hip", "k_cem_members.hip",
-         "random_step.hip", "k_random.hip", "k_random_learned.hip", "k_random_members.hip"]
+         "random_step.hip", "k_random.hip", "k_random_learned.hip", "k_random_members.hip", "k_mlp_rollout.hip"]
 OUT = os.path.join(HERE, "libicem_hip.so")
 # the same objects with exchange.hip compiled under -DICEM_FAULT_INJECTION (ICEM_XCHG_FAIL drills: tests/test_gpu_exchange_faults.py
 # loads it through ICEM_HIP_LIB); the product library carries no fault injection

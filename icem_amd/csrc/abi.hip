@@ -4,6 +4,7 @@
 #include "host_common.h"
 #include "cost_terms_dev.h"
 #include "icem_rssm.h"
+#include "icem_mlp.h"
 
 using namespace icem;
 
@@ -930,6 +931,45 @@ int icem_rssm_rollout_cost_w(int32_t n, int32_t horizon, int32_t act_dim, int32_
 int icem_rssm_rollout_cost(int32_t n, int32_t horizon, int32_t cost_mode, const void* params, const void* obs0,
                            const void* actions, void* costs, void* stream) {
     return icem_rssm_rollout_cost_w(n, horizon, rssm::ACT, cost_mode, params, obs0, actions, costs, stream);
+}
+
+// ---- the feed-forward learned dynamics (icem_mlp.h, k_mlp_rollout.hip): stateless, nothing allocated ----
+static_assert(mlp::RELU == ICEM_MLP_RELU && mlp::SWISH == ICEM_MLP_SWISH, "the kernel's activation codes are the header's");
+static_assert(mlp::OBS_MAX == ICEM_MLP_MAX_OBS_DIM && mlp::ACT_MAX == ICEM_MLP_MAX_ACT_DIM && mlp::LAYERS_MAX == ICEM_MLP_MAX_LAYERS,
+              "the kernel's ranges are the header's");
+
+size_t icem_mlp_param_elems(int32_t obs_dim, int32_t act_dim, int32_t layers) { return mlp::param_units(obs_dim, act_dim, layers); }
+
+int icem_mlp_rollout_cost(int32_t n, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
+                          int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const void* params,
+                          const void* obs0, const void* actions, void* costs, void* observations, void* stream) {
+    if (!cost || !params || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: null pointer");
+    if (n < 0) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: n must be >= 0");
+    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: bad cost_mode");
+    if (activation != ICEM_MLP_RELU && activation != ICEM_MLP_SWISH)
+        return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
+    if (obs_dim < 1 || obs_dim > mlp::OBS_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: obs_dim must be in [1, 64]");
+    if (act_dim < 1 || act_dim > mlp::ACT_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: act_dim must be in [1, 32]");
+    if (layers < 1 || layers > mlp::LAYERS_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: layers must be in [1, 4]");
+    if (horizon < 1 || horizon > ICEM_MAX_HORIZON) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: horizon must be in [1, 64]");
+    if (terms != nullptr) {   // icem_set_cost_terms' rules
+        if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: n_terms must be in [0, 8]");
+        for (int j = 0; j < terms->n_terms; ++j) {
+            const icem_cost_term& tm = terms->terms[j];
+            if (tm.kind < ICEM_TERM_NORM || tm.kind > ICEM_TERM_STEP_GT) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: unknown cost term kind");
+            if (tm.len < 1 || tm.len > ICEM_MAX_TERM_LEN) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: cost term len must be in [1, 64]");
+        }
+        if (terms->box_from >= 0 && terms->health_idx < 0)
+            return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: box_from is part of the health term: health_idx must be set");
+    }
+    const icem_cost_terms* on = cost_terms_on(terms) ? terms : nullptr;
+    if (const char* e = cost_indices_error(*cost, on, obs_dim)) return fail(ICEM_E_INVALID, std::string("icem_mlp_rollout_cost: ") + e);
+    if (n == 0) return ICEM_OK;
+    CostArgs<float> cs;
+    fill_cost_args_f32(*cost, on, cs);
+    ICEM_HIP_TRY(launch_mlp_rollout(n, horizon, obs_dim, act_dim, layers, activation, cost_mode, cs, (const unsigned short*)params,
+                                    (const float*)obs0, (const float*)actions, (float*)costs, (float*)observations, (hipStream_t)stream));
+    return ICEM_OK;
 }
 
 int icem_rssm_rollout_cost_batch(int32_t n_problems, const int32_t* rows_host, int32_t horizon, int32_t cost_mode,

@@ -69,5 +69,8 @@ __device__ __forceinline__ T cost_terms(const CostArgs<T>& cs, bool bad, Obs obs
 // host side (generic_kernels.hip): the handle's cost spec + terms in kernel-argument form
 void fill_cost_args_f32(const icem_handle* h, CostArgs<float>& cs);
 void fill_cost_args_f64(const icem_handle* h, CostArgs<double>& cs);
+// ... from a spec + terms pair without a handle (icem_mlp_rollout_cost): terms NULL, or with nothing switched on = no list
+bool cost_terms_on(const icem_cost_terms* terms);
+void fill_cost_args_f32(const icem_cost_spec& cost, const icem_cost_terms* terms, CostArgs<float>& cs);
 
 }  // namespace icem

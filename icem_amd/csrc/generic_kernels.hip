@@ -724,27 +724,27 @@ int launch_rollout_k(const icem_handle* h, const RolloutArgs<T>& a, const Launch
     return ICEM_OK;
 }
 
+// a cost spec + a term list (has_terms: the list is on) in kernel-argument form -- from a handle or from the pair itself
 template <typename T>
-void fill_cost_args(const icem_handle* h, CostArgs<T>& cs) {
-    cs.ctrl_w = (T)h->cost.ctrl_weight;
-    cs.lin_w = (T)h->cost.lin_weight;
-    cs.flip_pen = (T)h->cost.flip_penalty;
-    cs.flip_th = (T)h->cost.flip_thresh;
-    cs.lin_idx = h->cost.lin_idx;
-    cs.flip_idx = h->cost.flip_idx;
-    const icem_cost_terms& t = h->terms;
-    cs.ext = h->has_terms ? 1 : 0;
+void fill_cost_args_pair(const icem_cost_spec& cost, const icem_cost_terms& t, bool has_terms, CostArgs<T>& cs) {
+    cs.ctrl_w = (T)cost.ctrl_weight;
+    cs.lin_w = (T)cost.lin_weight;
+    cs.flip_pen = (T)cost.flip_penalty;
+    cs.flip_th = (T)cost.flip_thresh;
+    cs.lin_idx = cost.lin_idx;
+    cs.flip_idx = cost.flip_idx;
+    cs.ext = has_terms ? 1 : 0;
     cs.diff_w = (T)t.diff_weight;
     cs.health_pen = (T)t.health_penalty;
     cs.health_lo = (T)t.health_lo;
     cs.health_hi = (T)t.health_hi;
     cs.box_lo = (T)t.box_lo;
     cs.box_hi = (T)t.box_hi;
-    cs.diff_idx = h->has_terms ? t.diff_idx : -1;
-    cs.health_idx = h->has_terms ? t.health_idx : -1;
+    cs.diff_idx = has_terms ? t.diff_idx : -1;
+    cs.health_idx = has_terms ? t.health_idx : -1;
     cs.health_closed = t.health_closed;
-    cs.box_from = (h->has_terms && t.health_idx >= 0) ? t.box_from : -1;
-    cs.n_terms = h->has_terms ? t.n_terms : 0;
+    cs.box_from = (has_terms && t.health_idx >= 0) ? t.box_from : -1;
+    cs.n_terms = has_terms ? t.n_terms : 0;
     for (int j = 0; j < ICEM_MAX_COST_TERMS; ++j) {
         const icem_cost_term& tm = t.terms[j];
         cs.terms[j].w = (T)tm.weight;
@@ -758,14 +758,28 @@ void fill_cost_args(const icem_handle* h, CostArgs<T>& cs) {
     }
 }
 
+template <typename T>
+void fill_cost_args(const icem_handle* h, CostArgs<T>& cs) {
+    fill_cost_args_pair<T>(h->cost, h->terms, h->has_terms, cs);
+}
+
 void fill_cost_args_f32(const icem_handle* h, CostArgs<float>& cs) { fill_cost_args<float>(h, cs); }
 void fill_cost_args_f64(const icem_handle* h, CostArgs<double>& cs) { fill_cost_args<double>(h, cs); }
 
+bool cost_terms_on(const icem_cost_terms* t) { return t != nullptr && (t->diff_idx >= 0 || t->health_idx >= 0 || t->n_terms > 0); }
+
+void fill_cost_args_f32(const icem_cost_spec& cost, const icem_cost_terms* terms, CostArgs<float>& cs) {
+    static const icem_cost_terms none = {};
+    fill_cost_args_pair<float>(cost, terms ? *terms : none, cost_terms_on(terms), cs);
+}
+
 // every index a cost term reads lies inside an observation of width o
-const char* cost_indices_error(const icem_handle* h, int o) {
-    if (h->cost.lin_idx < 0 || h->cost.lin_idx >= o || h->cost.flip_idx >= o) return "cost index outside the observation";
-    if (!h->has_terms) return nullptr;
-    const icem_cost_terms& t = h->terms;
+const char* cost_indices_error(const icem_handle* h, int o) { return cost_indices_error(h->cost, h->has_terms ? &h->terms : nullptr, o); }
+
+const char* cost_indices_error(const icem_cost_spec& cost, const icem_cost_terms* terms, int o) {
+    if (cost.lin_idx < 0 || cost.lin_idx >= o || cost.flip_idx >= o) return "cost index outside the observation";
+    if (terms == nullptr) return nullptr;
+    const icem_cost_terms& t = *terms;
     if (t.diff_idx >= o || t.health_idx >= o || t.box_from >= o) return "cost term index outside the observation";
     for (int j = 0; j < t.n_terms; ++j) {
         const icem_cost_term& tm = t.terms[j];

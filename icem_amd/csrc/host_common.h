@@ -457,6 +457,8 @@ int gk_select_refit(const icem_handle* h, int n_cand, int n_loc, const void* cos
                     const LaunchCtx& cx);
 // every index a cost term reads lies inside an observation of width o (nullptr = fine)
 const char* cost_indices_error(const icem_handle* h, int o);
+// ... of a cost spec + term list pair (terms: NULL = no list), the rule the handle's goes by
+const char* cost_indices_error(const icem_cost_spec& cost, const icem_cost_terms* terms, int o);
 
 // ---- k_rollout_f64.hip: the float64 rollout on the f64 matrix cores (icem_set_f64_arith(ICEM_F64_MFMA)) ----------------
 size_t f64_mfma_lds_bytes(int o, int d);   // dynamic LDS of a launch (two buffers of 16 padded rows)

@@ -128,5 +128,27 @@ __device__ __forceinline__ void fin_dense(const float* bs, size_t boff, const v4
     }
     __builtin_amdgcn_sched_barrier(0);
 }
+// fin_dense with the activation as a template argument (0: relu, 1: swish = x sigmoid(x)) and the layer's 16 x 13 biases
+// handed over as a pointer into LDS (k_mlp_rollout.hip: its layers are not the RSSM's bias table)
+template <int ACTV>
+__device__ __forceinline__ v4s act_pack(v4f a) {
+    if (ACTV == 0) return relu_pack(a);
+    return pack4(a[0] * sigmoidf_(a[0]), a[1] * sigmoidf_(a[1]), a[2] * sigmoidf_(a[2]), a[3] * sigmoidf_(a[3]));
+}
+template <int KB, int TT, int ACTV>
+__device__ __forceinline__ void fin_dense_act(const float* bias, const v4i (&A)[NOB][KB], const unsigned short* X, int xts,
+                                              unsigned short* Y, int w, int g) {
+#pragma unroll
+    for (int i = 0; i < NOB; ++i) {
+        const int ob = own_block(w, i);
+        const v4f b = *reinterpret_cast<const v4f*>(bias + ob * 16 + 4 * g);
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+            const v4f a = mma<KB>(A[i], X + tt * xts, b);
+            if (w + WAVES * i < 13) *reinterpret_cast<v4s*>(Y + tt * 16 * RS + ob * 16) = act_pack<ACTV>(a);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
 }  // namespace rssm_dev
 }  // namespace icem

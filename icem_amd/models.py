@@ -574,3 +574,194 @@ class DeviceRSSMEnsemble(ForwardModel):
     def predict(self, *, observations, states, actions):
         """Member 0's successor state (the reference-style interface returns one; the planning costs are the ensemble's)."""
         return self.models[0].predict(observations=observations, states=states, actions=actions)
+
+
+# ---- feed-forward learned dynamics (PETS / MBPO style): icem_amd/csrc/icem_mlp.h, icem_mlp_rollout_cost ---------------------
+MLP_ACTIVATIONS = ("relu", "swish")
+
+
+def declared_mlp(obs_dim: int, act_dim: int, hidden: int = 200, layers: int = 2, activation: str = "relu", seed: int = 0, dtype=None,
+                 device="cuda:0", env=None) -> TorchForwardModel:
+    """An observation-space MLP that predicts the next observation as a residual -- the model most people who train dynamics
+    for MPC have (PETS, MBPO), and the one the reference's ``cost_fn``s presuppose:
+    ``x1 = act(W1 [s | a] + b1)``, ``xk = act(Wk x(k-1) + bk)`` for ``k = 2 .. layers``, ``s' = s + Wout x_layers + bout`` with
+    ``act`` = ``"relu"`` or ``"swish"`` (``x * sigmoid(x)``, PETS's).  Random weights reproducible from ``seed`` (in
+    ``declared_rssm``'s manner).  The module has ``hidden`` (the ``layers`` hidden ``Linear``s), ``out`` and ``activation``;
+    it comes back as a ``TorchForwardModel`` with ``cost=None``: the controllers score its graph-replayed torch rollout with
+    the env's ``cost_spec``.  ``DeviceMLPModel`` runs the same module (``hidden`` = 200, ``layers`` 1 .. 4, ``obs_dim`` 1 .. 64,
+    ``act_dim`` 1 .. 32) with rollout and cost fused into one HIP launch."""
+    import torch
+    if activation not in MLP_ACTIVATIONS:
+        raise ValueError(f"activation must be 'relu' or 'swish', not {activation!r}")
+    if layers < 1 or obs_dim < 1 or act_dim < 1 or hidden < 1:
+        raise ValueError("obs_dim, act_dim, hidden and layers must be >= 1")
+
+    class MLP(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.obs_dim, self.act_dim, self.activation = obs_dim, act_dim, activation
+            self.hidden = torch.nn.ModuleList([torch.nn.Linear(obs_dim + act_dim if k == 0 else hidden, hidden) for k in range(layers)])
+            self.out = torch.nn.Linear(hidden, obs_dim)
+
+        def forward(self, obs, act):
+            x = torch.cat([obs, act], dim=-1)
+            for lin in self.hidden:
+                x = lin(x)
+                x = torch.relu(x) if self.activation == "relu" else x * torch.sigmoid(x)
+            return obs + self.out(x)
+
+    gen = torch.Generator().manual_seed(seed)
+    net = MLP()
+    with torch.no_grad():
+        for p in net.parameters():   # reproducible weights, independent of torch's global RNG state
+            bound = 1.0 / math.sqrt(p.shape[-1]) if p.ndim > 1 else 0.05
+            p.copy_((torch.rand(p.shape, generator=gen) * 2 - 1) * bound)
+    if dtype is not None:
+        net = net.to(dtype)
+    return TorchForwardModel(net, None, obs_dim, act_dim, dtype=dtype, device=device, env=env)
+
+
+def fold_input_norm(weight, bias, in_mean, in_std):
+    """``(W', b')`` (float64) of an input layer that takes the raw ``[s | a]`` where ``(weight, bias)`` takes the normalised
+    ``([s | a] - mean) / std``: ``W' = W / std`` column by column, ``b' = b - W' mean``."""
+    import torch
+    w, b = weight.detach().double().cpu(), bias.detach().double().cpu()
+    mean = torch.zeros(w.shape[1], dtype=torch.float64) if in_mean is None else torch.as_tensor(np.asarray(in_mean, dtype=np.float64))
+    std = torch.ones(w.shape[1], dtype=torch.float64) if in_std is None else torch.as_tensor(np.asarray(in_std, dtype=np.float64))
+    if mean.shape != (w.shape[1],) or std.shape != (w.shape[1],):
+        raise ValueError(f"in_mean / in_std must have the input layer's {w.shape[1]} entries ([s | a])")
+    if not bool((std != 0).all()):
+        raise ValueError("in_std must not contain zeros")
+    w2 = w / std[None, :]
+    return w2, b - w2 @ mean
+
+
+def _mlp_shape(module):
+    """(obs_dim, act_dim, layers, activation) of a ``declared_mlp``-shaped module, checked against what the device kernel serves."""
+    hidden = list(module.hidden)
+    o = module.out.out_features
+    d = hidden[0].in_features - o
+    act = getattr(module, "activation", "relu")
+    ok = (1 <= len(hidden) <= 4 and 1 <= o <= 64 and 1 <= d <= 32 and act in MLP_ACTIVATIONS and module.out.in_features == 200
+          and all(lin.out_features == 200 for lin in hidden) and all(lin.in_features == 200 for lin in hidden[1:]))
+    if not ok:
+        raise ValueError("icem_mlp_rollout_cost is compiled for hidden width 200, 1 to 4 hidden layers, 1 to 64 observation and 1 to 32 "
+                         "action dimensions, relu or swish")
+    return o, d, len(hidden), act
+
+
+def pack_mlp(module, in_mean=None, in_std=None):
+    """The packed bf16 parameter buffer ``icem_mlp_rollout_cost`` reads (layout: icem_amd/csrc/icem_mlp.h) from a
+    ``declared_mlp``-shaped module: every weight padded (outputs to multiples of 16, contractions to multiples of 32) and cut
+    into 16 x 32 blocks stored as ``v_mfma_f32_16x16x32_bf16`` A operands ``[out block][k block][lane = 16*g + i][v]`` =
+    ``W[16*ob + i][32*kb + 8*g + v]``, each layer followed by its f32 bias.  The input layer's state columns sit at
+    ``0 .. obs_dim - 1`` and its action columns at ``32*SK ..`` (``SK = ceil(obs_dim / 32)``), zeros elsewhere.  ``in_mean`` /
+    ``in_std`` (``[obs_dim + act_dim]``): an input normalisation ``([s | a] - mean) / std`` in front of the module, folded into
+    the input layer (``fold_input_norm``) before it is rounded."""
+    import torch
+    o, d, L, _ = _mlp_shape(module)
+    sk, ob_n = (o + 31) // 32, (o + 15) // 16
+    hidden = list(module.hidden)
+    w1, b1 = fold_input_norm(hidden[0].weight, hidden[0].bias, in_mean, in_std)
+
+    def pad(w, rows, cols, col_map=None):
+        out = torch.zeros(rows, cols)
+        w = w.detach().float().cpu()
+        for (s0, s1, d0) in (col_map or [(0, w.shape[1], 0)]):
+            out[:w.shape[0], d0:d0 + (s1 - s0)] = w[:, s0:s1]
+        return out
+
+    def vec(b, n):
+        return pad(b.detach().float().cpu()[None], 1, n)[0]
+
+    layers = [(pad(w1, 208, 32 * (sk + 1), [(0, o, 0), (o, o + d, 32 * sk)]), vec(b1, 208))]
+    layers += [(pad(lin.weight, 208, 224), vec(lin.bias, 208)) for lin in hidden[1:]]
+    layers.append((pad(module.out.weight, 16 * ob_n, 224), vec(module.out.bias, 16 * ob_n)))
+    chunks = []
+    for w, b in layers:
+        ob, kb = w.shape[0] // 16, w.shape[1] // 32
+        blocks = w.reshape(ob, 16, kb, 4, 8).permute(0, 2, 3, 1, 4).contiguous()   # [ob, kb, g, i, v]
+        chunks.append(blocks.to(torch.bfloat16).view(torch.int16).reshape(-1))
+        chunks.append(b.contiguous().view(torch.int16).reshape(-1))                 # f32 bias as two 16-bit words each
+    return torch.cat(chunks)
+
+
+class DeviceMLPModel(ForwardModel):
+    """A ``declared_mlp``-shaped residual MLP with its whole h-step rollout AND the environment's parametric cost fused into one
+    HIP launch on the bf16 matrix cores (``icem_mlp_rollout_cost``).  ``reference`` is the f32 torch module the weights come
+    from -- ``declared_mlp(obs_dim, act_dim, layers=, activation=, seed=)``'s, or a copy of the caller's trained ``module``
+    (hidden width 200; with ``in_mean`` / ``in_std`` the copy's input layer has the normalisation folded in, so that
+    ``reference`` maps raw ``[s | a]`` like the device buffer does); ``predict`` serves the reference-style NumPy interface
+    through it.  The cost is ``cost_spec``, or else ``env.cost_spec`` (an ``envs.CostSpec``).  The controllers plan through it
+    stage by stage (``rollout_cost`` + ``params``); there is no batched launch."""
+
+    def __init__(self, obs_dim=None, act_dim=None, layers: int = 2, activation: str = "relu", seed: int = 0, device="cuda:0", env=None,
+                 module=None, cost_spec=None, in_mean=None, in_std=None):
+        super().__init__(env=env)
+        import copy
+        import torch
+        from . import _lib as L
+        if cost_spec is None:
+            cost_spec = getattr(env, "cost_spec", None)
+        if cost_spec is None:
+            raise ValueError("DeviceMLPModel scores its rollouts with a parametric cost: give cost_spec= or an env that has one")
+        if module is None:
+            if obs_dim is None or act_dim is None:
+                raise ValueError("give obs_dim and act_dim, or a module")
+            if not (1 <= int(obs_dim) <= L.MLP_MAX_OBS_DIM and 1 <= int(act_dim) <= L.MLP_MAX_ACT_DIM and 1 <= int(layers) <= L.MLP_MAX_LAYERS):
+                raise ValueError(f"the device MLP takes 1 to {L.MLP_MAX_OBS_DIM} observation and 1 to {L.MLP_MAX_ACT_DIM} action dimensions and "
+                                 f"1 to {L.MLP_MAX_LAYERS} hidden layers, not ({obs_dim}, {act_dim}, {layers})")
+            net = declared_mlp(int(obs_dim), int(act_dim), hidden=L.MLP_HIDDEN, layers=int(layers), activation=activation, seed=seed,
+                               device="cpu").module
+        else:
+            net = copy.deepcopy(module).float().cpu()
+        self.obs_dim, self.act_dim, self.layers, self.activation = _mlp_shape(net)
+        if in_mean is not None or in_std is not None:
+            w1, b1 = fold_input_norm(net.hidden[0].weight, net.hidden[0].bias, in_mean, in_std)
+            with torch.no_grad():
+                net.hidden[0].weight.copy_(w1.float())
+                net.hidden[0].bias.copy_(b1.float())
+        self.cost_spec = cost_spec
+        self._cost_c, self._terms_c = L.cost_spec_structs(cost_spec)
+        self.device = torch.device(device)
+        self.lib = L.load_library()
+        L.maybe_follow_environment()   # (tools only: icem_amd._lib.follow_environment)
+        self._tm = TorchForwardModel(net, None, self.obs_dim, self.act_dim, device=device, env=env)
+        self.reference = self._tm.module
+        self.params = pack_mlp(self.reference).to(self.device)
+        self._obs_host = self._obs_dev = None
+        if self.params.numel() != self.lib.icem_mlp_param_elems(self.obs_dim, self.act_dim, self.layers):
+            raise RuntimeError("packed MLP parameters do not match the library's layout")
+
+    def rollout_cost(self, obs, actions, cost_mode: int = 0, return_observations: bool = False):
+        """costs ``[n]`` (f32 device tensor) of f32 device action sequences ``[n, h, act_dim]`` from observation ``obs [obs_dim]``
+        under the model's cost (``cost_mode``: 0 sum, 1 best, 2 final).  ``return_observations=True``: ``(costs, states)`` with
+        states ``[n, h + 1, obs_dim]`` = ``s_0 .. s_h`` -- one more than the h observations a controller's rollout holds: its
+        "last predicted observation" (the one in front of the last action) is index ``h - 1``, not ``-1``.  The costs are the
+        same bit for bit with and without the states."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        if actions.ndim != 3 or actions.shape[2] != self.act_dim:
+            raise ValueError(f"actions must be [n, h, {self.act_dim}], got {tuple(actions.shape)}")
+        actions = actions.to(torch.float32).contiguous()
+        n, h, _ = actions.shape
+        ob = np.asarray(obs, dtype=np.float32)
+        if ob.shape != (self.obs_dim,):
+            raise ValueError(f"obs must be [{self.obs_dim}], got {ob.shape}")
+        if self._obs_host is None or not np.array_equal(ob, self._obs_host):   # the CEM iterations of a step share it
+            self._obs_host, self._obs_dev = ob.copy(), torch.as_tensor(ob, device=self.device)
+        costs = torch.empty((n,), dtype=torch.float32, device=self.device)
+        states = torch.empty((n, h + 1, self.obs_dim), dtype=torch.float32, device=self.device) if return_observations else None
+        if n == 0:   # (empty tensors have no address to hand over; the entry launches nothing for n == 0 either)
+            return (costs, states) if return_observations else costs
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_mlp_rollout_cost(n, h, self.obs_dim, self.act_dim, self.layers, L.MLP_ACTIVATIONS[self.activation], cost_mode,
+                                               C.byref(self._cost_c), C.byref(self._terms_c) if self._terms_c is not None else None,
+                                               C.c_void_p(self.params.data_ptr()), C.c_void_p(self._obs_dev.data_ptr()),
+                                               C.c_void_p(actions.data_ptr()), C.c_void_p(costs.data_ptr()),
+                                               C.c_void_p(states.data_ptr()) if states is not None else None, st))
+        return (costs, states) if return_observations else costs
+
+    def predict(self, *, observations, states, actions):
+        return self._tm.predict(observations=observations, states=states, actions=actions)

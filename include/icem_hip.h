@@ -959,6 +959,34 @@ int icem_rssm_rollout_cost_ensemble(int32_t members, const void* const* params_h
                                     int32_t cost_mode, int32_t reduce, const void* obs0, const void* actions, void* member_costs,
                                     void* costs, void* stream);
 
+/* Feed-forward learned dynamics (PETS / MBPO style; no reference counterpart: the reference's cost_fns presuppose such a
+ * model, it ships none): an observation-space MLP that predicts the next observation as a residual,
+ *   x1 = act(W1 [s | a] + b1), xk = act(Wk x(k-1) + bk) for k = 2 .. layers, s' = s + Wout x_layers + bout,
+ * hidden width 200, act = relu (ICEM_MLP_RELU) or swish x sigmoid(x) (ICEM_MLP_SWISH), obs_dim in [1, 64], act_dim in [1, 32],
+ * layers in [1, 4].  params: the packed bf16 parameter buffer (device) of icem_mlp_param_elems(obs_dim, act_dim, layers) 16-bit
+ * words (layout: icem_amd/csrc/icem_mlp.h; packer: icem_amd.models.pack_mlp); the function returns 0 for a shape outside the
+ * ranges. */
+#define ICEM_MLP_MAX_OBS_DIM 64
+#define ICEM_MLP_MAX_ACT_DIM 32
+#define ICEM_MLP_MAX_LAYERS 4
+enum { ICEM_MLP_RELU = 0, ICEM_MLP_SWISH = 1 };
+size_t icem_mlp_param_elems(int32_t obs_dim, int32_t act_dim, int32_t layers);
+/* costs [n] (f32, device) of actions [n, horizon, act_dim] (f32, device) rolled out through that model from obs0 [obs_dim]
+ * (f32, device) in ONE launch on the bf16 matrix cores, scored by the parametric cost:
+ *   costs[i] = reduce_t c(s_t, a_t, s_{t+1}),  s_{t+1} = s_t + f(s_t, a_t),  s_0 = obs0,
+ * c = icem_set_cost's form (*cost) plus icem_set_cost_terms' list (*terms; NULL: none), reduced by cost_mode as
+ * icem_rollout_cost does -- its semantics with the MLP in the model's place.  Weights, the state and the hidden activations
+ * enter the matrix products rounded to bf16; the state itself, the residual add and the cost are f32.  observations: NULL, or
+ * [n, horizon + 1, obs_dim] (f32, device) for s_0 .. s_h; the costs do not depend on it bit for bit.  No handle, no state,
+ * nothing allocated: the call may be captured into a graph from the first one on.
+ *   ICEM_E_INVALID: a NULL cost / params / obs0 / actions / costs, n < 0, a cost_mode or activation outside its enum, a term
+ * list icem_set_cost_terms refuses, a cost or term index outside obs_dim.  ICEM_E_UNSUPPORTED: obs_dim, act_dim or layers
+ * outside the ranges above, horizon outside [1, ICEM_MAX_HORIZON].  Whatever is refused is refused before anything is
+ * launched.  n == 0: ICEM_OK, nothing launched. */
+int icem_mlp_rollout_cost(int32_t n, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
+                          int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const void* params,
+                          const void* obs0, const void* actions, void* costs, void* observations, void* stream);
+
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action
  * [act_dim] (+ the best cost of the last pool, if best_cost_host != NULL) comes back as float64 after ONE stream

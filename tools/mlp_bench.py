@@ -1,0 +1,99 @@
+"""Feed-forward learned dynamics (GPU box): DeviceMLPModel.rollout_cost -- rollout and env cost fused into one launch -- against
+the TorchForwardModel graph-replay path on the SAME module (h graph-replayed torch steps + icem_trajectory_cost), and
+MpcICemHip.get_action on both models.  HalfCheetah shape (o = 17, d = 6, h = 30), N = 1024 and 4096, 2 and 4 hidden layers,
+relu and swish.  Both paths run in one process, alternating window by window; every shape is warmed up; a window is timed
+with device events and lasts at least 0.5 s; the line gives the median window and the spread (min .. max) per path.
+usage: python tools/mlp_bench.py [--windows 5] [--seconds 0.5]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from icem_amd import DeviceMLPModel, MpcICemHip, TorchForwardModel, declared_mlp, halfcheetah_env  # noqa: E402
+
+O, D, H = 17, 6, 30
+DEV = "cuda:0"
+
+
+def controller(model, N):
+    asp = dict(alpha=0.1, elites_size=10, opt_iterations=3, init_std=0.5, use_mean_actions=True, keep_previous_elites=True,
+               shift_elites_over_time=True, fraction_elites_reused=0.3, noise_beta=2.0)
+    return MpcICemHip(env=halfcheetah_env(O), forward_model=model, horizon=H, num_simulated_trajectories=N, factor_decrease_num=1.25,
+                      cost_along_trajectory="sum", dtype="f32", seed=1, action_sampler_params=asp)
+
+
+def window(fn, seconds):
+    """us per call of fn over one window of at least `seconds`, by device events."""
+    reps, done, total_ms = 8, 0, 0.0
+    while total_ms < seconds * 1e3:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        total_ms += a.elapsed_time(b)
+        done += reps
+        reps = min(reps * 2, 4096)
+    return total_ms * 1e3 / done
+
+
+def alternate(fns, windows, seconds):
+    """{name: [us per call per window]} with the paths taking turns window by window."""
+    out = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            out[k].append(window(fn, seconds))
+    return out
+
+
+def fmt(v):
+    return f"{np.median(v):9.1f} us ({min(v):.1f} .. {max(v):.1f})"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--seconds", type=float, default=0.5)
+    args = ap.parse_args()
+    rs = np.random.RandomState(0)
+    obs = 0.1 * rs.randn(O)
+    print(f"# {torch.cuda.get_device_name(0)}; o={O} d={D} h={H}; {args.windows} windows of >= {args.seconds} s per path, alternating", flush=True)
+    for layers in (2, 4):
+        for act in ("relu", "swish"):
+            net = declared_mlp(O, D, layers=layers, activation=act, seed=0, device="cpu").module
+            with torch.no_grad():
+                net.out.weight.mul_(0.1)   # keeps the random network's state bounded over 30 steps
+            dev_model = DeviceMLPModel(module=net, env=halfcheetah_env(O), device=DEV)
+            torch_model = TorchForwardModel(net, None, O, D, device=DEV, env=halfcheetah_env(O))
+            for N in (1024, 4096):
+                cd, ct = controller(dev_model, N), controller(torch_model, N)
+                assert cd.rssm_path and ct.torch_path and ct.torch_spec_cost
+                actions = torch.as_tensor(rs.uniform(-1, 1, (N, H, D)), dtype=torch.float32, device=DEV)
+                fns = {"fused": lambda: cd._costs_of(obs, actions), "torch": lambda: ct._costs_of(obs, actions)}
+                for fn in fns.values():   # warm-up: the graph capture of the torch chain, lazy initialisations
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                a, b = fns["fused"]().float(), fns["torch"]().float()
+                diff = float((a - b).abs().max() / (1 + b.abs().max()))
+                r = alternate(fns, args.windows, args.seconds)
+                print(f"rollout_cost  L={layers} {act:5s} N={N:5d}  fused {fmt(r['fused'])}  torch graph {fmt(r['torch'])}  "
+                      f"ratio {np.median(r['torch']) / np.median(r['fused']):5.2f}  max cost diff {diff:.1e} (bf16 vs f32 operands)", flush=True)
+                for c in (cd, ct):
+                    c.beginning_of_rollout(observation=obs, state=None, mode="train")
+                steps = {"fused": lambda: cd.get_action(obs, None), "torch": lambda: ct.get_action(obs, None)}
+                for fn in steps.values():
+                    for _ in range(3):
+                        fn()
+                g = alternate(steps, max(args.windows // 2, 2), args.seconds)
+                print(f"get_action    L={layers} {act:5s} N={N:5d}  fused {fmt(g['fused'])}  torch graph {fmt(g['torch'])}  "
+                      f"ratio {np.median(g['torch']) / np.median(g['fused']):5.2f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
