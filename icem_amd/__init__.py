@@ -12,7 +12,8 @@ from .planner import IcemConfig, IcemPlanner  # noqa: F401
 from .envs import (CostSpec, CostTerm, SyntheticEnv, door_env, relocate_env, halfcheetah_env, humanoid_standup_env, ant_env, hopper_env, humanoid_env,  # noqa: F401
                    reacher_env, fetch_pick_and_place_env, fetch_reach_env)
 from .models import (DeviceSyntheticModel, DeviceRSSMModel, DeviceRSSMEnsemble, TorchForwardModel, declared_rssm, pack_rssm,  # noqa: F401
-                     rssm_rollout_cost_models, DeviceMLPModel, declared_mlp, pack_mlp)
+                     rssm_rollout_cost_models, DeviceMLPModel, DeviceMLPEnsemble, declared_mlp, pack_mlp,
+                     mlp_rollout_cost_models)
 from .controllers import (MpcICemHip, MpcCemStdHip, MpcRandomHip, controller_from_string, ControllerFactory)  # noqa: F401
 
 __version__ = "0.1.0"

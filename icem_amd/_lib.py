@@ -92,10 +92,16 @@ class IcemRssmProblemC(C.Structure):
     _fields_ = [("params", C.c_void_p), ("action_row0", C.c_int64), ("rows", C.c_int32), ("obs_row", C.c_int32)]
 
 
+class IcemMlpProblemC(C.Structure):
+    """include/icem_hip.h: struct icem_mlp_problem."""
+    _fields_ = [("params", C.c_void_p), ("action_row0", C.c_int64), ("rows", C.c_int32), ("obs_row", C.c_int32)]
+
+
 RSSM_REDUCE = {"mean": 0, "max": 1}   # include/icem_hip.h: ICEM_RSSM_REDUCE_*
 RSSM_BATCH_MAX = 32                   # problems / members of one learned-dynamics launch
 MLP_ACTIVATIONS = {"relu": 0, "swish": 1}   # include/icem_hip.h: ICEM_MLP_RELU / ICEM_MLP_SWISH
 MLP_MAX_OBS_DIM, MLP_MAX_ACT_DIM, MLP_MAX_LAYERS, MLP_HIDDEN = 64, 32, 4, 200
+MLP_MAX_PROBLEMS = 32                 # include/icem_hip.h: ICEM_MLP_MAX_PROBLEMS
 
 
 def cost_spec_structs(spec):
@@ -140,6 +146,10 @@ SYMBOLS = [
     ("icem_mlp_param_elems", _SZ, [_I32, _I32, _I32]),
     ("icem_mlp_rollout_cost", C.c_int, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(IcemCostSpecC), C.POINTER(IcemCostTermsC),
                                         _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("icem_mlp_rollout_cost_models", C.c_int, [_I32, C.POINTER(IcemMlpProblemC), _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(IcemCostSpecC),
+                                               C.POINTER(IcemCostTermsC), _VP, _I32, _VP, _I64, _VP, _VP, _VP]),
+    ("icem_mlp_rollout_cost_ensemble", C.c_int, [_I32, C.POINTER(_VP), _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(IcemCostSpecC),
+                                                 C.POINTER(IcemCostTermsC), _VP, _VP, _VP, _VP, _VP]),
     ("icem_set_rssm_act_dim", C.c_int, [_VP, _I32]),
     ("icem_rssm_act_dim", _I32, [_VP]),
     ("icem_get_action", C.c_int, [_H, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -940,35 +940,106 @@ static_assert(mlp::OBS_MAX == ICEM_MLP_MAX_OBS_DIM && mlp::ACT_MAX == ICEM_MLP_M
 
 size_t icem_mlp_param_elems(int32_t obs_dim, int32_t act_dim, int32_t layers) { return mlp::param_units(obs_dim, act_dim, layers); }
 
+// what every MLP rollout entry checks of the launch's own arguments (`who` names the entry in the message): the modes, the
+// shape and horizon ranges, the cost pair.  -> ICEM_OK with *on = the term list that is switched on (or NULL)
+static int admit_mlp_launch(const char* who, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
+                            int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const icem_cost_terms** on) {
+    auto say = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return say(ICEM_E_INVALID, "bad cost_mode");
+    if (activation != ICEM_MLP_RELU && activation != ICEM_MLP_SWISH) return say(ICEM_E_INVALID, "activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
+    if (obs_dim < 1 || obs_dim > mlp::OBS_MAX) return say(ICEM_E_UNSUPPORTED, "obs_dim must be in [1, 64]");
+    if (act_dim < 1 || act_dim > mlp::ACT_MAX) return say(ICEM_E_UNSUPPORTED, "act_dim must be in [1, 32]");
+    if (layers < 1 || layers > mlp::LAYERS_MAX) return say(ICEM_E_UNSUPPORTED, "layers must be in [1, 4]");
+    if (horizon < 1 || horizon > ICEM_MAX_HORIZON) return say(ICEM_E_UNSUPPORTED, "horizon must be in [1, 64]");
+    if (terms != nullptr) {   // icem_set_cost_terms' rules
+        if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return say(ICEM_E_INVALID, "n_terms must be in [0, 8]");
+        for (int j = 0; j < terms->n_terms; ++j) {
+            const icem_cost_term& tm = terms->terms[j];
+            if (tm.kind < ICEM_TERM_NORM || tm.kind > ICEM_TERM_STEP_GT) return say(ICEM_E_INVALID, "unknown cost term kind");
+            if (tm.len < 1 || tm.len > ICEM_MAX_TERM_LEN) return say(ICEM_E_INVALID, "cost term len must be in [1, 64]");
+        }
+        if (terms->box_from >= 0 && terms->health_idx < 0)
+            return say(ICEM_E_INVALID, "box_from is part of the health term: health_idx must be set");
+    }
+    *on = cost_terms_on(terms) ? terms : nullptr;
+    if (const char* e = cost_indices_error(*cost, *on, obs_dim)) return say(ICEM_E_INVALID, e);
+    return ICEM_OK;
+}
+
 int icem_mlp_rollout_cost(int32_t n, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
                           int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const void* params,
                           const void* obs0, const void* actions, void* costs, void* observations, void* stream) {
     if (!cost || !params || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: null pointer");
     if (n < 0) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: n must be >= 0");
-    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: bad cost_mode");
-    if (activation != ICEM_MLP_RELU && activation != ICEM_MLP_SWISH)
-        return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
-    if (obs_dim < 1 || obs_dim > mlp::OBS_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: obs_dim must be in [1, 64]");
-    if (act_dim < 1 || act_dim > mlp::ACT_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: act_dim must be in [1, 32]");
-    if (layers < 1 || layers > mlp::LAYERS_MAX) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: layers must be in [1, 4]");
-    if (horizon < 1 || horizon > ICEM_MAX_HORIZON) return fail(ICEM_E_UNSUPPORTED, "icem_mlp_rollout_cost: horizon must be in [1, 64]");
-    if (terms != nullptr) {   // icem_set_cost_terms' rules
-        if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: n_terms must be in [0, 8]");
-        for (int j = 0; j < terms->n_terms; ++j) {
-            const icem_cost_term& tm = terms->terms[j];
-            if (tm.kind < ICEM_TERM_NORM || tm.kind > ICEM_TERM_STEP_GT) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: unknown cost term kind");
-            if (tm.len < 1 || tm.len > ICEM_MAX_TERM_LEN) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: cost term len must be in [1, 64]");
-        }
-        if (terms->box_from >= 0 && terms->health_idx < 0)
-            return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost: box_from is part of the health term: health_idx must be set");
-    }
-    const icem_cost_terms* on = cost_terms_on(terms) ? terms : nullptr;
-    if (const char* e = cost_indices_error(*cost, on, obs_dim)) return fail(ICEM_E_INVALID, std::string("icem_mlp_rollout_cost: ") + e);
+    const icem_cost_terms* on = nullptr;
+    if (int rc = admit_mlp_launch("icem_mlp_rollout_cost", horizon, obs_dim, act_dim, layers, activation, cost_mode, cost, terms, &on)) return rc;
     if (n == 0) return ICEM_OK;
     CostArgs<float> cs;
     fill_cost_args_f32(*cost, on, cs);
     ICEM_HIP_TRY(launch_mlp_rollout(n, horizon, obs_dim, act_dim, layers, activation, cost_mode, cs, (const unsigned short*)params,
                                     (const float*)obs0, (const float*)actions, (float*)costs, (float*)observations, (hipStream_t)stream));
+    return ICEM_OK;
+}
+
+// admission of an MLP launch of problems with a model each (both entries below): everything that is refused, before any device call
+static_assert(mlp::PROBLEMS_MAX == ICEM_MLP_MAX_PROBLEMS, "the kernel's problem table is the header's");
+static int admit_mlp_models(const char* who, int32_t n_problems, const icem_mlp_problem* pr, int32_t horizon, int32_t obs_dim,
+                            int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, const icem_cost_spec* cost,
+                            const icem_cost_terms* terms, int32_t n_obs, int64_t n_action_rows, mlp::Problem* out, CostArgs<float>& cs) {
+    auto say = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+    if (n_problems < 1 || n_problems > mlp::PROBLEMS_MAX) return say(ICEM_E_INVALID, "n_problems / members must be in [1, 32]");
+    long long workgroups = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        if (!pr[p].params) return say(ICEM_E_INVALID, "null params entry");
+        if (pr[p].rows < 1) return say(ICEM_E_INVALID, "every problem needs at least one row");
+        if (pr[p].action_row0 < 0 || pr[p].action_row0 > n_action_rows - pr[p].rows)
+            return say(ICEM_E_INVALID, "a problem's action rows (action_row0 .. action_row0 + rows) must lie inside [0, n_action_rows]");
+        if (pr[p].obs_row < 0 || pr[p].obs_row >= n_obs) return say(ICEM_E_INVALID, "obs_row must be in [0, n_obs)");
+        out[p] = {(const unsigned short*)pr[p].params, (long long)pr[p].action_row0, pr[p].rows, pr[p].obs_row};
+        workgroups += ((long long)pr[p].rows + 15) / 16;
+    }
+    const icem_cost_terms* on = nullptr;
+    if (int rc = admit_mlp_launch(who, horizon, obs_dim, act_dim, layers, activation, cost_mode, cost, terms, &on)) return rc;
+    if (workgroups > mlp::WORKGROUPS_MAX) return say(ICEM_E_UNSUPPORTED, "the problems' tiles (the sum of ceil(rows / 16)) exceed one launch's grid");
+    fill_cost_args_f32(*cost, on, cs);
+    return ICEM_OK;
+}
+
+int icem_mlp_rollout_cost_models(int32_t n_problems, const icem_mlp_problem* problems_host, int32_t horizon, int32_t obs_dim,
+                                 int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, const icem_cost_spec* cost,
+                                 const icem_cost_terms* terms, const void* obs0, int32_t n_obs, const void* actions, int64_t n_action_rows,
+                                 void* costs, void* observations, void* stream) {
+    if (!problems_host || !cost || !obs0 || !actions || !costs) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost_models: null pointer");
+    mlp::Problem pr[mlp::PROBLEMS_MAX];
+    CostArgs<float> cs;
+    if (int rc = admit_mlp_models("icem_mlp_rollout_cost_models", n_problems, problems_host, horizon, obs_dim, act_dim, layers, activation,
+                                  cost_mode, cost, terms, n_obs, n_action_rows, pr, cs))
+        return rc;
+    ICEM_HIP_TRY(launch_mlp_rollout_models(n_problems, pr, horizon, obs_dim, act_dim, layers, activation, cost_mode, cs, (const float*)obs0,
+                                           (const float*)actions, (float*)costs, (float*)observations, (hipStream_t)stream));
+    return ICEM_OK;
+}
+
+int icem_mlp_rollout_cost_ensemble(int32_t members, const void* const* params_host, int32_t n, int32_t horizon, int32_t obs_dim,
+                                   int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, int32_t reduce,
+                                   const icem_cost_spec* cost, const icem_cost_terms* terms, const void* obs0, const void* actions,
+                                   void* member_costs, void* costs, void* stream) {
+    if (!params_host || !cost || !obs0 || !actions || !member_costs || !costs)
+        return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost_ensemble: null pointer");
+    if (members < 1 || members > mlp::PROBLEMS_MAX) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost_ensemble: members must be in [1, 32]");
+    if (n < 1) return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost_ensemble: n (rows) must be >= 1");
+    if (reduce != ICEM_RSSM_REDUCE_MEAN && reduce != ICEM_RSSM_REDUCE_MAX)
+        return fail(ICEM_E_INVALID, "icem_mlp_rollout_cost_ensemble: reduce must be ICEM_RSSM_REDUCE_MEAN or ICEM_RSSM_REDUCE_MAX");
+    icem_mlp_problem in[mlp::PROBLEMS_MAX];
+    for (int e = 0; e < members; ++e) in[e] = {params_host[e], 0, n, 0};   // every member: all n rows, from the one observation
+    mlp::Problem pr[mlp::PROBLEMS_MAX];
+    CostArgs<float> cs;
+    if (int rc = admit_mlp_models("icem_mlp_rollout_cost_ensemble", members, in, horizon, obs_dim, act_dim, layers, activation, cost_mode, cost,
+                                  terms, 1, n, pr, cs))
+        return rc;
+    ICEM_HIP_TRY(launch_mlp_rollout_models(members, pr, horizon, obs_dim, act_dim, layers, activation, cost_mode, cs, (const float*)obs0,
+                                           (const float*)actions, (float*)member_costs, nullptr, (hipStream_t)stream));
+    ICEM_HIP_TRY(launch_rssm_ensemble_reduce(members, n, reduce, (const float*)member_costs, (float*)costs, (hipStream_t)stream));
     return ICEM_OK;
 }
 

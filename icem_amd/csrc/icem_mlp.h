@@ -26,6 +26,8 @@ constexpr int HID = 200, HIDB = 13, HIDK = 7;   // hidden width, its 16-wide out
 constexpr int OBS_MAX = 64, ACT_MAX = 32, LAYERS_MAX = 4;
 constexpr int BLK = 64 * 8;                     // bf16 elements of one 16 x 32 A-operand block (rssm::BLK)
 constexpr int RELU = 0, SWISH = 1;              // ICEM_MLP_RELU / ICEM_MLP_SWISH
+constexpr int PROBLEMS_MAX = 32;                // problems of one launch (ICEM_MLP_MAX_PROBLEMS): their table travels in the kernel arguments
+constexpr long long WORKGROUPS_MAX = 0x7fffffffLL;   // of one launch: the grid's x extent
 __host__ __device__ constexpr int state_kblocks(int o) { return (o + 31) / 32; }
 __host__ __device__ constexpr int state_oblocks(int o) { return (o + 15) / 16; }
 // sizes in 16-bit units: the input layer with its bias, a further hidden layer with its bias, the output layer with its bias
@@ -39,6 +41,13 @@ inline size_t param_units(int o, int d, int layers) {
     if (!shape_ok(o, d, layers)) return 0;
     return first_units(state_kblocks(o)) + (size_t)(layers - 1) * hidden_units() + out_units(state_oblocks(o));
 }
+// one problem of a launch of problems with a model each (icem_mlp_problem)
+struct Problem {
+    const unsigned short* params;   // its packed parameter buffer
+    long long action_row0;          // its first row of `actions`
+    int rows;                       // >= 1
+    int obs_row;                    // its start observation: row of obs0 [n_obs, obs_dim]
+};
 }  // namespace mlp
 
 // costs[i] = reduce_t c(s_t, a_t, s_{t+1}) along s_{t+1} = s_t + f(s_t, a_t) from s_0 = obs0 (cost_mode: 0 sum, 1 best, 2 final;
@@ -47,4 +56,15 @@ inline size_t param_units(int o, int d, int layers) {
 hipError_t launch_mlp_rollout(int n, int horizon, int obs_dim, int act_dim, int layers, int activation, int cost_mode,
                               const CostArgs<float>& cs, const unsigned short* params, const float* obs0, const float* actions,
                               float* costs, float* observations, hipStream_t st);
+
+// launch_mlp_rollout for n_problems (1 .. mlp::PROBLEMS_MAX) problems with a MODEL EACH in one launch: problem p rolls the action
+// rows action_row0 .. action_row0 + rows - 1 out from row obs_row of obs0 [n_obs, obs_dim] through its own params, on
+// ceil(rows / 16) workgroups of its own.  costs [sum rows] and observations (NULL, or [sum rows, horizon + 1, obs_dim]): the
+// problems back to back in problem order, each bit for bit what launch_mlp_rollout gives for it alone.  The shape, the
+// activation, the horizon, cost_mode and the cost are the launch's.  `problems` is read before the call returns (the table
+// travels by value in the kernel arguments); allocates nothing.  hipErrorInvalidValue: what launch_mlp_rollout refuses, a
+// problem without params or rows, more than mlp::WORKGROUPS_MAX workgroups.  The caller checks the rows against the buffers.
+hipError_t launch_mlp_rollout_models(int n_problems, const mlp::Problem* problems, int horizon, int obs_dim, int act_dim, int layers,
+                                     int activation, int cost_mode, const CostArgs<float>& cs, const float* obs0, const float* actions,
+                                     float* costs, float* observations, hipStream_t st);
 }  // namespace icem

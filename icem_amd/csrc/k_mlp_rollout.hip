@@ -16,13 +16,16 @@ static_assert(mlp::HIDB == HIDB && mlp::HIDK == HIDK && mlp::BLK == BLK, "the hi
 constexpr int SS = 68;   // f32 row stride of the state (64 + 4: rows start in different banks)
 constexpr int AS = 32;   // f32 row stride of a step's actions
 
+// The rollout of ONE tile of 16 trajectories -- rows base .. base + 15 of a problem of n rows -- by one workgroup: the body of
+// both kernels below.  Pg, obs0, actions, costs and obs_out are the PROBLEM's: its parameter buffer, its start observation, its
+// first action row, its first cost (and first state row).  Everything is wave-uniform.
 // SK: the 32-wide K blocks of the state (1: obs_dim <= 32, 2: <= 64); ACTV: mlp::RELU / mlp::SWISH.  Everything else is a
 // runtime value: o = obs_dim, d = act_dim, L = the number of hidden layers, the horizon, the cost, `observations`.
 template <int SK, int ACTV>
-__global__ __launch_bounds__(NTHR) void mlp_rollout_kernel(int n, int horizon, int o, int d, int L, int cost_mode, CostArgs<float> cs_arg,
-                                                          const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
-                                                          const float* __restrict__ actions, float* __restrict__ costs,
-                                                          float* __restrict__ obs_out) {
+__device__ __forceinline__ void mlp_rollout_tile(const int base, const int n, const int horizon, const int o, const int d, const int L,
+                                                 const int cost_mode, const CostArgs<float>& cs_arg, const unsigned short* __restrict__ Pg,
+                                                 const float* __restrict__ obs0, const float* __restrict__ actions,
+                                                 float* __restrict__ costs, float* __restrict__ obs_out) {
     // the cost's argument block goes to LDS once: left in the kernel arguments its term list stays live in scalar registers
     // across the whole step loop (500 of them spilled to lanes of vector registers and restored every step)
     __shared__ CostArgs<float> cs;
@@ -38,7 +41,6 @@ __global__ __launch_bounds__(NTHR) void mlp_rollout_kernel(int n, int horizon, i
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: block addresses stay scalar
     const int j = lane & 15, g = lane >> 4;
-    const int base = blockIdx.x * 16;
     const int OB = mlp::state_oblocks(o);
     const size_t first = mlp::first_units(SK), hid = mlp::hidden_units();
     const size_t wout = first + (size_t)(L - 1) * hid;        // Wout's offset; its bias sits OB * HIDK * BLK behind
@@ -183,6 +185,46 @@ __global__ __launch_bounds__(NTHR) void mlp_rollout_kernel(int n, int horizon, i
         if (g == 0 && row < n) costs[row] = acc_cost;
     }
 }
+
+// One problem: workgroup b rolls out rows 16 b .. 16 b + 15 of the launch's n.
+template <int SK, int ACTV>
+__global__ __launch_bounds__(NTHR) void mlp_rollout_kernel(int n, int horizon, int o, int d, int L, int cost_mode, CostArgs<float> cs_arg,
+                                                          const unsigned short* __restrict__ Pg, const float* __restrict__ obs0,
+                                                          const float* __restrict__ actions, float* __restrict__ costs,
+                                                          float* __restrict__ obs_out) {
+    mlp_rollout_tile<SK, ACTV>(blockIdx.x * 16, n, horizon, o, d, L, cost_mode, cs_arg, Pg, obs0, actions, costs, obs_out);
+}
+
+// The problems of a launch in which every problem names its OWN model, by value in the kernel arguments (icem_rssm_split.hip's
+// ModelsTable; 1152 bytes).  Problem p owns the workgroups wg0[p] .. wg0[p] + ceil(rows[p] / 16) - 1; its rows[p] trajectories are
+// the ACTION rows arow0[p] .. (several problems may name the same rows: an ensemble's members score one population) and the
+// COST rows crow0[p] .. (back to back in problem order, not rounded to 16; the rows of `observations` alike); it starts from
+// row obs[p] of the observation table and runs through the packed parameter buffer params[p].
+struct MlpTable {
+    gptr params[mlp::PROBLEMS_MAX];   // (declared global: read out of the kernel arguments as generic ones, every access behind them would be FLAT)
+    long long arow0[mlp::PROBLEMS_MAX], crow0[mlp::PROBLEMS_MAX];
+    int wg0[mlp::PROBLEMS_MAX], rows[mlp::PROBLEMS_MAX], obs[mlp::PROBLEMS_MAX];
+};
+
+// mlp_rollout_kernel with a problem table in front.  A workgroup finds its problem ONCE, here: a wave-uniform scan over the
+// (at most 32) first workgroups, kept scalar; behind it only the problem's five values are live -- its parameters, its
+// observation, its first action row, its row count, its first cost row -- and mlp_rollout_tile runs on them as it does on the
+// solo kernel's arguments: a tile holds 16 rows of ONE problem in the problem's own order (the padding rows of a problem's
+// last tile repeat ITS last row and are never stored), so every cost and state is bit for bit the solo launch's.
+template <int SK, int ACTV>
+__global__ __launch_bounds__(NTHR) void mlp_rollout_models_kernel(const MlpTable tab, int n_problems, int horizon, int o, int d, int L,
+                                                                 int cost_mode, CostArgs<float> cs_arg, const float* __restrict__ obs0,
+                                                                 const float* __restrict__ actions, float* __restrict__ costs,
+                                                                 float* __restrict__ obs_out) {
+    const int b = blockIdx.x;
+    int p = 0;
+    for (int q = 1; q < n_problems; ++q) p = b >= tab.wg0[q] ? q : p;
+    p = __builtin_amdgcn_readfirstlane(p);
+    const long long crow0 = tab.crow0[p];
+    mlp_rollout_tile<SK, ACTV>((b - tab.wg0[p]) * 16, tab.rows[p], horizon, o, d, L, cost_mode, cs_arg, (const unsigned short*)tab.params[p],
+                               obs0 + (size_t)tab.obs[p] * o, actions + (size_t)tab.arow0[p] * horizon * d, costs + crow0,
+                               obs_out != nullptr ? obs_out + (size_t)crow0 * (horizon + 1) * o : nullptr);
+}
 }  // namespace
 
 hipError_t launch_mlp_rollout(int n, int horizon, int obs_dim, int act_dim, int layers, int activation, int cost_mode,
@@ -196,6 +238,35 @@ hipError_t launch_mlp_rollout(int n, int horizon, int obs_dim, int act_dim, int 
 #define ICEM_MLP_LAUNCH(SKV, AV)                                                                                                   \
     hipLaunchKernelGGL((mlp_rollout_kernel<SKV, AV>), grid, block, 0, st, n, horizon, obs_dim, act_dim, layers, cost_mode, cs, params, \
                        obs0, actions, costs, observations)
+    if (sk == 1 && activation == mlp::RELU) ICEM_MLP_LAUNCH(1, mlp::RELU);
+    else if (sk == 1) ICEM_MLP_LAUNCH(1, mlp::SWISH);
+    else if (activation == mlp::RELU) ICEM_MLP_LAUNCH(2, mlp::RELU);
+    else ICEM_MLP_LAUNCH(2, mlp::SWISH);
+#undef ICEM_MLP_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_mlp_rollout_models(int n_problems, const mlp::Problem* problems, int horizon, int obs_dim, int act_dim, int layers,
+                                     int activation, int cost_mode, const CostArgs<float>& cs, const float* obs0, const float* actions,
+                                     float* costs, float* observations, hipStream_t st) {
+    if (!mlp::shape_ok(obs_dim, act_dim, layers) || horizon < 1 || (activation != mlp::RELU && activation != mlp::SWISH) ||
+        n_problems < 1 || n_problems > mlp::PROBLEMS_MAX)
+        return hipErrorInvalidValue;
+    MlpTable tab{};
+    long long wgs = 0, row = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const mlp::Problem& q = problems[p];
+        if (!q.params || q.rows < 1 || q.action_row0 < 0 || q.obs_row < 0) return hipErrorInvalidValue;
+        tab.params[p] = (gptr)q.params; tab.arow0[p] = q.action_row0; tab.obs[p] = q.obs_row;
+        tab.wg0[p] = (int)wgs; tab.crow0[p] = row; tab.rows[p] = q.rows;
+        wgs += ((long long)q.rows + 15) / 16; row += q.rows;
+        if (wgs > mlp::WORKGROUPS_MAX) return hipErrorInvalidValue;
+    }
+    const dim3 grid((unsigned)wgs), block(NTHR);
+    const int sk = mlp::state_kblocks(obs_dim);
+#define ICEM_MLP_LAUNCH(SKV, AV)                                                                                                      \
+    hipLaunchKernelGGL((mlp_rollout_models_kernel<SKV, AV>), grid, block, 0, st, tab, n_problems, horizon, obs_dim, act_dim, layers,  \
+                       cost_mode, cs, obs0, actions, costs, observations)
     if (sk == 1 && activation == mlp::RELU) ICEM_MLP_LAUNCH(1, mlp::RELU);
     else if (sk == 1) ICEM_MLP_LAUNCH(1, mlp::SWISH);
     else if (activation == mlp::RELU) ICEM_MLP_LAUNCH(2, mlp::RELU);

@@ -408,8 +408,9 @@ def _rssm_models_launch(lib, device, act_dim, params_ptrs, obs_rows, arow0, rows
     return costs
 
 
-def _check_problem_shapes(act_dim, n_problems, observations, actions, rows, action_row0):
-    """The shape checks of ``rollout_cost_batch`` for problems that may share action rows (needs nothing of a device).
+def _check_problem_shapes(act_dim, n_problems, observations, actions, rows, action_row0, obs_dim: int = 230):
+    """The shape checks of ``rollout_cost_batch`` for problems that may share action rows (needs nothing of a device);
+    ``obs_dim``: the width of a start observation (the RSSM's 230, or an MLP's own).
     -> (rows, action_row0, observations: a device tensor as it came, or an f32 array)."""
     import torch
     rows = [int(r) for r in rows]
@@ -433,8 +434,8 @@ def _check_problem_shapes(act_dim, n_problems, observations, actions, rows, acti
     on_device = isinstance(observations, torch.Tensor) and observations.is_cuda
     if not on_device:
         observations = np.asarray(observations, dtype=np.float32)
-    if tuple(observations.shape) != (len(rows), 230):
-        raise ValueError(f"observations must be [{len(rows)}, 230] (one start state per problem), got {tuple(observations.shape)}")
+    if tuple(observations.shape) != (len(rows), obs_dim):
+        raise ValueError(f"observations must be [{len(rows)}, {obs_dim}] (one start state per problem), got {tuple(observations.shape)}")
     if on_device and (observations.dtype != torch.float32 or not observations.is_contiguous()):
         raise ValueError("a device tensor of observations must be contiguous float32")
     return rows, action_row0, observations
@@ -693,7 +694,10 @@ class DeviceMLPModel(ForwardModel):
     (hidden width 200; with ``in_mean`` / ``in_std`` the copy's input layer has the normalisation folded in, so that
     ``reference`` maps raw ``[s | a]`` like the device buffer does); ``predict`` serves the reference-style NumPy interface
     through it.  The cost is ``cost_spec``, or else ``env.cost_spec`` (an ``envs.CostSpec``).  The controllers plan through it
-    stage by stage (``rollout_cost`` + ``params``); there is no batched launch."""
+    stage by stage (``rollout_cost`` + ``params``).  Several models in ONE launch: ``mlp_rollout_cost_models`` (a model per
+    problem) and ``DeviceMLPEnsemble`` (the members of an ensemble).  The model itself has no ``rollout_cost_batch``:
+    controllers that want to step together (``MpcICemHip.get_action_batch``) share a ``DeviceMLPEnsemble`` -- one member is
+    allowed and gives this model's bits."""
 
     def __init__(self, obs_dim=None, act_dim=None, layers: int = 2, activation: str = "relu", seed: int = 0, device="cuda:0", env=None,
                  module=None, cost_spec=None, in_mean=None, in_std=None):
@@ -765,3 +769,185 @@ class DeviceMLPModel(ForwardModel):
 
     def predict(self, *, observations, states, actions):
         return self._tm.predict(observations=observations, states=states, actions=actions)
+
+
+def _mlp_cost_bytes(model) -> bytes:
+    """The cost program of a ``DeviceMLPModel`` as the library reads it: the bytes of the two ctypes structs."""
+    import ctypes as C
+    terms = model._terms_c
+    return C.string_at(C.addressof(model._cost_c), C.sizeof(model._cost_c)) + (b"" if terms is None else C.string_at(C.addressof(terms), C.sizeof(terms)))
+
+
+def _check_mlp_models(models):
+    """``models`` (``DeviceMLPModel``s) may share a launch: 1 to 32 of one shape, one activation, one device and one cost
+    program (compared by the bytes of the ctypes structs).  Needs nothing of a device.  -> the list."""
+    from . import _lib as L
+    models = list(models)
+    if not 1 <= len(models) <= L.MLP_MAX_PROBLEMS:
+        raise ValueError(f"one launch takes 1 to {L.MLP_MAX_PROBLEMS} problems, not {len(models)}")
+    m0 = models[0]
+    shapes = [(m.obs_dim, m.act_dim, m.layers) for m in models]
+    if any(sh != shapes[0] for sh in shapes):
+        raise ValueError(f"the models must share one shape (obs_dim, act_dim, layers), got {sorted(set(shapes))}")
+    if any(m.activation != m0.activation for m in models):
+        raise ValueError(f"the models must share one activation, got {sorted({m.activation for m in models})}")
+    if any(m.params.device != m0.params.device for m in models):
+        raise ValueError("the models' parameter buffers must be on one device")
+    cost = _mlp_cost_bytes(m0)
+    if any(_mlp_cost_bytes(m) != cost for m in models[1:]):
+        raise ValueError("the models must share one cost program (the launch scores every problem with the same cost_spec)")
+    return models
+
+
+def _mlp_models_launch(m0, params_ptrs, obs_rows, arow0, rows, obs_dev, n_obs, actions, cost_mode, out=None, states=None):
+    """One ``icem_mlp_rollout_cost_models`` launch with ``m0``'s shape, activation and cost: problem p = (params_ptrs[p],
+    obs_rows[p], arow0[p], rows[p]) over the f32 device tensors ``obs_dev [n_obs, obs_dim]`` and ``actions [n_action_rows, h,
+    act_dim]`` -> costs ``[sum rows]`` (``out``, or new); ``states``: None, or ``[sum rows, h + 1, obs_dim]`` to fill."""
+    import ctypes as C
+    import torch
+    from . import _lib as L
+    n = len(rows)
+    costs = torch.empty((sum(rows),), dtype=torch.float32, device=m0.device) if out is None else out
+    problems = (L.IcemMlpProblemC * n)(*[L.IcemMlpProblemC(int(params_ptrs[p]), int(arow0[p]), int(rows[p]), int(obs_rows[p]))
+                                          for p in range(n)])
+    st = C.c_void_p(torch.cuda.current_stream(m0.device).cuda_stream)
+    L.check(m0.lib.icem_mlp_rollout_cost_models(n, problems, actions.shape[1], m0.obs_dim, m0.act_dim, m0.layers, L.MLP_ACTIVATIONS[m0.activation],
+                                                cost_mode, C.byref(m0._cost_c), C.byref(m0._terms_c) if m0._terms_c is not None else None,
+                                                C.c_void_p(obs_dev.data_ptr()), n_obs, C.c_void_p(actions.data_ptr()), actions.shape[0],
+                                                C.c_void_p(costs.data_ptr()), C.c_void_p(states.data_ptr()) if states is not None else None, st))
+    return costs
+
+
+def mlp_rollout_cost_models(models, observations, actions, rows, action_row0=None, cost_mode: int = 0, return_observations: bool = False):
+    """``DeviceMLPModel.rollout_cost`` of B problems with a MODEL EACH in ONE launch (``icem_mlp_rollout_cost_models``; the
+    sibling of ``rssm_rollout_cost_models``: parallel episodes, each with its own trained model): problem p scores ``rows[p]``
+    action sequences of ``actions [n, h, act_dim]`` (f32 device tensor) -- from row ``action_row0[p]`` on, or back to back with
+    ``action_row0=None``; the rows of different problems may overlap or coincide -- from ``observations[p]`` (``[B, obs_dim]``
+    array-like, or an f32 device tensor that is used as is) through ``models[p]`` (``DeviceMLPModel``s of one shape, one
+    activation and one cost program on one device, otherwise ``ValueError``; the same model may serve several problems).
+    -> costs ``[sum rows]``, problem p's rows back to back in problem order, each bit for bit what ``models[p].rollout_cost``
+    gives for it alone; ``return_observations=True``: ``(costs, states [sum rows, h + 1, obs_dim])``, the states laid out and
+    equal in the same way.  B <= 32."""
+    import torch
+    models = _check_mlp_models(models)
+    m0 = models[0]
+    rows, action_row0, observations = _check_problem_shapes(m0.act_dim, len(models), observations, actions, rows, action_row0, m0.obs_dim)
+    o = observations if isinstance(observations, torch.Tensor) else torch.as_tensor(observations, device=m0.device)
+    actions = actions.to(torch.float32).contiguous()
+    states = (torch.empty((sum(rows), actions.shape[1] + 1, m0.obs_dim), dtype=torch.float32, device=m0.device)
+              if return_observations else None)
+    costs = _mlp_models_launch(m0, [m.params.data_ptr() for m in models], range(len(models)), action_row0, rows, o, len(models), actions,
+                               cost_mode, states=states)
+    return (costs, states) if return_observations else costs
+
+
+class DeviceMLPEnsemble(ForwardModel):
+    """E ``DeviceMLPModel``s that score every candidate plan together (PETS plans through about five such networks, trained
+    from different seeds): a plan's cost is the members' mean (``reduce="mean"``) or the worst member's (``"max"``), so that
+    one model's error is not exploited.  Built from ``models=[DeviceMLPModel, ...]`` or from ``seeds=[...]`` (+
+    ``DeviceMLPModel``'s shape keywords: ``obs_dim``, ``act_dim``, ``layers``, ``activation``, ``cost_spec`` / ``env``, ...); 1 to
+    32 members of one shape, one activation and one cost program.  ``rollout_cost`` is ONE launch for all members
+    (``icem_mlp_rollout_cost_ensemble``) + the reduction; ``member_costs`` holds the last ``[E, n]`` (row e: member e alone, bit
+    for bit).  ``params`` are the members' packed buffers stacked ``[E, elems]`` on one device -- the launch reads these.
+
+    The sibling of ``DeviceRSSMEnsemble``, and deliberately neither a subclass of it nor a ``DeviceMLPModel``: the library's
+    fused ``*_learned_models`` steps run the RSSM, so the controllers plan through this model stage by stage
+    (``rollout_cost`` + ``params``), and ``MpcICemHip.get_action_batch`` steps controllers that share one ensemble together
+    through ``rollout_cost_batch``; one member is allowed and gives the plain model's bits.  ``predict`` -- the
+    reference-style interface needs ONE successor state -- delegates to member 0."""
+
+    def __init__(self, models=None, seeds=None, reduce: str = "mean", **model_kw):
+        import torch
+        from . import _lib as L
+        super().__init__(env=model_kw.get("env"))
+        if reduce not in L.RSSM_REDUCE:
+            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        if (models is None) == (seeds is None):
+            raise ValueError("give either models=[DeviceMLPModel, ...] or seeds=[...]")
+        count = len(models) if models is not None else len(seeds)
+        if not 1 <= count <= L.MLP_MAX_PROBLEMS:
+            raise ValueError(f"an ensemble has 1 to {L.MLP_MAX_PROBLEMS} members (one launch serves them all), not {count}")
+        if models is None:
+            if "seed" in model_kw or "module" in model_kw:
+                raise ValueError("seeds=[...] builds every member from its seed: give neither seed= nor module=")
+            models = [DeviceMLPModel(seed=int(s), **model_kw) for s in seeds]
+        elif model_kw:
+            raise ValueError(f"models=[...] come with their own shape: unexpected {sorted(model_kw)}")
+        models = list(models)
+        if not all(isinstance(m, DeviceMLPModel) for m in models):
+            raise ValueError("the members of a DeviceMLPEnsemble are DeviceMLPModels")
+        _check_mlp_models(models)
+        m0 = models[0]
+        self.models, self.members, self.reduce = models, len(models), reduce
+        self.obs_dim, self.act_dim, self.layers, self.activation = m0.obs_dim, m0.act_dim, m0.layers, m0.activation
+        self.cost_spec, self._cost_c, self._terms_c = m0.cost_spec, m0._cost_c, m0._terms_c
+        self.device = m0.device
+        self.params = torch.stack([m.params.to(self.device) for m in models])
+        self.lib = m0.lib
+        self.member_costs = None
+        self._obs_host = self._obs_dev = None
+
+    def _param_ptrs(self):
+        stride = self.params.shape[1] * self.params.element_size()
+        return [self.params.data_ptr() + e * stride for e in range(self.members)]
+
+    def rollout_cost(self, obs, actions, cost_mode: int = 0):
+        """costs ``[n]`` (f32 device tensor): the members' reduced costs of f32 device action sequences ``[n, h, act_dim]`` from
+        observation ``obs [obs_dim]``; ``member_costs [E, n]`` is kept."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        if actions.ndim != 3 or actions.shape[2] != self.act_dim:
+            raise ValueError(f"actions must be [n, h, {self.act_dim}], got {tuple(actions.shape)}")
+        if actions.shape[0] < 1:
+            raise ValueError("actions must have at least one row")
+        ob = np.asarray(obs, dtype=np.float32)
+        if ob.shape != (self.obs_dim,):
+            raise ValueError(f"obs must be [{self.obs_dim}], got {ob.shape}")
+        actions = actions.to(torch.float32).contiguous()
+        n, h, _ = actions.shape
+        if self._obs_host is None or not np.array_equal(ob, self._obs_host):   # the CEM iterations of a step share it
+            self._obs_host, self._obs_dev = ob.copy(), torch.as_tensor(ob, device=self.device)
+        member_costs = torch.empty((self.members, n), dtype=torch.float32, device=self.device)
+        costs = torch.empty((n,), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_mlp_rollout_cost_ensemble(self.members, (C.c_void_p * self.members)(*self._param_ptrs()), n, h, self.obs_dim,
+                                                        self.act_dim, self.layers, L.MLP_ACTIVATIONS[self.activation], cost_mode,
+                                                        L.RSSM_REDUCE[self.reduce], C.byref(self._cost_c),
+                                                        C.byref(self._terms_c) if self._terms_c is not None else None,
+                                                        C.c_void_p(self._obs_dev.data_ptr()), C.c_void_p(actions.data_ptr()),
+                                                        C.c_void_p(member_costs.data_ptr()), C.c_void_p(costs.data_ptr()), st))
+        self.member_costs = member_costs
+        return costs
+
+    def rollout_cost_batch(self, observations, actions, rows, cost_mode: int = 0):
+        """``rollout_cost`` of B planners in ONE launch of B x E problems (+ one reduction): planner b scores its ``rows[b]``
+        action sequences -- back to back in ``actions [sum rows, h, act_dim]`` -- from ``observations[b]`` (``[B, obs_dim]``)
+        through every member.  -> costs ``[sum rows]``; ``member_costs [E, sum rows]`` is kept.  One launch holds 32 problems:
+        B x E beyond that raises a ``ValueError`` (step fewer planners together)."""
+        import ctypes as C
+        import torch
+        from . import _lib as L
+        rows = [int(r) for r in rows]
+        if len(rows) * self.members > L.MLP_MAX_PROBLEMS:
+            raise ValueError(f"{len(rows)} planners x {self.members} members = {len(rows) * self.members} problems, but one "
+                             f"launch holds {L.MLP_MAX_PROBLEMS}: step at most {L.MLP_MAX_PROBLEMS // self.members} planners together")
+        rows, row0, observations = _check_problem_shapes(self.act_dim, len(rows), observations, actions, rows, None, self.obs_dim)
+        o = observations if isinstance(observations, torch.Tensor) else torch.as_tensor(observations, device=self.device)
+        actions = actions.to(torch.float32).contiguous()
+        B, total = len(rows), sum(rows)
+        member_costs = torch.empty((self.members, total), dtype=torch.float32, device=self.device)
+        ptrs = self._param_ptrs()
+        # member-major: problem e * B + b writes member_costs[e, row0[b] : row0[b] + rows[b]]
+        _mlp_models_launch(self, [ptrs[e] for e in range(self.members) for _ in range(B)], list(range(B)) * self.members,
+                           row0 * self.members, rows * self.members, o, B, actions, cost_mode, out=member_costs.view(-1))
+        costs = torch.empty((total,), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.icem_rssm_ensemble_reduce(self.members, total, L.RSSM_REDUCE[self.reduce], C.c_void_p(member_costs.data_ptr()),
+                                                   C.c_void_p(costs.data_ptr()), st))
+        self.member_costs = member_costs
+        return costs
+
+    def predict(self, *, observations, states, actions):
+        """Member 0's successor state (the reference-style interface returns one; the planning costs are the ensemble's)."""
+        return self.models[0].predict(observations=observations, states=states, actions=actions)

@@ -986,6 +986,41 @@ size_t icem_mlp_param_elems(int32_t obs_dim, int32_t act_dim, int32_t layers);
 int icem_mlp_rollout_cost(int32_t n, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
                           int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const void* params,
                           const void* obs0, const void* actions, void* costs, void* observations, void* stream);
+/* Problems with an MLP EACH in one launch of that rollout (icem_rssm_rollout_cost_models' layout with the MLP in the model's
+ * place): parallel episodes that each own a trained model, and the members of a PETS-style ensemble.  Problem p rolls the rows
+ * action_row0 .. action_row0 + rows of actions [n_action_rows, horizon, act_dim] (f32, device; the rows of different problems may
+ * overlap or coincide, and are only read) out from row obs_row of obs0 [n_obs, obs_dim] (f32, device) through its own packed
+ * parameter buffer (device; icem_mlp_param_elems() 16-bit words; the same buffer may serve several problems).  obs_dim, act_dim,
+ * layers, activation, horizon, cost_mode and the cost pair are the launch's, shared by all problems.  costs [sum rows] (f32):
+ * problem p's rows back to back in problem order (not rounded to tiles), observations (NULL, or [sum rows, horizon + 1, obs_dim])
+ * alike; every cost and every state bit for bit what icem_mlp_rollout_cost gives for that problem alone with its params.
+ * n_problems in [1, ICEM_MLP_MAX_PROBLEMS]; problems_host is read before the call returns (the problem table travels in the
+ * kernel arguments).  Nothing is allocated: the call may be captured into a graph from the first one on.
+ *   ICEM_E_INVALID: a NULL pointer or a NULL params entry, n_problems outside [1, 32], rows < 1, action_row0 < 0 or
+ * action_row0 + rows > n_action_rows, obs_row outside [0, n_obs), and what icem_mlp_rollout_cost calls invalid about
+ * cost_mode, the activation and the cost pair.  ICEM_E_UNSUPPORTED: its shape and horizon ranges (and 2^31 tiles or more).
+ * Whatever is refused is refused before anything is launched. */
+#define ICEM_MLP_MAX_PROBLEMS 32
+typedef struct icem_mlp_problem {
+    const void* params;   /* this problem's packed MLP (icem_mlp_param_elems() 16-bit words) */
+    int64_t action_row0;  /* its first row of `actions`; problems may overlap or coincide */
+    int32_t rows;         /* >= 1 */
+    int32_t obs_row;      /* its start observation: row of obs0 [n_obs, obs_dim] */
+} icem_mlp_problem;
+int icem_mlp_rollout_cost_models(int32_t n_problems, const icem_mlp_problem* problems_host, int32_t horizon, int32_t obs_dim,
+                                 int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, const icem_cost_spec* cost,
+                                 const icem_cost_terms* terms, const void* obs0, int32_t n_obs, const void* actions, int64_t n_action_rows,
+                                 void* costs, void* observations /* NULL or [sum rows, h + 1, obs_dim] */, void* stream);
+/* An ensemble of `members` MLPs (params_host [members]: host array of device pointers, read before the call returns) scores
+ * the SAME n rows of actions [n, horizon, act_dim] from one observation obs0 [obs_dim]: ONE models launch of `members` problems
+ * that share the action rows, then icem_rssm_ensemble_reduce (which knows nothing of the model; `reduce`: ICEM_RSSM_REDUCE_MEAN
+ * or _MAX).  member_costs [members, n] is an OUTPUT (row e: member e alone, bit for bit icem_mlp_rollout_cost with its params),
+ * costs [n] their reduction.  members == 1 gives the solo launch's bits in both.  Refusals as above (members outside [1, 32],
+ * n < 1, a bad reduce: ICEM_E_INVALID), before anything is launched; nothing is allocated. */
+int icem_mlp_rollout_cost_ensemble(int32_t members, const void* const* params_host, int32_t n, int32_t horizon, int32_t obs_dim,
+                                   int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, int32_t reduce,
+                                   const icem_cost_spec* cost, const icem_cost_terms* terms, const void* obs0, const void* actions,
+                                   void* member_costs /* [members, n], output */, void* costs /* [n] */, void* stream);
 
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action

@@ -3,7 +3,12 @@ the TorchForwardModel graph-replay path on the SAME module (h graph-replayed tor
 MpcICemHip.get_action on both models.  HalfCheetah shape (o = 17, d = 6, h = 30), N = 1024 and 4096, 2 and 4 hidden layers,
 relu and swish.  Both paths run in one process, alternating window by window; every shape is warmed up; a window is timed
 with device events and lasts at least 0.5 s; the line gives the median window and the spread (min .. max) per path.
-usage: python tools/mlp_bench.py [--windows 5] [--seconds 0.5]"""
+usage: python tools/mlp_bench.py [--windows 5] [--seconds 0.5]
+
+--models: several models in ONE launch against a launch each, same shape (2-layer relu and 4-layer swish, N = 1024 and 4096
+rows per model): DeviceMLPEnsemble.rollout_cost for E = 2, 5, 8 members against E DeviceMLPModel.rollout_cost calls + a torch
+mean, and mlp_rollout_cost_models for B = 4, 8 problems with a model each against B solo calls.  The two arms alternate window
+by window as above."""
 import argparse
 import os
 import sys
@@ -13,7 +18,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from icem_amd import DeviceMLPModel, MpcICemHip, TorchForwardModel, declared_mlp, halfcheetah_env  # noqa: E402
+from icem_amd import (DeviceMLPEnsemble, DeviceMLPModel, MpcICemHip, TorchForwardModel, declared_mlp, halfcheetah_env,  # noqa: E402
+                      mlp_rollout_cost_models)
 
 O, D, H = 17, 6, 30
 DEV = "cuda:0"
@@ -55,14 +61,58 @@ def fmt(v):
     return f"{np.median(v):9.1f} us ({min(v):.1f} .. {max(v):.1f})"
 
 
+def models_bench(args):
+    """One launch for several models against a launch per model."""
+    rs = np.random.RandomState(0)
+    obs = 0.1 * rs.randn(O)
+    for layers, act in ((2, "relu"), (4, "swish")):
+        members = []
+        for seed in range(8):
+            net = declared_mlp(O, D, layers=layers, activation=act, seed=seed, device="cpu").module
+            with torch.no_grad():
+                net.out.weight.mul_(0.1)   # keeps the random network's state bounded over 30 steps
+            members.append(DeviceMLPModel(module=net, env=halfcheetah_env(O), device=DEV))
+        for N in (1024, 4096):
+            actions = torch.as_tensor(rs.uniform(-1, 1, (N, H, D)), dtype=torch.float32, device=DEV)
+            for E in (2, 5, 8):
+                ens = DeviceMLPEnsemble(models=members[:E])
+                fns = {"one": lambda: ens.rollout_cost(obs, actions),
+                       "each": lambda: torch.stack([m.rollout_cost(obs, actions) for m in members[:E]]).mean(0)}
+                for fn in fns.values():
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                assert torch.equal(ens.member_costs, torch.stack([m.rollout_cost(obs, actions) for m in members[:E]]))
+                r = alternate(fns, args.windows, args.seconds)
+                print(f"ensemble  L={layers} {act:5s} N={N:5d} E={E}  one launch + reduce {fmt(r['one'])}  E launches + torch mean {fmt(r['each'])}  "
+                      f"ratio {np.median(r['each']) / np.median(r['one']):5.2f}", flush=True)
+            for B in (4, 8):
+                many = torch.as_tensor(rs.uniform(-1, 1, (B * N, H, D)), dtype=torch.float32, device=DEV)
+                slices = [many[b * N:(b + 1) * N] for b in range(B)]
+                obs_dev = torch.as_tensor(np.tile(obs.astype(np.float32), (B, 1)), device=DEV)
+                fns = {"one": lambda: mlp_rollout_cost_models(members[:B], obs_dev, many, [N] * B),
+                       "each": lambda: [m.rollout_cost(obs, a) for m, a in zip(members[:B], slices)]}
+                for fn in fns.values():
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                assert torch.equal(fns["one"](), torch.cat(fns["each"]()))
+                r = alternate(fns, args.windows, args.seconds)
+                print(f"models    L={layers} {act:5s} N={N:5d} B={B}  one launch {fmt(r['one'])}  B launches {fmt(r['each'])}  "
+                      f"ratio {np.median(r['each']) / np.median(r['one']):5.2f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--models", action="store_true", help="several models in one launch against a launch each")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     obs = 0.1 * rs.randn(O)
     print(f"# {torch.cuda.get_device_name(0)}; o={O} d={D} h={H}; {args.windows} windows of >= {args.seconds} s per path, alternating", flush=True)
+    if args.models:
+        return models_bench(args)
     for layers in (2, 4):
         for act in ("relu", "swish"):
             net = declared_mlp(O, D, layers=layers, activation=act, seed=0, device="cpu").module
