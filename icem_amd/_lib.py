@@ -97,6 +97,12 @@ class IcemMlpProblemC(C.Structure):
     _fields_ = [("params", C.c_void_p), ("action_row0", C.c_int64), ("rows", C.c_int32), ("obs_row", C.c_int32)]
 
 
+class IcemMlpStepModelC(C.Structure):
+    """include/icem_hip.h: struct icem_mlp_step_model."""
+    _fields_ = [("obs_dim", C.c_int32), ("layers", C.c_int32), ("activation", C.c_int32),
+                ("cost", C.POINTER(IcemCostSpecC)), ("terms", C.POINTER(IcemCostTermsC))]
+
+
 RSSM_REDUCE = {"mean": 0, "max": 1}   # include/icem_hip.h: ICEM_RSSM_REDUCE_*
 RSSM_BATCH_MAX = 32                   # problems / members of one learned-dynamics launch
 MLP_ACTIVATIONS = {"relu": 0, "swish": 1}   # include/icem_hip.h: ICEM_MLP_RELU / ICEM_MLP_SWISH
@@ -234,6 +240,10 @@ SYMBOLS = [
     ("icem_plan_step_learned_models_ok", C.c_int, [_H, _I32, _I32]),
     ("icem_plan_step_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), _I32, C.POINTER(_VP), _I32,
                                                 C.POINTER(_I32), _VP, _VP, _VP]),
+    ("icem_plan_step_mlp_ok", C.c_int, [_H, _I32, _I32]),
+    ("icem_plan_step_mlp", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemPlanBuffersC), C.POINTER(IcemMlpStepModelC), _I32, C.POINTER(_VP), _I32,
+                                     C.POINTER(_I32), _VP, _VP, _VP]),
+    ("icem_mlp_step_launches", C.c_int64, [_H]),
     ("icem_plan_step_cem_learned_models_ok", C.c_int, [_H, _I32, _I32]),
     ("icem_plan_step_cem_learned_models", C.c_int, [C.POINTER(_H), _I32, C.POINTER(IcemCemBuffersC), C.POINTER(IcemCemParamsC), _I32,
                                                     C.POINTER(_VP), _I32, C.POINTER(_I32), _VP, _VP, _VP]),

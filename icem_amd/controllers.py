@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .envs import Box, Discrete
-from .models import DeviceSyntheticModel, TrajectoryBatch, rssm_rollout_cost_models
+from .models import DeviceSyntheticModel, TrajectoryBatch, mlp_rollout_cost_models, rssm_rollout_cost_models
 from .planner import IcemConfig, IcemPlanner
 from ._lib import COST_MODES as L_COST_MODES
 
@@ -344,6 +344,27 @@ class MpcController(ModelBasedController, StatefulController, ABC):
                 and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
                 and m.params.device == self.planner.device)
 
+    def _model_is_the_library_mlp(self) -> bool:
+        """:meth:`_model_is_the_library_rssm`'s rule for ``icem_plan_step_mlp``: the model is a ``DeviceMLPModel`` whose
+        ``rollout_cost`` is the class's own and which was given no ``rollout_cost_batch``, on the type or on the instance --
+        an instrumented model is called stage by stage, as it asks to be."""
+        from .models import DeviceMLPModel
+        m = self.forward_model
+        return (isinstance(m, DeviceMLPModel) and type(m).rollout_cost is DeviceMLPModel.rollout_cost
+                and getattr(type(m), "rollout_cost_batch", None) is None
+                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
+                and m.params.device == self.planner.device)
+
+    def _model_is_the_library_mlp_ensemble(self) -> bool:
+        """... and :meth:`_model_is_the_library_ensemble`'s: a ``DeviceMLPEnsemble`` whose ``rollout_cost`` /
+        ``rollout_cost_batch`` are the class's own, on the type and on the instance."""
+        from .models import DeviceMLPEnsemble
+        m = self.forward_model
+        return (isinstance(m, DeviceMLPEnsemble) and type(m).rollout_cost is DeviceMLPEnsemble.rollout_cost
+                and type(m).rollout_cost_batch is DeviceMLPEnsemble.rollout_cost_batch
+                and "rollout_cost" not in vars(m) and "rollout_cost_batch" not in vars(m)
+                and m.params.device == self.planner.device)
+
     def _steps_through_an_ensemble(self) -> bool:
         """The fused step of this (baseline) controller is the one through models of their own: its model is the library's
         own ensemble (``icem_plan_step_cem_learned_models`` / ``icem_plan_step_random_learned_models``)."""
@@ -624,6 +645,8 @@ class MpcICemHip(MpcController):
             executed_action = self._get_action_learned(obs)   # the whole step one library call (icem_plan_step_learned)
         elif self._learned_models_ok(noise, 1):
             executed_action = self._get_action_learned_models(obs)   # ... through an ensemble (icem_plan_step_learned_models)
+        elif self._mlp_step_ok(noise, 1):
+            executed_action = self._get_action_mlp(obs)   # ... through a DeviceMLPModel / DeviceMLPEnsemble (icem_plan_step_mlp)
         else:
             executed_action = self._get_action_stagewise(obs, noise)
         return self._finish_action(obs, executed_action)
@@ -664,7 +687,10 @@ class MpcICemHip(MpcController):
         where it serves them (``IcemPlanner.learned_models_step_ok``): the whole step in the library, 3 launches per iteration
         for all controllers and members, the same bits; an ensemble whose rollout was instrumented is still called stage by
         stage; controllers that each own an ENSEMBLE (one size, one reduction) are served by the same entry with ``own_models=True``
-        where it serves the batch, and refused elsewhere.  Without the
+        where it serves the batch, and refused elsewhere.  Controllers on the feed-forward model go the same way through
+        ``icem_plan_step_mlp`` (``IcemPlanner.mlp_step_ok``): those that share one ``DeviceMLPEnsemble``, and with
+        ``own_models=True`` those with a ``DeviceMLPModel`` each or a ``DeviceMLPEnsemble`` each; controllers that share one
+        plain ``DeviceMLPModel`` are refused (it has no ``rollout_cost_batch``: share an ensemble of one).  Without the
         keyword, controllers whose parameter buffers differ are refused as they always were: two copies of one model are
         more often a mistake than a wish.  Anything else: call ``get_action`` per controller."""
         ctrls = list(controllers)
@@ -692,6 +718,12 @@ class MpcICemHip(MpcController):
         elif rssm and not shared and all(c._learned_models_ok(None, n) for c in ctrls):
             # a plain model each (own_models=True, or the batch was refused above): the same entry with one member per problem
             host = MpcICemHip._get_action_batch_learned_models(ctrls, observations, [c.forward_model for c in ctrls])
+        elif shared and all(c.forward_model is ctrls[0].forward_model and c._mlp_step_ok(None, n) for c in ctrls):
+            # one DeviceMLPEnsemble for all of them: icem_plan_step_mlp, the members' pointers repeated per problem
+            host = MpcICemHip._get_action_batch_mlp(ctrls, observations, ctrls[0].forward_model)
+        elif rssm and not shared and all(c._mlp_step_ok(None, n) for c in ctrls):
+            # a DeviceMLPModel or a DeviceMLPEnsemble each (own_models=True): the same entry, every problem its own pointers
+            host = MpcICemHip._get_action_batch_mlp(ctrls, observations, [c.forward_model for c in ctrls])
         elif rssm:
             host = MpcICemHip._get_action_batch_rssm(ctrls, observations)
         else:
@@ -918,6 +950,54 @@ class MpcICemHip(MpcController):
             c._elites_from_planner()
         return results.cpu().numpy().astype(np.float64)
 
+    # -- ... and through the feed-forward model (icem_plan_step_mlp): a DeviceMLPModel, a DeviceMLPEnsemble, one of either each
+    def _mlp_step_ok(self, noise, n) -> bool:
+        """Does ``icem_plan_step_mlp`` serve ``n`` controllers like this one through the library's own ``DeviceMLPModel`` /
+        ``DeviceMLPEnsemble`` they plan with?"""
+        if not (self.rssm_path and not self.device_path and noise is None and self.planner.cfg.world == 1 and not self.verbose):
+            return False
+        if self._model_is_the_library_mlp_ensemble():
+            members = self.forward_model.members
+        elif self._model_is_the_library_mlp():
+            members = 1
+        else:
+            return False
+        return self.planner.mlp_step_ok(n, members, self.forward_model)
+
+    def _get_action_mlp(self, obs):
+        from ._lib import IcemError, ICEM_E_UNSUPPORTED
+        self._elites_into_planner()
+        try:
+            results = IcemPlanner.plan_step_mlp([self.planner], self.forward_model, [obs])
+        except IcemError as e:
+            if e.code != ICEM_E_UNSUPPORTED:
+                raise
+            return self._get_action_stagewise(obs, None)   # (refused before anything ran)
+        self._elites_from_planner()
+        host = results[0].cpu().numpy().astype(np.float64)   # one device-to-host copy, one synchronisation
+        self.last_min_cost = float(host[-1])
+        return host[:-1]
+
+    @staticmethod
+    def _get_action_batch_mlp(ctrls, observations, models):
+        """-> [B, d + 1] host array of executed actions and best costs (one device-to-host copy, one synchronisation); a
+        batch the entry does not serve as a whole steps stage-wise, as :meth:`_get_action_batch_learned_models`' does."""
+        from ._lib import IcemError, ICEM_E_UNSUPPORTED
+        for c in ctrls:
+            c._elites_into_planner()
+        try:
+            results = IcemPlanner.plan_step_mlp([c.planner for c in ctrls], models, observations)
+        except IcemError as e:
+            if e.code != ICEM_E_UNSUPPORTED:
+                raise
+            if IcemPlanner._ensembles_each(models):   # (the stage-wise step has no launch for an ensemble each)
+                raise NotImplementedError(f"get_action_batch: the library does not serve these controllers with an ensemble each ({e}); "
+                                          "call get_action per controller") from e
+            return MpcICemHip._get_action_batch_rssm(ctrls, observations)   # (refused before anything ran)
+        for c in ctrls:
+            c._elites_from_planner()
+        return results.cpu().numpy().astype(np.float64)
+
     @staticmethod
     def _share_params(m, m0) -> bool:
         return m is m0 or (m.params.data_ptr() == m0.params.data_ptr() and m.params.numel() == m0.params.numel())
@@ -929,7 +1009,11 @@ class MpcICemHip(MpcController):
         c0 = ctrls[0]
         if not all(c.rssm_path for c in ctrls):
             return "learned-dynamics controllers cannot be mixed with controllers of another path"
-        if not all(hasattr(c.forward_model, "rollout_cost_batch") for c in ctrls):
+        # (a DeviceMLPModel has none: controllers with one EACH step through icem_plan_step_mlp -- or, where that refuses,
+        #  around mlp_rollout_cost_models -- on request; controllers that share one are refused as they always were)
+        mlp_each = (own_models and all(k._model_is_the_library_mlp() for k in ctrls)
+                    and not all(MpcICemHip._share_params(k.forward_model, c0.forward_model) for k in ctrls))
+        if not mlp_each and not all(hasattr(c.forward_model, "rollout_cost_batch") for c in ctrls):
             return "the learned-dynamics model has no rollout_cost_batch"
         for c in ctrls:
             if c._noise_fn() is not None or c.planner.cfg.world != 1 or c.verbose:
@@ -939,14 +1023,18 @@ class MpcICemHip(MpcController):
                 # a model each: served on request while every model is the library's own RSSM (one launch reads B parameter buffers)
                 # -- or every model the library's own ensemble, where icem_plan_step_learned_models serves the batch (the stage-wise
                 # step has no launch for an ensemble each)
-                each_ens = all(k._model_is_the_library_ensemble() for k in ctrls)
-                if not own_models or not (each_ens or all(k._model_is_the_library_rssm() for k in ctrls)):
+                mlp_ens = all(k._model_is_the_library_mlp_ensemble() for k in ctrls)
+                each_ens = mlp_ens or all(k._model_is_the_library_ensemble() for k in ctrls)
+                if not own_models or not (each_ens or mlp_each or all(k._model_is_the_library_rssm() for k in ctrls)):
                     return ("learned-dynamics controllers must share one parameter buffer (the same DeviceRSSMModel, or the same params "
                             "storage); controllers with a plain DeviceRSSMModel each, or a DeviceRSSMEnsemble each, are stepped together "
                             "with own_models=True")
                 if each_ens and (m.members != m0.members or m.reduce != m0.reduce):
                     return "learned-dynamics controllers with an ensemble each need ensembles of one size and one reduction"
-                if each_ens and not all(k._learned_models_ok(None, len(ctrls)) for k in ctrls):
+                if mlp_ens and not all(k._mlp_step_ok(None, len(ctrls)) for k in ctrls):
+                    return ("the library does not serve these controllers with an ensemble each in one call "
+                            "(IcemPlanner.mlp_step_ok): call get_action per controller")
+                if each_ens and not mlp_ens and not all(k._learned_models_ok(None, len(ctrls)) for k in ctrls):
                     return ("the library does not serve these controllers with an ensemble each in one call "
                             "(IcemPlanner.learned_models_step_ok): call get_action per controller")
                 if m.act_dim != m0.act_dim or m.params.device != m0.params.device:
@@ -971,9 +1059,9 @@ class MpcICemHip(MpcController):
             slices = list(torch.split(actions, rows))
             for c, a in zip(ctrls, slices):
                 c._stage_sample(i, None, a)
-            if own:
-                costs = rssm_rollout_cost_models([c.forward_model for c in ctrls], obs_dev, actions, rows, None,
-                                                 L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
+            if own:   # (the library's RSSM each, or its MLP each)
+                costs = (mlp_rollout_cost_models if ctrls[0]._model_is_the_library_mlp() else rssm_rollout_cost_models)(
+                    [c.forward_model for c in ctrls], obs_dev, actions, rows, None, L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
             else:
                 costs = m.rollout_cost_batch(obs_dev, actions, rows, L_COST_MODES[p0.cfg.cost_mode]).to(p0.dt)
             for c, a, k in zip(ctrls, slices, torch.split(costs, rows)):

@@ -177,6 +177,32 @@ int rssm_launch_result(hipError_t e) {
     return ICEM_OK;
 }
 
+// what every MLP rollout entry checks of the launch's own arguments (`who` names the entry in the message): the modes, the
+// shape and horizon ranges, the cost pair -- icem_plan_step_mlp (learned_step.hip) asks the same of its model.  -> ICEM_OK with *on = the term list that is switched on (or NULL)
+int admit_mlp_launch(const char* who, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
+                     int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const icem_cost_terms** on) {
+    auto say = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return say(ICEM_E_INVALID, "bad cost_mode");
+    if (activation != ICEM_MLP_RELU && activation != ICEM_MLP_SWISH) return say(ICEM_E_INVALID, "activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
+    if (obs_dim < 1 || obs_dim > mlp::OBS_MAX) return say(ICEM_E_UNSUPPORTED, "obs_dim must be in [1, 64]");
+    if (act_dim < 1 || act_dim > mlp::ACT_MAX) return say(ICEM_E_UNSUPPORTED, "act_dim must be in [1, 32]");
+    if (layers < 1 || layers > mlp::LAYERS_MAX) return say(ICEM_E_UNSUPPORTED, "layers must be in [1, 4]");
+    if (horizon < 1 || horizon > ICEM_MAX_HORIZON) return say(ICEM_E_UNSUPPORTED, "horizon must be in [1, 64]");
+    if (terms != nullptr) {   // icem_set_cost_terms' rules
+        if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return say(ICEM_E_INVALID, "n_terms must be in [0, 8]");
+        for (int j = 0; j < terms->n_terms; ++j) {
+            const icem_cost_term& tm = terms->terms[j];
+            if (tm.kind < ICEM_TERM_NORM || tm.kind > ICEM_TERM_STEP_GT) return say(ICEM_E_INVALID, "unknown cost term kind");
+            if (tm.len < 1 || tm.len > ICEM_MAX_TERM_LEN) return say(ICEM_E_INVALID, "cost term len must be in [1, 64]");
+        }
+        if (terms->box_from >= 0 && terms->health_idx < 0)
+            return say(ICEM_E_INVALID, "box_from is part of the health term: health_idx must be set");
+    }
+    *on = cost_terms_on(terms) ? terms : nullptr;
+    if (const char* e = cost_indices_error(*cost, *on, obs_dim)) return say(ICEM_E_INVALID, e);
+    return ICEM_OK;
+}
+
 }  // namespace icem
 
 // what icem_profile_overhead times: one wave that spins for `ticks` of the 100 MHz wall clock and reports how long it
@@ -939,32 +965,6 @@ static_assert(mlp::OBS_MAX == ICEM_MLP_MAX_OBS_DIM && mlp::ACT_MAX == ICEM_MLP_M
               "the kernel's ranges are the header's");
 
 size_t icem_mlp_param_elems(int32_t obs_dim, int32_t act_dim, int32_t layers) { return mlp::param_units(obs_dim, act_dim, layers); }
-
-// what every MLP rollout entry checks of the launch's own arguments (`who` names the entry in the message): the modes, the
-// shape and horizon ranges, the cost pair.  -> ICEM_OK with *on = the term list that is switched on (or NULL)
-static int admit_mlp_launch(const char* who, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
-                            int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const icem_cost_terms** on) {
-    auto say = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
-    if (cost_mode < ICEM_COST_SUM || cost_mode > ICEM_COST_FINAL) return say(ICEM_E_INVALID, "bad cost_mode");
-    if (activation != ICEM_MLP_RELU && activation != ICEM_MLP_SWISH) return say(ICEM_E_INVALID, "activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
-    if (obs_dim < 1 || obs_dim > mlp::OBS_MAX) return say(ICEM_E_UNSUPPORTED, "obs_dim must be in [1, 64]");
-    if (act_dim < 1 || act_dim > mlp::ACT_MAX) return say(ICEM_E_UNSUPPORTED, "act_dim must be in [1, 32]");
-    if (layers < 1 || layers > mlp::LAYERS_MAX) return say(ICEM_E_UNSUPPORTED, "layers must be in [1, 4]");
-    if (horizon < 1 || horizon > ICEM_MAX_HORIZON) return say(ICEM_E_UNSUPPORTED, "horizon must be in [1, 64]");
-    if (terms != nullptr) {   // icem_set_cost_terms' rules
-        if (terms->n_terms < 0 || terms->n_terms > ICEM_MAX_COST_TERMS) return say(ICEM_E_INVALID, "n_terms must be in [0, 8]");
-        for (int j = 0; j < terms->n_terms; ++j) {
-            const icem_cost_term& tm = terms->terms[j];
-            if (tm.kind < ICEM_TERM_NORM || tm.kind > ICEM_TERM_STEP_GT) return say(ICEM_E_INVALID, "unknown cost term kind");
-            if (tm.len < 1 || tm.len > ICEM_MAX_TERM_LEN) return say(ICEM_E_INVALID, "cost term len must be in [1, 64]");
-        }
-        if (terms->box_from >= 0 && terms->health_idx < 0)
-            return say(ICEM_E_INVALID, "box_from is part of the health term: health_idx must be set");
-    }
-    *on = cost_terms_on(terms) ? terms : nullptr;
-    if (const char* e = cost_indices_error(*cost, *on, obs_dim)) return say(ICEM_E_INVALID, e);
-    return ICEM_OK;
-}
 
 int icem_mlp_rollout_cost(int32_t n, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
                           int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const void* params,

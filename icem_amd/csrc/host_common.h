@@ -61,6 +61,7 @@ struct LearnedCtx {
     int pool_n = 0;
     int* idx = nullptr;                      // [ICEM_MAX_BATCH, ICEM_MAX_ELITES]: the updates' index output (not kept)
     long long launches = 0;                  // kernel launches of the last learned step this handle led
+    long long mlp_launches = 0;              // ... and of the last icem_plan_step_mlp
     // the pool of a batch of n problems with cap_rows rows in all (icem_plan_step_learned_batch, icem_plan_step_cem_learned_batch:
     // both lay it out as above); it only grows, behind a synchronisation of `st` (an earlier step's launches may still use the old one)
     hipError_t reserve(size_t cap_rows, int n, int hd, hipStream_t st) {
@@ -501,6 +502,9 @@ int launch_fast_rollout(icem_handle* h, int n_rows, int n_cand, int K, const voi
                         void* costs, float* part_c, int* part_i, const LaunchCtx& cx, int* lists_out,
                         unsigned long long* part_k = nullptr, int n_tail = 0, int* tail_out = nullptr);
 int rssm_launch_result(hipError_t e);   // abi.hip: a learned-dynamics launch's HIP result as an ICEM_* code (+ message)
+// abi.hip: what every MLP rollout entry (and icem_plan_step_mlp) checks of a launch's own arguments; *on = the term list switched on
+int admit_mlp_launch(const char* who, int32_t horizon, int32_t obs_dim, int32_t act_dim, int32_t layers, int32_t activation,
+                     int32_t cost_mode, const icem_cost_spec* cost, const icem_cost_terms* terms, const icem_cost_terms** on);
 // abi.hip: the launch icem_rollout_cost picks for this handle (the matrix-pipe rollout where it serves the handle and no
 // observations are asked for, else the generic one) -- icem_plan_step_cem (cem_step.hip) rolls out through the same dispatch, and
 // icem_plan_step_cem_batch records it (cx.rec: nothing is launched)

@@ -23,8 +23,17 @@
 // the update is update_small_members_batch_kernel, which reduces the members' costs while it builds its keys -- still 3
 // launches per iteration, and the same code below (StepModels, step_models.h: shared with the two baselines' steps through such
 // models, cem_step.hip and random_step.hip).
+//
+// icem_plan_step_mlp is that models step with the feed-forward model (icem_mlp.h) in the RSSM's place: the rollout of an
+// iteration is ONE launch_mlp_rollout_models of n * members problems in the same member-major order, the observation table is
+// [n, obs_dim], and neither the RSSM's staging area nor its status word nor a handle's RSSM binding is involved.  Everything
+// else -- the sampler, the shifted rows, the updates with the members' reduction and the epilogue, the argument blocks -- is the
+// code below as it stands (StepMlp switches the rollout and what "served" asks), so a controller may alternate between this
+// step, the RSSM steps and the stage-wise loop on one handle.
 #include "block_layout.h"
+#include "cost_terms_dev.h"
 #include "host_common.h"
+#include "icem_mlp.h"
 #include "icem_rssm.h"
 #include "step_models.h"
 
@@ -38,14 +47,22 @@ int max_rows(const icem_handle* h) {
     return m;
 }
 
-// the per-handle part of "who is served" (nullptr: this handle is)
-const char* learned_unserved(const icem_handle* h) {
+// the rollout of icem_plan_step_mlp: the model's shape (act_dim is the handles') and the launch's cost
+struct StepMlp {
+    int obs_dim, layers, activation;
+    CostArgs<float> cs;
+};
+
+// the per-handle part of "who is served" (nullptr: this handle is) -- rssm: by the steps through the declared RSSM, which ask
+// for its action width and the split launch on top of what every step below needs; else by icem_plan_step_mlp
+const char* step_unserved(const icem_handle* h, bool rssm) {
     const icem_config& c = h->cfg;
-    if (opt_i(OPT_LEARNED_STEP) == 0) return "option learned_step is 0";
+    if (rssm && opt_i(OPT_LEARNED_STEP) == 0) return "option learned_step is 0";
+    if (!rssm && opt_i(OPT_MLP_STEP) == 0) return "option mlp_step is 0";
     if (c.dtype != ICEM_F32) return "dtype f32 only";
     if (c.world != 1) return "world must be 1";
     // (a handle bound to an RSSM of its own width -- icem_set_rssm_act_dim, which takes no other -- passes; one never bound is served at 6)
-    if (c.act_dim != rssm_width(h)) return "the declared RSSM takes 6 action dimensions";
+    if (rssm && c.act_dim != rssm_width(h)) return "the declared RSSM takes 6 action dimensions";
     if (!h->use_fast) return "the handle's fast path is off";
     if (h->profiling) return "per-kernel profiling is per launch of one handle: switch it off";
     if (!fast_sample_supported(c.horizon, c.act_dim) || c.horizon > 32)
@@ -54,26 +71,29 @@ const char* learned_unserved(const icem_handle* h) {
     if (c.rng_rounds != 10) return "the batched sampler is compiled for the default generator (rng_rounds 10)";
     if ((int)h->pop.size() != c.opt_iters || c.opt_iters < 1) return "opt_iters";
     if (!topk_small_ok(max_rows(h) + std::max(0, h->n_reuse), c.num_elites)) return "the one-launch update does not take this pool / num_elites (<= 16384 candidates, <= 32 elites)";
-    if (!rssm_split_ok(max_rows(h), c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
+    if (rssm && !rssm_split_ok(max_rows(h), c.horizon)) return "the population's tiles exceed the split launch's limit, or the split launch is switched off";
     return nullptr;
 }
+const char* learned_unserved(const icem_handle* h) { return step_unserved(h, true); }
 
+// mlp (with mo): the step of icem_plan_step_mlp; who: the entry's name + ": " in front of the refusals
 int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* buffers, const void* params, const int32_t* steps,
-                 void* results, hipStream_t st, const StepModels* mo = nullptr) {
+                 void* results, hipStream_t st, const StepModels* mo = nullptr, const StepMlp* mlp = nullptr,
+                 const std::string& who = "icem_plan_step_learned: ") {
     icem_handle* h0 = handles[0];
     const icem_config& c = h0->cfg;
     const int H = c.horizon, d = c.act_dim, hd = h0->hd, K = c.num_elites, iters = c.opt_iters, n_reuse = std::max(0, h0->n_reuse);
     // ---- refusals: all of them before anything is launched or any handle touched ----
     for (int i = 0; i < n; ++i) {
-        if (steps[i] < 0) return fail(ICEM_E_INVALID, "icem_plan_step_learned: negative mpc_step");
+        if (steps[i] < 0) return fail(ICEM_E_INVALID, who + "negative mpc_step");
         const icem_plan_buffers& b = buffers[i];
         if (!b.mean || !b.std || !b.low || !b.high || !b.obs0 || !b.actions || !b.costs || !b.elites || !b.executed || !b.best_cost)
-            return fail(ICEM_E_INVALID, "icem_plan_step_learned: null buffer (mean, std, low, high, obs0, actions, costs, elites, executed, best_cost)");
+            return fail(ICEM_E_INVALID, who + "null buffer (mean, std, low, high, obs0, actions, costs, elites, executed, best_cost)");
     }
     for (int i = 0; i < n; ++i) {
-        if (const char* why = learned_unserved(handles[i])) return fail(ICEM_E_UNSUPPORTED, std::string("icem_plan_step_learned: ") + why);
+        if (const char* why = step_unserved(handles[i], mlp == nullptr)) return fail(ICEM_E_UNSUPPORTED, who + why);
         const icem_plan_buffers& b = buffers[i];
-        if (b.z_r || b.z_i || b.z_r_shift || b.z_i_shift) return fail(ICEM_E_UNSUPPORTED, "icem_plan_step_learned: external noise (z_*) is not served");
+        if (b.z_r || b.z_i || b.z_r_shift || b.z_i_shift) return fail(ICEM_E_UNSUPPORTED, who + "external noise (z_*) is not served");
     }
     // rows of every problem and iteration; the largest launch's tiles
     std::vector<int> rows((size_t)iters * n), all_rows((size_t)iters);
@@ -86,8 +106,14 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             all += rows[(size_t)it * n + p];
             shift_max = std::max(shift_max, shift_rows(handles[p], steps[p], it));
         }
-        int tiles;
-        if (mo) {
+        int tiles = 0;
+        if (mlp) {   // (no staging area to fit: the grid's x extent is the limit)
+            long long wgs = 0;
+            for (int p = 0; p < n; ++p) wgs += (rows[(size_t)it * n + p] + 15) / 16;
+            if (wgs * mo->members > mlp::WORKGROUPS_MAX)
+                return fail(ICEM_E_UNSUPPORTED, who + "the tiles of an iteration (members x the sum over the problems of ceil(rows / 16)) exceed "
+                                                      "one launch's grid; nothing was launched");
+        } else if (mo) {
             rssm::Problem pr[rssm::BATCH_MAX];
             models_problems(*mo, n, &rows[(size_t)it * n], pr);
             tiles = rssm_models_tiles(n * mo->members, pr);
@@ -105,7 +131,8 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         all_rows[it] = (int)all;
     }
     // the rollout's staging area and its host-visible status word, BEFORE the first launch: a refused step leaves everything as it was
-    if (int rc = rssm_launch_result(rssm_split_prepare(tiles_max, H, st))) return rc;
+    if (!mlp)
+        if (int rc = rssm_launch_result(rssm_split_prepare(tiles_max, H, st))) return rc;
     // ---- the step's own memory (first call, or a larger batch than before) ----
     LearnedCtx* ctx = &h0->learned;
     if (!ctx->idx) ICEM_HIP_TRY(hipMalloc((void**)&ctx->idx, (size_t)ICEM_MAX_BATCH * ICEM_MAX_ELITES * sizeof(int)));
@@ -187,7 +214,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
     // ---- the launches ----
     const unsigned char* dev = (const unsigned char*)ctx->args.dev(slot);
     long long launches = 0;
-    ctx->launches = 0;
+    (mlp ? ctx->mlp_launches : ctx->launches) = 0;
     LaunchKey sk;   // the sampler's: the grid's x extent is the largest problem's (all of them draw pop[it] rows)
     sk.family = LAUNCH_SAMPLE, sk.h = H, sk.d = d, sk.form = 10;
     for (int it = 0; it < iters; ++it) {
@@ -195,7 +222,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         if (n > 1 && it == 0) {
             for (int p = 0; p < n; ++p) og.src[p] = (const float*)buffers[p].obs0;
             og.dst = pool_o;
-            og.width = rssm::DET + rssm::STOCH;
+            og.width = mlp ? mlp->obs_dim : rssm::DET + rssm::STOCH;
         }
         sk.wgs[0] = sample_row_workgroups(h0->pop[it], d);
         launch_sample_batch(sk, (const FastSampleArgs*)(dev + per_it * it), bases, og, n, st);
@@ -206,7 +233,13 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
             ++launches;
         }
         hipError_t e;
-        if (mo) {
+        if (mlp) {
+            mlp::Problem pr[mlp::PROBLEMS_MAX];
+            models_problems(*mo, n, &rows[(size_t)it * n], pr);
+            e = launch_mlp_rollout_models(n * mo->members, pr, H, mlp->obs_dim, d, mlp->layers, mlp->activation, c.cost_mode, mlp->cs,
+                                          n == 1 ? (const float*)buffers[0].obs0 : pool_o, n == 1 ? (const float*)buffers[0].actions : pool_a,
+                                          member_costs, nullptr, st);
+        } else if (mo) {
             rssm::Problem pr[rssm::BATCH_MAX];
             models_problems(*mo, n, &rows[(size_t)it * n], pr);
             e = launch_rssm_split_models(n * mo->members, pr, H, d, c.cost_mode, n == 1 ? (const float*)buffers[0].obs0 : pool_o,
@@ -223,7 +256,7 @@ int learned_step(icem_handle* const* handles, int n, const icem_plan_buffers* bu
         ICEM_HIP_TRY(hipGetLastError());
         ++launches;
     }
-    ctx->launches = launches;
+    (mlp ? ctx->mlp_launches : ctx->launches) = launches;
     return ICEM_OK;
 }
 
@@ -269,5 +302,39 @@ int icem_plan_step_learned_models(icem_handle* const* handles, int32_t n, const 
     const StepModels mo{members, reduce, params_host, (float*)member_costs};
     return learned_step(handles, n, buffers, nullptr, mpc_steps_host, results, (hipStream_t)stream, &mo);
 }
+
+static_assert(mlp::PROBLEMS_MAX == rssm::BATCH_MAX, "models_args_refusal's limit is both launches' problem table");
+
+int icem_plan_step_mlp_ok(const icem_handle* h, int32_t n, int32_t members) {
+    if (!h || step_unserved(h, false) || n < 1 || n > ICEM_MAX_BATCH || members < 1 || members > mlp::PROBLEMS_MAX || n * members > mlp::PROBLEMS_MAX)
+        return 0;
+    if (h->cfg.act_dim > mlp::ACT_MAX) return 0;
+    return (long long)n * members * ((max_rows(h) + 15) / 16) <= mlp::WORKGROUPS_MAX ? 1 : 0;
+}
+
+int icem_plan_step_mlp(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const icem_mlp_step_model* model,
+                       int32_t members, const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host, void* member_costs,
+                       void* results, void* stream) {
+    const std::string who = "icem_plan_step_mlp: ";
+    // (what the counts, the table and the model's own fields decide comes first: no handle has been looked at)
+    if (int rc = models_args_refusal(who, handles && buffers && model && mpc_steps_host, n, members, params_host, reduce)) return rc;
+    if (!model->cost) return fail(ICEM_E_INVALID, who + "null cost");
+    if (model->activation != ICEM_MLP_RELU && model->activation != ICEM_MLP_SWISH)
+        return fail(ICEM_E_INVALID, who + "activation must be ICEM_MLP_RELU or ICEM_MLP_SWISH");
+    if (!mlp::shape_ok(model->obs_dim, 1, model->layers)) return fail(ICEM_E_UNSUPPORTED, who + "obs_dim must be in [1, 64] and layers in [1, 4]");
+    if (int rc = admit_batch(handles, n, true, true, who.c_str(), "icem_plan_step_mlp: the handles must share one configuration (everything but the seed)"))
+        return rc;
+    const icem_config& c = handles[0]->cfg;
+    const icem_cost_terms* on = nullptr;
+    if (int rc = admit_mlp_launch("icem_plan_step_mlp", c.horizon, model->obs_dim, c.act_dim, model->layers, model->activation, c.cost_mode,
+                                  model->cost, model->terms, &on))
+        return rc;
+    StepMlp ml{model->obs_dim, model->layers, model->activation, {}};
+    fill_cost_args_f32(*model->cost, on, ml.cs);
+    const StepModels mo{members, reduce, params_host, (float*)member_costs};
+    return learned_step(handles, n, buffers, nullptr, mpc_steps_host, results, (hipStream_t)stream, &mo, &ml, who);
+}
+
+int64_t icem_mlp_step_launches(const icem_handle* h) { return h ? (int64_t)h->learned.mlp_launches : 0; }
 
 }  // extern "C"

@@ -38,6 +38,7 @@ namespace icem {
     X(BATCH_AHEAD_MIN_ROWS, "batch_ahead_min_rows", 49152.0)   /* ... from this many rows of all problems' first iterations together */ \
     X(BATCH_MAX_RW, "batch_max_rw", 0.0)             /* icem_plan_step_batch: cap of the tiles per workgroup (0: as one population of all rows) */ \
     X(LEARNED_STEP, "learned_step", 1.0)             /* 0: icem_plan_step_learned* refuse (the controllers then run the stage-wise loop) */ \
+    X(MLP_STEP, "mlp_step", 1.0)                     /* 0: icem_plan_step_mlp refuses (the controllers then run the stage-wise loop through the MLP) */ \
     X(CEM_STEP, "cem_step", 1.0)                     /* 0: icem_plan_step_cem*, the learned-dynamics entries included, refuse (MpcCemStdHip then runs the stage-wise loop) */ \
     X(RANDOM_STEP, "random_step", 1.0)               /* 0: icem_plan_step_random* refuse (MpcRandomHip then runs the operator chain) */ \
     X(XCHG_LOOPBACK,"xchg_loopback", 0.0)           /* 1: time one rank without its peers (tools/sharded_rank_bench.py) */ \

@@ -17,7 +17,9 @@ struct StepModels {
 
 // the rollout of such a step's iteration: n * members problems in member-major order -- problem e * n + p reads problem p's
 // action rows and observation row p, so that the costs land as [members, the iteration's rows of all problems]
-inline void models_problems(const StepModels& mo, int n, const int* rows, rssm::Problem* out) {
+// (Problem: rssm::Problem, or mlp::Problem of icem_plan_step_mlp -- the same four fields)
+template <typename Problem>
+inline void models_problems(const StepModels& mo, int n, const int* rows, Problem* out) {
     for (int e = 0; e < mo.members; ++e) {
         long long row0 = 0;
         for (int p = 0; p < n; ++p) {

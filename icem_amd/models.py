@@ -693,11 +693,13 @@ class DeviceMLPModel(ForwardModel):
     from -- ``declared_mlp(obs_dim, act_dim, layers=, activation=, seed=)``'s, or a copy of the caller's trained ``module``
     (hidden width 200; with ``in_mean`` / ``in_std`` the copy's input layer has the normalisation folded in, so that
     ``reference`` maps raw ``[s | a]`` like the device buffer does); ``predict`` serves the reference-style NumPy interface
-    through it.  The cost is ``cost_spec``, or else ``env.cost_spec`` (an ``envs.CostSpec``).  The controllers plan through it
-    stage by stage (``rollout_cost`` + ``params``).  Several models in ONE launch: ``mlp_rollout_cost_models`` (a model per
-    problem) and ``DeviceMLPEnsemble`` (the members of an ensemble).  The model itself has no ``rollout_cost_batch``:
-    controllers that want to step together (``MpcICemHip.get_action_batch``) share a ``DeviceMLPEnsemble`` -- one member is
-    allowed and gives this model's bits."""
+    through it.  The cost is ``cost_spec``, or else ``env.cost_spec`` (an ``envs.CostSpec``).  ``MpcICemHip`` takes the whole MPC step
+    through it as one library call (``icem_plan_step_mlp``) where that entry serves the planner -- a model whose
+    ``rollout_cost`` was replaced to time or record the rollouts is called stage by stage, as the two baselines always call it
+    (``rollout_cost`` + ``params``).  Several models in ONE launch: ``mlp_rollout_cost_models`` (a model per problem) and
+    ``DeviceMLPEnsemble`` (the members of an ensemble).  The model itself has no ``rollout_cost_batch``: controllers that want
+    to step together (``MpcICemHip.get_action_batch``) share a ``DeviceMLPEnsemble`` -- one member is allowed and gives this
+    model's bits -- or bring a model each and say ``own_models=True``."""
 
     def __init__(self, obs_dim=None, act_dim=None, layers: int = 2, activation: str = "relu", seed: int = 0, device="cuda:0", env=None,
                  module=None, cost_spec=None, in_mean=None, in_std=None):
@@ -851,9 +853,13 @@ class DeviceMLPEnsemble(ForwardModel):
     for bit).  ``params`` are the members' packed buffers stacked ``[E, elems]`` on one device -- the launch reads these.
 
     The sibling of ``DeviceRSSMEnsemble``, and deliberately neither a subclass of it nor a ``DeviceMLPModel``: the library's
-    fused ``*_learned_models`` steps run the RSSM, so the controllers plan through this model stage by stage
-    (``rollout_cost`` + ``params``), and ``MpcICemHip.get_action_batch`` steps controllers that share one ensemble together
-    through ``rollout_cost_batch``; one member is allowed and gives the plain model's bits.  ``predict`` -- the
+    fused ``*_learned_models`` steps run the RSSM.  ``MpcICemHip`` takes the whole MPC step through it as one library call of
+    its own (``icem_plan_step_mlp``: one launch of all members per iteration, their reduction inside the update launch) where
+    that entry serves the planner, ``get_action_batch`` likewise for controllers that share one ensemble or, with
+    ``own_models=True``, have one each; it leaves ``member_costs`` as the stage-wise loop does (with an ensemble per planner:
+    its planner's columns of the step's one table, a view).  An instrumented ensemble and the two baselines plan through it
+    stage by stage (``rollout_cost`` / ``rollout_cost_batch`` + ``params``); one member is allowed and gives the plain model's
+    bits.  ``predict`` -- the
     reference-style interface needs ONE successor state -- delegates to member 0."""
 
     def __init__(self, models=None, seeds=None, reduce: str = "mean", **model_kw):

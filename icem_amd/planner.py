@@ -616,12 +616,16 @@ class IcemPlanner:
 
     @staticmethod
     def _ensembles_each(models):
-        """``models`` as the list of ``DeviceRSSMEnsemble`` it is where every planner plans through an ensemble of its own, else None."""
-        from .models import DeviceRSSMEnsemble
-        if isinstance(models, DeviceRSSMEnsemble):
+        """``models`` as the list of ``DeviceRSSMEnsemble`` (or of ``DeviceMLPEnsemble``: :meth:`plan_step_mlp`) it is where every
+        planner plans through an ensemble of its own, else None."""
+        from .models import DeviceMLPEnsemble, DeviceMLPModel, DeviceRSSMEnsemble
+        if isinstance(models, (DeviceRSSMEnsemble, DeviceMLPEnsemble, DeviceMLPModel)):
             return None
         models = list(models)
-        return models if models and all(isinstance(m, DeviceRSSMEnsemble) for m in models) else None
+        for kind in (DeviceRSSMEnsemble, DeviceMLPEnsemble):
+            if models and all(isinstance(m, kind) for m in models):
+                return models
+        return None
 
     @staticmethod
     def _leave_member_costs(ens, models, member_costs, members: int, rows):
@@ -730,6 +734,106 @@ class IcemPlanner:
         for pl in pls:
             pl.mpc_step += 1
         IcemPlanner._leave_member_costs(ens, models, member_costs, members, last_rows)
+        return results
+
+    # ------------------------------------------------------------------ the same step through the feed-forward model (DeviceMLPModel)
+    def mlp_step_ok(self, n: int = 1, members: int = 1, model=None) -> bool:
+        """Does ``icem_plan_step_mlp`` serve a batch of ``n`` handles like THIS one through ``members`` MLPs per problem?  (f32,
+        one GPU, a horizon of the folded sampler, the default generator, option ``mlp_step`` on, ``n * members <= 32`` ...:
+        asked of the handle; no RSSM binding is involved.)  ``model``: ask for a step through this ``DeviceMLPModel`` /
+        ``DeviceMLPEnsemble``, whose ``act_dim`` must be the planner's and whose parameters must be on its device."""
+        if model is not None and (int(getattr(model, "act_dim", -1)) != self.d or model.params.device != self.device):
+            return False
+        return bool(self.lib.icem_plan_step_mlp_ok(self._h, int(n), int(members)))
+
+    @property
+    def mlp_step_launches(self) -> int:
+        """Kernel launches of the last ``icem_plan_step_mlp`` this planner led (``icem_mlp_step_launches``)."""
+        return int(self.lib.icem_mlp_step_launches(self._h))
+
+    @staticmethod
+    def _mlp_models_table(models, n: int, reduce):
+        """``models`` of :meth:`plan_step_mlp` -> ``(ens, per, table, reduce)``: the ``DeviceMLPEnsemble`` all planners share or
+        None, the model or ensemble of every planner, the parameter pointers ``[n][members]`` and the reduction's name (None:
+        the ensembles' own, else ``"mean"``).  One kind for all planners, and ``_check_mlp_models``' rules: one shape, one
+        activation, one device, one cost program; ensembles of one size and -- unless ``reduce`` names one -- one reduction."""
+        from .models import DeviceMLPEnsemble, DeviceMLPModel, _check_mlp_models
+        per = [models] * n if isinstance(models, (DeviceMLPModel, DeviceMLPEnsemble)) else list(models)
+        if len(per) != n:
+            raise ValueError(f"{n} planners but models for {len(per)}")
+        each_ens = bool(per) and all(isinstance(m, DeviceMLPEnsemble) for m in per)
+        if per and not each_ens and not all(isinstance(m, DeviceMLPModel) for m in per):
+            raise ValueError("the models of plan_step_mlp are DeviceMLPModels or DeviceMLPEnsembles (one kind for all planners)")
+        distinct = list({id(m): m for m in per}.values())
+        if 1 <= len(distinct) <= L.MLP_MAX_PROBLEMS:   # (an ensemble carries its members' shape, activation, cost and device)
+            _check_mlp_models(distinct)
+        if each_ens:
+            if len({m.members for m in per}) > 1:
+                raise ValueError(f"every planner needs the same number (>= 1) of models, got {[m.members for m in per]}")
+            if len({m.reduce for m in per}) > 1 and reduce is None:
+                raise ValueError("the planners' ensembles reduce differently: name one reduce for the step")
+            reduce = per[0].reduce if reduce is None else reduce
+            table = [m._param_ptrs() for m in per]
+        else:
+            reduce = "mean" if reduce is None else reduce
+            table = [[m.params.data_ptr()] for m in per]
+        if reduce not in L.RSSM_REDUCE:
+            raise ValueError(f"reduce must be 'mean' or 'max', not {reduce!r}")
+        ens = per[0] if each_ens and len(distinct) == 1 else None
+        return ens, per, table, reduce
+
+    @staticmethod
+    def plan_step_mlp(planners: Sequence["IcemPlanner"], models, observations, reduce=None, member_costs=None) -> torch.Tensor:
+        """One MPC step of every planner of ``planners`` (one configuration; seeds, episodes, step counts and observations of
+        their own) through feed-forward models as ``icem_plan_step_mlp``: :meth:`plan_step_learned_models` with the MLP launch
+        in the rollout's place.  ``models``: a ``DeviceMLPModel`` or a ``DeviceMLPEnsemble`` for all planners, or a list with
+        one of either per planner (one shape, one activation, one device, one cost program; ensembles of one size and one
+        reduction).  ``observations``: ``[B, obs_dim]``.  A plan's cost is the mean or the worst of its problem's members:
+        ``reduce`` ``"mean"`` / ``"max"`` (None: the ensembles' own, else ``"mean"``).  Every stage is one launch for all
+        problems and members, 3 per CEM iteration (+ 1 in a step that shifts elites: :attr:`mlp_step_launches` of the first
+        planner).  Each planner's ``mean``, ``std``, elites, ``executed`` and ``best_cost`` afterwards are bit for bit those of
+        the stage-wise loop through its members' ``rollout_cost``; with one planner ``actions`` / ``costs`` hold the last pool
+        as well.  Returns the results ``[B, d + 1]`` (executed action | best cost per planner; device tensor, no host sync;
+        kept with the first planner -- its next call of this batch size overwrites it).  The members' costs of the LAST
+        iteration, ``[members, its rows of all planners]``, are left in ``member_costs`` (an f32 device tensor of at least
+        ``members * B * max rows`` elements) when one is given, and in the ensembles' ``member_costs`` as their own
+        ``rollout_cost`` / ``rollout_cost_batch`` would leave them (with an ensemble each: its planner's columns, a view).
+        Raises ``IcemError`` before anything is launched -- and before any planner has advanced -- where the batch is not served
+        (the observations have then been copied into the first planner's private ``[B, obs_dim]`` tensor, nothing else).  That
+        tensor and the results are kept per ``(B, obs_dim)`` with the first planner and released with it."""
+        pls = list(planners)
+        n = len(pls)
+        ens, per, table, reduce = IcemPlanner._mlp_models_table(models, n, reduce)
+        if n == 0:   # (the entry's own refusal: n outside [1, 32])
+            L.check(L.load_library().icem_plan_step_mlp(None, 0, None, None, 1, None, 0, None, None, None, None))
+        members = len(table[0])
+        p0, m0 = pls[0], per[0]
+        obs = np.ascontiguousarray(np.asarray(observations, dtype=np.float32).reshape(n, -1))
+        if obs.shape[1] != m0.obs_dim:
+            raise ValueError(f"expected observations of shape ({n}, {m0.obs_dim})")
+        need = members * n * max(p0.population_sizes[it] + (p0.n_reuse if it == 0 else 0) for it in range(len(p0.population_sizes)))
+        member_costs = IcemPlanner._models_member_costs(p0, ens, member_costs, need, per)
+        # (the observations and the results of a batch size live with the first planner for as long as it does -- their addresses
+        #  sit in the argument blocks, so the steady state uploads nothing; the observations are copied there before the entry
+        #  can refuse, which no planner's state sees)
+        kept = p0.__dict__.setdefault("_mlp_step_io", {})
+        if (n, m0.obs_dim) not in kept:
+            kept[(n, m0.obs_dim)] = (torch.empty((n, m0.obs_dim), dtype=torch.float32, device=p0.device),
+                                     torch.empty((n, p0.d + 1), dtype=torch.float32, device=p0.device))
+        obs_dev, results = kept[(n, m0.obs_dim)]
+        obs_dev.copy_(torch.as_tensor(obs), non_blocking=False)   # one host-to-device copy for the whole batch
+        hs = (C.c_void_p * n)(*[pl._h for pl in pls])
+        bs = (L.IcemPlanBuffersC * n)(*[pl._learned_buffers(obs_dev[i].data_ptr()) for i, pl in enumerate(pls)])
+        steps = (C.c_int32 * n)(*[pl.mpc_step for pl in pls])
+        ptrs = (C.c_void_p * (n * members))(*[p for row in table for p in row])
+        last_rows = [pl._step_rows(len(pl.population_sizes) - 1) for pl in pls]
+        model_c = L.IcemMlpStepModelC(m0.obs_dim, m0.layers, L.MLP_ACTIVATIONS[m0.activation], C.pointer(m0._cost_c),
+                                      C.pointer(m0._terms_c) if m0._terms_c is not None else None)
+        L.check(p0.lib.icem_plan_step_mlp(hs, n, bs, C.byref(model_c), members, ptrs, L.RSSM_REDUCE[reduce], steps,
+                                          None if member_costs is None else _ptr(member_costs), _ptr(results), p0._stream()))
+        for pl in pls:
+            pl.mpc_step += 1
+        IcemPlanner._leave_member_costs(ens, per, member_costs, members, last_rows)
         return results
 
     # ------------------------------------------------------------------ the CEM baseline's step (MpcCemStd)

@@ -1021,6 +1021,45 @@ int icem_mlp_rollout_cost_ensemble(int32_t members, const void* const* params_ho
                                    int32_t act_dim, int32_t layers, int32_t activation, int32_t cost_mode, int32_t reduce,
                                    const icem_cost_spec* cost, const icem_cost_terms* terms, const void* obs0, const void* actions,
                                    void* member_costs /* [members, n], output */, void* costs /* [n] */, void* stream);
+/* The iCEM MPC step through that model as ONE call: icem_plan_step_learned_models (above) with the MLP launch in the rollout's
+ * place -- for one planner or n, through one model, a model each, one shared ensemble or an ensemble each.  params_host
+ * [n * members] (host array of device pointers, problem-major, read before the call returns): problem p's members are
+ * params_host[p * members .. (p + 1) * members), each a packed buffer of icem_mlp_param_elems(model->obs_dim, act_dim,
+ * model->layers) words.  A shared model is members == 1 with the same pointer n times, a shared ensemble repeats its `members`
+ * pointers per problem, a model each / an ensemble each name distinct buffers.  *model: the shape and activation all of them share
+ * and the cost pair that scores every problem (act_dim, the horizon and cost_mode are the handles').
+ *   Semantics: icem_plan_step_learned_models' in every point -- noise offsets, elite halves, the shifted rows of a problem reset
+ * later than its peers, the epilogue, `results` [n, act_dim + 1], member_costs (NULL, or at least members * n * the largest
+ * iteration's rows of one problem; afterwards the LAST iteration's [members, rows of all problems]), the argument blocks with
+ * handles[0] uploaded only when a byte changed, free alternation with the other steps and the stage-wise operators on one
+ * handle.  b->obs0 is [model->obs_dim] f32.  The rollout of an iteration is ONE icem_mlp_rollout_cost_models launch of
+ * n * members problems in member-major order over the observation table [n, obs_dim] (n == 1: b->obs0 itself, and the
+ * problem's own actions / costs; n > 1: a pool of handles[0]'s); the update reduces the members' costs in
+ * icem_rssm_ensemble_reduce's arithmetic.  3 launches per iteration, + 1 in a step that shifts elites, whatever n and members
+ * (icem_mlp_step_launches of handles[0]); no host synchronisation; no staging area, no status word, no
+ * icem_set_rssm_act_dim binding.  Every problem's mean, std, both elite halves with their costs, executed, best_cost and its
+ * results row are bit for bit what the stage-wise operators (icem_sample_clip, icem_mlp_rollout_cost_ensemble / _models,
+ * icem_update_distribution, icem_shift) give, for n == 1 the last pool in actions / costs too; members == 1 gives the bits of
+ * the loop through icem_mlp_rollout_cost.
+ *   Served: what icem_plan_step_learned asks of a handle except the RSSM's action width and the split launch's limit (f32,
+ * world == 1, the fast path on, profiling off, rng_rounds 10, a horizon of the folded sampler, horizon * act_dim <= 512, at
+ * most 16 384 candidates and 32 elites per update), act_dim <= 32, n * members <= 32; development option mlp_step = 0
+ * switches the entry off.  ICEM_E_INVALID: a NULL argument, cost or params_host entry, n or members outside [1, 32], a bad
+ * reduce or activation, a negative step, a NULL required buffer, the same handle twice, unequal configurations, a cost pair
+ * icem_mlp_rollout_cost calls invalid (a term index outside obs_dim among it).  ICEM_E_UNSUPPORTED: n * members > 32, obs_dim
+ * or layers outside the MLP's ranges (these, like the counts, before any handle is looked at), act_dim > 32, a non-NULL z_*,
+ * a handle that is not served.  All of it before anything is launched or any handle touched.  icem_plan_step_mlp_ok: would n
+ * handles like this one be served with `members` models each (the model's own shape is not asked)? */
+typedef struct icem_mlp_step_model {
+    int32_t obs_dim, layers, activation;     /* act_dim and cost_mode are the handles' */
+    const icem_cost_spec*  cost;             /* required */
+    const icem_cost_terms* terms;            /* may be NULL */
+} icem_mlp_step_model;
+int icem_plan_step_mlp_ok(const icem_handle* h, int32_t n, int32_t members);
+int icem_plan_step_mlp(icem_handle* const* handles, int32_t n, const icem_plan_buffers* buffers, const icem_mlp_step_model* model,
+                       int32_t members, const void* const* params_host, int32_t reduce, const int32_t* mpc_steps_host,
+                       void* member_costs, void* results, void* stream);
+int64_t icem_mlp_step_launches(const icem_handle* h); /* kernel launches of the last icem_plan_step_mlp this handle led (handles[0]); measurement */
 
 /* MpcICem.get_action (icem/controllers/icem.py:106-189) as ONE call for a host caller: obs_host [obs_dim] float64
  * goes to b->obs0 through a pinned staging buffer of the handle, icem_plan_step runs, and the executed action

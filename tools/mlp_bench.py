@@ -8,7 +8,14 @@ usage: python tools/mlp_bench.py [--windows 5] [--seconds 0.5]
 --models: several models in ONE launch against a launch each, same shape (2-layer relu and 4-layer swish, N = 1024 and 4096
 rows per model): DeviceMLPEnsemble.rollout_cost for E = 2, 5, 8 members against E DeviceMLPModel.rollout_cost calls + a torch
 mean, and mlp_rollout_cost_models for B = 4, 8 problems with a model each against B solo calls.  The two arms alternate window
-by window as above."""
+by window as above.
+
+--step: one MpcICemHip MPC step (get_action: 3 iterations, kept and shifted elites, one device-to-host copy of the result)
+through a DeviceMLPEnsemble of E = 1 and E = 5 two-layer relu members two ways -- the stage-wise loop (development option
+mlp_step = 0: per iteration a sampler, a rollout, a reduction and an update call from Python) and the fused call
+(icem_plan_step_mlp: 3 launches per iteration, + 1 for the shifted elites) -- at N = 128 and at the benchmark's headline
+population, N = 4096.  Two equal controllers, warmed up into the steady state (steps that shift elites), first checked to execute
+the same bits, then timed alternating window by window as above; the line also gives the fused step's launch count."""
 import argparse
 import os
 import sys
@@ -102,17 +109,53 @@ def models_bench(args):
                       f"ratio {np.median(r['each']) / np.median(r['one']):5.2f}", flush=True)
 
 
+def step_bench(args):
+    """One MPC step through a DeviceMLPEnsemble: the stage-wise loop against the fused call."""
+    from icem_amd import _lib as L
+    rs = np.random.RandomState(0)
+    obs = 0.1 * rs.randn(O)
+    members = []
+    for seed in range(5):
+        net = declared_mlp(O, D, layers=2, activation="relu", seed=seed, device="cpu").module
+        with torch.no_grad():
+            net.out.weight.mul_(0.1)   # keeps the random network's state bounded over 30 steps
+        members.append(DeviceMLPModel(module=net, env=halfcheetah_env(O), device=DEV))
+    for E in (1, 5):
+        for N in (128, 4096):
+            legs = {"stage": controller(DeviceMLPEnsemble(models=members[:E]), N), "fused": controller(DeviceMLPEnsemble(models=members[:E]), N)}
+
+            def step(name):
+                L.set_option("mlp_step", 1 if name == "fused" else 0)
+                try:
+                    return legs[name].get_action(obs, None)
+                finally:
+                    L.set_option("mlp_step", 1)
+            for c in legs.values():
+                c.beginning_of_rollout(observation=obs, state=None, mode="train")
+            for k in range(5):   # warm-up into the steady state, and the two arrangements' bits
+                a, b = step("stage"), step("fused")
+                assert np.array_equal(a, b) and legs["stage"].last_min_cost == legs["fused"].last_min_cost, (E, N, k)
+            launches = legs["fused"].planner.mlp_step_launches
+            assert launches == 3 * 3 + 1 and legs["stage"].planner.mlp_step_launches == 0, "which path each leg took"
+            r = alternate({k: (lambda k=k: step(k)) for k in legs}, args.windows, args.seconds)
+            print(f"mpc step  E={E} N={N:5d}  stage-wise {fmt(r['stage'])}  fused {fmt(r['fused'])}  "
+                  f"ratio {np.median(r['stage']) / np.median(r['fused']):5.2f}  fused launches {launches}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--models", action="store_true", help="several models in one launch against a launch each")
+    ap.add_argument("--step", action="store_true", help="one MPC step through an ensemble: the stage-wise loop against the fused call")
     args = ap.parse_args()
     rs = np.random.RandomState(0)
     obs = 0.1 * rs.randn(O)
     print(f"# {torch.cuda.get_device_name(0)}; o={O} d={D} h={H}; {args.windows} windows of >= {args.seconds} s per path, alternating", flush=True)
     if args.models:
         return models_bench(args)
+    if args.step:
+        return step_bench(args)
     for layers in (2, 4):
         for act in ("relu", "swish"):
             net = declared_mlp(O, D, layers=layers, activation=act, seed=0, device="cpu").module
